@@ -2,11 +2,14 @@
 """Headline benchmark of the HIP hot path: PLE 3-domain training step (BASELINE.json configs[1]).
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py ... --full                             (+ roofline, CPU baseline, replay depth, per-rank-BN step)
+    python bench.py ... --dump-outputs DIR                 (+ what the last timed step computed, as DIR/<name>.npy)
 
 One step = one full training step of run.py:481-493 (forward, BCE, L2 term over every registered tensor incl. the
 whole embedding table, backward, Adam on every parameter) on one resident synthetic batch.  Prints ONE JSON line.
-`roofline` is for the dominant kernel of the step, timed with HIP events on the launch stream; `cpu_baseline` is the
-CPU oracle (reference semantics, stock torch CPU ops) timed on this host's cores on a bounded sample (rank 0, N=1).
+A plain run sets up, warms up, times the K steps and prints the line; `ms_per_step` is the wall time of one timed step.
+With --full: `roofline` is for the dominant kernel of the step, timed with HIP events on the launch stream; `cpu_baseline`
+is the CPU oracle (reference semantics, stock torch CPU ops) timed on this host's cores on a bounded sample (rank 0, N=1).
 """
 import argparse
 import json
@@ -44,16 +47,26 @@ def parse():
     ap.add_argument("--table-mode", default="lazy", choices=["dense", "lazy"])
     ap.add_argument("--graph", type=int, default=1, help="replay the step as one hipGraph (single GPU)")
     ap.add_argument("--id-dist", default="uniform", choices=["uniform", "zipf"])
-    ap.add_argument("--cpu-baseline", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, after the timed steps: the roofline of the step's "
+                         "dominant kernel (instrumented eager steps, back-to-back re-runs), the CPU baseline (--cpu-baseline), the "
+                         "replay depth of the lazy table and, N>1 with --sync-bn 1, the per-rank-statistics step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64): the BCE "
+                         "and L2 losses, the predictions, every dense parameter and buffer, and the table rows of the last batch "
+                         "plus a fixed seeded sample of the others (the lazy table is brought up to date for the read and put back, "
+                         "so that the run goes on from the state the timed steps left)")
+    ap.add_argument("--cpu-baseline", type=int, default=1, help="with --full: time the CPU oracle's step (N=1)")
     ap.add_argument("--cpu-steps", type=int, default=4)
     ap.add_argument("--sync-bn", type=int, default=1,
                     help="N>1: 1 (default, the parity semantic of SURVEY 8e) = BatchNorm statistics over the global batch, bit for bit "
                          "the single-process step on the concatenated batch; 0 = per-rank statistics over the local rows.  With 1 "
-                         "the per-rank-statistics throughput is measured as well and reported as `value_per_rank_bn`")
+                         "and --full the per-rank-statistics throughput is measured as well and reported as `value_per_rank_bn`")
     ap.add_argument("--table-dist", default=None, choices=["sharded", "replicated"], help="N>1: default sharded (lazy table)")
     ap.add_argument("--simulate-world", type=int, default=0,
                     help="diagnostic, single process: run ONE rank's launch work of a W-rank step with the collectives replaced "
-                         "by local copies (timing of the compute side only; the numbers it trains on are meaningless)")
+                         "by local copies (timing of the compute side only; the numbers it trains on are meaningless).  Its line is built "
+                         "from the per-launch breakdown, which it measures with or without --full")
     ap.add_argument("--atten", type=int, default=0,
                     help="1: the reference's default attention branch (config.py:24-28: 3 x MultiheadAttention(64, 2 heads) + residual) "
                          "on top of the BASELINE configuration, which is defined without it")
@@ -219,6 +232,58 @@ def replay_depth(opt):
     return float((t - last.double()).clamp_(min=0).mean().item())
 
 
+DUMP_SAMPLE_ROWS = 65536          # table rows dumped besides the last batch's (fixed seed)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, ts, opt, X_last, rank):
+    """--dump-outputs: what a caller of the timed step holds after its last call, as out_dir/<name>.npy: the two losses step()
+    returns, the model's output for that batch (one column per domain tower), every dense tensor of the state_dict, and rows of the
+    embedding table (1.6 GB at the headline size): the rows the last batch looked up and a fixed seeded sample of all rows, each
+    with its row ids.  The lazy table is brought up to date for the read, as state_dict() needs, and then put back bit for bit,
+    so that what runs after this (--full) continues from the state the timed steps left.  Every rank takes part (the row-sharded
+    table is gathered by collectives); rank 0 writes."""
+    table = opt.table.detach()
+    keep = None
+    if opt.table_mode == "lazy":
+        keep = [(t, t.clone()) for t in (table, opt.table_m, opt.table_v, opt.table_last)]
+    ts.gather_table()
+    try:
+        if rank != 0:
+            return
+        R, D = table.shape
+        rng = np.random.default_rng(0)
+        offsets = np.asarray(ts.model.embedding.offsets, dtype=np.int64)          # first row of every field
+        last_ids = np.unique(X_last.cpu().numpy().astype(np.int64) + offsets[None, :])
+        cap = max(1, (16 << 20) // (4 * D))
+        if len(last_ids) > cap:
+            last_ids = np.sort(rng.choice(last_ids, cap, replace=False))
+        sample_ids = np.sort(rng.choice(R, min(R, DUMP_SAMPLE_ROWS), replace=False))
+
+        def rows(ids):
+            return table[torch.from_numpy(ids).to(table.device)].float().cpu().numpy()
+
+        out = {"bce_loss": ts.loss.detach().float().cpu().numpy().reshape(-1),
+               "reg_loss": torch.as_tensor(ts.reg).detach().double().cpu().numpy().reshape(-1),
+               "output": ts.out.tensor().detach().float().cpu().numpy()}
+        for name, t in ts.model.state_dict().items():
+            if t.data_ptr() != table.data_ptr():
+                t = t.detach().cpu()
+                out["state." + name] = (t.float() if t.is_floating_point() else t.double()).numpy()
+        out.update({"table_rows_last_batch": rows(last_ids), "table_rows_last_batch_ids": last_ids.astype(np.float64),
+                    "table_rows_sample": rows(sample_ids), "table_rows_sample_ids": sample_ids.astype(np.float64)})
+        total = sum(a.nbytes for a in out.values())
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f"bench.py: --dump-outputs would write {total / 2**20:.1f} MB (> {DUMP_MAX_BYTES >> 20} MB)")
+        os.makedirs(out_dir, exist_ok=True)
+        for name, a in out.items():
+            np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    finally:
+        if keep is not None:
+            for t, k in keep:
+                t.copy_(k)
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -258,7 +323,7 @@ def main():
     # N>1: the headline runs with global-batch BatchNorm statistics (the parity semantic); the per-rank-statistics step
     # (torch DDP without SyncBatchNorm) is timed beside it on the same model and optimiser state
     ts_local = None
-    if dp is not None and world > 1 and args.sync_bn:
+    if args.full and dp is not None and world > 1 and args.sync_bn:
         ts_local = TrainStep(model, opt, args.batch, mode="multi", use_graph=use_graph, dist=dp, sync_bn=False,
                              table_dist=args.table_dist)
 
@@ -302,23 +367,27 @@ def main():
     run(ts, args.preroll)                        # untimed, independent of --warmup: reach the steady state
     run(ts, max(args.warmup, 1))
     elapsed = timed(ts, args.steps)
+    loss_val = float(ts.loss.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ts, opt, Xd[(cursor[0] - 1) % args.pool], rank)
     # (host-synchronising and the first use of a few torch kernels: behind the timed region — in front of the warm-up it left the
     # first ~100 steps 3 % slower, which is what a --steps 20 --warmup 5 run then measured; the replay depth is a periodic function
     # of the step count in steady state)
-    depth = replay_depth(opt)
+    depth = replay_depth(opt) if (args.full or sim is not None) else None
     if os.environ.get("CDC_BENCH_REPEAT"):                     # development: the same bracket again (is the first one special?)
         print("brackets ms/step:", [round(elapsed / args.steps * 1e3, 4)] + [round(timed(ts, args.steps) / args.steps * 1e3, 4) for _ in range(4)], file=sys.stderr)
-    loss_val = float(ts.loss.item())
     elapsed_local = None
     if ts_local is not None:
         run(ts_local, max(args.warmup, 4))
         elapsed_local = timed(ts_local, args.steps)
 
     # ---- roofline of the dominant kernel, HIP events on the launch stream (instrumented eager steps) ----------
-    roof = measure_roofline(args, ts, opt, Xd, yd, gd, depth, elapsed / args.steps * 1e3)
+    roof = None
+    if args.full or sim is not None:
+        roof = measure_roofline(args, ts, opt, Xd, yd, gd, depth, elapsed / args.steps * 1e3)
 
     cpu = None
-    if args.cpu_baseline and world == 1 and rank == 0 and sim is None:
+    if args.full and args.cpu_baseline and world == 1 and rank == 0 and sim is None:
         Xc = [Xr[i * B:(i + 1) * B] for i in range(min(args.pool, 1 + args.cpu_steps))]
         yc = [yr[i * B:(i + 1) * B].astype(np.float32) for i in range(len(Xc))]
         gc = [gr[i * B:(i + 1) * B] for i in range(len(Xc))]
@@ -331,7 +400,7 @@ def main():
                           "one_rank_compute_ms_per_step": elapsed / args.steps * 1e3,
                           "kernel_ms_per_step_sum": roof["kernel_ms_per_step_sum"], "launch_ms_per_step": dict(top)}), flush=True)
         return
-    if os.environ.get("CDC_BENCH_BREAKDOWN_ALL") != "1":
+    if roof is not None and os.environ.get("CDC_BENCH_BREAKDOWN_ALL") != "1":
         roof.pop("breakdown_all", None)
     if rank == 0:
         ms = elapsed / args.steps * 1e3
@@ -350,7 +419,7 @@ def main():
                        # step (RCCL); "segments": launch segments replayed, collectives issued by the host in between (fallback)
                        "exchange": None if not ts.dp_on else ("rccl, one_graph" if ts._one_graph_ok else "rccl, segments"),
                        "bn_stats": None if world == 1 else ("global batch (sync)" if args.sync_bn else "per rank"),
-                       "steady_state": bool(steady), "preroll_steps": args.preroll,
+                       "full": bool(args.full), "steady_state": bool(steady), "preroll_steps": args.preroll,
                        "mean_replay_depth_of_next_slice_flush": depth, "flush_every": args.flush_every if table_mode == "lazy" else None,
                        "last_bce_loss": loss_val},
             "roofline": roof, "cpu_baseline": cpu,

@@ -5,7 +5,7 @@ mkdir -p $d
 i=0
 for kv in "$@"; do
   i=$((i+1))
-  env $kv python bench.py --steps 300 --warmup 20 --cpu-baseline 0 > $d/bench_$i.json 2> $d/err_$i.log || { tail -20 $d/err_$i.log; exit 1; }
+  env $kv python bench.py --full --steps 300 --warmup 20 --cpu-baseline 0 > $d/bench_$i.json 2> $d/err_$i.log || { tail -20 $d/err_$i.log; exit 1; }
   python - "$d/bench_$i.json" "$kv" <<'PY'
 import json, sys
 for l in open(sys.argv[1]):

@@ -6,7 +6,7 @@ i=0
 for spec in "$@"; do
   i=$((i+1))
   envs="${spec%%--*}"; args="${spec#*--}"
-  env $envs python bench.py --steps 300 --warmup 20 --cpu-baseline 0 $args > $d/bench_$i.json 2> $d/err_$i.log || { tail -20 $d/err_$i.log; exit 1; }
+  env $envs python bench.py --full --steps 300 --warmup 20 --cpu-baseline 0 $args > $d/bench_$i.json 2> $d/err_$i.log || { tail -20 $d/err_$i.log; exit 1; }
   python - "$d/bench_$i.json" "$spec" <<'PY'
 import json, sys
 for l in open(sys.argv[1]):

@@ -1,9 +1,10 @@
 # usage: bash tools/gpu_prof.sh <outdir> [bench args...]   -> per-kernel per-step table from rocprofv3 --kernel-trace --stats
 O=$1; shift
 mkdir -p $O
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/kt -- python3 $GRAFT_REPO_ROOT/bench.py --cpu-baseline 0 --preroll 200 --warmup 10 --steps 200 "$@" > $GRAFT_REPO_ROOT/$O/bench.json 2> $GRAFT_REPO_ROOT/$O/err.log
-cd $GRAFT_REPO_ROOT
+rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$O/kt -- python3 $ROOT/bench.py --full --cpu-baseline 0 --preroll 200 --warmup 10 --steps 200 "$@" > $ROOT/$O/bench.json 2> $ROOT/$O/err.log
+cd $ROOT
 find $O/kt -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats.csv \;
 rm -rf $O/kt
 python - $O <<'PY'

@@ -7,7 +7,7 @@
 set -o pipefail
 O=gpurun_out/$1
 mkdir -p $O
-python bench.py > $O/bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }
 echo "bench default done"
 python bench.py --steps 20 --warmup 5 --cpu-baseline 0 > $O/bench_short.json 2> $O/bench_short.err || exit 1
 python bench.py --steps 1000 --warmup 20 --cpu-baseline 0 > $O/bench_long.json 2> $O/bench_long.err || exit 1
