@@ -189,22 +189,29 @@ class FusedAdam:
                   self.table.shape[0], self.table.shape[1], self._hp(), self.step_dev.data_ptr(), -1, self.flush_every,
                   self.own_mod, self.own_rem), self._stream(), nbytes=nb)
 
-    def table_catchup_rows(self, idx, B, F, D, tag="", runs=0, flush=True):
-        """lazy mode, BEFORE the gather of this step, on already computed row indices [B,F] (the gathered batch under DP).
-        flush=False: the caller issues flush_slice() itself, later in the step."""
+    def catchup(self, B, F, D, tag=""):
+        """lazy mode, BEFORE the gather of this step: replays the rows whose sorted list is in workspace `tag` (sort_rows() or
+        begin_step_sort() of this or the previous step) up to step t-1.  The launch alone: the caller issues flush_slice()."""
         assert self.table_mode == "lazy"
-        s = self._stream()
-        ws = self.sort_rows(idx, B, F, D, tag, runs)
+        ws = self._workspace(B, F, D, tag)
         L.launch("cdc_embed_lazy_catchup", self.lib.cdc_embed_lazy_catchup,
                  (ws["uniq"].data_ptr(), ws["cnt"].data_ptr(), self.table.data_ptr(), self.table_m.data_ptr(),
-                  self.table_v.data_ptr(), self.table_last.data_ptr(), self._hp(), self.step_dev.data_ptr(), None, 0, B, F, D), s)
-        if flush:
-            self.flush_slice()
+                  self.table_v.data_ptr(), self.table_last.data_ptr(), self._hp(), self.step_dev.data_ptr(), None, 0, B, F, D), self._stream())
+
+    def catchup_gather(self, B, F, D, tag, out_ptr, out_h, ld_out_h):
+        """catchup() whose launch also IS the gather of the step (cdc_embed_lazy_catchup_gather): the lanes that bring a row up to
+        date write it to every batch position that looks it up — `out` [B, F*D] fp32 (+ the bf16 shadow)."""
+        assert self.table_mode == "lazy"
+        ws = self._workspace(B, F, D, tag)
+        L.launch("cdc_embed_lazy_catchup_gather", self.lib.cdc_embed_lazy_catchup_gather,
+                 (ws["uniq"].data_ptr(), ws["cnt"].data_ptr(), ws["seg"].data_ptr(), ws["perm"].data_ptr(), self.table.data_ptr(),
+                  self.table_m.data_ptr(), self.table_v.data_ptr(), self.table_last.data_ptr(), self._hp(), self.step_dev.data_ptr(),
+                  out_ptr, out_h, ld_out_h, B, F, D), self._stream(), nbytes=float(B) * F * (D * 4 + 4 + D * 4))
 
     def begin_step_sort(self, ids, offsets, B, F, D, tag="", err=None, begin=True):
         """begin_step() + table_index() + sort_rows() in the sort's launches: the sort reads the raw ids (row = id + field
         offset, out-of-range -> -1 and `err`), and its first launch also advances the step counter and clears the accumulators.
-        begin=False: the sort alone (a batch sorted one step ahead: the step counter is not its business)."""
+        begin=False: the sort alone (the staging launch begins the step, or the batch is sorted one step ahead)."""
         ws = self._workspace(B, F, D, tag)
         L.launch("cdc_embed_sort_dedupe", self.lib.cdc_embed_sort_dedupe_ids,
                  (ids.data_ptr(), offsets.data_ptr(), self.table.shape[0], self.step_dev.data_ptr() if begin else None,
@@ -213,46 +220,6 @@ class FusedAdam:
                   ws["uniq"].data_ptr(), ws["seg"].data_ptr(), ws["perm"].data_ptr(), ws["cnt"].data_ptr(),
                   None if ws["scratch"] is None else ws["scratch"].data_ptr(), B, F), self._stream())
         return ws
-
-    def catchup_sorted(self, B, F, D, tag=""):
-        """lazy mode: the catch-up of the rows whose sorted list is in workspace `tag` (begin_step_sort(..., tag) of this or the
-        previous step), without the slice (the caller issues flush_slice())."""
-        assert self.table_mode == "lazy"
-        ws = self._workspace(B, F, D, tag)
-        L.launch("cdc_embed_lazy_catchup", self.lib.cdc_embed_lazy_catchup,
-                 (ws["uniq"].data_ptr(), ws["cnt"].data_ptr(), self.table.data_ptr(), self.table_m.data_ptr(),
-                  self.table_v.data_ptr(), self.table_last.data_ptr(), self._hp(), self.step_dev.data_ptr(), None, 0, B, F, D), self._stream())
-
-    def begin_step_catchup(self, ids, offsets, B, F, D, flush=True):
-        """begin_step() + table_catchup() of a single-GPU lazy step with two launches less (begin_step_sort)."""
-        assert self.table_mode == "lazy"
-        s = self._stream()
-        ws = self.begin_step_sort(ids, offsets, B, F, D)
-        L.launch("cdc_embed_lazy_catchup", self.lib.cdc_embed_lazy_catchup,
-                 (ws["uniq"].data_ptr(), ws["cnt"].data_ptr(), self.table.data_ptr(), self.table_m.data_ptr(),
-                  self.table_v.data_ptr(), self.table_last.data_ptr(), self._hp(), self.step_dev.data_ptr(), None, 0, B, F, D), s)
-        if flush:
-            self.flush_slice()
-
-    def begin_step_catchup_gather(self, ids, offsets, out_ptr, out_h, ld_out_h, B, F, D, err=None, flush=True):
-        """begin_step_catchup() whose catch-up launch also IS the gather of the step (cdc_embed_lazy_catchup_gather): the lanes
-        that bring a row up to date write it to every batch position that looks it up — `out` [B, F*D] fp32 (+ the bf16 shadow)."""
-        assert self.table_mode == "lazy"
-        s = self._stream()
-        ws = self.begin_step_sort(ids, offsets, B, F, D, err=err)
-        L.launch("cdc_embed_lazy_catchup_gather", self.lib.cdc_embed_lazy_catchup_gather,
-                 (ws["uniq"].data_ptr(), ws["cnt"].data_ptr(), ws["seg"].data_ptr(), ws["perm"].data_ptr(), self.table.data_ptr(),
-                  self.table_m.data_ptr(), self.table_v.data_ptr(), self.table_last.data_ptr(), self._hp(), self.step_dev.data_ptr(),
-                  out_ptr, out_h, ld_out_h, B, F, D), s, nbytes=float(B) * F * (D * 4 + 4 + D * 4))
-        if flush:
-            self.flush_slice()
-
-    def table_catchup(self, ids, offsets, idx, B, F, D, flush=True):
-        """lazy mode, BEFORE the gather of this step: row indices -> dedupe -> replay the rows up to step t-1."""
-        assert self.table_mode == "lazy"
-        L.launch("cdc_embed_index", self.lib.cdc_embed_index,
-                 (ids.data_ptr(), offsets.data_ptr(), idx.data_ptr(), None, B, F, self.table.shape[0]), self._stream())
-        self.table_catchup_rows(idx, B, F, D, flush=flush)
 
     def table_step(self, idx, d_out, B, F, D, tag="", short_segments=False):
         """Adam step t on the table from the batch's row indices [B,F] and the gradient of the gathered rows [B,F*D].
@@ -272,7 +239,7 @@ class FusedAdam:
             L.launch("cdc_embed_adam_patch", self.lib.cdc_embed_adam_patch,
                      (ws["side"].data_ptr(), ws["uniq"].data_ptr(), ws["cnt"].data_ptr(), w, m, v, B, F, D), s)
         else:
-            ws = self._workspace(B, F, D, tag)   # rows were sorted by table_catchup of this step
+            ws = self._workspace(B, F, D, tag)   # rows were sorted for the catch-up of this step
             # per-row gradient sums and the rows' Adam step in one launch
             L.launch("cdc_embed_segsum_lazy_update", self.lib.cdc_embed_segsum_lazy_update,
                      (d_out.data_ptr(), ws["seg"].data_ptr(), ws["perm"].data_ptr(), ws["cnt"].data_ptr(), ws["uniq"].data_ptr(),
@@ -356,51 +323,46 @@ class FusedAdam:
                 # more tensors than one kernel-argument block holds: ONE launch whose descriptors and workgroup map are device arrays
                 tab = (L.AdamTensor * len(items))()
                 wg_t, wg_c = [], []
-                for i, (p, g, st) in enumerate(items):
-                    T = tab[i]
-                    T.w, T.g, T.m, T.v, T.n = p.data_ptr(), g.data_ptr(), st[0].data_ptr(), st[1].data_ptr(), p.numel()
-                    T.l2 = float(torch.tensor(self._l2_of.get(id(p), 0.0), dtype=torch.float64).to(torch.float32))
-                    sl = slabs.get(g.data_ptr())
-                    T.slabs, T.slab_stride, T.n_slabs = sl if sl is not None else (None, 0, 0)
-                    nck = -(-p.numel() // L.ADAM_CHUNK)
+                for i, item in enumerate(items):
+                    self._adam_tensor(tab[i], item, slabs)
+                    nck = -(-item[0].numel() // L.ADAM_CHUNK)
                     wg_t += [i] * nck
                     wg_c += list(range(nck))
-                hdr = L.AdamArgs()
-                hdr.n_tensors = 0
-                hdr.lerp_w, hdr.beta2, hdr.one_minus_beta2, hdr.eps, hdr.weight_decay = self._lerp_w, self._beta2, self._omb2, self._eps, self._wd
-                hdr.step_scalars, hdr.n_scalars = self.scalars.data_ptr(), self.scalars.shape[0]
-                hdr.grad_scale = self.grad_scale
-                hdr.step_dev = self.step_dev.data_ptr()
-                hdr.reg_sum = self.reg_sum.data_ptr()
-                hdr.reg_seed = self.table_reg.data_ptr() if self.table_mode == "lazy" else 0
+                hdr = self._adam_header(0, seed_reg=True)
                 dev_tab = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(self.device)
                 self._dense_table = (hdr, dev_tab, torch.tensor(wg_t, dtype=torch.int32, device=self.device),
                                      torch.tensor(wg_c, dtype=torch.int32, device=self.device), len(wg_t))
                 items = []
             args = []
             for c0 in range(0, len(items), L.MAX_TENSORS):
-                a = L.AdamArgs()
                 chunk = items[c0:c0 + L.MAX_TENSORS]
-                a.n_tensors = len(chunk)
-                a.lerp_w, a.beta2, a.one_minus_beta2, a.eps, a.weight_decay = self._lerp_w, self._beta2, self._omb2, self._eps, self._wd
-                a.step_scalars, a.n_scalars = self.scalars.data_ptr(), self.scalars.shape[0]
-                a.grad_scale = self.grad_scale
-                a.step_dev = self.step_dev.data_ptr()
-                a.reg_sum = self.reg_sum.data_ptr()
-                # lazy table: the step's reg figure = dense parameters' sum + the table term cached by refresh_table_reg()
-                a.reg_seed = self.table_reg.data_ptr() if (self.table_mode == "lazy" and c0 == 0) else 0
-                for i, (p, g, st) in enumerate(chunk):
-                    T = a.t[i]
-                    T.w, T.g, T.m, T.v, T.n = p.data_ptr(), g.data_ptr(), st[0].data_ptr(), st[1].data_ptr(), p.numel()
-                    T.l2 = float(torch.tensor(self._l2_of.get(id(p), 0.0), dtype=torch.float64).to(torch.float32))
-                    sl = slabs.get(g.data_ptr())
-                    if sl is not None:
-                        T.slabs, T.slab_stride, T.n_slabs = sl
-                    else:
-                        T.slabs, T.slab_stride, T.n_slabs = None, 0, 0
+                a = self._adam_header(len(chunk), seed_reg=c0 == 0)
+                for i, item in enumerate(chunk):
+                    self._adam_tensor(a.t[i], item, slabs)
                 args.append(a)
             self._dense_args, self._dense_sig = args, sig
             cache[sig] = (args, self._dense_table)
+
+    def _adam_header(self, n_tensors, seed_reg):
+        """a dense Adam launch's argument block without its tensors (cdc_adam_args); seed_reg: the launch that starts the step's reg
+        figure — lazy table: dense parameters' sum + the table term cached by refresh_table_reg()"""
+        a = L.AdamArgs()
+        a.n_tensors = n_tensors
+        a.lerp_w, a.beta2, a.one_minus_beta2, a.eps, a.weight_decay = self._lerp_w, self._beta2, self._omb2, self._eps, self._wd
+        a.step_scalars, a.n_scalars = self.scalars.data_ptr(), self.scalars.shape[0]
+        a.grad_scale = self.grad_scale
+        a.step_dev = self.step_dev.data_ptr()
+        a.reg_sum = self.reg_sum.data_ptr()
+        a.reg_seed = self.table_reg.data_ptr() if (self.table_mode == "lazy" and seed_reg) else 0
+        return a
+
+    def _adam_tensor(self, T, item, slabs):
+        """fills one parameter's descriptor (cdc_adam_tensor) from (parameter, gradient, (m, v))"""
+        p, g, st = item
+        T.w, T.g, T.m, T.v, T.n = p.data_ptr(), g.data_ptr(), st[0].data_ptr(), st[1].data_ptr(), p.numel()
+        T.l2 = float(torch.tensor(self._l2_of.get(id(p), 0.0), dtype=torch.float64).to(torch.float32))
+        sl = slabs.get(g.data_ptr())
+        T.slabs, T.slab_stride, T.n_slabs = sl if sl is not None else (None, 0, 0)
 
     def reg_loss(self):
         """device double: the step's regularisation term sum(l2*w^2) (dense params + table).  Lazy mode: the table's part is the

@@ -17,6 +17,26 @@ from . import _lib as L
 from .optim import FusedAdam
 
 
+def _run_steps(steps):
+    """a launch piece of a data-parallel sequence: plan steps issued on the current stream"""
+    def fn():
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        for s_ in steps:
+            s_(st)
+    return fn
+
+
+def _merge_pieces(seq):
+    """[(is_comm, fn)] -> [(is_comm, [fn...])]: neighbouring launch pieces fused into one segment"""
+    merged = []
+    for is_comm, fn in seq:
+        if merged and not is_comm and not merged[-1][0]:
+            merged[-1][1].append(fn)
+        else:
+            merged.append((is_comm, [fn]))
+    return merged
+
+
 class TrainStep:
     """mode:
          "multi"   multi-tower models (PLE / MMoE / CDC split): pred = model(X).gather(1, group)  (run.py:481-484)
@@ -37,13 +57,13 @@ class TrainStep:
         table_dist (data parallel only): "sharded" (row r owned by rank r % world; default with the lazy table optimiser)
         or "replicated" (every rank applies the global batch's table update).  shard_slack: capacity of the per-owner,
         per-field row lists as a multiple of the even share B/world (an overflow raises in check_ids()).
-        overlap / overlap_waves / sort_ahead / fuse_gather (single GPU, lazy table; for tests and A/B runs — the defaults are what is
         global_rows / cap_rows (data parallel, the ragged last global batch of an epoch: TrainStep.sibling): the batch's true global
         size (the BCE mean runs over it; this rank's share is batch_size) and the largest share any rank holds (row-list capacities
         are a property of the exchange, equal on every rank).
+        overlap / overlap_waves / sort_ahead / fuse_gather (single GPU, lazy table; for tests and A/B runs — the defaults are what is
         measured and shipped): the replay slice in the background on a second chain (waves per SIMD of its capped grid), the next
-        batch's row sort on that chain (step(..., next_X=)), the catch-up launch that also writes the gathered embeddings (slower:
-        profiles/round3/README.md section 3)."""
+        batch's row sort on that chain (step(..., next_X=); sort_ahead=False ignores next_X), the catch-up launch that also writes
+        the gathered embeddings (slower: profiles/round3/README.md section 3)."""
         self.model, self.opt, self.B, self.mode = model, optimizer, int(batch_size), mode
         self.lib = L.load()
         self.dist = dist
@@ -56,7 +76,6 @@ class TrainStep:
         self.device = dev
         self.train_mode = bool(train_mode)
         self._overlap_ok, self._overlap_waves = bool(overlap), int(overlap_waves)
-        self._sort_ahead_wanted, self._fuse_gather_wanted = sort_ahead, bool(fuse_gather)
         # the two updates that end a single-GPU step with the lazy table (the step's rows; the dense parameters) as one launch
         self._rows_dense_one = bool(rows_dense_one_launch) and not self.dp_on
         self.tower_one_launch = bool(tower_one_launch)        # the fused towers' forward and backward as one launch (cdc_tower_step)
@@ -124,6 +143,33 @@ class TrainStep:
             self.zero_offsets = torch.zeros(F, dtype=torch.int32, **z)
             optimizer.own_mod, optimizer.own_rem = N, dist.rank
             self._loss_behind_arena()
+        # ---- how a step goes out, decided once -------------------------------------------------------------------------
+        lazy_one = optimizer.table_mode == "lazy" and not self.dp_on
+        D = self.emb.D
+        # single GPU, lazy table: the catch-up launch writes the gathered embeddings itself (csrc/embedding.hip
+        # k_lazy_catchup_gather); needs a row's 16-byte lanes inside one wave.  Off by default: measured at C2
+        # (profiles/round2/README.md) the fused launch takes 48 us against 28.5 + 7.2 us for catch-up + gather — the wave that owns the
+        # domain column's three rows writes ~B positions on its own while the rest of the chip has finished; it wins only where no
+        # row is looked up by more than a few samples
+        self._fuse_gather_ok = lazy_one and bool(fuse_gather) and D % 4 == 0 and 64 % (D // 4) == 0
+        # single GPU, lazy table, slice in the background: the sort + dedupe of batch t+1's rows (30 us of three dependent launches
+        # that read nothing but the ids) goes out on the side chain of step t, behind the slice, when the caller names the next batch
+        # (step(..., next_X=)); step t+1 then starts at the catch-up.  Otherwise every step sorts its own batch at the head of the
+        # side chain
+        self._ahead_ok = lazy_one and self._overlap_ok and bool(sort_ahead) and not self._fuse_gather_ok
+        # data parallel, row-sharded table: the local sort, the bucketing and the id exchange of batch t+1 leave step t+1's critical
+        # path when the caller names the next batch; see _dp_sequence_sharded.  (A forced one-rank group has no transfer for the
+        # moved work to hide under — measured 0.803 -> 0.818 ms/step on the one-GPU box, the step there is bound by the host-side
+        # issue of its segments — so it takes part only with sort_ahead="force", which the RCCL call-path test sets)
+        self._ahead_dp_ok = (self.dp_on and self.table_dist == "sharded" and bool(sort_ahead) and
+                             (self.world > 1 or sort_ahead == "force"))
+        # the staging launch also begins the step (cdc_stage_batch_next: ++step, accumulators cleared) where the step's first
+        # launch is not one that can: one GPU with the lazy table (the sort may have run a step ahead), the data-parallel look-ahead
+        self._stage_begins = lazy_one or self._ahead_dp_ok
+        self._parity, self._sorted_for = 0, None          # the look-ahead's bookkeeping (_lookahead)
+        self._graphs, self._dp_seqs = {}, {}              # per (have, prefetch, p): single GPU graphs, data-parallel sequences
+        if self._ahead_ok or self._ahead_dp_ok:
+            self.ids_next = torch.zeros_like(self.emb.ids)
 
     def _loss_behind_arena(self):
         """Data parallel: the loss scalar sits right behind the used part of the flat gradient arena, so ONE all-reduce covers the
@@ -228,21 +274,6 @@ class TrainStep:
                   self.loss.data_ptr(), og.ptr, og.ld, self.B, self.out.cols, 1.0 / self.global_B),
                  C.c_void_p(torch.cuda.current_stream().cuda_stream))
 
-    def _fuse_gather(self):
-        """single GPU, lazy table: the catch-up launch writes the gathered embeddings itself (csrc/embedding.hip
-        k_lazy_catchup_gather); needs a row's 16-byte lanes inside one wave"""
-        hit = self.__dict__.get("_fuse_gather_ok")
-        if hit is None:
-            import os
-            D = self.emb.D
-            # off by default: measured at C2 (profiles/round2/README.md) the fused launch takes 48 us against 28.5 + 7.2 us for
-            # catch-up + gather — the wave that owns the domain column's three rows writes ~B positions on its own while the rest
-            # of the chip has finished; it wins only where no row is looked up by more than a few samples
-            hit = D % 4 == 0 and 64 % (D // 4) == 0 and self._fuse_gather_wanted
-            self._fuse_gather_ok = hit
-            self._fwd_after_gather = [s_ for s_ in self.plan.fwd_steps if s_ is not self.emb.fwd_step]
-        return hit
-
     def _reg(self):
         # part of the (graph-replayed) launch sequence, so that step() issues nothing else per call.  Dense table mode: the
         # streaming pass sums w^2 of the whole table every step (reg_sum[1]).  Lazy table: nobody walks the table in a step;
@@ -262,182 +293,112 @@ class TrainStep:
         sharded = self.dp_on and self.table_dist == "sharded"
         return self.opt.refresh_table_reg(self.dist if sharded else None)
 
-    def _launch_all(self):
-        self._towers_one_launch(True)
-        try:
-            self._launch_all_seq()
-        finally:
-            self._towers_one_launch(False)
-
-    def _launch_all_seq(self):
-        """single GPU: the whole step is one launch sequence (one hipGraph when use_graph)."""
-        opt, plan, emb = self.opt, self.plan, self.emb
-        B, F, D = self.B, emb.F, emb.D
-        if opt.table_mode == "lazy":
-            # sort -> catch-up of the batch's rows [which also writes the gathered embeddings (+ shadow): hot rows staged in LDS and
-            # written by a whole workgroup, the plan's own gather launch skipped] -> this step's slice of the whole-table replay.
-            # With the slice in the BACKGROUND, two chains on two hardware queues (two branches of the hipGraph when captured):
-            #   main:  sort, catch-up(+gather) | forward, BCE, backward, grad-weight launches, dense Adam | per-row sums + Adam on the
-            #   side:                          | the slice                                                |   step's rows, reg
-            # The slice is VALU-only and touches no row of the batch (those are at step t-1 after the catch-up and are skipped); it
-            # goes out capped (two waves per SIMD) at the lowest issue priority (cdc_embed_lazy_flush_bg) while the chain's kernels
-            # raise theirs (CDC_PRIO_MAIN): it takes the issue cycles the chain leaves idle while waiting on L2 / LDS / MFMA results.
-            # The table update needs the slice finished: it goes last on the main chain, behind the one join.
-            fused, bg = self._fuse_gather(), self._overlap()
-            if fused:
-                oh, ldh = (plan.shadow_view(emb.out) if (plan.use_g2 and plan.has_shadow(emb.out)) else (None, 0))
-                opt.begin_step_catchup_gather(emb.ids, emb.offsets, emb.out.ptr, oh, ldh, B, F, D, err=emb.err, flush=not bg)
-            else:
-                opt.begin_step_catchup(emb.ids, emb.offsets, B, F, D, flush=not bg)
-            main = torch.cuda.current_stream()
-            if bg:
-                side = self._side_stream()
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    opt.flush_slice(background_waves=self._overlap_waves)
-            if fused:
-                st = C.c_void_p(main.cuda_stream)
-                for fn in self._fwd_after_gather:
-                    fn(st)
-            else:
-                plan.forward()
-            self._bce()
-            plan.backward()
-            if self._rows_dense_one:
-                if bg:
-                    main.wait_stream(side)
-                opt.rows_and_dense_step(emb.idx, emb.out.grad.root, B, F, D, plan.param_grads, plan._param_refs, plan.grad_slabs)
-                self._reg()
-                return
-            opt.dense_step(plan.param_grads, plan._param_refs, plan.grad_slabs)
-            if bg:
-                main.wait_stream(side)
-            opt.table_step(emb.idx, emb.out.grad.root, B, F, D)
-            self._reg()
-            return
-        opt.begin_step()
-        plan.forward()
-        self._bce()
-        plan.backward()
-        opt.table_step(emb.idx, emb.out.grad.root, B, F, D)
-        opt.dense_step(plan.param_grads, plan._param_refs, plan.grad_slabs)
-        self._reg()
-
-    def _sort_ahead(self):
-        """Single GPU, lazy table, slice in the background: the sort + dedupe of batch t+1's rows (30 us of three dependent launches
-        that read nothing but the ids) goes out on the side chain of step t, behind the slice, when the caller names the next batch
-        (step(..., next_X=)); step t+1 then starts at the catch-up.  TrainStep(sort_ahead=False): every step sorts its own batch first."""
-        if getattr(self, "_ahead_ok", None) is None:
-            self._ahead_ok = (not self.dp_on and self.opt.table_mode == "lazy" and self._overlap() and not self._fuse_gather() and
-                              bool(self._sort_ahead_wanted))
-            if self._ahead_ok:
-                self.ids_next = torch.zeros_like(self.emb.ids)
-                self._parity, self._sorted_for, self._graphs = 0, None, {}
-        return self._ahead_ok
-
-    def _launch_ahead(self, have, prefetch, p):
-        self._towers_one_launch(True)
-        try:
-            self._launch_ahead_seq(have, prefetch, p)
-        finally:
-            self._towers_one_launch(False)
-
-    def _launch_ahead_seq(self, have, prefetch, p):
-        """_launch_all's lazy branch with the row sort out of the chain and the catch-up on the SIDE chain: have = this batch's
-        sorted rows are in workspace a<p> (sorted by the previous step), prefetch = sort the batch in ids_next into workspace
-        a<1-p>.  begin_step's work was done by the staging launch (cdc_stage_batch_next).
+    def _launch(self, have, prefetch, p):
+        """Single GPU: the whole step as one launch sequence (one hipGraph per (have, prefetch, p) when use_graph).  Lazy table:
+        have = this batch's sorted rows are in workspace a<p> (sorted by the previous step), prefetch = sort the batch in ids_next
+        into workspace a<1-p>; begin_step's work was done by the staging launch (cdc_stage_batch_next).
             side:  [sort] catch-up * | slice, [sort of the next batch]
             main:  weight shadows    | (wait *) gather, forward, BCE, backward, grad-weight launches, dense Adam | join | row update
-        The fork sits at the head of the step: the weight-shadow launch reads nothing of the table and covers the cross-queue edge
-        (by the kernel trace, profiles/round3/step_timeline.txt, the fork-after-catch-up form left 12 us between the catch-up and
-        the first forward launch)."""
+        The side chain is a second stream on its own hardware queue (two branches of the hipGraph when captured) when the slice runs
+        in the BACKGROUND (overlap, the default), and the main stream itself otherwise: no fork, no event, no join, and the slice
+        goes out with its full grid.  The fork sits at the head of the step: the weight-shadow launch reads nothing of the table and
+        covers the cross-queue edge (by the kernel trace, profiles/round3/step_timeline.txt, the fork-after-catch-up form left 12 us
+        between the catch-up and the first forward launch).
+        The slice is VALU-only and touches no row of the batch (those are at step t-1 after the catch-up and are skipped); in the
+        background it goes out capped (overlap_waves per SIMD) at the lowest issue priority (cdc_embed_lazy_flush_bg) while the
+        chain's kernels raise theirs (CDC_PRIO_MAIN): it takes the issue cycles the chain leaves idle while waiting on L2 / LDS / MFMA
+        results.  Measured at C2 (profiles/round3/README.md): serial 0.550 ms/step; side by side with the full grid 0.596 (round 2:
+        its 4096 workgroups take every wave slot); capped at two waves per SIMD, lowest priority, table update behind a single join:
+        0.515.  The table update needs the slice finished: it goes last on the main chain, behind the one join.
+        fuse_gather: the catch-up launch also writes the gathered embeddings (+ shadow; hot rows staged in LDS and written by a whole
+        workgroup), and the plan's own gather launch is skipped."""
         opt, plan, emb = self.opt, self.plan, self.emb
         B, F, D = self.B, emb.F, emb.D
-        cur, nxt = f"a{p}", f"a{1 - p}"
         main = torch.cuda.current_stream()
-        side = self._side_stream()
-        # measured (same box, ms/step): fork after the catch-up + row update behind the join 0.411 / 0.412; catch-up on the side chain
-        # under the weight-shadow launch 0.403; row update on the side chain as well (waiting for dE by an event, beside the
-        # grad-weight launches and the dense Adam) 0.420 / 0.424 — two more cross-queue edges cost more than the 24 us they free;
-        # main chain captured FIRST behind the catch-up (so that it stays on the origin queue and the side chain takes the
-        # cross-queue edge): the replayed graph then starts the slice 150 us late, 0.476
         st = C.c_void_p(main.cuda_stream)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            if not have:
-                opt.begin_step_sort(emb.ids, emb.offsets, B, F, D, tag=cur, begin=False)
-            opt.catchup_sorted(B, F, D, tag=cur)
-            rows_ready = torch.cuda.Event()
-            rows_ready.record(side)
-            opt.flush_slice(background_waves=self._overlap_waves)
-            if prefetch:          # behind the slice (ahead of it the sort delays the whole side chain into the backward: 0.401 -> 0.443 ms;
+        self._towers_one_launch(True)
+        try:
+            if opt.table_mode != "lazy":
+                opt.begin_step()
+                plan.forward()
+                self._bce()
+                plan.backward()
+                opt.table_step(emb.idx, emb.out.grad.root, B, F, D)
+                opt.dense_step(plan.param_grads, plan._param_refs, plan.grad_slabs)
+                self._reg()
+                return
+            cur, nxt = f"a{p}", f"a{1 - p}"
+            bg, fused = self._overlap_ok, self._fuse_gather_ok
+            side = self._side_stream() if bg else main
+            # measured (same box, ms/step): fork after the catch-up + row update behind the join 0.411 / 0.412; catch-up on the side
+            # chain under the weight-shadow launch 0.403; row update on the side chain as well (waiting for dE by an event, beside the
+            # grad-weight launches and the dense Adam) 0.420 / 0.424 — two more cross-queue edges cost more than the 24 us they free;
+            # main chain captured FIRST behind the catch-up (so that it stays on the origin queue and the side chain takes the
+            # cross-queue edge): the replayed graph then starts the slice 150 us late, 0.476
+            if bg:
+                side.wait_stream(main)
+            with torch.cuda.stream(side):
+                if not have:
+                    opt.begin_step_sort(emb.ids, emb.offsets, B, F, D, tag=cur, err=emb.err if fused else None, begin=False)
+                if fused:
+                    oh, ldh = plan.shadow_view(emb.out) if (plan.use_g2 and plan.has_shadow(emb.out)) else (None, 0)
+                    opt.catchup_gather(B, F, D, cur, emb.out.ptr, oh, ldh)
+                else:
+                    opt.catchup(B, F, D, cur)
+                if bg:
+                    rows_ready = torch.cuda.Event()
+                    rows_ready.record(side)
+                opt.flush_slice(background_waves=self._overlap_waves if bg else 0)
+                if prefetch:      # behind the slice (ahead of it the sort delays the whole side chain into the backward: 0.401 -> 0.443 ms;
                                   # held back by an event until the backward chain has run: 0.408 -> 0.427)
-                opt.begin_step_sort(self.ids_next, emb.offsets, B, F, D, tag=nxt, begin=False)
-        nws = getattr(plan, "n_wshadow_steps", 0)
-        for fn in plan.fwd_steps[:nws]:
-            fn(st)
-        main.wait_event(rows_ready)
-        for fn in plan.fwd_steps[nws:]:
-            fn(st)
-        self._bce()
-        late = set(id(s_) for s_ in plan.deferred_dw_steps)
-        for fn in plan.bwd_steps:
-            if id(fn) not in late:
+                    opt.begin_step_sort(self.ids_next, emb.offsets, B, F, D, tag=nxt, begin=False)
+            nws = plan.n_wshadow_steps
+            for fn in plan.fwd_steps[:nws]:
                 fn(st)
-        for fn in plan.deferred_dw_steps:
-            fn(st)
-        if self._rows_dense_one:
-            # the step's rows and the dense parameters in one launch behind the join (optim.rows_and_dense_step)
-            main.wait_stream(side)
-            opt.rows_and_dense_step(emb.idx, emb.out.grad.root, B, F, D, plan.param_grads, plan._param_refs, plan.grad_slabs, tag=cur)
+            if bg:
+                main.wait_event(rows_ready)
+            for fn in plan.fwd_steps[nws:]:
+                if not (fused and fn is emb.fwd_step):
+                    fn(st)
+            self._bce()
+            plan.backward()                   # (ends with the grad-weight launches: plan.deferred_dw_steps)
+            if self._rows_dense_one:
+                # the step's rows and the dense parameters in one launch behind the join (optim.rows_and_dense_step)
+                if bg:
+                    main.wait_stream(side)
+                opt.rows_and_dense_step(emb.idx, emb.out.grad.root, B, F, D, plan.param_grads, plan._param_refs, plan.grad_slabs, tag=cur)
+            else:
+                opt.dense_step(plan.param_grads, plan._param_refs, plan.grad_slabs)
+                # (the row update on the side chain beside these two, or on this chain in front of them as soon as the slice has ended,
+                # was measured again in round 4: 0.345 and 0.350 ms against 0.338 — every additional cross-queue edge of the replayed
+                # graph moves nodes to another hardware queue and costs ~10 us where it lands, profiles/round4/README.md section 6)
+                if bg:
+                    main.wait_stream(side)
+                opt.table_step(emb.idx, emb.out.grad.root, B, F, D, tag=cur)
             self._reg()
-            return
-        opt.dense_step(plan.param_grads, plan._param_refs, plan.grad_slabs)
-        # (the row update on the side chain beside these two, or on this chain in front of them as soon as the slice has ended, was
-        # measured again in round 4: 0.345 and 0.350 ms against 0.338 — every additional cross-queue edge of the replayed graph moves
-        # nodes to another hardware queue and costs ~10 us where it lands, profiles/round4/README.md section 6)
-        main.wait_stream(side)
-        opt.table_step(emb.idx, emb.out.grad.root, B, F, D, tag=cur)
-        self._reg()
+        finally:
+            self._towers_one_launch(False)
 
-    def _step_ahead(self, X, nx):
-        # the remembered tensor is kept alive (its storage cannot be handed to another batch) and its version pins its contents
+    def _lookahead(self, X, nx):
+        """(have, prefetch, p) of a step with the look-ahead sort, and the bookkeeping moved on: have = X is the batch the previous
+        step announced (its rows were sorted into buffer p), prefetch = this step sorts nx into buffer 1 - p.  The remembered tensor
+        is kept alive (its storage cannot be handed to another batch) and its version pins its contents."""
         key = (X.data_ptr(), X._version) if torch.is_tensor(X) else None
         have = self._sorted_for is not None and self._sorted_for[:2] == key
-        prefetch = nx is not None
         p = self._parity
-        if self.use_graph and self._warm >= 2:
-            g = self._graphs.get((have, prefetch, p))
-            if g is None:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._launch_ahead(have, prefetch, p)
-                self._graphs[(have, prefetch, p)] = g
-                self.graph = g
-            g.replay()
-        else:
-            self._launch_ahead(have, prefetch, p)
-            self._warm += 1
-        if prefetch:
+        if nx is not None:
             self._parity = 1 - p
             self._sorted_for = (nx.data_ptr(), nx._version, nx)
         else:
             self._sorted_for = None
-
-    def _overlap(self):
-        """The replay slice of the lazy table on a second stream beside the forward/backward (single GPU).  TrainStep(overlap=False)
-        puts it back on the main chain, overlap_waves sets the slice's waves per SIMD.  Measured at C2 (profiles/round3/README.md):
-        serial 0.550 ms/step; side by side with the full grid 0.596 (round 2: its 4096 workgroups take every wave slot); capped at
-        two waves per SIMD, lowest priority, table update behind a single join: 0.515."""
-        return self._overlap_ok
+        return have, nx is not None, p
 
     def _drop_graphs(self):
         """releases every captured graph (before the process group is destroyed: DataParallel.close)"""
         self._step_graphs.clear()
         self._stage_graphs.clear()
+        self._graphs.clear()
         self.graph = None
-        if hasattr(self, "_graphs"):
-            self._graphs.clear()
 
     def _side_stream(self):
         if getattr(self, "_side", None) is None:
@@ -458,7 +419,9 @@ class TrainStep:
 
         def catchup():
             if opt.table_mode == "lazy":
-                opt.table_catchup_rows(self.idx_all, self.global_B, F, D)
+                opt.sort_rows(self.idx_all, self.global_B, F, D)
+                opt.catchup(self.global_B, F, D)
+                opt.flush_slice()
 
         def exchange():
             dp.all_reduce_sum(self.arena_and_loss)                      # dense gradients + the loss scalar behind them
@@ -469,27 +432,12 @@ class TrainStep:
             opt.dense_step(plan.param_grads, plan._param_refs, plan.grad_slabs)
             self._reg()
 
-        def run_steps(steps):
-            def fn():
-                st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-                for s_ in steps:
-                    s_(st)
-            return fn
-
         seq = [(False, stage0), (True, lambda: dp.all_gather_rows(self.idx_all, emb.idx)), (False, catchup)]
-        for is_comm, steps in plan.segments(plan.fwd_steps):
-            seq.append((is_comm, run_steps(steps)))
+        seq += [(is_comm, _run_steps(steps)) for is_comm, steps in plan.segments(plan.fwd_steps)]
         seq.append((False, self._bce))
-        for is_comm, steps in plan.segments(plan.bwd_steps):
-            seq.append((is_comm, run_steps(steps)))
+        seq += [(is_comm, _run_steps(steps)) for is_comm, steps in plan.segments(plan.bwd_steps)]
         seq += [(True, exchange), (False, update)]
-        merged = []                                   # fuse neighbouring launch pieces into one segment
-        for is_comm, fn in seq:
-            if merged and not is_comm and not merged[-1][0]:
-                merged[-1][1].append(fn)
-            else:
-                merged.append((is_comm, [fn]))
-        return merged
+        return _merge_pieces(seq)
 
     def _dp_sequence_sharded(self, ahead=False, have=False, prefetch=False, p=0):
         """Row-sharded table: [(is_comm, [fn...])].  Per step and rank the table work is that of the LOCAL batch:
@@ -529,7 +477,8 @@ class TrainStep:
             sort_bucket(self.ids_next, begin=False)
 
         def serve():
-            opt.table_catchup_rows(recv_cur, Bv, F, D, "owner", runs=N, flush=False)   # each sender's list is sorted
+            opt.sort_rows(recv_cur, Bv, F, D, "owner", runs=N)           # each sender's list is sorted
+            opt.catchup(Bv, F, D, "owner")
             if side_ok:                               # the slice of the owned rows in the background, until the row update
                 main, side = torch.cuda.current_stream(), self._side_stream()
                 side.wait_stream(main)
@@ -595,40 +544,25 @@ class TrainStep:
         def join_side():
             torch.cuda.current_stream().wait_stream(self._side_stream())
 
-        def run_steps(steps):
-            def fn():
-                s_ = st()
-                for step in steps:
-                    step(s_)
-            return fn
-
         if have:
             seq = [(True, ids_await), (False, serve)]
         else:
             seq = [(False, stage0), (True, lambda: dp.all_to_all(recv_cur, self.send_ids)), (False, serve)]
         seq += [(True, lambda: dp.all_to_all(self.rows_recv, self.rows_send)), (False, expand)]
         fwd = [s_ for s_ in plan.fwd_steps if s_ is not emb.fwd_step]
-        for is_comm, steps in plan.segments(fwd):
-            seq.append((is_comm, run_steps(steps)))
+        seq += [(is_comm, _run_steps(steps)) for is_comm, steps in plan.segments(fwd)]
         seq.append((False, self._bce))
         late = set(id(s_) for s_ in plan.deferred_dw_steps)
-        for is_comm, steps in plan.segments([s_ for s_ in plan.bwd_steps if id(s_) not in late]):
-            seq.append((is_comm, run_steps(steps)))
+        seq += [(is_comm, _run_steps(steps)) for is_comm, steps in plan.segments([s_ for s_ in plan.bwd_steps if id(s_) not in late])]
         if prefetch and side_ok:
-            seq += [(False, pack), (False, stage0_next_side), (True, exchange_rows_start), (False, run_steps(plan.deferred_dw_steps)),
+            seq += [(False, pack), (False, stage0_next_side), (True, exchange_rows_start), (False, _run_steps(plan.deferred_dw_steps)),
                     (False, join_side)]
         else:
-            seq += [(False, pack), (True, exchange_rows_start), (False, run_steps(plan.deferred_dw_steps))]
+            seq += [(False, pack), (True, exchange_rows_start), (False, _run_steps(plan.deferred_dw_steps))]
             if prefetch:
                 seq.append((False, stage0_next))
         seq += [(True, exchange_finish), (False, update)]
-        merged = []
-        for is_comm, fn in seq:
-            if merged and not is_comm and not merged[-1][0]:
-                merged[-1][1].append(fn)
-            else:
-                merged.append((is_comm, [fn]))
-        return merged
+        return _merge_pieces(seq)
 
     def gather_table(self):
         """Row-sharded table: bring every owner's rows up to date and give every rank the whole table (and its Adam
@@ -644,36 +578,13 @@ class TrainStep:
             self.dist.all_reduce_sum(t)
         opt.table_last.fill_(int(opt.step_dev.item()))
 
-    def _ahead_dp(self):
-        """Data parallel, row-sharded table: the local sort, the bucketing and the id exchange of batch t+1 leave step t+1's
-        critical path when the caller names the next batch (step(..., next_X=)); see _dp_sequence_sharded.  sort_ahead=False: off;
-        sort_ahead="force": also with a forced one-rank group."""
-        if getattr(self, "_ahead_dp_ok", None) is None:
-            # (a forced one-rank group has no transfer for the moved work to hide under — measured 0.803 -> 0.818 ms/step on the
-            #  one-GPU box, the step there is bound by the host-side issue of its segments — so it takes part only with
-            #  sort_ahead="force", which the RCCL call-path test sets)
-            want = self._sort_ahead_wanted
-            self._ahead_dp_ok = (self.dp_on and self.table_dist == "sharded" and bool(want) and (self.world > 1 or want == "force"))
-            if self._ahead_dp_ok:
-                self.ids_next = torch.zeros_like(self.emb.ids)
-                self._parity, self._sorted_for, self._dp_seqs = 0, None, {}
-        return self._ahead_dp_ok
-
     def _step_dp(self, X=None, nx=None):
         key = None
-        if getattr(self, "_ahead_dp_ok", False):
-            xk = (X.data_ptr(), X._version) if torch.is_tensor(X) else None
-            have = self._sorted_for is not None and self._sorted_for[:2] == xk
-            if not have:
+        if self._ahead_dp_ok:
+            key = self._lookahead(X, nx)
+            if not key[0]:
                 self.__dict__.pop("_ids_pending", None)                 # (an exchange started for a batch that did not come: its
-            prefetch = nx is not None                                   #  buffer is simply overwritten by the next one)
-            p = self._parity
-            key = (have, prefetch, p)
-            if prefetch:
-                self._parity = 1 - p
-                self._sorted_for = (nx.data_ptr(), nx._version, nx)
-            else:
-                self._sorted_for = None
+                                                                        #  buffer is simply overwritten by the next one)
 
         def sequence():
             if key is not None:
@@ -718,8 +629,7 @@ class TrainStep:
                     g = None
                     # the sequences were built with a side chain, which launch segments cannot hold: build them again without
                     self._dp_seq = None
-                    if hasattr(self, "_dp_seqs"):
-                        self._dp_seqs.clear()
+                    self._dp_seqs.clear()
                     seq = sequence()
                 else:
                     if self._one_graph_ok is None:
@@ -759,9 +669,9 @@ class TrainStep:
 
     def step(self, X, y, group=None, next_X=None):
         """One training step. X int32 [B,F]; y int16/float [B] or [B,1]; group int64 [B] or [B,1] (multi mode).
-        next_X (optional, single GPU): the ids of the batch the NEXT call will be given (device int32 [B,F], not modified until
-        then) — its rows are sorted beside this step's forward/backward (_sort_ahead); a next call with another tensor simply sorts
-        its own.  Returns (bce_loss, reg_loss) as device tensors (no host synchronisation)."""
+        next_X (optional): the ids of the batch the NEXT call will be given (device int32 [B,F], not modified until then) — with the
+        look-ahead sort (_ahead_ok; data parallel: _ahead_dp_ok) its rows are sorted beside this step's forward/backward; a next call
+        with another tensor simply sorts its own.  Returns (bce_loss, reg_loss) as device tensors (no host synchronisation)."""
         gdst = self.group if self.group is not None else (self.group_in if self.mode == "single_group" else None)
         yf = y.reshape(-1)
         gf = None if (group is None or gdst is None) else group.reshape(-1)
@@ -771,25 +681,20 @@ class TrainStep:
         if not self._reg_checked or (self.opt.table_mode == "lazy" and not self.opt.table_reg_ready):
             # the first reported loss of a lazy run carries the table's L2 term like every later one (a freshly built or LOADED
             # optimiser has not evaluated it yet: load_state_dict clears table_reg_ready, also for a TrainStep that already ran).
-            # Before the staging launch: with the look-ahead sort that launch advances the step counter, and the refresh brings
-            # the table to the counter's step
+            # Before the staging launch: that launch may advance the step counter (_stage_begins), and the refresh brings the
+            # table to the counter's step
             self._reg_checked = True
             if self.opt.table_mode == "lazy" and not self.opt.table_reg_ready:
                 self.refresh_table_reg()
-        ahead = (not self.dp_on) and self._sort_ahead() and self._overlap()      # (profile(overlap=False) switches the side chain off)
-        if not ahead and getattr(self, "_ahead_ok", False):
-            self._sorted_for = None
-        ahead_dp = self.dp_on and self._ahead_dp()
-        ahead = ahead or ahead_dp
         nx = None
-        if fast and ahead:                                        # + the next batch's ids for the look-ahead sort, + begin_step
-            if (next_X is not None and next_X.is_cuda and next_X.dtype == torch.int32 and next_X.is_contiguous() and
-                    tuple(next_X.shape) == (self.B, self.emb.F)):
+        if fast and self._stage_begins:                           # + begin_step, + the next batch's ids for the look-ahead sort
+            if ((self._ahead_ok or self._ahead_dp_ok) and next_X is not None and next_X.is_cuda and next_X.dtype == torch.int32 and
+                    next_X.is_contiguous() and tuple(next_X.shape) == (self.B, self.emb.F)):
                 nx = next_X
             L.launch("cdc_stage_batch", self.lib.cdc_stage_batch_next,
                      (X.data_ptr(), yf.data_ptr(), None if gdst is None else gf.data_ptr(), self.emb.ids.data_ptr(), self.y.data_ptr(),
                       None if gdst is None else gdst.data_ptr(), self.B, self.emb.F, None if nx is None else nx.data_ptr(),
-                      self.ids_next.data_ptr(), self.opt.step_dev.data_ptr(), self.opt.reg_sum.data_ptr(), 2,
+                      None if nx is None else self.ids_next.data_ptr(), self.opt.step_dev.data_ptr(), self.opt.reg_sum.data_ptr(), 2,
                       self.field_dims_dev.data_ptr(), self.alias.data_ptr()),
                      C.c_void_p(torch.cuda.current_stream().cuda_stream))
         elif fast:                                                # one launch instead of three copies
@@ -804,21 +709,22 @@ class TrainStep:
             self.y.copy_(yf)
             if gdst is not None:
                 gdst.copy_(gf)
-            if ahead:
+            if self._stage_begins:
                 self.opt.begin_step()
         if self.dp_on:
             self._step_dp(X if fast else None, nx)
-        elif ahead:
-            self._step_ahead(X if fast else None, nx)
-        elif self.use_graph and self._warm >= 2:
-            if self.graph is None:
+            return self.loss, self.reg
+        key = self._lookahead(X if fast else None, nx)
+        if self.use_graph and self._warm >= 2:
+            g = self._graphs.get(key)
+            if g is None:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
-                    self._launch_all()
-                self.graph = g
-            self.graph.replay()
+                    self._launch(*key)
+                self._graphs[key] = self.graph = g
+            g.replay()
         else:
-            self._launch_all()
+            self._launch(*key)
             self._warm += 1
         return self.loss, self.reg
 
@@ -826,9 +732,9 @@ class TrainStep:
         """Per-launch timing of `n_steps` eager steps (HIP events on the stream each launch goes to); the first `skip` are not
         counted.  Returns {name: {"ms_per_step", "launches_per_step", "flops_per_step", "bytes_per_step"}}.  Events are read back
         and released every few steps: the runtime backs each timed event with a signal from a bounded pool.
-        overlap=False: the whole step on one stream, i.e. every kernel's duration with the chip to itself."""
+        overlap=False: the whole step on one stream (the main stream is the side chain), i.e. every kernel's duration with the chip
+        to itself."""
         was_graph, self.use_graph = self.use_graph, False
-        self._overlap()
         was_overlap, self._overlap_ok = self._overlap_ok, bool(self._overlap_ok and overlap)
         rec = []
         out = {}

@@ -45,7 +45,7 @@ def _run(cuda, table_mode, use_graph=False, n=4, fast_replay=False, precision="f
     losses = []
     Xd = [torch.from_numpy(X[s]).to(cuda) for s in range(n)]
     for s in range(n):
-        # announce: every step names the next batch, whose rows are then sorted on the side chain of this step (trainer._sort_ahead)
+        # announce: every step names the next batch, whose rows are then sorted on the side chain of this step (TrainStep._ahead_ok)
         nxt = Xd[s + 1] if (announce and s + 1 < n) else None
         bce, _ = ts.step(Xd[s], torch.from_numpy(y[s]).to(cuda), torch.from_numpy(g[s]).to(cuda), next_X=nxt)
         losses.append(bce.clone())

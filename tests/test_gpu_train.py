@@ -246,7 +246,7 @@ def test_split_k_slabs_summed_by_the_adam_launch_train_bit_identically(cuda, mon
 
 @pytest.mark.parametrize("use_graph", [False, True])
 def test_row_sort_one_batch_ahead_trains_bit_identically(cuda, monkeypatch, use_graph):
-    """Single GPU, lazy table: step(..., next_X=) sorts the NEXT batch's rows on the side chain of this step (trainer._sort_ahead).
+    """Single GPU, lazy table: step(..., next_X=) sorts the NEXT batch's rows on the side chain of this step (TrainStep._ahead_ok).
     The sort reads nothing but ids, so the trajectory is bit-identical to steps that sort their own batch first — also when the
     announced batch is not the one that comes (the step then sorts its own), when no batch is announced, and across a ragged
     announcement (wrong shape: ignored)."""
@@ -283,7 +283,7 @@ def test_row_sort_one_batch_ahead_trains_bit_identically(cuda, monkeypatch, use_
             bce, _ = ts.step(Xs[i], ys[i], gs[i], next_X=nxt)
             losses.append(float(bce.item()))
         # (the look-ahead rides on the side chain: TrainStep(overlap=False) or the fused catch-up + gather switch it off)
-        assert bool(getattr(ts, "_ahead_ok", False)) == (ahead == "1" and ts._overlap() and not ts._fuse_gather())
+        assert bool(getattr(ts, "_ahead_ok", False)) == (ahead == "1" and ts._overlap_ok and not ts._fuse_gather_ok)
         opt.flush_table()
         res[ahead] = (losses, {k: v.detach().cpu().clone() for k, v in model.state_dict().items()},
                       {k: (v["exp_avg"].cpu(), v["exp_avg_sq"].cpu()) for k, v in opt.state_dict()["state"].items()})
@@ -684,7 +684,7 @@ def test_fused_catchup_gather_equals_the_two_launches(cuda, monkeypatch, D, prec
         model = PLE(fd, D, 3, 1, 1, ((16,), (8,)), (8,), dropout=0.0).to(cuda).set_precision(precision)
         opt = FusedAdam(model, table_mode="lazy", flush_every=4)
         ts = TrainStep(model, opt, B, use_graph=False, fuse_gather=(fused == "1"))
-        assert ts._fuse_gather() == (fused == "1")
+        assert ts._fuse_gather_ok == (fused == "1")
         losses, embs = [], []
         for b in batches:
             bce, _ = ts.step(*b)
