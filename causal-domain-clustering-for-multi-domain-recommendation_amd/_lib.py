@@ -135,6 +135,31 @@ class PoolBwdArgs(C.Structure):
                 ("mask_scale", c_f), ("accumulate", c_i32), ("d_experts_h", c_p), ("ld_dexp_h", c_i64), ("gate", PoolBwdGate * MAX_GATES)]
 
 
+WIDE_MAX_SEL, WIDE_MAX_GATES, WIDE_MAX_EXPERT = 256, 32, 1024
+
+
+class PoolWideFwdGate(C.Structure):
+    _fields_ = [("logits", c_p), ("ld_logits", c_i64), ("out", c_p), ("ld_out", c_i64), ("probs", c_p),
+                ("out_h", c_p), ("ld_out_h", c_i64), ("n_sel", c_i32), ("pad_", c_i32)]
+
+
+class PoolWideFwdArgs(C.Structure):
+    _fields_ = [("n_gates", c_i32), ("n_expert", c_i32), ("H", c_i32), ("B", c_i64), ("experts", c_p),
+                ("ld_exp", c_i64), ("table", c_p), ("gate", PoolWideFwdGate * WIDE_MAX_GATES)]
+
+
+class PoolWideBwdGate(C.Structure):
+    _fields_ = [("d_out", c_p), ("ld_dout", c_i64), ("probs", c_p), ("d_logits", c_p), ("ld_dlogits", c_i64),
+                ("d_logits_h", c_p), ("ld_dlogits_h", c_i64), ("n_sel", c_i32), ("pad_", c_i32)]
+
+
+class PoolWideBwdArgs(C.Structure):
+    _fields_ = [("n_gates", c_i32), ("n_expert", c_i32), ("H", c_i32), ("B", c_i64), ("experts", c_p),
+                ("ld_exp", c_i64), ("d_experts", c_p), ("ld_dexp", c_i64), ("mask_relu", c_i32),
+                ("mask_scale", c_f), ("accumulate", c_i32), ("d_experts_h", c_p), ("ld_dexp_h", c_i64), ("table", c_p),
+                ("gate", PoolWideBwdGate * WIDE_MAX_GATES)]
+
+
 MID_MAX_EXPERT, MID_MAX_GATE = 16, 8
 
 
@@ -359,6 +384,9 @@ _SIGNATURES = {
     "cdc_cgc_mid_fits": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "cdc_expert_pair_fwd": (c_i32, [C.POINTER(ExpertPairArgs), c_p]),
     "cdc_gate_pool_bwd": (c_i32, [C.POINTER(PoolBwdArgs), c_p]),
+    "cdc_gate_pool_wide_table": (c_i32, [c_i32, c_i32, c_p, c_p, c_p, c_i64]),
+    "cdc_gate_pool_wide_fwd": (c_i32, [C.POINTER(PoolWideFwdArgs), c_p]),
+    "cdc_gate_pool_wide_bwd": (c_i32, [C.POINTER(PoolWideBwdArgs), c_p]),
     "cdc_bn_fwd": (c_i32, [C.POINTER(BnFwdArgs), c_p]),
     "cdc_bn_bwd": (c_i32, [C.POINTER(BnBwdArgs), c_p]),
     "cdc_rowdot_fwd": (c_i32, [C.POINTER(RowdotFwdArgs), c_p]),

@@ -284,6 +284,190 @@ extern "C" int cdc_gate_pool_bwd(const cdc_pool_bwd_args* a, void* stream) {
     return 0;
 }
 
+// ---- wide form: up to CDC_WIDE_MAX_SEL selections per gate, selection lists in a device table (include/cdcmdr.h) ----
+#define WIDE_SLOTS (CDC_WIDE_MAX_SEL / 64)        // logits per lane
+
+extern "C" int cdc_gate_pool_wide_table(int32_t n_gates, int32_t n_expert, const int32_t* n_sel, const int32_t* sel, int32_t* table,
+                                        int64_t cap) {
+    CDC_CHECK_ARG(n_gates > 0 && n_gates <= CDC_WIDE_MAX_GATES && n_expert > 0 && n_expert <= CDC_WIDE_MAX_EXPERT && n_sel && sel,
+                  CDC_E_BADARG, "gate_pool_wide_table: bad argument");
+    int64_t total = 0;
+    for (int g = 0; g < n_gates; ++g) {
+        CDC_CHECK_ARG(n_sel[g] > 0 && n_sel[g] <= CDC_WIDE_MAX_SEL, CDC_E_BADARG, "gate_pool_wide_table: gate %d selects %d experts", g,
+                      n_sel[g]);
+        total += n_sel[g];
+    }
+    for (int64_t q = 0; q < total; ++q)
+        CDC_CHECK_ARG(sel[q] >= 0 && sel[q] < n_expert, CDC_E_BADARG, "gate_pool_wide_table: selection %lld out of range", (long long)q);
+    const int64_t base = (int64_t)n_gates + n_expert + 2, len = base + 2 * total;
+    if (!table || cap == 0) return (int)len;
+    CDC_CHECK_ARG(cap >= len, CDC_E_BADARG, "gate_pool_wide_table: table holds %lld of %lld entries", (long long)cap, (long long)len);
+    int32_t* sel_off = table;
+    int32_t* inv_off = table + n_gates + 1;
+    int32_t* sel_out = table + base;
+    int32_t* inv = sel_out + total;
+    sel_off[0] = 0;
+    for (int g = 0; g < n_gates; ++g) sel_off[g + 1] = sel_off[g] + n_sel[g];
+    for (int e = 0; e <= n_expert; ++e) inv_off[e] = 0;
+    for (int64_t q = 0; q < total; ++q) {
+        sel_out[q] = sel[q];
+        ++inv_off[sel[q] + 1];
+    }
+    for (int e = 0; e < n_expert; ++e) inv_off[e + 1] += inv_off[e];
+    // entries of one expert in (gate, slot) order: the order the backward sums them in
+    for (int e = 0; e < n_expert; ++e) {
+        int32_t k = inv_off[e];
+        for (int g = 0; g < n_gates; ++g)
+            for (int j = 0; j < n_sel[g]; ++j)
+                if (sel[sel_off[g] + j] == e) inv[k++] = (g << 16) | j;
+    }
+    return (int)len;
+}
+
+__global__ void __launch_bounds__(ROW_THREADS) k_gate_pool_wide_fwd(const cdc_pool_wide_fwd_args a) {
+    CDC_PRIO_MAIN();
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
+    if (row >= a.B) return;
+    const float* ex = a.experts + row * a.ld_exp;
+    const int32_t* sel_all = a.table + a.n_gates + a.n_expert + 2;
+    for (int g = 0; g < a.n_gates; ++g) {
+        const auto& G = a.gate[g];
+        const int n = G.n_sel;
+        const int32_t* sel = sel_all + a.table[g];
+        const float* lg = G.logits + row * G.ld_logits;
+        // lane l holds logits l, l+64, ...: max and sum as wave reductions
+        float p[WIDE_SLOTS];
+        int e[WIDE_SLOTS];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < WIDE_SLOTS; ++k) {
+            const int j = lane + 64 * k;
+            p[k] = j < n ? lg[j] : -INFINITY;
+            e[k] = j < n ? sel[j] : 0;
+            mx = fmaxf(mx, p[k]);
+        }
+        mx = wave_max(mx);
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < WIDE_SLOTS; ++k) {
+            p[k] = lane + 64 * k < n ? expf(p[k] - mx) : 0.f;
+            s += p[k];
+        }
+        const float inv = 1.f / wave_sum(s);
+#pragma unroll
+        for (int k = 0; k < WIDE_SLOTS; ++k) {
+            p[k] *= inv;
+            if (G.probs && lane + 64 * k < n) G.probs[row * n + lane + 64 * k] = p[k];
+        }
+        // out[h] = sum_j p_j * experts[sel_j][h] in j order; p_j and sel_j are read out of lane j % 64 (wave-uniform)
+        for (int h0 = 0; h0 < a.H; h0 += 64) {
+            const int h = h0 + lane;
+            const bool on = h < a.H;
+            float acc = 0.f;
+#pragma unroll
+            for (int k = 0; k < WIDE_SLOTS; ++k) {
+                const int nk = min(n - 64 * k, 64);
+                for (int jj = 0; jj < nk; ++jj) {
+                    const float pj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p[k]), jj));
+                    const int ej = __builtin_amdgcn_readlane(e[k], jj);
+                    if (on && (unsigned)ej < (unsigned)a.n_expert) acc += pj * ex[(int64_t)ej * a.H + h];
+                }
+            }
+            if (on) {
+                G.out[row * G.ld_out + h] = acc;
+                if (G.out_h) reinterpret_cast<__bf16*>(G.out_h)[row * G.ld_out_h + h] = (__bf16)acc;
+            }
+        }
+    }
+}
+
+extern "C" int cdc_gate_pool_wide_fwd(const cdc_pool_wide_fwd_args* a, void* stream) {
+    CDC_CHECK_ARG(a && a->n_gates > 0 && a->n_gates <= CDC_WIDE_MAX_GATES && a->n_expert > 0 && a->n_expert <= CDC_WIDE_MAX_EXPERT &&
+                      a->H > 0 && a->B >= 0 && a->experts && a->table, CDC_E_BADARG, "gate_pool_wide_fwd: bad argument");
+    for (int g = 0; g < a->n_gates; ++g)
+        CDC_CHECK_ARG(a->gate[g].logits && a->gate[g].out && a->gate[g].n_sel > 0 && a->gate[g].n_sel <= CDC_WIDE_MAX_SEL, CDC_E_BADARG,
+                      "gate_pool_wide_fwd: gate %d malformed", g);
+    if (a->B == 0) return 0;
+    hipLaunchKernelGGL(k_gate_pool_wide_fwd, dim3(cdc_ceil_div(a->B, WAVES_PER_BLOCK)), dim3(ROW_THREADS), 0, (hipStream_t)stream, *a);
+    CDC_LAUNCH_CHECK("gate_pool_wide_fwd");
+    return 0;
+}
+
+__global__ void __launch_bounds__(ROW_THREADS) k_gate_pool_wide_bwd(const cdc_pool_wide_bwd_args a) {
+    CDC_PRIO_MAIN();
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
+    if (row >= a.B) return;
+    const float* ex = a.experts + row * a.ld_exp;
+    const int32_t* inv_off = a.table + a.n_gates + 1;
+    const int32_t* sel_all = a.table + a.n_gates + a.n_expert + 2;
+    const int32_t* inv = sel_all + a.table[a.n_gates];
+    // (1) gate gradients: lane l forms dp_j = <d_out, expert_sel_j> for j = l, l+64, ...; one wave sum for sum_k p_k dp_k
+    for (int g = 0; g < a.n_gates; ++g) {
+        const auto& G = a.gate[g];
+        const int n = G.n_sel;
+        const int32_t* sel = sel_all + a.table[g];
+        const float* dout = G.d_out + row * G.ld_dout;
+        float dp[WIDE_SLOTS], pj[WIDE_SLOTS];
+        float part = 0.f;
+#pragma unroll
+        for (int k = 0; k < WIDE_SLOTS; ++k) {
+            const int j = lane + 64 * k;
+            dp[k] = 0.f;
+            pj[k] = 0.f;
+            if (j < n && (unsigned)sel[j] < (unsigned)a.n_expert) {
+                const float* x = ex + (int64_t)sel[j] * a.H;
+                float s = 0.f;
+                for (int h = 0; h < a.H; ++h) s += dout[h] * x[h];
+                dp[k] = s;
+                pj[k] = G.probs[row * n + j];
+                part += pj[k] * s;
+            }
+        }
+        const float dot = wave_sum(part);
+#pragma unroll
+        for (int k = 0; k < WIDE_SLOTS; ++k) {
+            const int j = lane + 64 * k;
+            if (j < n) {
+                const float dl = pj[k] * (dp[k] - dot);
+                G.d_logits[row * G.ld_dlogits + j] = dl;
+                if (G.d_logits_h) reinterpret_cast<__bf16*>(G.d_logits_h)[row * G.ld_dlogits_h + j] = (__bf16)dl;
+            }
+        }
+    }
+    // (2) expert gradients gathered per expert from its (gate, slot) entries, in (gate, slot) order; then the expert's mask
+    float* dex = a.d_experts + row * a.ld_dexp;
+    for (int e = 0; e < a.n_expert; ++e) {
+        const int q0 = inv_off[e], q1 = inv_off[e + 1];
+        for (int h = lane; h < a.H; h += 64) {
+            float v = 0.f;
+            for (int q = q0; q < q1; ++q) {
+                const int gj = inv[q];
+                const auto& G = a.gate[gj >> 16];
+                v += G.probs[row * G.n_sel + (gj & 0xFFFF)] * G.d_out[row * G.ld_dout + h];
+            }
+            if (a.mask_relu) v = ex[(int64_t)e * a.H + h] > 0.f ? v * a.mask_scale : 0.f;
+            float* dst = dex + (int64_t)e * a.H + h;
+            v = a.accumulate ? *dst + v : v;
+            *dst = v;
+            if (a.d_experts_h) reinterpret_cast<__bf16*>(a.d_experts_h)[row * a.ld_dexp_h + (int64_t)e * a.H + h] = (__bf16)v;
+        }
+    }
+}
+
+extern "C" int cdc_gate_pool_wide_bwd(const cdc_pool_wide_bwd_args* a, void* stream) {
+    CDC_CHECK_ARG(a && a->n_gates > 0 && a->n_gates <= CDC_WIDE_MAX_GATES && a->n_expert > 0 && a->n_expert <= CDC_WIDE_MAX_EXPERT &&
+                      a->H > 0 && a->B >= 0 && a->experts && a->d_experts && a->table, CDC_E_BADARG, "gate_pool_wide_bwd: bad argument");
+    for (int g = 0; g < a->n_gates; ++g)
+        CDC_CHECK_ARG(a->gate[g].d_out && a->gate[g].probs && a->gate[g].d_logits && a->gate[g].n_sel > 0 &&
+                          a->gate[g].n_sel <= CDC_WIDE_MAX_SEL, CDC_E_BADARG, "gate_pool_wide_bwd: gate %d malformed", g);
+    if (a->B == 0) return 0;
+    hipLaunchKernelGGL(k_gate_pool_wide_bwd, dim3(cdc_ceil_div(a->B, WAVES_PER_BLOCK)), dim3(ROW_THREADS), 0, (hipStream_t)stream, *a);
+    CDC_LAUNCH_CHECK("gate_pool_wide_bwd");
+    return 0;
+}
+
 // =================================================================================================
 // BatchNorm1d (+ReLU +dropout)  (model/layer.py:187,199-205 ; model/star.py:117-181)
 // block = 64 columns x 64 rows: lane = column, wave w takes rows w, w+4, ...

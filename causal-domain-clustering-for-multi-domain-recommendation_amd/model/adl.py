@@ -15,8 +15,6 @@ from torch import nn
 from .. import plan as P
 from .layer import BaseModel, CrossNetwork, MultiLayerPerceptron, _bn_seg, _reg_filter
 
-MAX_GROUPED_TOWERS = 32
-
 
 class ADL(BaseModel):
     def __init__(self, feature_dims, embed_dim, n_tower, tower_dims, domain_idx=None, dropout=0.2, l2_reg_embedding=1e-5,
@@ -67,8 +65,6 @@ class ADL(BaseModel):
             raise RuntimeError("use_dcn=True cannot run: the reference adds a [B,E] cross output in place to a [B,1] logit "
                                "(model/adl.py:98-115) and raises; so do we")
         n, E = self.n_tower, emb.out
-        if n > MAX_GROUPED_TOWERS:
-            raise NotImplementedError(f"ADL supports up to {MAX_GROUPED_TOWERS} towers per launch")
         route = P.HostStep(plan)                                  # filled in below: needs the partition op's group tensor
         part = P.GroupPartition(plan, E, n)
         et = E.tensor()

@@ -14,8 +14,6 @@ from torch.nn.modules.batchnorm import _NormBase
 from .. import plan as P
 from .layer import BaseModel, CrossNetwork, DNN, _reg_filter
 
-MAX_GROUPED_TOWERS = 32
-
 
 class MDR_BatchNorm(_NormBase):
     """Parameter container of the partitioned normalisation (model/star.py:117-187): affine terms are combined with the
@@ -70,8 +68,6 @@ class STAR(BaseModel):
         E = emb.out
         ins, extra, ro = [], [], None
         if grouped:
-            if n > MAX_GROUPED_TOWERS:
-                raise NotImplementedError(f"grouped STAR forward supports up to {MAX_GROUPED_TOWERS} towers per launch")
             part = P.GroupPartition(plan, E, n)
             X, ro = part.out, part.row_offsets
             ins, extra = [part.group], [part.order]
@@ -113,9 +109,10 @@ class STAR(BaseModel):
         wl = P.StarFuse(plan, [l.weight for l in self.domain_dnn_linears], self.shared_dnn_linear.weight, "mul")
         bl = P.StarFuse(plan, [l.bias for l in self.domain_dnn_linears], self.shared_dnn_linear.bias, "add")
         out = plan.new(1 if grouped else n)
-        for c0 in range(0, n, 32):
+        step = n if grouped else 32                   # (ragged rows: one op, which chunks its launches along row_offsets)
+        for c0 in range(0, n, step):
             P.RowDot(plan, [{"x": per_domain(cur, g, cur_w), "w": wl.views[g], "b": bl.views[g],
-                             "out": out if grouped else out.slice(g, g + 1)} for g in range(c0, min(n, c0 + 32))],
+                             "out": out if grouped else out.slice(g, g + 1)} for g in range(c0, min(n, c0 + step))],
                      addends=[wide] if atten is None else [wide, atten], sigmoid=True, row_offsets=ro)
         return [out], ins, extra
 

@@ -614,6 +614,7 @@ class Plan:
 
         def run(stream):
             L.launch(what, fn, args, stream, flops, nbytes)
+        run.what = what                   # (the launch's name: tests compare plans by their kernel sequences)
         return run
 
 
@@ -651,6 +652,29 @@ class EmbedGather:
         if not gs.is_set(self.out):
             g = self.out.grad
             plan.bwd_steps.append(plan.call("cdc_fill_f32", g.cptr(), C.c_float(0.0), C.c_int64(g.rows * g.ld)))
+
+
+def _pack_bwd_x(outs, max_out, max_seg):
+    """Packs grad-input outputs (x, [group indices]) into launches of <= max_out outputs and <= max_seg segments, in order.
+    An input read by more than max_seg groups (one tower per domain: every gate and expert reads the embeddings) is split
+    into runs of max_seg groups, each in a launch of its own and in group order: the first run writes x.grad, the later ones
+    add to it (the plan's gradient bookkeeping sees the later runs claim an initialised region)."""
+    launches, cur_o, cur_s = [], [], 0
+    for x, gis in outs:
+        if len(gis) > max_seg:
+            if cur_o:
+                launches.append(cur_o)
+            launches += [[(x, gis[k:k + max_seg])] for k in range(0, len(gis), max_seg)]
+            cur_o, cur_s = [], 0
+            continue
+        if cur_o and (len(cur_o) + 1 > max_out or cur_s + len(gis) > max_seg):
+            launches.append(cur_o)
+            cur_o, cur_s = [], 0
+        cur_o.append((x, gis))
+        cur_s += len(gis)
+    if cur_o:
+        launches.append(cur_o)
+    return launches
 
 
 class GLinear:
@@ -861,26 +885,17 @@ class GLinear:
                     break
             else:
                 outs.append((x, [gi]))
-        # pack outputs into launches of <= MAX_GROUPS outputs / segments
-        launches, cur_o, cur_s = [], [], 0
-        for o in outs:
-            if len(o[1]) > L.MAX_GROUPS:
-                raise RuntimeError("more than %d linear groups share one input" % L.MAX_GROUPS)
-            if cur_o and (len(cur_o) + 1 > L.MAX_GROUPS or cur_s + len(o[1]) > L.MAX_GROUPS):
-                launches.append(cur_o)
-                cur_o, cur_s = [], 0
-            cur_o.append(o)
-            cur_s += len(o[1])
-        if cur_o:
-            launches.append(cur_o)
         if self.row_offsets is not None:
             # ragged rows: group g owns rows [ro[g], ro[g+1]) of the (shared) buffers: one output per group, in group
-            # order, and ONE accumulate decision per distinct input buffer
+            # order, launches of <= MAX_GROUPS consecutive groups (row_offsets based at the first), and ONE accumulate
+            # decision per distinct input buffer
             outs = [(g["x"], [gi]) for gi, g in enumerate(self.groups) if not g.get("no_dx")]
-            assert len(outs) == len(self.groups) and len(outs) <= L.MAX_GROUPS, "ragged launch limited to one chunk"
-            launches = [outs]
-        if self.g2:
+            assert len(outs) == len(self.groups), "a ragged launch forms the grad-input of every group"
+            launches = [outs[c0:c0 + L.MAX_GROUPS] for c0 in range(0, len(outs), L.MAX_GROUPS)]
+        elif self.g2:
             return self._build_bwd_x_g2(plan, gs, outs, allg)
+        else:
+            launches = _pack_bwd_x(outs, L.MAX_GROUPS, L.MAX_GROUPS)
         ragged_acc = {}
         for la in launches:
             # all outputs of one launch share the mask scale (one plan-wide dropout rate)
@@ -931,17 +946,7 @@ class GLinear:
     def _build_bwd_x_g2(self, plan, gs, outs, allg):
         """grad-input from the bf16 shadows of dZ and the per-step W^T copies; outputs: x.grad in fp32, plus its bf16 shadow
         when the layer that produced x reads its dZ through one"""
-        launches, cur_o, cur_s = [], [], 0
-        for o in outs:
-            if len(o[1]) > L.G2_MAX_SEG:
-                raise RuntimeError("more than %d linear groups share one input" % L.G2_MAX_SEG)
-            if cur_o and (len(cur_o) + 1 > L.G2_MAX_OUT or cur_s + len(o[1]) > L.G2_MAX_SEG):
-                launches.append(cur_o)
-                cur_o, cur_s = [], 0
-            cur_o.append(o)
-            cur_s += len(o[1])
-        if cur_o:
-            launches.append(cur_o)
+        launches = _pack_bwd_x(outs, L.G2_MAX_OUT, L.G2_MAX_SEG)
         for la in launches:
             a = L.G2Args()
             a.n_out = len(la)
@@ -1000,16 +1005,53 @@ class GatePool:
         self.gates = gates
         self.outs = outs if outs is not None else [plan.new(H) for _ in gates]
         self.probs = [torch.empty((plan.B, len(sel)), dtype=torch.float32, device=plan.device) for _, sel in gates]
+        # more selections per gate, or more experts per launch, than the kernel-argument form holds (one tower per domain):
+        # the wide form, whose selection lists live in a device table (cdc_gate_pool_wide_*)
+        self.wide = any(len(sel) > L.MAX_SEL for _, sel in gates) or n_expert > 2 * L.MAX_SEL
         for _, sel in gates:
-            if len(sel) > L.MAX_SEL:
-                raise RuntimeError(f"a gate mixes {len(sel)} experts; the pooling kernel supports {L.MAX_SEL}")
+            if len(sel) > L.WIDE_MAX_SEL:
+                raise RuntimeError(f"a gate mixes {len(sel)} experts; the pooling kernels support {L.WIDE_MAX_SEL}")
+        if n_expert > L.WIDE_MAX_EXPERT:
+            raise RuntimeError(f"{n_expert} experts in one pooling launch; the pooling kernels support {L.WIDE_MAX_EXPERT}")
         self._keep = []
+        self.tables = []
+        if self.wide:
+            for c0 in range(0, len(gates), L.WIDE_MAX_GATES):
+                chunk = gates[c0:c0 + L.WIDE_MAX_GATES]
+                n_sel = (C.c_int32 * len(chunk))(*[len(sel) for _, sel in chunk])
+                flat = [int(e) for _, sel in chunk for e in sel]
+                sel = (C.c_int32 * len(flat))(*flat)
+                n = plan.lib.cdc_gate_pool_wide_table(len(chunk), n_expert, n_sel, sel, None, 0)       # length (or < 0: bad lists)
+                if n > 0:
+                    tab = (C.c_int32 * n)()
+                    n = plan.lib.cdc_gate_pool_wide_table(len(chunk), n_expert, n_sel, sel, tab, n)
+                if n <= 0:
+                    L.check(n or -1, "cdc_gate_pool_wide_table")
+                self.tables.append(torch.tensor(list(tab), dtype=torch.int32).to(plan.device))   # (filled once, read by both directions)
         plan.add(self)
 
+    def _forms(self, direction):
+        """(argument struct, entry point, gates per launch) of this op's form; the wide form carries a table per launch instead
+        of the selection lists"""
+        if self.wide:
+            return (L.PoolWideFwdArgs, "cdc_gate_pool_wide_fwd", L.WIDE_MAX_GATES) if direction == "fwd" else \
+                (L.PoolWideBwdArgs, "cdc_gate_pool_wide_bwd", L.WIDE_MAX_GATES)
+        return (L.PoolFwdArgs, "cdc_gate_pool_fwd", L.MAX_GATES) if direction == "fwd" else \
+            (L.PoolBwdArgs, "cdc_gate_pool_bwd", L.MAX_GATES)
+
+    def _sel(self, a, G, sel, launch):
+        G.n_sel = len(sel)
+        if self.wide:
+            a.table = self.tables[launch].data_ptr()
+        else:
+            for j, e in enumerate(sel):
+                G.sel[j] = e
+
     def build_fwd(self, plan):
-        for c0 in range(0, len(self.gates), L.MAX_GATES):
-            a = L.PoolFwdArgs()
-            chunk = self.gates[c0:c0 + L.MAX_GATES]
+        Args, fn, per = self._forms("fwd")
+        for t, c0 in enumerate(range(0, len(self.gates), per)):
+            a = Args()
+            chunk = self.gates[c0:c0 + per]
             a.n_gates, a.n_expert, a.H, a.B = len(chunk), self.n_expert, self.H, plan.B
             a.experts, a.ld_exp = self.experts.ptr, self.experts.ld
             for i, (lg, sel) in enumerate(chunk):
@@ -1022,17 +1064,16 @@ class GatePool:
                 else:
                     G.out_h = None
                 G.probs = self.probs[c0 + i].data_ptr()
-                G.n_sel = len(sel)
-                for j, e in enumerate(sel):
-                    G.sel[j] = e
+                self._sel(a, G, sel, t)
             self._keep.append(a)
-            plan.fwd_steps.append(plan.call("cdc_gate_pool_fwd", C.byref(a)))
+            plan.fwd_steps.append(plan.call(fn, C.byref(a)))
 
     def build_bwd(self, plan, gs):
+        Args, fn, per = self._forms("bwd")
         acc = gs.claim(self.experts)
-        for c0 in range(0, len(self.gates), L.MAX_GATES):
-            a = L.PoolBwdArgs()
-            chunk = self.gates[c0:c0 + L.MAX_GATES]
+        for t, c0 in enumerate(range(0, len(self.gates), per)):
+            a = Args()
+            chunk = self.gates[c0:c0 + per]
             a.n_gates, a.n_expert, a.H, a.B = len(chunk), self.n_expert, self.H, plan.B
             a.experts, a.ld_exp = self.experts.ptr, self.experts.ld
             eg = self.experts.grad
@@ -1063,11 +1104,9 @@ class GatePool:
                     plan.mark_shadow(lgg)
                 else:
                     G.d_logits_h = None
-                G.n_sel = len(sel)
-                for j, e in enumerate(sel):
-                    G.sel[j] = e
+                self._sel(a, G, sel, t)
             self._keep.append(a)
-            plan.bwd_steps.append(plan.call("cdc_gate_pool_bwd", C.byref(a)))
+            plan.bwd_steps.append(plan.call(fn, C.byref(a)))
 
 
 class CGCMid:
@@ -1599,7 +1638,7 @@ class RowDot:
         self.groups, self.addends, self.sigmoid = groups, list(addends), sigmoid
         self.row_offsets = row_offsets
         self.M = plan.B if M is None else M
-        assert len(groups) <= L.MAX_GROUPS and len(self.addends) <= 4
+        assert len(self.addends) <= 4
         kmax = 0
         for g in groups:
             K = g["w"].numel()
@@ -1609,7 +1648,7 @@ class RowDot:
             kmax = max(kmax, K)
         self.kmax = kmax
         self.outs = [g["out"] for g in groups]
-        plan.need_rowdot_ws(len(groups) * L.ROWDOT_PARTS * (kmax + 1))
+        plan.need_rowdot_ws(min(len(groups), L.MAX_GROUPS) * L.ROWDOT_PARTS * (kmax + 1))
         if self.addends:
             if row_offsets is not None:
                 shared = plan.new(1)                      # ragged groups own disjoint rows of one buffer
@@ -1620,21 +1659,24 @@ class RowDot:
         plan.add(self)
 
     def build_fwd(self, plan):
-        a = L.RowdotFwdArgs()
-        a.n_groups, a.sigmoid, a.n_addend, a.M = len(self.groups), 1 if self.sigmoid else 0, len(self.addends), self.M
-        a.row_offsets = None if self.row_offsets is None else self.row_offsets.data_ptr()
-        for i, ad in enumerate(self.addends):
-            a.addend[i], a.ld_addend[i] = ad.ptr, ad.ld
-        for i, g in enumerate(self.groups):
-            G = a.g[i]
-            G.x, G.ldx = g["x"].ptr, g["x"].ld
-            G.w = g["w"].data_ptr()
-            G.bias = None if g.get("b") is None else g["b"].data_ptr()
-            G.out, G.ld_out = g["out"].ptr, g["out"].ld
-            G.logit = None
-            G.K = g["w"].numel()
-        self._keep.append(a)
-        plan.fwd_steps.append(plan.call("cdc_rowdot_fwd", C.byref(a)))
+        # launches of <= MAX_GROUPS groups; ragged rows: row_offsets based at the launch's first group
+        for c0 in range(0, len(self.groups), L.MAX_GROUPS):
+            chunk = self.groups[c0:c0 + L.MAX_GROUPS]
+            a = L.RowdotFwdArgs()
+            a.n_groups, a.sigmoid, a.n_addend, a.M = len(chunk), 1 if self.sigmoid else 0, len(self.addends), self.M
+            a.row_offsets = None if self.row_offsets is None else self.row_offsets.data_ptr() + 4 * c0
+            for i, ad in enumerate(self.addends):
+                a.addend[i], a.ld_addend[i] = ad.ptr, ad.ld
+            for i, g in enumerate(chunk):
+                G = a.g[i]
+                G.x, G.ldx = g["x"].ptr, g["x"].ld
+                G.w = g["w"].data_ptr()
+                G.bias = None if g.get("b") is None else g["b"].data_ptr()
+                G.out, G.ld_out = g["out"].ptr, g["out"].ld
+                G.logit = None
+                G.K = g["w"].numel()
+            self._keep.append(a)
+            plan.fwd_steps.append(plan.call("cdc_rowdot_fwd", C.byref(a)))
 
     def build_bwd(self, plan, gs):
         # groups that read the SAME x (CrossNetMix's gate scores) would race on dx inside one launch: they go out
@@ -1651,7 +1693,8 @@ class RowDot:
                 waves.append({"keys": {key}, "idx": [i]})
         ragged_acc = {}
         for w in waves:
-            self._build_bwd_launch(plan, gs, w["idx"], ragged_acc)
+            for c0 in range(0, len(w["idx"]), L.MAX_GROUPS):
+                self._build_bwd_launch(plan, gs, w["idx"][c0:c0 + L.MAX_GROUPS], ragged_acc)
 
     def _build_bwd_launch(self, plan, gs, idxs, ragged_acc):
         a = L.RowdotBwdArgs()
@@ -1704,7 +1747,8 @@ class RowDot:
                 G.dbias = None
             if self.addends:
                 G.dlogit, G.ld_dlogit = self.dlogit[i].ptr, self.dlogit[i].ld
-                if self.row_offsets is not None and i == 0:
+                if self.row_offsets is not None and i == len(self.groups) - 1:
+                    # (after the launch that writes the last group's rows of the shared logit gradient)
                     for ad in self.addends:
                         adg = ad.grad
                         if gs.claim(ad):

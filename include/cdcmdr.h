@@ -438,6 +438,64 @@ typedef struct {
 int cdc_gate_pool_bwd(const cdc_pool_bwd_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Wide form of the gate softmax + pooling: gates that mix more than CDC_MAX_SEL experts, or a launch over more than
+ * 2*CDC_MAX_SEL experts (PLE with one tower per domain: the shared gate of level 1 mixes 2n+2 experts at n domains, 102 at 50).
+ * Same arithmetic as cdc_gate_pool_fwd / _bwd: a max-subtracted softmax over the gate's n_sel logits (max and sum as wave64
+ * reductions), out[b,:] = sum_j p_j * experts[b, sel_j, :] summed in j order in fp32; backward
+ *   d_logit_j = p_j * (<d_out, expert_sel_j> - sum_k p_k <d_out, expert_sel_k>),
+ *   d_experts[b, e, :] = mask( sum over (gate g, slot j) with sel_g[j] == e, in (g, j) order, of p_gj * d_out_g[b, :] )
+ * with the relu / mask_scale / accumulate semantics of cdc_gate_pool_bwd.  No atomics: the order of every sum is fixed, so two
+ * runs are bit-identical.  One wave per batch row.
+ *
+ * The selection lists do not travel in the kernel arguments: cdc_gate_pool_wide_table packs them (and the inverse lists the
+ * backward gathers d_experts with) into an int32 table on the host, checking every index; the caller copies it to the device
+ * once and passes that copy as `table`.  table == NULL / cap == 0: returns the length the table needs.  Returns the number of
+ * int32 written, or CDC_E_BADARG for n_gates outside [1, CDC_WIDE_MAX_GATES], n_expert outside [1, CDC_WIDE_MAX_EXPERT],
+ * an n_sel outside [1, CDC_WIDE_MAX_SEL], a selection outside [0, n_expert) or a table shorter than needed.
+ * Layout: [0, n_gates]: offsets of each gate's selections; [n_gates+1, n_gates+n_expert+1]: offsets of each expert's
+ * (gate, slot) entries; then the selections, then the entries (gate << 16 | slot).
+ * ---------------------------------------------------------------------------------------- */
+#define CDC_WIDE_MAX_SEL    256
+#define CDC_WIDE_MAX_GATES  32
+#define CDC_WIDE_MAX_EXPERT 1024
+int cdc_gate_pool_wide_table(int32_t n_gates, int32_t n_expert, const int32_t* n_sel, const int32_t* sel, int32_t* table, int64_t cap);
+
+typedef struct {
+    int32_t n_gates, n_expert, H;
+    int64_t B;
+    const float* experts; int64_t ld_exp;
+    const int32_t* table;                         /* device copy of cdc_gate_pool_wide_table's output for these gates */
+    struct {
+        const float* logits; int64_t ld_logits;   /* [B, n_sel] */
+        float* out; int64_t ld_out;               /* [B, H] */
+        float* probs;                             /* [B, n_sel] contiguous (saved for backward), or NULL */
+        void* out_h; int64_t ld_out_h;            /* optional bf16 shadow of out, or NULL */
+        int32_t n_sel, pad_;
+    } gate[CDC_WIDE_MAX_GATES];
+} cdc_pool_wide_fwd_args;
+int cdc_gate_pool_wide_fwd(const cdc_pool_wide_fwd_args* a, void* stream);
+
+typedef struct {
+    int32_t n_gates, n_expert, H;
+    int64_t B;
+    const float* experts; int64_t ld_exp;         /* forward expert outputs (post-activation) */
+    float* d_experts; int64_t ld_dexp;            /* [B, n_expert, H]: every expert column written */
+    int32_t mask_relu;                            /* 1: d_experts = (experts > 0) ? d * mask_scale : 0 */
+    float mask_scale;
+    int32_t accumulate;                           /* 1: d_experts += (a second launch for more than CDC_WIDE_MAX_GATES gates) */
+    void* d_experts_h; int64_t ld_dexp_h;         /* optional bf16 shadow of d_experts (the value after the +=), or NULL */
+    const int32_t* table;                         /* as in cdc_pool_wide_fwd_args */
+    struct {
+        const float* d_out; int64_t ld_dout;      /* [B, H] */
+        const float* probs;                       /* [B, n_sel] */
+        float* d_logits; int64_t ld_dlogits;      /* [B, n_sel] */
+        void* d_logits_h; int64_t ld_dlogits_h;   /* optional bf16 shadow of d_logits, or NULL */
+        int32_t n_sel, pad_;
+    } gate[CDC_WIDE_MAX_GATES];
+} cdc_pool_wide_bwd_args;
+int cdc_gate_pool_wide_bwd(const cdc_pool_wide_bwd_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The boundary between two extraction levels of PLE as ONE launch per direction (reference: model/ple.py:96-125 called twice
  * from model/ple.py:54-57): level k's gate softmax + pooling, level k+1's single-layer experts and its gates (nn.Linear
  * (+ReLU +dropout): model/layer.py:185-191; gates model/ple.py:89-94), and level k+1's gate softmax + pooling.  A workgroup
