@@ -96,7 +96,8 @@ extern "C" int cdc_embed_index(const int32_t* ids, const int32_t* offsets, int32
 }
 
 // ------------------------------------------------------------------------------------------------
-// per-field sort + dedupe: one workgroup per field, bitonic sort of (row<<32 | b) in LDS
+// per-field sort + dedupe: one workgroup per field in LDS — bitonic sort of (row<<32 | b) up to 1024 rows, radix sort of the
+// rows up to SORT_RADIX_MAX; above that, chunks sorted by separate workgroups and merged by rank
 // ------------------------------------------------------------------------------------------------
 #define SORT_THREADS 1024
 #define SORT_CHUNK CDC_SORT_MAX_B        /* keys one workgroup sorts in LDS (16384 x 8 B = 128 KB) */
@@ -209,7 +210,7 @@ __device__ __forceinline__ void sort_begin_step(const SortSrc& s, int tid) {
     }
 }
 
-// B <= SORT_CHUNK: sort + dedupe in one workgroup per field
+// B <= 1024 (and SORT_RADIX_MAX < B <= SORT_CHUNK when no scratch buffer is given): sort + dedupe in one workgroup per field
 __global__ void __launch_bounds__(SORT_THREADS) k_sort_dedupe(const SortSrc src, int32_t* __restrict__ uniq_row,
                                                               int32_t* __restrict__ seg_start, int32_t* __restrict__ perm,
                                                               int32_t* __restrict__ uniq_cnt, int32_t B, int32_t F,
@@ -230,7 +231,163 @@ __global__ void __launch_bounds__(SORT_THREADS) k_sort_dedupe(const SortSrc src,
     dedupe_sorted(keys, B, scan, uniq_row + (int64_t)f * B, seg_start + (int64_t)f * (B + 1), perm + (int64_t)f * B, uniq_cnt + f, tid);
 }
 
-// Chunked path (a scratch buffer is given and B > 1024): one workgroup's LDS moves 16 bytes per key and stage, and a
+// 1024 < B <= SORT_RADIX_MAX: the same result from one workgroup per field with a stable least-significant-digit radix sort
+// of the 32-bit rows (8 bits a pass, the batch position rides along as the value).  Rows enter in batch order, so ties end in
+// ascending batch position — the order of the 64-bit (row, position) keys above.  A pass costs a few LDS round trips per key
+// where the bitonic network costs 78, and passes whose 8 bits are equal over the field's rows are skipped (a field of 2^20 ids
+// pays three).  Nothing leaves the workgroup before the results: no scratch buffer, no flag, no other workgroup is waited for.
+//   wave w owns the keys [w * per_wave, (w + 1) * per_wave) of the current order, 64 at a time (`rounds` rounds);
+//   rank:    peers = the lanes of the round with the same digit (8 ballots); the lowest of them adds their number to the wave's
+//            own counter hist[w][digit] and hands the old value on: a key's rank among the wave's keys of its digit;
+//   scan:    exclusive prefix over hist in (digit, wave) order = where each wave's keys of each digit start;
+//   scatter: keys and positions (held in registers since the rank phase) go to their places in the same LDS arrays.
+// Padding keys (index >= B, row 0xffffffff) start behind the real keys and a stable pass never moves them in front of one:
+// they are left out of the bit reduction that decides which passes run, and of the dedupe.
+#define SORT_RADIX_MAX 4096
+#define SORT_RADIX_ITEMS (SORT_RADIX_MAX / SORT_THREADS)
+#define SORT_WAVES (SORT_THREADS / 64)
+__global__ void __launch_bounds__(SORT_THREADS) k_sort_dedupe_radix(const SortSrc src, int32_t* __restrict__ uniq_row,
+                                                                    int32_t* __restrict__ seg_start, int32_t* __restrict__ perm,
+                                                                    int32_t* __restrict__ uniq_cnt, int32_t B, int32_t F) {
+    __shared__ uint32_t rows[SORT_RADIX_MAX];
+    __shared__ uint32_t pos[SORT_RADIX_MAX];
+    __shared__ int32_t hist[SORT_WAVES * 256];                           // [wave][digit]
+    __shared__ int32_t wave_tot[SORT_RADIX_ITEMS * SORT_WAVES];          // scan scratch; head counts per (round, wave) in the dedupe
+    __shared__ uint32_t red_or[SORT_WAVES], red_and[SORT_WAVES];
+    const int f = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (B > SORT_RADIX_MAX) return;                                      // the launcher never asks for it
+    const int rounds = (B + SORT_THREADS - 1) / SORT_THREADS;            // 2 .. SORT_RADIX_ITEMS, uniform
+
+    // load in batch order; OR / AND of the real rows
+    uint32_t any = 0u, all = ~0u;
+#pragma unroll
+    for (int r = 0; r < SORT_RADIX_ITEMS; ++r) {
+        const int i = r * SORT_THREADS + tid;
+        if (r < rounds) {
+            uint32_t k = ~0u;
+            if (i < B) {
+                k = sort_row(src, i, f, F);
+                any |= k;
+                all &= k;
+            }
+            rows[i] = k;
+            pos[i] = (uint32_t)i;
+        }
+    }
+    sort_begin_step(src, tid);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        any |= (uint32_t)__shfl_xor((int)any, off, 64);
+        all &= (uint32_t)__shfl_xor((int)all, off, 64);
+    }
+    if (lane == 0) { red_or[wave] = any; red_and[wave] = all; }
+    __syncthreads();
+    any = 0u; all = ~0u;
+#pragma unroll
+    for (int w = 0; w < SORT_WAVES; ++w) { any |= red_or[w]; all &= red_and[w]; }
+    const uint32_t differ = any ^ all;                                   // bits that are not the same in every real row (uniform)
+
+    const int per_wave = rounds * 64;
+    const uint64_t lanes_below = (1ull << lane) - 1ull;
+    for (int shift = 0; shift < 32; shift += 8) {
+        if (((differ >> shift) & 0xffu) == 0u) continue;                 // uniform: every thread skips the same passes
+        // the wave clears its own counters (nobody else touches them before the barrier below)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) hist[wave * 256 + j * 64 + lane] = 0;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        uint32_t k[SORT_RADIX_ITEMS], v[SORT_RADIX_ITEMS];
+        int rk[SORT_RADIX_ITEMS];
+#pragma unroll
+        for (int r = 0; r < SORT_RADIX_ITEMS; ++r) {
+            k[r] = 0u; v[r] = 0u; rk[r] = 0;
+            if (r < rounds) {
+                const int i = wave * per_wave + r * 64 + lane;
+                k[r] = rows[i];
+                v[r] = pos[i];
+                const uint32_t d = (k[r] >> shift) & 0xffu;
+                uint64_t peers = ~0ull;                                  // all 64 lanes hold a key (padding included)
+#pragma unroll
+                for (int b = 0; b < 8; ++b) {
+                    const bool bit = (d >> b) & 1u;
+                    const uint64_t m = __ballot(bit);
+                    peers &= bit ? m : ~m;
+                }
+                const int before = __popcll(peers & lanes_below);
+                int old = 0;
+                if (before == 0) old = atomicAdd(&hist[wave * 256 + (int)d], (int)__popcll(peers));
+                rk[r] = __shfl(old, __ffsll((unsigned long long)peers) - 1, 64) + before;
+            }
+        }
+        __syncthreads();
+        // thread t holds the entries 4t .. 4t+3 of the (digit, wave) order: digit t / 4, waves 4 * (t % 4) ..
+        {
+            const int d = tid >> 2, w0 = (tid & 3) * 4;
+            int h[4], sum = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { h[j] = hist[(w0 + j) * 256 + d]; sum += h[j]; }
+            int total;
+            int run = block_exclusive_scan(sum, wave_tot, tid, total);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { hist[(w0 + j) * 256 + d] = run; run += h[j]; }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < SORT_RADIX_ITEMS; ++r) {
+            if (r < rounds) {
+                const int dst = hist[wave * 256 + (int)((k[r] >> shift) & 0xffu)] + rk[r];
+                rows[dst] = k[r];
+                pos[dst] = v[r];
+            }
+        }
+        __syncthreads();
+    }
+
+    // dedupe: thread tid looks at the sorted keys r * SORT_THREADS + tid; heads are counted per (round, wave) by ballot
+    bool head[SORT_RADIX_ITEMS];
+    uint64_t hmask[SORT_RADIX_ITEMS];
+#pragma unroll
+    for (int r = 0; r < SORT_RADIX_ITEMS; ++r) {
+        const int i = r * SORT_THREADS + tid;
+        head[r] = (r < rounds) && (i < B) && (i == 0 || rows[i] != rows[i - 1]);
+        hmask[r] = __ballot(head[r]);
+        if (lane == 0) wave_tot[r * SORT_WAVES + wave] = (int)__popcll(hmask[r]);
+    }
+    __syncthreads();
+    int inc = wave_tot[lane];                                            // SORT_RADIX_ITEMS * SORT_WAVES == 64 entries, in key order
+    const int own = inc;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int t = __shfl_up(inc, off, 64);
+        if (lane >= off) inc += t;
+    }
+    const int total = __shfl(inc, 63, 64);
+    const int excl = inc - own;
+    int32_t* urow = uniq_row + (int64_t)f * B;
+    int32_t* sst = seg_start + (int64_t)f * (B + 1);
+    int32_t* prm = perm + (int64_t)f * B;
+#pragma unroll
+    for (int r = 0; r < SORT_RADIX_ITEMS; ++r) {
+        const int i = r * SORT_THREADS + tid;
+        const int base = __shfl(excl, r * SORT_WAVES + wave, 64);
+        if (r < rounds && i < B) {
+            if (head[r]) {
+                const int u = base + (int)__popcll(hmask[r] & lanes_below);
+                urow[u] = (int32_t)rows[i];
+                sst[u] = i;
+            }
+            prm[i] = (int32_t)pos[i];
+        }
+    }
+    if (tid == 0) {
+        sst[total] = B;
+        uniq_cnt[f] = total;
+    }
+}
+static_assert(SORT_RADIX_ITEMS * SORT_WAVES == 64, "the dedupe scans its (round, wave) head counts inside one wave");
+
+// Chunked path (a scratch buffer is given and B > SORT_RADIX_MAX): one workgroup's LDS moves 16 bytes per key and stage, and a
 // 4096-key sort has 78 stages — a single workgroup per field is bound by its CU's LDS bandwidth (45 us at B = 4096, 26 CUs
 // busy).  So (1) chunks of `chunk` rows are sorted by separate workgroups (fewer stages, more CUs) and written out,
 // (2) the sorted runs are merged by rank — a key's final position is the sum over the runs of the number of smaller keys;
@@ -352,6 +509,11 @@ static int sort_dedupe_launch(const SortSrc& src, int32_t* uniq_row, int32_t* se
         attr_set = true;
     }
     hipStream_t st = (hipStream_t)stream;
+    if (B > 1024 && B <= SORT_RADIX_MAX) {                  // `scratch` is not needed
+        hipLaunchKernelGGL(k_sort_dedupe_radix, dim3(F), dim3(SORT_THREADS), 0, st, src, uniq_row, seg_start, perm, uniq_cnt, (int32_t)B, F);
+        CDC_LAUNCH_CHECK("embed_sort_dedupe_radix");
+        return 0;
+    }
     if (B <= 1024 || (!scratch && B <= SORT_CHUNK)) {
         int n_pad = SORT_THREADS;   // at least one key per thread keeps the chunking simple
         while (n_pad < B) n_pad <<= 1;
