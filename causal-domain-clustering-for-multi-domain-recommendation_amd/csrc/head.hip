@@ -11,6 +11,7 @@
 // gradient (their sum), all input gradients and the per-part weight-gradient partial sums in the same pass.  Cross-row
 // reductions stay order-fixed: CDC_ROWDOT_PARTS row parts, LDS accumulators per wave, waves then parts added in index order.
 #include "common.h"
+#include <utility>
 
 #define HEAD_THREADS 256
 #define HEAD_WAVES (HEAD_THREADS / 64)
@@ -339,6 +340,19 @@ extern "C" int64_t cdc_head_workspace_floats(const cdc_head_args* a) {
     return (int64_t)CDC_ROWDOT_PARTS * head_width(a);
 }
 
+// Two input gradients of one launch that share memory: [M,K0] at p0 and [M,K1] at p1, both with leading dimension ld (column
+// slices of one buffer side by side are disjoint and allowed).  With different leading dimensions only the same start counts.
+static bool head_dx_overlap(const float* p0, int K0, int64_t ld0, const float* p1, int K1, int64_t ld1, int64_t M) {
+    if (!p0 || !p1 || M <= 0) return false;
+    if (p0 == p1) return true;
+    if (ld0 != ld1 || ld0 <= 0) return false;
+    if (p0 > p1) { std::swap(p0, p1); std::swap(K0, K1); }
+    const int64_t delta = (int64_t)(((uintptr_t)p1 - (uintptr_t)p0) / sizeof(float));
+    const int64_t q = delta / ld0, c = delta % ld0;                      // p1's row i starts in p0's row q + i at column c
+    if (q < M && c < K0) return true;
+    return q + 1 < M && c + K1 > ld0;                                    // ... and runs on into the next row's first columns
+}
+
 extern "C" int cdc_head_bwd(const cdc_head_args* a, void* stream) {
     CDC_CHECK_ARG(a && a->n_tower > 0 && a->n_tower <= CDC_HEAD_MAX_TOWERS && a->M >= 0 && a->out && a->workspace &&
                       a->n_addend >= 0 && a->n_addend <= 2, CDC_E_BADARG, "head_bwd: bad argument");
@@ -348,6 +362,15 @@ extern "C" int cdc_head_bwd(const cdc_head_args* a, void* stream) {
                   "head_bwd: the fused BCE needs sigmoid outputs, a loss pointer and the partial-sum buffer");
     for (int t = 0; t < a->n_tower; ++t)
         CDC_CHECK_ARG(a->t[t].x && a->t[t].w && a->t[t].K > 0, CDC_E_BADARG, "head_bwd: tower %d malformed", t);
+    // every load of a row is issued before its first store, so an input gradient that two towers (or a tower and the wide term)
+    // share would keep the last writer's term only: such a fan-in needs separate buffers and cdc_add_n
+    for (int t = 0; t < a->n_tower; ++t) {
+        for (int u = 0; u < t; ++u)
+            CDC_CHECK_ARG(!head_dx_overlap(a->t[u].dx, a->t[u].K, a->t[u].lddx, a->t[t].dx, a->t[t].K, a->t[t].lddx, a->M), CDC_E_BADARG,
+                          "head_bwd: towers %d and %d share an input gradient", u, t);
+        CDC_CHECK_ARG(!a->wide_x || !head_dx_overlap(a->wide_dx, a->wide_K, a->ld_wide_dx, a->t[t].dx, a->t[t].K, a->t[t].lddx, a->M),
+                      CDC_E_BADARG, "head_bwd: tower %d shares its input gradient with the wide term", t);
+    }
     const int width = head_width(a);
     CDC_CHECK_ARG((size_t)HEAD_BWD_WAVES * width * 4 <= 64 * 1024, CDC_E_TOOBIG, "head_bwd: too many weight-gradient columns for one pass");
     hipStream_t st = (hipStream_t)stream;

@@ -465,6 +465,11 @@ class BaseModel(HipModule):
         head_cols += 0 if wide_in is None else wide_in.cols + 1
         fused = (wide_in is not None and n <= P.L.HEAD_MAX_TOWERS and len(other_outs) <= 2 and head_cols <= 2048 and
                  all(t.out_linear is not None for t in self.towers))
+        # towers without hidden layers read the inputs they were given; the fused head cannot fan several towers' gradients into one
+        # input buffer (plan.TowerHead), the row-dot launches can
+        ins = (list(tower_inputs) if len(self.towers[0].hidden) == 0 else []) + ([wide_in] if wide_in is not None else [])
+        fused = fused and not any(p.root is q.root and p.col0 < q.col0 + q.cols and q.col0 < p.col0 + p.cols
+                                  for i, p in enumerate(ins) for q in ins[:i])
         if wide_in is not None and not fused:
             other_outs = [self.linear.describe(plan, wide_in)] + list(other_outs)
         if fused:

@@ -1795,6 +1795,13 @@ class TowerHead:
                 raise RuntimeError("the tower head cannot consume an activation-fused linear output")
         if wide is not None:
             assert wide["x"].cols == wide["w"].numel()
+        # the backward launch loads a row's gradients before it stores any (csrc/head.hip), so two of its inputs cannot share one
+        # gradient buffer: cdc_head_bwd rejects that; say so here, where the model is described
+        ins = [t["x"] for t in towers] + ([wide["x"]] if wide is not None else [])
+        for i, p in enumerate(ins):
+            for q in ins[:i]:
+                if p.root is q.root and p.col0 < q.col0 + q.cols and q.col0 < p.col0 + p.cols:
+                    raise RuntimeError("the tower head cannot take one input buffer twice (its gradients would need a fan-in add)")
         width = sum(t["w"].numel() + 1 for t in towers) + (wide["w"].numel() + 1 if wide is not None else 0)
         self.ws = torch.empty(L.ROWDOT_PARTS * width, dtype=torch.float32, device=plan.device)
         self._keep = []

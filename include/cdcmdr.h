@@ -775,6 +775,8 @@ int cdc_rowdot_bwd(const cdc_rowdot_bwd_args* a, void* stream);
  * backward: d_t = d_out[b,t] (or the fused BCE gradient) * out (1 - out);  dx_t = d_t w_t;  dw_t = sum_b d_t x_t;  db_t = sum_b d_t;
  *   dsum = sum_t d_t  ->  d_addend_i (+)= dsum;  wide_dx (+)= dsum wide_w;  wide_dw = sum_b dsum wide_x;  wide_dbias = sum_b dsum.
  * Cross-row sums: CDC_ROWDOT_PARTS row parts in `workspace` (cdc_head_workspace_floats), added in index order (deterministic).
+ * No two of the input gradients of one launch (the towers' dx, wide_dx) may share memory, accumulating or not: a row's gradients
+ * are loaded before any is stored (CDC_E_BADARG).  Column slices of one buffer side by side are separate gradients.
  * ---------------------------------------------------------------------------------------- */
 #define CDC_HEAD_MAX_TOWERS 8
 typedef struct {

@@ -121,3 +121,94 @@ def compare_param_grads(named_params, want, rtol, atol, bf16=False, all_names=No
         med, p90 = float(np.median(rels)), float(np.quantile(rels, 0.9))
         assert med < (median_rel or BF16_GRAD_MEDIAN), f"median relative L2 error of the gradient tensors {med:.3e}"
         assert p90 < (p90_rel or BF16_GRAD_P90), f"90th percentile of the gradient tensors' relative L2 errors {p90:.3e}"
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Direct kernel tests against float64 (tests/test_gpu_head.py, tests/test_gpu_rowkernels.py): padded buffers and DERIVED bounds
+# ----------------------------------------------------------------------------------------------------------------------
+U24 = 2.0 ** -24                      # unit roundoff of fp32
+PAD = 3                               # extra columns of every matrix: rows are not 16-byte aligned
+OUT_SENTINEL = -777.25                # output padding: finite, must come back bit-unchanged (input padding is NaN)
+OUT_FIG = (1e-5, 1e-6)                # the suite's present (rtol, atol) for a kernel's outputs ...
+SUM_FIG = (1e-4, 1e-5)                # ... and for cross-row sums (test_gpu_ops.py)
+
+
+class PadBuf:
+    """A [rows, cols] fp32 matrix inside a [rows, cols + PAD] allocation.  fill = NaN for an input (a kernel that reads past `cols`
+    poisons its result), OUT_SENTINEL for an output; read() checks that the padding came back bit-unchanged."""
+
+    def __init__(self, dev, values, out=False, pad=PAD):
+        values = np.asarray(values, dtype=np.float32)
+        if values.ndim == 1:
+            values = values.reshape(1, -1)
+        self.rows, self.cols = values.shape
+        self.ld = self.cols + pad
+        host = np.full((self.rows, self.ld), OUT_SENTINEL if out else np.nan, dtype=np.float32)
+        host[:, :self.cols] = values
+        self.host0 = host
+        self.t = torch.from_numpy(host.copy()).to(dev)
+
+    @property
+    def ptr(self):
+        return self.t.data_ptr()
+
+    def read(self, what="buffer"):
+        h = self.t.cpu().numpy()
+        assert np.array_equal(h[:, self.cols:].view(np.int32), self.host0[:, self.cols:].view(np.int32)), f"{what}: padding written"
+        return h[:, :self.cols].copy()
+
+
+def nan_like(rows, cols):
+    return np.full((rows, cols), np.nan, dtype=np.float32)
+
+
+def ulp32(v):
+    """Spacing of fp32 at |v| (float64 array)."""
+    return np.spacing(np.abs(np.asarray(v, dtype=np.float64)).astype(np.float32)).astype(np.float64)
+
+
+def host_ulps(f32_result, f64_result):
+    """Worst distance of an fp32 evaluation from float64, in ulps of the result (at least 0.5: correctly rounded)."""
+    a, b = np.asarray(f32_result, dtype=np.float64), np.asarray(f64_result, dtype=np.float64)
+    ok = np.isfinite(a) & np.isfinite(b)
+    return max(0.5, float(np.max(np.abs(a - b)[ok] / ulp32(b)[ok]))) if ok.any() else 0.5
+
+
+def sum_bound(sum_abs_terms, n, c):
+    """Allowed error of a sum of n fp32 terms with c further roundings: (n + c) 2^-24 sum |term_i| (terms from float64)."""
+    return (n + c) * U24 * np.asarray(sum_abs_terms, dtype=np.float64)
+
+
+def capped(bound, want, fig):
+    """The derived bound, and never looser than the suite's present figure for this kind of quantity: the tighter of the two at
+    every element.  (The worst-case bound over n terms alone exceeds the figure for long dot products and cancelling sums.)"""
+    rtol, atol = fig
+    return np.minimum(np.asarray(bound, dtype=np.float64), atol + rtol * np.abs(np.asarray(want, dtype=np.float64)))
+
+
+def assert_bounded(got, want, bound, what=""):
+    """|got - want| <= bound element by element (NaN fails); records the used fraction like assert_close."""
+    a = np.asarray(got, dtype=np.float64)
+    b = np.asarray(want, dtype=np.float64)
+    bound = np.broadcast_to(np.asarray(bound, dtype=np.float64), b.shape)
+    assert a.shape == b.shape, f"{what}: shape {a.shape} vs {b.shape}"
+    if not a.size:
+        return
+    err = np.abs(a - b)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        frac = np.where(err == 0, 0.0, err / bound)
+    rec = os.environ.get("CDC_RECORD_MARGINS")
+    if rec:
+        with open(rec, "a") as f:
+            f.write(f"{os.environ.get('PYTEST_CURRENT_TEST', '?').split(' ')[0]}\t{what}\t{float(np.nanmax(err)):.3e}\t"
+                    f"{float(np.nanmax(frac)):.3e}\tderived\t{float(bound.max()):.3e}\n")
+    bad = ~(err <= bound)
+    if bad.any():
+        i = int(np.argmax(np.where(np.isnan(frac), np.inf, frac)))
+        raise AssertionError(f"{what}: {int(bad.sum())}/{a.size} off; worst |d|={err.flat[i]:.3e} allowed {bound.flat[i]:.3e} "
+                             f"got {a.flat[i]:.9e} want {b.flat[i]:.9e}")
+
+
+def assert_bits_equal(a, b, what=""):
+    a, b = np.ascontiguousarray(a, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
+    assert a.shape == b.shape and np.array_equal(a.view(np.int32), b.view(np.int32)), f"{what}: bits differ"
