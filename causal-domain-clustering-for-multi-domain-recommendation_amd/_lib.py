@@ -366,6 +366,8 @@ _SIGNATURES = {
     "cdc_embed_merge_dedupe": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_i32, c_p]),
     "cdc_eval_workspace_bytes": (c_i64, [c_i64, c_i32]),
     "cdc_eval_metrics": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i32, c_p, c_p, c_p, c_p, c_i64, c_p]),
+    "cdc_eval_gauc_workspace_bytes": (c_i64, [c_i64, c_i32, c_i64]),
+    "cdc_eval_gauc": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_i32, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p]),
     "cdc_shard_bucket": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_p]),
     "cdc_shard_expand": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_p]),
     "cdc_shard_pack": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_p]),

@@ -211,3 +211,268 @@ extern "C" int cdc_eval_metrics(const float* pred, const int16_t* label, const i
     CDC_LAUNCH_CHECK("eval_metrics(final)");
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// GAUC (base.py:33-64, gauc_score): the AUC of every user's rows, averaged over the users that have both classes with a
+// weight (the user's row count, or a caller-supplied value per user).  Per domain the groups are (domain, user) pairs, for
+// the pseudo-domain "all rows" they are users — millions of sparse ids, so nothing here is indexed by a group id:
+//
+//   keys    every row twice, key = (d * n_user + u) << 32 | score_key; ONE radix sort over the bits a key can have lays every
+//           group out as a contiguous, score-ordered run, the groups of one (pseudo-)domain next to each other
+//   scan 1  (rocPRIM, one pass, elements formed on the fly from the sorted keys): for every sorted position i the first
+//           position of its group h(i), the first position of its tie run f(i) (running maxima of the positions where the
+//           group / the whole key changes) and cn(i) = negatives at positions <= i
+//   scan 2  (rocPRIM) W = running sum of every row's share of 2U, an integer formed from scan 1 alone: a positive adds twice the
+//           negatives of its group below its tie run plus the negatives of the run in front of it, a negative adds the positives
+//           of its tie run in front of it — every (positive, negative) pair counts 2 when ordered, 1 when tied (by whichever
+//           of the two stands later in the run), so the total per group does not depend on the order of tied rows
+//   sum     a group's (2U, N, rows) are differences of W and cn between its last row and the row before its first: no
+//           atomics, no per-group array.  Every (pseudo-)domain's stretch of the sorted array is cut into GAUC_SLICES equal
+//           slices; one workgroup per slice adds w * U/(P*N) and w of the groups ENDING in its slice (strided per thread, then
+//           a tree), a last launch adds the slices' partial sums in a tree.  The order of every addition is a function of the
+//           sorted keys alone, and those do not depend on the order of the rows: same rows, same bits.
+// All launches have host-known dimensions; nothing is allocated, synchronised or read back.
+#define GAUC_THREADS 256
+#define GAUC_SLICES 64
+
+struct GaucScan { uint32_t h, f, cn; };
+struct GaucScanOp {
+    __host__ __device__ GaucScan operator()(const GaucScan& a, const GaucScan& b) const {
+        GaucScan r;
+        r.h = a.h > b.h ? a.h : b.h;
+        r.f = a.f > b.f ? a.f : b.f;
+        r.cn = a.cn + b.cn;
+        return r;
+    }
+};
+struct GaucScanIn {                     // element i of scan 1
+    const uint64_t* keys;
+    const uint8_t* vals;
+    __host__ __device__ GaucScan operator()(uint32_t i) const {
+        GaucScan r;
+        const uint64_t k = keys[i], kp = i ? keys[i - 1] : 0ull;
+        r.h = (i && (k >> 32) != (kp >> 32)) ? i : 0u;
+        r.f = (i && k != kp) ? i : 0u;
+        r.cn = vals[i] ? 0u : 1u;
+        return r;
+    }
+};
+struct GaucShareIn {                    // element i of scan 2: row i's share of its group's 2U
+    const GaucScan* sc;
+    const uint8_t* vals;
+    __host__ __device__ unsigned long long operator()(uint32_t i) const {
+        const GaucScan s = sc[i];
+        const uint32_t cn_f = s.f ? sc[s.f - 1].cn : 0u;
+        if (vals[i]) {
+            const uint32_t cn_h = s.h ? sc[s.h - 1].cn : 0u;
+            return 2ull * (cn_f - cn_h) + (s.cn - cn_f);
+        }
+        return (unsigned long long)(i - s.f) - (s.cn - 1u - cn_f);
+    }
+};
+typedef rocprim::transform_iterator<rocprim::counting_iterator<uint32_t>, GaucScanIn, GaucScan> GaucScanIt;
+typedef rocprim::transform_iterator<rocprim::counting_iterator<uint32_t>, GaucShareIn, unsigned long long> GaucShareIt;
+
+__global__ void __launch_bounds__(MET_THREADS) k_gauc_keys(const float* __restrict__ pred, const int16_t* __restrict__ label,
+                                                           const int32_t* __restrict__ user, int64_t ld_user, int64_t n_user,
+                                                           const int32_t* __restrict__ domain, int64_t ld_domain, int32_t n_domain,
+                                                           int64_t n, uint64_t* __restrict__ keys, uint8_t* __restrict__ vals,
+                                                           int32_t* __restrict__ err) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float p = pred[i];
+        int32_t d = domain ? domain[i * ld_domain] : 0;
+        int64_t u = user[i * ld_user];
+        const int16_t y = label[i];
+        if (p != p || d < 0 || d >= n_domain || u < 0 || u >= n_user || (y != 0 && y != 1)) {
+            if (err) atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
+            d = d < 0 ? 0 : (d >= n_domain ? n_domain - 1 : d);           // the ids are clamped whether or not the flag is wanted:
+            u = u < 0 ? 0 : (u >= n_user ? n_user - 1 : u);               // u indexes user_weight
+        }
+        const uint32_t sk = score_key(p);
+        keys[i] = (((uint64_t)d * (uint64_t)n_user + (uint64_t)u) << 32) | sk;
+        keys[n + i] = (((uint64_t)n_domain * (uint64_t)n_user + (uint64_t)u) << 32) | sk;
+        vals[i] = vals[n + i] = (uint8_t)(y != 0);
+    }
+}
+
+// start[d] = first sorted position of (pseudo-)domain d's groups, d in [0, n_seg]; start[n_seg] = 2n
+__global__ void k_gauc_starts(const uint64_t* __restrict__ keys, int64_t n2, int32_t n_seg, int64_t n_user, int64_t* __restrict__ start) {
+    const int d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d <= n_seg) start[d] = d == n_seg ? n2 : lower_bound_u64(keys, 0, n2, ((uint64_t)d * (uint64_t)n_user) << 32);
+}
+
+// workgroup (d, slice): the groups of (pseudo-)domain d whose LAST row lies in the slice
+__global__ void __launch_bounds__(GAUC_THREADS) k_gauc_sum(const uint64_t* __restrict__ keys, const GaucScan* __restrict__ sc,
+                                                           const unsigned long long* __restrict__ W, const int64_t* __restrict__ start,
+                                                           const double* __restrict__ user_weight, int64_t n_user, int64_t n2,
+                                                           double* __restrict__ part, int64_t* __restrict__ part_cnt) {
+    __shared__ double s_num[GAUC_THREADS], s_den[GAUC_THREADS];
+    __shared__ int64_t s_in[GAUC_THREADS], s_out[GAUC_THREADS];
+    const int d = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
+    const int64_t s0 = start[d], s1 = start[d + 1];
+    const int64_t per = (s1 - s0 + GAUC_SLICES - 1) / GAUC_SLICES;
+    const int64_t a = s0 + (int64_t)sl * per, b = a + per < s1 ? a + per : s1;
+    const uint64_t base = (uint64_t)d * (uint64_t)n_user;
+    double num = 0.0, den = 0.0;
+    int64_t n_in = 0, n_out = 0;
+    for (int64_t i = a + tid; i < b; i += GAUC_THREADS) {
+        const uint64_t g = keys[i] >> 32;
+        if (i + 1 < n2 && (keys[i + 1] >> 32) == g) continue;              // not the last row of its group
+        const GaucScan e = sc[i];
+        const int64_t h = e.h;
+        const int64_t rows = i - h + 1;
+        const int64_t N = (int64_t)(e.cn - (h ? sc[h - 1].cn : 0u)), P = rows - N;
+        if (P == 0 || N == 0) { ++n_out; continue; }
+        const unsigned long long u2 = W[i] - (h ? W[h - 1] : 0ull);         // twice the Mann-Whitney U of the group
+        const double auc = (double)u2 / (2.0 * (double)P * (double)N);      // exact integers below 2^53: one rounding
+        const double w = user_weight ? user_weight[g - base] : (double)rows;
+        num += w * auc;
+        den += w;
+        ++n_in;
+    }
+    s_num[tid] = num; s_den[tid] = den; s_in[tid] = n_in; s_out[tid] = n_out;
+    __syncthreads();
+    for (int off = GAUC_THREADS / 2; off > 0; off >>= 1) {
+        if (tid < off) {
+            s_num[tid] += s_num[tid + off]; s_den[tid] += s_den[tid + off];
+            s_in[tid] += s_in[tid + off];   s_out[tid] += s_out[tid + off];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const int64_t o = ((int64_t)d * GAUC_SLICES + sl) * 2;
+        part[o] = s_num[0];     part[o + 1] = s_den[0];
+        part_cnt[o] = s_in[0];  part_cnt[o + 1] = s_out[0];
+    }
+}
+
+__global__ void __launch_bounds__(GAUC_SLICES) k_gauc_final(const double* __restrict__ part, const int64_t* __restrict__ part_cnt,
+                                                            int32_t n_seg, double* __restrict__ out, int64_t* __restrict__ counts) {
+    __shared__ double s_num[GAUC_SLICES], s_den[GAUC_SLICES];
+    __shared__ int64_t s_in[GAUC_SLICES], s_out[GAUC_SLICES];
+    const int d = blockIdx.x, tid = threadIdx.x;
+    const int64_t o = ((int64_t)d * GAUC_SLICES + tid) * 2;
+    s_num[tid] = part[o];    s_den[tid] = part[o + 1];
+    s_in[tid] = part_cnt[o]; s_out[tid] = part_cnt[o + 1];
+    __syncthreads();
+    for (int off = GAUC_SLICES / 2; off > 0; off >>= 1) {
+        if (tid < off) {
+            s_num[tid] += s_num[tid + off]; s_den[tid] += s_den[tid + off];
+            s_in[tid] += s_in[tid + off];   s_out[tid] += s_out[tid + off];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        out[d] = s_in[0] > 0 ? s_num[0] / s_den[0] : __longlong_as_double(0x7ff8000000000000ll);   // no countable group: NaN
+        counts[d] = s_in[0];
+        counts[n_seg + d] = s_out[0];
+    }
+}
+
+struct GaucLayout {
+    int64_t keys_in, keys_out, vals_in, vals_out, scan, start, part, part_cnt, temp, temp_bytes, total;
+};
+// everything but rocPRIM's temporary storage: plain arithmetic (argument checks use it before any HIP or rocPRIM call)
+static void gauc_fixed_layout(int64_t n, int32_t n_domain, GaucLayout* L) {
+    const int64_t n2 = 2 * n, seg = (int64_t)n_domain + 1;
+    int64_t off = 0;
+    L->keys_in = off;  off += align_up(n2 * 8);               // after the sort: W, the running sum of scan 2
+    L->keys_out = off; off += align_up(n2 * 8);
+    L->vals_in = off;  off += align_up(n2);
+    L->vals_out = off; off += align_up(n2);
+    L->scan = off;     off += align_up(n2 * (int64_t)sizeof(GaucScan));
+    L->start = off;    off += align_up((seg + 1) * 8);
+    L->part = off;     off += align_up(seg * GAUC_SLICES * 2 * 8);
+    L->part_cnt = off; off += align_up(seg * GAUC_SLICES * 2 * 8);
+    L->temp = off;
+    L->temp_bytes = 0;
+    L->total = off;
+}
+static int gauc_layout(int64_t n, int32_t n_domain, GaucLayout* L) {
+    gauc_fixed_layout(n, n_domain, L);
+    const size_t n2 = (size_t)(2 * n);
+    size_t t_sort = 0, t_scan = 0, t_share = 0;
+    hipError_t e = rocprim::radix_sort_pairs(nullptr, t_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint8_t*)nullptr,
+                                             (uint8_t*)nullptr, n2, 0, 64, (hipStream_t)0, false);
+    if (e == hipSuccess)
+        e = rocprim::inclusive_scan(nullptr, t_scan, GaucScanIt(rocprim::counting_iterator<uint32_t>(0), GaucScanIn{nullptr, nullptr}),
+                                    (GaucScan*)nullptr, n2, GaucScanOp(), (hipStream_t)0, false);
+    if (e == hipSuccess)
+        e = rocprim::inclusive_scan(nullptr, t_share, GaucShareIt(rocprim::counting_iterator<uint32_t>(0), GaucShareIn{nullptr, nullptr}),
+                                    (unsigned long long*)nullptr, n2, rocprim::plus<unsigned long long>(), (hipStream_t)0, false);
+    if (e != hipSuccess) { cdc_set_error("eval_gauc: rocprim size query failed: %s", hipGetErrorString(e)); return (int)e; }
+    L->temp_bytes = (int64_t)std::max(t_sort, std::max(t_scan, t_share));     // the three run one after the other
+    L->total = L->temp + align_up(L->temp_bytes);
+    return 0;
+}
+// (n_domain + 1) * n_user group ids must fit the upper half of a key
+static bool gauc_sizes_ok(int64_t n, int32_t n_domain, int64_t n_user) {
+    return n > 0 && n < (1ll << 31) && n_domain > 0 && n_domain < (1 << 20) && n_user > 0 && n_user <= (1ll << 32) &&
+           ((int64_t)n_domain + 1) * n_user <= (1ll << 32);
+}
+
+extern "C" int64_t cdc_eval_gauc_workspace_bytes(int64_t n, int32_t n_domain, int64_t n_user) {
+    if (!gauc_sizes_ok(n, n_domain, n_user)) return 0;
+    GaucLayout L;
+    if (gauc_layout(n, n_domain, &L) != 0) return -1;
+    return L.total;
+}
+
+extern "C" int cdc_eval_gauc(const float* pred, const int16_t* label, const int32_t* user, int64_t ld_user, int64_t n_user,
+                             const int32_t* domain, int64_t ld_domain, int32_t n_domain, const double* user_weight, int64_t n,
+                             double* out, int64_t* counts, int32_t* err_flag, void* workspace, int64_t workspace_bytes, void* stream) {
+    CDC_CHECK_ARG(pred && label && user && out && counts && workspace, CDC_E_BADARG, "eval_gauc: null pointer");
+    CDC_CHECK_ARG(n > 0 && n < (1ll << 31) && n_domain > 0 && n_domain < (1 << 20) && n_user > 0 && ld_user >= 0 && ld_domain >= 0,
+                  CDC_E_BADARG, "eval_gauc: bad sizes n=%ld n_domain=%d n_user=%ld", (long)n, n_domain, (long)n_user);
+    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_gauc: n_domain=%d needs the domain column", n_domain);
+    CDC_CHECK_ARG(gauc_sizes_ok(n, n_domain, n_user), CDC_E_BADARG,
+                  "eval_gauc: (n_domain + 1) * n_user = %ld * %ld group ids exceed 2^32", (long)n_domain + 1, (long)n_user);
+    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_gauc: workspace must be 256-byte aligned");
+    GaucLayout L;
+    gauc_fixed_layout(n, n_domain, &L);
+    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_gauc: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
+    int rc = gauc_layout(n, n_domain, &L);
+    if (rc != 0) return rc;
+    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_gauc: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
+    char* base = (char*)workspace;
+    uint64_t* keys_in = (uint64_t*)(base + L.keys_in);
+    uint64_t* keys_out = (uint64_t*)(base + L.keys_out);
+    uint8_t* vals_in = (uint8_t*)(base + L.vals_in);
+    uint8_t* vals_out = (uint8_t*)(base + L.vals_out);
+    GaucScan* sc = (GaucScan*)(base + L.scan);
+    unsigned long long* W = (unsigned long long*)keys_in;          // the unsorted keys are dead once the sort has run
+    int64_t* start = (int64_t*)(base + L.start);
+    double* part = (double*)(base + L.part);
+    int64_t* part_cnt = (int64_t*)(base + L.part_cnt);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n2 = 2 * n;
+    const int seg = n_domain + 1;
+    const int blocks = (int)std::min<int64_t>(cdc_ceil_div(n, MET_THREADS), 4096);
+    hipLaunchKernelGGL(k_gauc_keys, dim3(blocks), dim3(MET_THREADS), 0, st, pred, label, user, ld_user, n_user, domain, ld_domain,
+                       n_domain, n, keys_in, vals_in, err_flag);
+    CDC_LAUNCH_CHECK("eval_gauc(keys)");
+    // the sort only has to look at the bits a key can have: 32 score bits + the bits of the largest group id
+    const uint64_t g_max = (uint64_t)seg * (uint64_t)n_user - 1;
+    int end_bit = 33;
+    while (end_bit < 64 && (g_max >> (end_bit - 32)) != 0) ++end_bit;
+    size_t temp_bytes = (size_t)L.temp_bytes;
+    hipError_t e = rocprim::radix_sort_pairs(base + L.temp, temp_bytes, (const uint64_t*)keys_in, keys_out, (const uint8_t*)vals_in,
+                                             vals_out, (size_t)n2, 0, end_bit, st, false);
+    if (e != hipSuccess) { cdc_set_error("eval_gauc: radix sort failed: %s", hipGetErrorString(e)); return (int)e; }
+    temp_bytes = (size_t)L.temp_bytes;
+    e = rocprim::inclusive_scan(base + L.temp, temp_bytes, GaucScanIt(rocprim::counting_iterator<uint32_t>(0), GaucScanIn{keys_out, vals_out}),
+                                sc, (size_t)n2, GaucScanOp(), st, false);
+    if (e != hipSuccess) { cdc_set_error("eval_gauc: group scan failed: %s", hipGetErrorString(e)); return (int)e; }
+    temp_bytes = (size_t)L.temp_bytes;
+    e = rocprim::inclusive_scan(base + L.temp, temp_bytes, GaucShareIt(rocprim::counting_iterator<uint32_t>(0), GaucShareIn{sc, vals_out}),
+                                W, (size_t)n2, rocprim::plus<unsigned long long>(), st, false);
+    if (e != hipSuccess) { cdc_set_error("eval_gauc: rank scan failed: %s", hipGetErrorString(e)); return (int)e; }
+    hipLaunchKernelGGL(k_gauc_starts, dim3((int)cdc_ceil_div(seg + 1, 64)), dim3(64), 0, st, keys_out, n2, seg, n_user, start);
+    CDC_LAUNCH_CHECK("eval_gauc(starts)");
+    hipLaunchKernelGGL(k_gauc_sum, dim3(seg, GAUC_SLICES), dim3(GAUC_THREADS), 0, st, keys_out, sc, W, start, user_weight, n_user, n2,
+                       part, part_cnt);
+    CDC_LAUNCH_CHECK("eval_gauc(sum)");
+    hipLaunchKernelGGL(k_gauc_final, dim3(seg), dim3(GAUC_SLICES), 0, st, part, part_cnt, seg, out, counts);
+    CDC_LAUNCH_CHECK("eval_gauc(final)");
+    return 0;
+}

@@ -6,6 +6,10 @@ the host (`.cpu().numpy()`, one synchronisation per batch) and calls sklearn's r
 and per domain (pandas groupby).  Here the forward runs on the HIP plans (eval mode: BatchNorm on running statistics, no
 dropout), predictions stay in HBM and ONE C-ABI call (`cdc_eval_metrics`) returns every figure; the only host
 synchronisation is reading the result.
+
+With a user column configured the same pass also yields GAUC — the reference's `gauc_score` (base.py:33-64): the AUC of every
+user's rows, averaged over the users that have both classes, weighted by their row count or a given weight — from one more
+C-ABI call (`cdc_eval_gauc`) on the same device-resident predictions.
 """
 import ctypes as C
 import math
@@ -53,6 +57,63 @@ def eval_metrics(pred, label, domain=None, n_domain=1):
     return out[:seg], out[seg:], counts[:seg], counts[seg:]
 
 
+def _id_column(col, n, what):
+    """int32 [n] or a strided column view (X[:, idx]) -> (tensor, element stride)"""
+    if col.dtype != torch.int32:
+        col = col.to(torch.int32)
+    col = col.reshape(-1) if col.dim() > 1 and col.is_contiguous() else col
+    if col.dim() != 1 or col.numel() != n:
+        raise ValueError(f"{what} must hold one entry per prediction")
+    return col, col.stride(0)
+
+
+def eval_gauc(pred, label, user, n_user, domain=None, n_domain=1, user_weight=None):
+    """GAUC (base.py:33-64, gauc_score) per domain and over all rows.  pred f32 [n], label int16 [n] (0/1); user and domain int32
+    [n] or strided column views (X[:, user_idx], X[:, domain_idx]) with ids in [0, n_user) / [0, n_domain); user_weight: f64
+    [n_user] (positive), or None for gauc_score's default, the user's row count.
+    Returns (gauc f64, counted i64, left_out i64): device tensors with n_domain + 1 entries each — domains 0..n_domain-1 (their rows
+    grouped by user), then ALL rows grouped by user across domains; counted / left_out are the users with both classes / with a
+    single class.  NaN where no user is counted (the reference divides by zero there).  No host synchronisation."""
+    lib = L.load()
+    n_user, n_domain = int(n_user), int(n_domain)
+    if n_user <= 0 or n_domain <= 0:
+        raise ValueError(f"n_user={n_user} and n_domain={n_domain} must be positive")
+    if (n_domain + 1) * n_user > 1 << 32:
+        raise ValueError(f"(n_domain + 1) * n_user = {(n_domain + 1) * n_user} group ids exceed 2^32, the upper half of a sort key")
+    if not pred.is_cuda:
+        raise L.HipExtensionError("eval_gauc needs device tensors; there is no CPU fallback")
+    pred = pred.reshape(-1).to(torch.float32).contiguous()
+    label = label.reshape(-1).to(torch.int16).contiguous()
+    n = pred.numel()
+    if label.numel() != n:
+        raise ValueError(f"{n} predictions but {label.numel()} labels")
+    user, ld_user = _id_column(user, n, "user")
+    ld_domain = 0
+    if domain is not None:
+        domain, ld_domain = _id_column(domain, n, "domain")
+    elif n_domain != 1:
+        raise ValueError("n_domain > 1 needs the domain column")
+    dev = pred.device
+    if user_weight is not None:
+        user_weight = torch.as_tensor(user_weight, dtype=torch.float64).to(dev).reshape(-1).contiguous()
+        if user_weight.numel() != n_user:
+            raise ValueError(f"user_weight holds {user_weight.numel()} entries for {n_user} users")
+    seg = n_domain + 1
+    out = torch.empty(seg, dtype=torch.float64, device=dev)
+    counts = torch.empty(2 * seg, dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    nbytes = lib.cdc_eval_gauc_workspace_bytes(n, n_domain, n_user)
+    if nbytes <= 0:
+        raise RuntimeError("cdc_eval_gauc_workspace_bytes failed")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    L.launch("cdc_eval_gauc", lib.cdc_eval_gauc,
+             (pred.data_ptr(), label.data_ptr(), user.data_ptr(), ld_user, n_user, None if domain is None else domain.data_ptr(),
+              ld_domain, n_domain, None if user_weight is None else user_weight.data_ptr(), n, out.data_ptr(), counts.data_ptr(),
+              err.data_ptr(), ws.data_ptr(), nbytes), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    eval_gauc.last_err = err
+    return out, counts[:seg], counts[seg:]
+
+
 class Evaluator:
     """Mirror of Run.test (run.py:647-690): the CDC, multi-tower and single-tower branches.
 
@@ -61,20 +122,38 @@ class Evaluator:
                 group: pred = model(X, mode='split', domain_i=d)                       (run.py:653-661, get_domain_data 499-526)
     mode "multi": batches are (X, y, group) and pred = model(X).gather(1, group)   (run.py:668-673)
     mode "single": batches are (X, y) and pred = model(X)                           (run.py:674-676)
-    domain_cnt_weight: {domain: weight} or a sequence, as Run.domain_cnt_weight (mean_auc / mean_loss, run.py:706-707)."""
+    domain_cnt_weight: {domain: weight} or a sequence, as Run.domain_cnt_weight (mean_auc / mean_loss, run.py:706-707).
+    user_idx: column of X that holds the user id (in [0, n_user)).  When set, test() adds GAUC (base.py:33-64): total_gauc, and
+              with per-domain evaluation domain_gauc and mean_gauc.  user_weight: f64 [n_user] or {user: weight} (a user missing
+              from the dict weighs NaN: the reference raises KeyError for it), None = the user's row count."""
 
-    def __init__(self, model, mode="multi", domain_idx=None, n_domain=1, domain_cnt_weight=None, is_evaluate_multi_domain=True):
+    def __init__(self, model, mode="multi", domain_idx=None, n_domain=1, domain_cnt_weight=None, is_evaluate_multi_domain=True,
+                 user_idx=None, n_user=None, user_weight=None):
         self.model, self.mode = model, mode
         self.domain_idx, self.n_domain = domain_idx, int(n_domain)
         self.domain_cnt_weight = domain_cnt_weight
         self.is_evaluate_multi_domain = bool(is_evaluate_multi_domain) and domain_idx is not None
+        self.user_idx = user_idx
+        if user_idx is not None:
+            if n_user is None:
+                raise ValueError("user_idx needs n_user, the size of the user id range")
+            self.n_user = int(n_user)
+            if isinstance(user_weight, dict):
+                dense = torch.full((self.n_user,), math.nan, dtype=torch.float64)
+                dense[torch.tensor(list(user_weight.keys()), dtype=torch.int64)] = torch.tensor(list(user_weight.values()), dtype=torch.float64)
+                user_weight = dense
+            self.user_weight = user_weight
 
     def predict(self, data_loader):
         """-> (pred f32 [n], label int16 [n], domain int32 [n] or None), all on the device."""
+        return self._score(data_loader)[:3]
+
+    def _score(self, data_loader):
+        """predict() and the user column: -> (pred, label, domain or None, user int32 [n] or None)"""
         model = self.model
         was_training = model.training
         model.eval()
-        preds, labels, domains = [], [], []
+        preds, labels, domains, users = [], [], [], []
         try:
             with torch.no_grad():
                 for batch in (self._domain_batches(*data_loader) if self.mode == "cdc" else data_loader):
@@ -91,11 +170,13 @@ class Evaluator:
                     labels.append(y.reshape(-1).to(torch.int16))
                     if self.domain_idx is not None:
                         domains.append(X[:, self.domain_idx].to(torch.int32))
+                    if self.user_idx is not None:
+                        users.append(X[:, self.user_idx].to(torch.int32))
         finally:
             model.train(was_training)
         if not preds:
             raise ValueError("empty evaluation set")
-        return torch.cat(preds), torch.cat(labels), (torch.cat(domains) if domains else None)
+        return torch.cat(preds), torch.cat(labels), (torch.cat(domains) if domains else None), (torch.cat(users) if users else None)
 
     @staticmethod
     def _domain_batches(loaders, domain_batch_seq):
@@ -114,10 +195,13 @@ class Evaluator:
             yield d, X, y
 
     def test(self, data_loader):
-        """The reference's result_dict: total_auc, total_loss (+ domain_auc, domain_loss, mean_auc, mean_loss)."""
-        pred, label, domain = self.predict(data_loader)
+        """The reference's result_dict: total_auc, total_loss (+ domain_auc, domain_loss, mean_auc, mean_loss); with user_idx also
+        total_gauc (+ domain_gauc, mean_gauc)."""
+        pred, label, domain, user = self._score(data_loader)
         multi = self.is_evaluate_multi_domain
         auc, loss, rows, pos = eval_metrics(pred, label, domain if multi else None, self.n_domain if multi else 1)
+        if user is not None:                                   # queued behind the metrics: still nothing has been read back
+            gauc = eval_gauc(pred, label, user, self.n_user, domain if multi else None, self.n_domain if multi else 1, self.user_weight)[0]
         auc, loss, rows, pos = auc.cpu().tolist(), loss.cpu().tolist(), rows.cpu().tolist(), pos.cpu().tolist()   # the one sync
         bad = int(eval_metrics.last_err.item())
         if bad:
@@ -136,6 +220,16 @@ class Evaluator:
                 mean_auc += w * auc[d]
                 mean_loss += w * loss[d]
             result.update({"domain_auc": domain_auc, "domain_loss": domain_loss, "mean_auc": mean_auc, "mean_loss": mean_loss})
+        if user is not None:
+            gauc = gauc.cpu().tolist()
+            bad = int(eval_gauc.last_err.item())
+            if bad:
+                raise ValueError(f"evaluation row {bad - 1}: user outside [0, {self.n_user})")
+            result["total_gauc"] = gauc[-1]
+            if multi:
+                domain_gauc = {d: gauc[d] for d in range(self.n_domain) if rows[d] > 0}
+                result["domain_gauc"] = domain_gauc
+                result["mean_gauc"] = sum(self._weight(d) * v for d, v in domain_gauc.items())     # as mean_auc; NaN when a domain has no countable user
         return result
 
     def _weight(self, d):

@@ -2,7 +2,10 @@
 (run.py:440-468) — train an epoch, evaluate on the validation set, keep the best checkpoint by `mean_auc` (falling back to
 `total_auc` when no per-domain evaluation is configured), stop after `num_trials` epochs without improvement, reload the best
 checkpoint and evaluate on the test set.  wandb logging, dataset preprocessing and model construction from `config` stay
-with the caller (they are the reference's control plane: SURVEY §2)."""
+with the caller (they are the reference's control plane: SURVEY §2).
+
+`select_by="mean_gauc"` / `"total_gauc"` makes the per-user GAUC of an Evaluator with a user column (evaluate.py) the criterion
+of both the best checkpoint and the early stop instead."""
 import torch
 
 from .data import train_epoch
@@ -10,9 +13,13 @@ from .evaluate import Evaluator
 
 
 class Runner:
-    def __init__(self, model, step, evaluator: Evaluator, save_model_path, num_trials=3, cdc_trainer=None, log=print):
+    def __init__(self, model, step, evaluator: Evaluator, save_model_path, num_trials=3, cdc_trainer=None, log=print, select_by=None):
         """step: the TrainStep (its optimiser is checkpointed); cdc_trainer: a CDCTrainer whose train_epoch replaces the
-        plain epoch for CDC models (run.py:738-750)."""
+        plain epoch for CDC models (run.py:738-750).  select_by: None = the reference's rule (mean_auc, else total_auc);
+        "mean_gauc" or "total_gauc" = that key of the evaluator's result."""
+        if select_by not in (None, "mean_gauc", "total_gauc"):
+            raise ValueError(f"select_by={select_by!r}: None, 'mean_gauc' or 'total_gauc'")
+        self.select_by, self.best_select = select_by, 0.0
         self.model, self.step, self.evaluator = model, step, evaluator
         self.save_model_path, self.num_trials = save_model_path, int(num_trials)
         self.cdc_trainer, self.log = cdc_trainer, log
@@ -40,11 +47,20 @@ class Runner:
         best = self.best_mean_auc
         if score is None:                       # is_evaluate_multi_domain off: the reference's commented-out total_auc criterion
             score, best = result_dict["total_auc"], self.best_auc
+        if self.select_by is not None:
+            if self.select_by not in result_dict:
+                raise KeyError(f"select_by={self.select_by!r} but the evaluator's result has no such key: construct the Evaluator with "
+                               f"user_idx (and n_user)" + (", and per-domain evaluation for mean_gauc" if self.select_by == "mean_gauc" else ""))
+            score, best = result_dict[self.select_by], self.best_select
         if score > best:
             self.trial_counter = 0
+            if self.select_by is not None:
+                self.best_select = score
             self.best_auc, self.best_loss = result_dict["total_auc"], result_dict["total_loss"]
             save = {"epoch": epoch_i + 1, "state_dict": self.model.state_dict(), "best_auc": self.best_auc,
                     "best_result": result_dict, "optimizer": self.step.opt.state_dict()}
+            if self.select_by is not None:
+                save["select_by"], save["best_" + self.select_by] = self.select_by, score
             if result_dict.get("mean_auc") is not None:
                 self.best_mean_auc, self.best_mean_loss = result_dict["mean_auc"], result_dict["mean_loss"]
                 save["best_mean_auc"], save["best_mean_loss"] = self.best_mean_auc, self.best_mean_loss

@@ -1133,6 +1133,29 @@ int cdc_eval_metrics(const float* pred, const int16_t* label, const int32_t* dom
                      int32_t n_domain, double* out, int64_t* counts, int32_t* err_flag, void* workspace,
                      int64_t workspace_bytes, void* stream);
 
+/* GAUC (base.py:33-64, gauc_score): the AUC of every user's rows, averaged over users with a weight.  user int32, element i at
+ * user[i*ld_user] in [0, n_user) (e.g. the user column of X: ld = F); pred, label, domain, n_domain as for cdc_eval_metrics.
+ * For every domain d the rows of d are grouped by user; for the pseudo-domain n_domain ("all rows") all rows are grouped by user
+ * across domains.  Per group: P positives, N negatives, U = the Mann-Whitney statistic with mid-ranks (-0.0 ties with +0.0).  A
+ * group with P == 0 or N == 0 is left out of numerator and denominator (gauc_score's `continue`).
+ *   out    [n_domain+1] doubles: out[d] = sum_g w_g * U_g / (P_g * N_g) / sum_g w_g over the counted groups of d, with
+ *          w_g = user_weight[user of g], or the group's row count when user_weight == NULL (gauc_score's weights=None).
+ *          NaN when no group of d is counted — where the reference divides by zero (ZeroDivisionError).
+ *   counts [2*(n_domain+1)] int64: counted groups per (pseudo-)domain, then the groups left out.
+ *   user_weight [n_user] doubles (positive, finite) or NULL.
+ *   err_flag (optional): 1 + the largest index of a row with a NaN score, a label other than 0/1, a domain outside
+ *          [0, n_domain) or a user outside [0, n_user); such a row is counted with its ids clamped into range.
+ * U is formed from integer rank sums, and the weighted sums are added in an order fixed by the sorted keys: the same rows in any
+ * order give the same bits.  Limits: n < 2^31 and (n_domain + 1) * n_user <= 2^32 (a group id is the upper half of a 64-bit sort
+ * key), CDC_E_BADARG otherwise — checked, like every argument, before anything is launched.  Stream-ordered: no allocation, no
+ * synchronisation, no state kept; the launch dimensions depend on (n, n_domain) alone, so the call can be captured in a graph.
+ * workspace: cdc_eval_gauc_workspace_bytes(n, n_domain, n_user) bytes (O(n): nothing is sized by n_user), 256-byte aligned;
+ * 0 is returned for sizes the call refuses. */
+int64_t cdc_eval_gauc_workspace_bytes(int64_t n, int32_t n_domain, int64_t n_user);
+int cdc_eval_gauc(const float* pred, const int16_t* label, const int32_t* user, int64_t ld_user, int64_t n_user,
+                  const int32_t* domain, int64_t ld_domain, int32_t n_domain, const double* user_weight, int64_t n,
+                  double* out, int64_t* counts, int32_t* err_flag, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
