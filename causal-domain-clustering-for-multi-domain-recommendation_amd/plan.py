@@ -15,6 +15,7 @@ Gradient conventions
     ones add; the builder works the flags out when the plan is finalised.
 """
 import ctypes as C
+import dataclasses
 import math
 import os
 
@@ -62,6 +63,14 @@ class Buf:
     def tensor(self):
         return self.root[:, self.col0:self.col0 + self.cols]
 
+    @property
+    def key(self):
+        """which columns of which root: equal for two views of the same values, whatever their row counts"""
+        return (id(self.root), self.col0, self.cols)
+
+    def same(self, other):
+        return self.key == other.key and self.rows == other.rows
+
     # ---- gradient view (same geometry inside the root's gradient tensor) ----
     @property
     def grad(self):
@@ -108,42 +117,235 @@ class TView:
         return self.tensor
 
 
+def _weight_key(w):
+    """what makes two weight objects the same weight: a PView is its parameter's slice, a TView its tensor"""
+    if isinstance(w, PView):
+        return (id(w.param), w.index)
+    return id(w.tensor) if isinstance(w, TView) else id(w)
+
+
+def _flops(M, weights):
+    """2 M N K over linear weights [N, K] applied to M rows"""
+    return sum(2.0 * M * w.shape[0] * w.shape[1] for w in weights)
+
+
+class _Intervals:
+    """Column intervals [c0, c1) per root tensor, kept sorted and disjoint: overlapping and adjacent adds merge."""
+
+    def __init__(self):
+        self.iv = {}        # id(root) -> [(c0, c1)]
+
+    def add(self, buf):
+        iv = self.iv.setdefault(id(buf.root), [])
+        iv.append((buf.col0, buf.col0 + buf.cols))
+        iv.sort()
+        merged = [iv[0]]
+        for a, b in iv[1:]:
+            if a <= merged[-1][1]:
+                merged[-1] = (merged[-1][0], max(merged[-1][1], b))
+            else:
+                merged.append((a, b))
+        iv[:] = merged
+
+    def covers(self, buf):
+        c0, c1 = buf.col0, buf.col0 + buf.cols
+        return any(a <= c0 and c1 <= b for a, b in self.iv.get(id(buf.root), []))
+
+    def overlaps(self, buf):
+        """the first interval that shares a column with buf, or None"""
+        c0, c1 = buf.col0, buf.col0 + buf.cols
+        return next(((a, b) for a, b in self.iv.get(id(buf.root), []) if a < c1 and c0 < b), None)
+
+    def remove_overlapping(self, buf):
+        iv = self.iv.get(id(buf.root))
+        if iv:
+            c0, c1 = buf.col0, buf.col0 + buf.cols
+            iv[:] = [(a, b) for a, b in iv if not (a < c1 and c0 < b)]
+
+
 class _GradState:
     """Tracks which column intervals of a root gradient tensor the backward sequence has initialised."""
 
     def __init__(self, plan=None):
-        self.done = {}      # id(root) -> list of (c0, c1)
+        self.done = _Intervals()
         self.plan = plan
+        self._once = {}     # (id(op), buffer key) -> what claim() answered the op's first launch (claim_once)
 
     def claim(self, buf):
         """Returns True if `buf`'s gradient region is already initialised (=> accumulate), else marks it."""
-        key = id(buf.root)
-        iv = self.done.setdefault(key, [])
-        c0, c1 = buf.col0, buf.col0 + buf.cols
         if self.plan is not None:
             # whoever claims the region is about to write it: a bf16 shadow of the gradient written earlier is stale from here on
             self.plan.invalidate_shadow(buf.grad)
-        for a, b in iv:
-            if a <= c0 and c1 <= b:
-                return True
-        for a, b in iv:
-            if not (c1 <= a or b <= c0):
-                raise RuntimeError(f"partial gradient overlap on a buffer: [{c0},{c1}) vs [{a},{b})")
-        iv.append((c0, c1))
-        # merge adjacent column intervals (slices claimed one by one later read as one whole buffer)
-        iv.sort()
-        merged = [iv[0]]
-        for a, b in iv[1:]:
-            if a == merged[-1][1]:
-                merged[-1] = (merged[-1][0], b)
-            else:
-                merged.append((a, b))
-        iv[:] = merged
+        if self.done.covers(buf):
+            return True
+        hit = self.done.overlaps(buf)
+        if hit is not None:
+            raise RuntimeError(f"partial gradient overlap on a buffer: [{buf.col0},{buf.col0 + buf.cols}) vs [{hit[0]},{hit[1]})")
+        self.done.add(buf)      # (adjacent slices claimed one by one later read as one whole buffer)
         return False
 
+    def claim_once(self, buf, op):
+        """claim() for an op with ragged rows: its groups own disjoint rows of one buffer, over several launches, so the op takes
+        ONE store-or-accumulate decision per distinct buffer"""
+        k = (id(op), buf.key)
+        if k not in self._once:
+            self._once[k] = self.claim(buf)
+        return self._once[k]
+
     def is_set(self, buf):
-        c0, c1 = buf.col0, buf.col0 + buf.cols
-        return any(a <= c0 and c1 <= b for a, b in self.done.get(id(buf.root), []))
+        return self.done.covers(buf)
+
+
+@dataclasses.dataclass
+class _DwGroup:
+    """One layer's grad-weight contraction dW [N,K] (+ db [N]) = dZ^T x over M rows, as addresses (GLinear._dw_group)."""
+    dz: int
+    lddz: int
+    x: int
+    ldx: int
+    dw: int
+    lddw: int
+    db: object
+    M: int
+    N: int
+    K: int
+    accumulate: int
+    dzh: tuple = None               # (address, row stride) of the bf16 shadows of dZ and of x: the csrc/gemm2.hip form
+    xh: tuple = None
+    needs_shadows: bool = False     # an operand exists as a shadow only
+
+    @property
+    def narrow(self):
+        return self.dzh is not None and self.N <= 64
+
+    @property
+    def slab(self):
+        """floats of one split-K slab: dW, then db"""
+        return self.N * self.K + self.N
+
+    def fill(self, G):
+        G.dz, G.lddz, G.x, G.ldx = self.dz, self.lddz, self.x, self.ldx
+        G.dw, G.lddw, G.db = self.dw, self.lddw, self.db
+        G.M, G.N, G.K, G.accumulate = self.M, self.N, self.K, self.accumulate
+        if self.dzh is not None:
+            (G.dzh, G.lddzh), (G.xh, G.ldxh) = self.dzh, self.xh
+
+
+class _DwLaunch:
+    """one launch of the batch: its groups, its argument block, and where its split-K slabs go"""
+
+    def __init__(self, groups):
+        self.groups = groups
+        self.args = L.LinBwdwArgs()
+        self.flops = sum(2.0 * g.M * g.N * g.K for g in groups)
+        self.shadowed = all(g.dzh is not None for g in groups)
+        self.slab = sum(g.slab for g in groups)
+        self.own = None             # offset of a workspace region of its own (the slabs outlive the launch), in floats
+
+    @property
+    def splittable(self):
+        return self.args.split_k > 1 and not any(g.accumulate for g in self.groups)
+
+
+class _DwBatch:
+    """All layers' grad-weight contractions are independent of the rest of backward once their dZ exists: they go out
+    together at the end, in launches that fill the chip (instead of one under-filled launch per layer)."""
+
+    def __init__(self, plan, groups):
+        self.plan = plan
+        self.launches = [_DwLaunch(chunk) for chunk in self._cut(self._classify(groups))]
+        for la in self.launches:
+            self._choose_split_k(la)
+        self.pair = self.pair_reduce = False
+
+    @staticmethod
+    def _classify(groups):
+        # narrow outputs (N <= 64: gates, the last expert level, towers) go to launches of their own: the grad-weight kernel then
+        # uses 64x64 tiles for them instead of padding each to 128 rows (a gate with 4 outputs filled 3 % of its tiles).  The
+        # order inside a class is kept (a group that accumulates follows its base; both have the same N)
+        return ([g for g in groups if g.dzh is not None and not g.narrow] + [g for g in groups if g.narrow] +
+                [g for g in groups if g.dzh is None])
+
+    @staticmethod
+    def _cut(groups):
+        launches, cur = [], []
+        for g in groups:
+            # (a launch is either all-shadows (csrc/gemm2.hip) or all-fp32-operands: layers too narrow for the bf16 tiles sit
+            # next to wide ones in small models)
+            if cur and (len(cur) >= L.MAX_GROUPS or g.accumulate or (g.dzh is None) != (cur[0].dzh is None) or g.narrow != cur[0].narrow):
+                launches.append(cur)
+                cur = []
+            cur.append(g)
+        if cur:
+            launches.append(cur)
+        return launches
+
+    def _choose_split_k(self, la):
+        chunk = la.groups
+        Mmax = max(g.M for g in chunk)
+        if any(g.needs_shadows for g in chunk) and not la.shadowed:
+            raise RuntimeError("a grad-weight launch mixes shadow-only activations with groups that have no shadows")
+        if la.shadowed:
+            # shadows (csrc/gemm2.hip k_g2_tn): 128x128 output tiles unless every group is at most 64x64; a row slice of at least
+            # four 64-row slabs per workgroup
+            T = 64 if all(g.N <= 64 for g in chunk) else 128
+            tiles = sum(math.ceil(g.N / T) * math.ceil(g.K / T) for g in chunk)
+            S = max(1, min(512 // max(tiles, 1), max(Mmax // 256, 1), 32))
+            if self.plan.defer_dw_reduce:                   # the Adam launch reads the slabs in rounds of eight (csrc/rowops.hip)
+                S = min(S, 8)
+        else:
+            tiles = sum(math.ceil(g.N / 64) * math.ceil(g.K / 64) for g in chunk)
+            S = max(1, min(1024 // max(tiles, 1), max(Mmax // 128, 1), 64))       # 1024: measured best of 384…2560 at C2
+        a = la.args
+        a.n_groups, a.split_k, a.row_offsets = len(chunk), S, None
+        if S > 1:
+            self.plan.need_gemm_ws(S * la.slab)
+        for i, g in enumerate(chunk):
+            g.fill(a.g[i])
+
+    def lay_out_slabs(self):
+        """Decides which launches leave their split-K slabs unreduced and whether the two classes go out as one launch; returns
+        the floats those launches need behind the shared workspace (their slabs must survive until the consumer has added them)."""
+        plan, ls = self.plan, self.launches
+        # the wide and the narrow class of the batched grad-weight contractions as ONE launch (csrc/gemm2.hip k_g2_tn_dual)?
+        two_classes = (len(ls) == 2 and ls[0].shadowed and ls[1].shadowed and any(g.N > 64 for g in ls[0].groups) and
+                       all(g.N <= 64 for g in ls[1].groups))
+        # ... whose slabs the consumer adds up (single GPU: the dense Adam launch) or, where the reduced gradient is needed at once (data
+        # parallelism all-reduces it), ONE more launch (cdc_glinear_bwd_w_pair_reduce): two launches instead of four
+        self.pair_reduce = (not plan.defer_dw_reduce) and two_classes and all(la.splittable for la in ls)
+        unreduced = plan.defer_dw_reduce or self.pair_reduce
+        extra = 0
+        for la in ls:
+            if unreduced and la.splittable:
+                la.own = extra
+                extra += (la.args.split_k * la.slab + 3) // 4 * 4
+        self.pair = two_classes and unreduced and all(la.own is not None or la.args.split_k <= 1 for la in ls)
+        return extra
+
+    def emit(self, ws, shared):
+        """ws: address of the workspace; the regions of lay_out_slabs start `shared` floats into it.  Returns the launch steps."""
+        plan = self.plan
+        for la in self.launches:
+            a = la.args
+            a.workspace = ws
+            if la.own is not None:
+                a.workspace = ws + 4 * (shared + la.own)
+                a.defer_reduce = 1
+                pos = 0
+                for g in la.groups:
+                    if plan.defer_dw_reduce:
+                        plan.grad_slabs[g.dw] = (a.workspace + 4 * pos, la.slab, a.split_k)
+                        if g.db:
+                            plan.grad_slabs[g.db] = (a.workspace + 4 * (pos + g.N * g.K), la.slab, a.split_k)
+                    pos += g.slab
+            plan._keep_args.append(a)
+        if not self.pair:
+            return [plan.call("cdc_glinear_bwd_w", C.byref(la.args), plan.prec, flops=la.flops) for la in self.launches]
+        # the two argument blocks travel as a device copy, made now that their workspaces are final
+        aw, an = self.launches[0].args, self.launches[1].args
+        plan._dw_pair_dev = torch.frombuffer(bytearray(bytes(aw) + bytes(an)), dtype=torch.uint8).to(plan.device)
+        return [plan.call("cdc_glinear_bwd_w_pair_reduce" if self.pair_reduce else "cdc_glinear_bwd_w_pair", C.byref(aw), C.byref(an),
+                          plan._dw_pair_dev.data_ptr(), what="cdc_glinear_bwd_w", flops=sum(la.flops for la in self.launches))]
 
 
 class Plan:
@@ -163,6 +365,8 @@ class Plan:
         self.ops = []
         self.fwd_steps = []
         self.bwd_steps = []
+        self._keep_args = []              # argument blocks of the plan's own launches (they must outlive the steps that point at them)
+        self._call_seq = 0                # launches named so far (CDC_PROFILE_DETAIL)
         self._grads = {}                  # id(root) -> grad tensor
         self._roots = {}
         self.param_grads = {}             # id(param) -> grad tensor
@@ -184,10 +388,10 @@ class Plan:
         self._gemm_ws = None
         self._gemm_ws_need = 0
         self._gemm_ws_users = []          # argument blocks whose .workspace is the grad-weight split-K buffer
-        self._lin_producer = {}           # linear output (root, col0, cols) -> its launch group (BatchNorm statistics fusion)
+        self._lin_producer = {}           # linear output (Buf.key) -> its launch group (BatchNorm statistics fusion)
         self._last_bn_step = 0
         self._wt = {}                     # weight key -> (weight object, transposed copy [K,N]) refreshed at the start of backward
-        self._deferred_dw = []            # grad-weight groups of every layer, launched together at the end of backward
+        self._deferred_dw = []            # grad-weight groups (_DwGroup) of every layer, launched together at the end of backward
         # defer_dw_reduce (the single-GPU training step): the batched grad-weight launches leave their split-K slabs unreduced and
         # the dense Adam launch adds them while it reads the gradient (cdc_adam_tensor.slabs): two launches and a round trip of
         # the gradients through memory less per step.  grad_slabs: address of a parameter gradient -> (first slab, stride, count);
@@ -201,8 +405,8 @@ class Plan:
         # (STAR's per-domain groups) take — so that the two paths can be held against each other
         self.use_g2 = self.prec == L.PREC_BF16 and bool(g2)
         self._shadows = {}                # id(fp32 root) -> (root, bf16 tensor [rows64, cols64 + 64], zero padded)
-        self._sh_have = {}                # id(root) -> [(c0, c1)] columns whose shadow is current at this point of the sequence
-        self._sh_wanted = {}              # id(root) -> [(c0, c1)] columns some contraction reads through the shadow
+        self._sh_have = _Intervals()      # columns whose shadow is current at this point of the sequence
+        self._sh_wanted = _Intervals()    # columns some contraction reads through the shadow
         self._wsh = {}                    # weight key -> (weight, straight copy [N, K64], transposed copy [K, N64])
         self._half_only = set()           # id(root): activations (and their gradients) that exist ONLY as bf16 shadows
 
@@ -247,7 +451,7 @@ class Plan:
             gs.claim(buf)
 
     def _claim_param(self, p):
-        key = (id(p.param), p.index) if isinstance(p, PView) else (id(p.tensor) if isinstance(p, TView) else id(p))
+        key = _weight_key(p)
         if key in self._param_grad_set:
             return True
         self._param_grad_set.add(key)
@@ -264,8 +468,7 @@ class Plan:
         """per-step transposed copy [K,N] of a linear weight [N,K]: grad-input then streams both operands with the
         reduction index contiguous (no transposing LDS stores).  half: the copy is written as bf16 (what the bf16 MFMA
         path would round the fp32 copy to while staging it) — half the operand bytes, no conversion in the loop."""
-        key = (id(w.param), w.index) if isinstance(w, PView) else (id(w.tensor) if isinstance(w, TView) else id(w))
-        key = (key, bool(half))
+        key = (_weight_key(w), bool(half))
         hit = self._wt.get(key)
         if hit is None:
             N, K = w.shape
@@ -287,66 +490,8 @@ class Plan:
                 if half:
                     mask |= 1 << i
             a.bf16_mask = mask
-            self._keep_args = getattr(self, "_keep_args", []) + [a]
+            self._keep_args.append(a)
             steps.append(self.call("cdc_transpose_multi", C.byref(a)))
-        return steps
-
-    def _emit_deferred_dw(self):
-        """All layers' grad-weight contractions are independent of the rest of backward once their dZ exists: they go out
-        together at the end, in launches that fill the chip (instead of one under-filled launch per layer)."""
-        groups = self._deferred_dw
-        # narrow outputs (N <= 64: gates, the last expert level, towers) go to launches of their own: the grad-weight kernel then
-        # uses 64x64 tiles for them instead of padding each to 128 rows (a gate with 4 outputs filled 3 % of its tiles).  The
-        # order inside a class is kept (a group that accumulates follows its base; both have the same N)
-        groups = ([g for g in groups if g.get("dzh") is not None and g["N"] > 64] +
-                  [g for g in groups if g.get("dzh") is not None and g["N"] <= 64] +
-                  [g for g in groups if g.get("dzh") is None])
-        launches, cur = [], []
-        narrow = lambda g: g.get("dzh") is not None and g["N"] <= 64      # noqa: E731
-        for g in groups:
-            # (a launch is either all-shadows (csrc/gemm2.hip) or all-fp32-operands: layers too narrow for the bf16 tiles sit
-            # next to wide ones in small models)
-            if cur and (len(cur) >= L.MAX_GROUPS or g["accumulate"] or (g.get("dzh") is None) != (cur[0].get("dzh") is None) or
-                        narrow(g) != narrow(cur[0])):
-                launches.append(cur)
-                cur = []
-            cur.append(g)
-        if cur:
-            launches.append(cur)
-        steps = []
-        for chunk in launches:
-            a = L.LinBwdwArgs()
-            a.n_groups = len(chunk)
-            Mmax = max(g["M"] for g in chunk)
-            if any(g.get("needs_shadows") for g in chunk) and not all(g.get("dzh") is not None for g in chunk):
-                raise RuntimeError("a grad-weight launch mixes shadow-only activations with groups that have no shadows")
-            if all(g.get("dzh") is not None for g in chunk):
-                # shadows (csrc/gemm2.hip k_g2_tn): 128x128 output tiles unless every group is at most 64x64; a row slice of at least
-                # four 64-row slabs per workgroup
-                T = 64 if all(g["N"] <= 64 for g in chunk) else 128
-                tiles = sum(math.ceil(g["N"] / T) * math.ceil(g["K"] / T) for g in chunk)
-                S = max(1, min(512 // max(tiles, 1), max(Mmax // 256, 1), 32))
-                if self.defer_dw_reduce:                   # the Adam launch reads the slabs in rounds of eight (csrc/rowops.hip)
-                    S = min(S, 8)
-            else:
-                tiles = sum(math.ceil(g["N"] / 64) * math.ceil(g["K"] / 64) for g in chunk)
-                S = max(1, min(1024 // max(tiles, 1), max(Mmax // 128, 1), 64))       # 1024: measured best of 384…2560 at C2
-            a.split_k = S
-            if S > 1:
-                self.need_gemm_ws(S * sum(g["N"] * g["K"] + g["N"] for g in chunk))
-            a.row_offsets = None
-            for i, g in enumerate(chunk):
-                G = a.g[i]
-                G.dz, G.lddz, G.x, G.ldx = g["dz"], g["lddz"], g["x"], g["ldx"]
-                G.dw, G.lddw, G.db = g["dw"], g["lddw"], g["db"]
-                G.M, G.N, G.K, G.accumulate = g["M"], g["N"], g["K"], g["accumulate"]
-                if g.get("dzh") is not None:
-                    (G.dzh, G.lddzh), (G.xh, G.ldxh) = g["dzh"], g["xh"]
-                else:
-                    G.dzh = G.xh = None
-            self._keep_args = getattr(self, "_keep_args", []) + [a]
-            fl = sum(2.0 * g["M"] * g["N"] * g["K"] for g in chunk)
-            steps.append((a, fl))
         return steps
 
     def need_gemm_ws(self, n):
@@ -370,61 +515,50 @@ class Plan:
         t = self._shadow_root(buf.root)
         return t.data_ptr() + 2 * buf.col0, t.stride(0)
 
-    @staticmethod
-    def _iv_covered(table, buf):
-        c0, c1 = buf.col0, buf.col0 + buf.cols
-        return any(a <= c0 and c1 <= b for a, b in table.get(id(buf.root), []))
-
-    @staticmethod
-    def _iv_add(table, buf):
-        iv = table.setdefault(id(buf.root), [])
-        iv.append((buf.col0, buf.col0 + buf.cols))
-        iv.sort()
-        merged = [iv[0]]
-        for a, b in iv[1:]:
-            if a <= merged[-1][1]:
-                merged[-1] = (merged[-1][0], max(merged[-1][1], b))
-            else:
-                merged.append((a, b))
-        iv[:] = merged
-
     def want_shadow(self, buf):
-        self._iv_add(self._sh_wanted, buf)
+        self._sh_wanted.add(buf)
 
     def shadow_wanted(self, buf):
-        c0, c1 = buf.col0, buf.col0 + buf.cols
-        return any(a < c1 and c0 < b for a, b in self._sh_wanted.get(id(buf.root), []))
+        return self._sh_wanted.overlaps(buf) is not None
 
     def mark_shadow(self, buf):
-        self._iv_add(self._sh_have, buf)
+        self._sh_have.add(buf)
 
     def has_shadow(self, buf):
-        return self._iv_covered(self._sh_have, buf)
+        return self._sh_have.covers(buf)
 
     def invalidate_shadow(self, buf):
-        iv = self._sh_have.get(id(buf.root))
-        if iv:
-            c0, c1 = buf.col0, buf.col0 + buf.cols
-            iv[:] = [(a, b) for a, b in iv if not (a < c1 and c0 < b)]
+        self._sh_have.remove_overlapping(buf)
+
+    def shadow_out(self, buf, force=False):
+        """For the launch that writes buf: (address, row stride) of buf's shadow, marked current from here on, when a later
+        contraction reads buf through it (or the caller has no other form of buf: force); (None, 0) otherwise."""
+        if not (force or (self.use_g2 and self.shadow_wanted(buf))):
+            return None, 0
+        self.mark_shadow(buf)
+        return self.shadow_view(buf)
+
+    def _shadow_args(self, bufs):
+        a = L.ShadowArgs()
+        a.n = len(bufs)
+        for T, b in zip(a.t, bufs):
+            T.src, T.ld_src = b.ptr, b.ld
+            T.dst, T.ld_dst = self.shadow_view(b)
+            T.rows, T.cols = b.rows, b.cols
+        self._keep_args.append(a)
+        return a
 
     def ensure_shadows(self, bufs, steps):
         """one conversion launch (appended to `steps`) for those of `bufs` whose shadow no producer has written"""
         todo = []
         for b in bufs:
-            if not self.has_shadow(b) and not any(t.root is b.root and t.col0 == b.col0 and t.cols == b.cols for t in todo):
+            if not self.has_shadow(b) and not any(t.key == b.key for t in todo):
                 todo.append(b)
         for c0 in range(0, len(todo), L.MAX_GROUPS):
             chunk = todo[c0:c0 + L.MAX_GROUPS]
-            a = L.ShadowArgs()
-            a.n = len(chunk)
-            for i, b in enumerate(chunk):
-                T = a.t[i]
-                T.src, T.ld_src = b.ptr, b.ld
-                T.dst, T.ld_dst = self.shadow_view(b)
-                T.rows, T.cols = b.rows, b.cols
+            steps.append(self.call("cdc_shadow_bf16", C.byref(self._shadow_args(chunk))))
+            for b in chunk:
                 self.mark_shadow(b)
-            self._keep_args = getattr(self, "_keep_args", []) + [a]
-            steps.append(self.call("cdc_shadow_bf16", C.byref(a)))
 
     def make_half_only(self, buf):
         """The buffer's values are only ever read by bf16 contractions (hidden activations of a BatchNorm-free MLP stack): keep
@@ -453,19 +587,12 @@ class Plan:
     def shadow_convert_step(self, buf):
         """a launch step that rewrites buf's shadow from its fp32 values (for a caller that fills buf behind the plan's back:
         the row-sharded trainer replaces the gather launch by its row exchange)"""
-        a = L.ShadowArgs()
-        a.n = 1
-        T = a.t[0]
-        T.src, T.ld_src = buf.ptr, buf.ld
-        T.dst, T.ld_dst = self.shadow_view(buf)
-        T.rows, T.cols = buf.rows, buf.cols
-        self._keep_args = getattr(self, "_keep_args", []) + [a]
-        return self.call("cdc_shadow_bf16", C.byref(a))
+        return self.call("cdc_shadow_bf16", C.byref(self._shadow_args([buf])))
 
     def wshadow(self, w):
         """bf16 copies of a linear weight [N,K], refreshed once per step ahead of the forward: the straight copy [N, K64]
         (forward's B operand) and the transposed copy [K, N64] (grad-input's B operand), zero padded to whole K-slabs"""
-        key = (id(w.param), w.index) if isinstance(w, PView) else id(w)
+        key = _weight_key(w)
         hit = self._wsh.get(key)
         if hit is None:
             N, K = w.shape
@@ -488,7 +615,7 @@ class Plan:
                 T.dst_h, T.ld_h = h.data_ptr(), h.stride(0)
                 T.dst_t, T.ld_t = t.data_ptr(), t.stride(0)
                 T.rows, T.cols = w.shape[0], w.shape[1]
-            self._keep_args = getattr(self, "_keep_args", []) + [a]
+            self._keep_args.append(a)
             steps.append(self.call("cdc_weight_shadows", C.byref(a)))
         return steps
 
@@ -501,7 +628,6 @@ class Plan:
         """outputs: list of Bufs whose .grad the caller seeds before backward()."""
         self._bn_ws = torch.empty(max(self._bn_ws_need, 1), dtype=torch.float64, device=self.device)
         self._rowdot_ws = torch.empty(max(self._rowdot_ws_need, 1), dtype=torch.float32, device=self.device)
-        self._gemm_ws = torch.empty(max(self._gemm_ws_need, 1), dtype=torch.float32, device=self.device)
         gs = _GradState(self)
         for o in outputs:
             gs.claim(o)
@@ -511,70 +637,33 @@ class Plan:
             op.build_fwd(self)
         for op in reversed(self.ops):
             op.build_bwd(self, gs)
-        dw = self._emit_deferred_dw()
-        if self._gemm_ws.numel() < self._gemm_ws_need:
-            self._gemm_ws = torch.empty(self._gemm_ws_need, dtype=torch.float32, device=self.device)
-        for a in self._gemm_ws_users:            # grad-weight launches built before the batched ones sized the workspace: a pointer
-            a.workspace = self._gemm_ws.data_ptr()   # taken earlier would dangle once the buffer has been re-allocated
-        self.deferred_dw_steps = []          # the tail of bwd_steps nothing else in the backward depends on
-        # launches that leave the slab reduction to the optimiser get a workspace region of their own behind the shared one
-        # (their slabs must survive until the dense Adam launch)
-        own, extra = {}, 0
-        shad = lambda a: all(a.g[i].dzh and a.g[i].xh for i in range(a.n_groups))      # noqa: E731
-        splittable = lambda a: a.split_k > 1 and not any(a.g[i].accumulate for i in range(a.n_groups))     # noqa: E731
-        # the wide and the narrow class of the batched grad-weight contractions as ONE launch (csrc/gemm2.hip k_g2_tn_dual)?
-        two_classes = (len(dw) == 2 and shad(dw[0][0]) and shad(dw[1][0]) and any(dw[0][0].g[i].N > 64 for i in range(dw[0][0].n_groups)) and
-                       all(dw[1][0].g[i].N <= 64 for i in range(dw[1][0].n_groups)))
-        # ... whose slabs the consumer adds up (single GPU: the dense Adam launch) or, where the reduced gradient is needed at once (data
-        # parallelism all-reduces it), ONE more launch (cdc_glinear_bwd_w_pair_reduce): two launches instead of four
-        pair_reduce = (not self.defer_dw_reduce) and two_classes and all(splittable(a) for a, _ in dw)
-        if self.defer_dw_reduce or pair_reduce:
-            for a, fl in dw:
-                if splittable(a):
-                    slab = sum(a.g[i].N * a.g[i].K + a.g[i].N for i in range(a.n_groups))
-                    own[id(a)] = (extra, slab)
-                    extra += (a.split_k * slab + 3) // 4 * 4
-        if extra:
-            shared = (self._gemm_ws_need + 3) // 4 * 4
-            self._gemm_ws = torch.empty(shared + extra, dtype=torch.float32, device=self.device)
-            for a in self._gemm_ws_users:
-                a.workspace = self._gemm_ws.data_ptr()
-        pair = None
-        if two_classes and all(id(a) in own or a.split_k <= 1 for a, _ in dw) and (self.defer_dw_reduce or pair_reduce):
-            pair = (dw[0][0], dw[1][0])
-        for a, fl in dw:
-            a.workspace = self._gemm_ws.data_ptr()
-            if id(a) in own:
-                off, slab = own[id(a)]
-                a.workspace = self._gemm_ws.data_ptr() + 4 * (shared + off)
-                a.defer_reduce = 1
-                pos = 0
-                for i in range(a.n_groups):
-                    G = a.g[i]
-                    if self.defer_dw_reduce:
-                        self.grad_slabs[G.dw] = (a.workspace + 4 * pos, slab, a.split_k)
-                        if G.db:
-                            self.grad_slabs[G.db] = (a.workspace + 4 * (pos + G.N * G.K), slab, a.split_k)
-                    pos += G.N * G.K + G.N
-            if pair is not None:
-                continue
-            step = self.call("cdc_glinear_bwd_w", C.byref(a), self.prec, flops=fl)
-            self.bwd_steps.append(step)
-            self.deferred_dw_steps.append(step)
-        if pair is not None:
-            # the wide and the narrow class of the batched grad-weight contractions in one launch (csrc/gemm2.hip k_g2_tn_dual): the
-            # two argument blocks travel as a device copy, made now that their workspaces are final
-            aw, an = pair
-            self._dw_pair_dev = torch.frombuffer(bytearray(bytes(aw) + bytes(an)), dtype=torch.uint8).to(self.device)
-            step = self.call("cdc_glinear_bwd_w_pair_reduce" if pair_reduce else "cdc_glinear_bwd_w_pair", C.byref(aw), C.byref(an),
-                             self._dw_pair_dev.data_ptr(), what="cdc_glinear_bwd_w", flops=sum(fl for _, fl in dw))
-            self.bwd_steps.append(step)
-            self.deferred_dw_steps.append(step)
+        self._emit_dw_batch()
         self.bwd_steps[0:0] = self._emit_transposes()
         wsh = self._emit_wshadows()
         self.fwd_steps[0:0] = wsh
         self.n_wshadow_steps = len(wsh)      # the head of fwd_steps that reads nothing but the weights (trainer: runs beside the catch-up)
         self.finalized = True
+
+    def _emit_dw_batch(self):
+        """The batched grad-weight launches (the tail of bwd_steps nothing else in the backward depends on: deferred_dw_steps) and
+        the split-K workspace of every grad-weight launch of the plan, sized now that all of them are known."""
+        batch = _DwBatch(self, self._deferred_dw)
+        # launches that leave the slab reduction to their consumer get a workspace region of their own behind the shared one
+        extra = batch.lay_out_slabs()
+        shared = (self._gemm_ws_need + 3) // 4 * 4 if extra else max(self._gemm_ws_need, 1)
+        self._gemm_ws = torch.empty(shared + extra, dtype=torch.float32, device=self.device)
+        for a in self._gemm_ws_users:
+            a.workspace = self._gemm_ws.data_ptr()
+        self.deferred_dw_steps = batch.emit(self._gemm_ws.data_ptr(), shared)
+        self.bwd_steps += self.deferred_dw_steps
+
+    def dp_phases(self, steps, launches, exchanges):
+        """Data parallel: a computation split into phases around the all-reduces of its global-batch sums is appended to `steps`:
+        launches[0], all-reduce of exchanges[0], launches[1], ..."""
+        for k, st in enumerate(launches):
+            steps.append(st)
+            if k < len(exchanges):
+                steps.append(self.comm(lambda ex=exchanges[k]: self.dist.all_reduce_sum(ex)))
 
     def comm(self, fn):
         """a collective between launches (runs eagerly; never part of a captured graph)"""
@@ -609,7 +698,7 @@ class Plan:
         fn = getattr(self.lib, fn_name)
         what = what or fn_name
         if os.environ.get("CDC_PROFILE_DETAIL") == "1":          # one timing bucket per launch of the sequence, not per entry point
-            self._call_seq = getattr(self, "_call_seq", 0) + 1
+            self._call_seq += 1
             what = f"{what}#{self._call_seq:03d}"
 
         def run(stream):
@@ -621,6 +710,35 @@ class Plan:
 # ======================================================================================================
 # ops
 # ======================================================================================================
+class Op:
+    """What the builder and the trainer may expect of every op that owns argument blocks."""
+
+    def __init__(self):
+        self._keep = []                   # argument blocks (and tensors) the op's launches point at
+        self.bwd_args = []                # backward argument blocks the trainer may complete (the fused BCE of a head's launch)
+        self.skip_bwd_x = False           # set by an op that absorbs this one and forms its grad-input itself
+
+
+def _fill_sel(G, sel):
+    G.n_sel = len(sel)
+    for j, e in enumerate(sel):
+        G.sel[j] = e
+
+
+def _fuse_runs(plan, cls, width):
+    """Replaces every run of `width` consecutive ops of plan.ops that cls.match accepts by ONE cls op (match answers None or
+    False for no, True for yes, or one further constructor argument); returns how many it built."""
+    n = i = 0
+    while i + width <= len(plan.ops):
+        run = plan.ops[i:i + width]
+        hit = cls.match(plan, *run)
+        if hit is not None and hit is not False:
+            cls(plan, *run, *(() if hit is True else (hit,)))
+            n += 1
+        i += 1
+    return n
+
+
 class EmbedGather:
     """model/layer.py:147-157 FeaturesEmbedding.forward(squeeze_dim=True)."""
 
@@ -636,11 +754,7 @@ class EmbedGather:
 
     def build_fwd(self, plan):
         R = self.table.shape[0]
-        oh, ldh = None, 0
-        if plan.use_g2 and plan.shadow_wanted(self.out):      # the contractions read the embeddings through their bf16 shadow
-            ptr, ldh = plan.shadow_view(self.out)
-            oh = C.c_void_p(ptr)
-            plan.mark_shadow(self.out)
+        oh, ldh = plan.shadow_out(self.out)                   # the contractions read the embeddings through their bf16 shadow
         self.fwd_step = plan.call("cdc_embed_gather_fwd_h", _p(self.ids), _p(self.offsets), _p(self.table.data),
                                   self.out.cptr(), oh, C.c_int64(ldh), _p(self.idx), _p(self.err), C.c_int64(plan.B), self.F, self.D,
                                   C.c_int64(R), what="cdc_embed_gather_fwd")
@@ -677,7 +791,7 @@ def _pack_bwd_x(outs, max_out, max_seg):
     return launches
 
 
-class GLinear:
+class GLinear(Op):
     """Several nn.Linear layers (optionally + ReLU + dropout) in one launch.
 
     groups: list of dicts {x: Buf, w: Parameter [N,K], b: Parameter [N] or None, act_cols: int or None}.
@@ -687,6 +801,7 @@ class GLinear:
     def __init__(self, plan, groups, relu=False, dropout=False, row_offsets=None, M=None):
         """a group with "half_only": True: its output feeds nothing but further bf16 contractions (the caller guarantees it); with
         the gemm2 path it and its gradient are kept as bf16 shadows only (no fp32 round trip through HBM)."""
+        super().__init__()
         self.groups = groups
         self.relu = relu
         self.drop_p = plan.dropout if dropout else 0.0
@@ -763,11 +878,7 @@ class GLinear:
                     O.y = None
                 else:
                     O.y, O.ldy = y.ptr, y.ld
-                if plan.shadow_wanted(y):                  # a later contraction reads y: its shadow comes out of this epilogue
-                    O.yh, O.ldyh = plan.shadow_view(y)
-                    plan.mark_shadow(y)
-                else:
-                    O.yh = None
+                O.yh, O.ldyh = plan.shadow_out(y)          # a later contraction reads y: its shadow comes out of this epilogue
                 O.bias = None if g.get("b") is None else g["b"].data_ptr()
                 O.mask, O.bn_partial = None, None
                 O.M, O.N, O.act_cols, O.accumulate, O.mask_bf16, O.stream_id = self.M, N, g["act_cols"], 0, 0, i
@@ -775,12 +886,10 @@ class GLinear:
                 wh, _ = plan.wshadow(g["w"])
                 S.b, S.ldb = wh.data_ptr(), wh.stride(0)
                 S.Kr, S.out = (K + 63) // 64 * 64, i
-                plan._lin_producer[(id(y.root), y.col0, y.cols)] = {"op": self, "G": O, "step": len(plan.fwd_steps), "taken": False}
-            self._keep = getattr(self, "_keep", []) + [a]
-            fl = sum(2.0 * self.M * g["w"].shape[0] * g["w"].shape[1] for g in chunk)
-            step = plan.call("cdc_gemm_bf16_nt", C.byref(a), what="cdc_glinear_fwd", flops=fl)
-            self._fwd_calls = getattr(self, "_fwd_calls", []) + [step]
-            plan.fwd_steps.append(step)
+                plan._lin_producer[y.key] = {"op": self, "G": O, "step": len(plan.fwd_steps), "taken": False}
+            self._keep.append(a)
+            plan.fwd_steps.append(plan.call("cdc_gemm_bf16_nt", C.byref(a), what="cdc_glinear_fwd",
+                                            flops=_flops(self.M, (g["w"] for g in chunk))))
 
     def build_fwd(self, plan):
         if self.g2:
@@ -805,11 +914,27 @@ class GLinear:
                 G.act_cols = g["act_cols"]
                 G.bn_partial = None
                 # a BatchNorm that normalises this output next may ask the epilogue for its partial sums (BatchNorm.build_fwd)
-                y = g["y"]
-                plan._lin_producer[(id(y.root), y.col0, y.cols)] = {"op": self, "G": G, "step": len(plan.fwd_steps), "taken": False}
-            self._keep = getattr(self, "_keep", []) + [a]
-            fl = sum(2.0 * self.M * g["w"].shape[0] * g["w"].shape[1] for g in chunk)
-            plan.fwd_steps.append(plan.call("cdc_glinear_fwd", C.byref(a), plan.prec, flops=fl))
+                plan._lin_producer[g["y"].key] = {"op": self, "G": G, "step": len(plan.fwd_steps), "taken": False}
+            self._keep.append(a)
+            plan.fwd_steps.append(plan.call("cdc_glinear_fwd", C.byref(a), plan.prec, flops=_flops(self.M, (g["w"] for g in chunk))))
+
+    def _dw_group(self, plan, g):
+        """the grad-weight contraction of group g; claims its parameters' gradients (a second user of a weight accumulates)"""
+        N, K = g["w"].shape
+        dz = g["y"].grad
+        gw = plan.param_grad(g["w"])
+        acc_w = plan._claim_param(g["w"])
+        db = None
+        if g.get("b") is not None:
+            gb = plan.param_grad(g["b"])
+            acc_b = plan._claim_param(g["b"])
+            assert acc_b == acc_w
+            db = gb.data_ptr()
+        rec = _DwGroup(dz.ptr, dz.ld, g["x"].ptr, g["x"].ld, gw.data_ptr(), K, db, self.M, N, K, 1 if acc_w else 0,
+                       needs_shadows=plan.is_half_only(g["x"]) or plan.is_half_only(g["y"]) or plan.is_half_only(dz))
+        if self.g2:
+            rec.dzh, rec.xh = plan.shadow_view(dz), plan.shadow_view(g["x"])
+        return rec
 
     def build_bwd(self, plan, gs):
         # dZ of every group lives in y.grad (pre-activation gradient, see module docstring)
@@ -826,51 +951,19 @@ class GLinear:
         # fused weights (STAR's W_d*W_s: their gradient feeds a further backward op) and ragged groups: right here.
         defer = self.row_offsets is None and not any(isinstance(g["w"], TView) or isinstance(g.get("b"), TView) for g in self.groups)
         if defer:
-            for g in self.groups:
-                N, K = g["w"].shape
-                dz = g["y"].grad
-                gw = plan.param_grad(g["w"])
-                acc_w = plan._claim_param(g["w"])
-                db = None
-                if g.get("b") is not None:
-                    gb = plan.param_grad(g["b"])
-                    acc_b = plan._claim_param(g["b"])
-                    assert acc_b == acc_w
-                    db = gb.data_ptr()
-                plan._deferred_dw.append({"dz": dz.ptr, "lddz": dz.ld, "x": g["x"].ptr, "ldx": g["x"].ld, "dw": gw.data_ptr(), "lddw": K,
-                                          "db": db, "M": self.M, "N": N, "K": K, "accumulate": 1 if acc_w else 0,
-                                          "dzh": plan.shadow_view(dz) if self.g2 else None,
-                                          "xh": plan.shadow_view(g["x"]) if self.g2 else None,
-                                          "needs_shadows": plan.is_half_only(g["x"]) or plan.is_half_only(g["y"]) or plan.is_half_only(dz)})
+            plan._deferred_dw += [self._dw_group(plan, g) for g in self.groups]
         for c0 in (range(0, len(self.groups), L.MAX_GROUPS) if not defer else []):
             chunk = self.groups[c0:c0 + L.MAX_GROUPS]
             a = L.LinBwdwArgs()
             a.n_groups = len(chunk)
             a.split_k = self.split_k[c0 // L.MAX_GROUPS]
-            plan._gemm_ws_users.append(a)          # .workspace is set when the plan is finalised (the buffer may still grow)
+            plan._gemm_ws_users.append(a)          # .workspace is set when the plan is finalised (the buffer is sized then)
             a.row_offsets = None if self.row_offsets is None else self.row_offsets.data_ptr() + 4 * c0
             for i, g in enumerate(chunk):
-                G = a.g[i]
-                N, K = g["w"].shape
-                dz = g["y"].grad
-                G.dz, G.lddz = dz.ptr, dz.ld
-                G.x, G.ldx = g["x"].ptr, g["x"].ld
-                gw = plan.param_grad(g["w"])
-                acc_w = plan._claim_param(g["w"])
-                G.dw, G.lddw = gw.data_ptr(), K
-                if g.get("b") is not None:
-                    gb = plan.param_grad(g["b"])
-                    acc_b = plan._claim_param(g["b"])
-                    assert acc_b == acc_w
-                    G.db = gb.data_ptr()
-                else:
-                    G.db = None
-                G.M, G.N, G.K = self.M, N, K
-                G.accumulate = 1 if acc_w else 0
+                self._dw_group(plan, g).fill(a.g[i])
             self._keep.append(a)
-            fl = sum(2.0 * self.M * g["w"].shape[0] * g["w"].shape[1] for g in chunk)
-            plan.bwd_steps.append(plan.call("cdc_glinear_bwd_w", C.byref(a), plan.prec, flops=fl))
-        if getattr(self, "skip_bwd_x", False):       # the grad-input of this launch is formed elsewhere (CGCMid)
+            plan.bwd_steps.append(plan.call("cdc_glinear_bwd_w", C.byref(a), plan.prec, flops=_flops(self.M, (g["w"] for g in chunk))))
+        if self.skip_bwd_x:                          # the grad-input of this launch is formed elsewhere (CGCMid, TowerChain)
             return
         # ---- grad-input: groups reading the same x reduce into one output
         outs = []      # list of (x Buf, [group indices]); indices run over this op's groups, then the adopted ones
@@ -880,7 +973,7 @@ class GLinear:
                 continue
             x = g["x"]
             for o in outs:
-                if o[0].root is x.root and o[0].col0 == x.col0 and o[0].cols == x.cols:
+                if o[0].key == x.key:
                     o[1].append(gi)
                     break
             else:
@@ -896,7 +989,6 @@ class GLinear:
             return self._build_bwd_x_g2(plan, gs, outs, allg)
         else:
             launches = _pack_bwd_x(outs, L.MAX_GROUPS, L.MAX_GROUPS)
-        ragged_acc = {}
         for la in launches:
             # all outputs of one launch share the mask scale (one plan-wide dropout rate)
             a = L.LinBwdxArgs()
@@ -917,13 +1009,7 @@ class GLinear:
                     O.mask_y = None
                     O.mask_cols = 0
                 O.M, O.K = self.M, x.cols
-                if self.row_offsets is not None:
-                    key = (id(x.root), x.col0, x.cols)
-                    if key not in ragged_acc:
-                        ragged_acc[key] = gs.claim(x)
-                    O.accumulate = 1 if ragged_acc[key] else 0
-                else:
-                    O.accumulate = 1 if gs.claim(x) else 0
+                O.accumulate = 1 if (gs.claim(x) if self.row_offsets is None else gs.claim_once(x, self)) else 0
                 for gi in gis:
                     g = self.groups[gi]
                     S = a.s[si]
@@ -939,9 +1025,8 @@ class GLinear:
                     si += 1
             a.n_seg = si
             self._keep.append(a)
-            fl = sum(2.0 * self.M * self.groups[gi]["w"].shape[0] * self.groups[gi]["w"].shape[1] for _, gis in la for gi in gis)
+            fl = _flops(self.M, (self.groups[gi]["w"] for _, gis in la for gi in gis))
             plan.bwd_steps.append(plan.call("cdc_glinear_bwd_x", C.byref(a), plan.prec, flops=fl))
-
 
     def _build_bwd_x_g2(self, plan, gs, outs, allg):
         """grad-input from the bf16 shadows of dZ and the per-step W^T copies; outputs: x.grad in fp32, plus its bf16 shadow
@@ -963,11 +1048,7 @@ class GLinear:
                     O.y = None
                 else:
                     O.y, O.ldy = xg.ptr, xg.ld
-                if half or plan.shadow_wanted(xg):
-                    O.yh, O.ldyh = plan.shadow_view(xg)
-                    plan.mark_shadow(xg)
-                else:
-                    O.yh = None
+                O.yh, O.ldyh = plan.shadow_out(xg, force=half)
                 O.bias, O.bn_partial = None, None
                 if x.mask is not None:
                     if plan.has_shadow(x):                 # the sign of the activation is the same in its bf16 shadow: half the bytes
@@ -989,17 +1070,18 @@ class GLinear:
                     si += 1
             a.n_seg = si
             self._keep.append(a)
-            fl = sum(2.0 * self.M * allg[gi]["w"].shape[0] * allg[gi]["w"].shape[1] for _, gis in la for gi in gis)
+            fl = _flops(self.M, (allg[gi]["w"] for _, gis in la for gi in gis))
             plan.bwd_steps.append(plan.call("cdc_gemm_bf16_nt", C.byref(a), what="cdc_glinear_bwd_x", flops=fl))
 
 
-class GatePool:
+class GatePool(Op):
     """softmax gates + weighted expert pooling (model/ple.py:105-123, model/mmoe.py:58-60).
 
     experts: Buf [B, n_expert*H]; gates: list of (logits Buf [B, n_sel], sel list[int]).
     """
 
     def __init__(self, plan, experts, n_expert, H, gates, outs=None):
+        super().__init__()
         assert experts.cols == n_expert * H
         self.experts, self.n_expert, self.H = experts, n_expert, H
         self.gates = gates
@@ -1013,7 +1095,6 @@ class GatePool:
                 raise RuntimeError(f"a gate mixes {len(sel)} experts; the pooling kernels support {L.WIDE_MAX_SEL}")
         if n_expert > L.WIDE_MAX_EXPERT:
             raise RuntimeError(f"{n_expert} experts in one pooling launch; the pooling kernels support {L.WIDE_MAX_EXPERT}")
-        self._keep = []
         self.tables = []
         if self.wide:
             for c0 in range(0, len(gates), L.WIDE_MAX_GATES):
@@ -1040,12 +1121,11 @@ class GatePool:
             (L.PoolBwdArgs, "cdc_gate_pool_bwd", L.MAX_GATES)
 
     def _sel(self, a, G, sel, launch):
-        G.n_sel = len(sel)
         if self.wide:
+            G.n_sel = len(sel)
             a.table = self.tables[launch].data_ptr()
         else:
-            for j, e in enumerate(sel):
-                G.sel[j] = e
+            _fill_sel(G, sel)
 
     def build_fwd(self, plan):
         Args, fn, per = self._forms("fwd")
@@ -1058,11 +1138,7 @@ class GatePool:
                 G = a.gate[i]
                 G.logits, G.ld_logits = lg.ptr, lg.ld
                 G.out, G.ld_out = self.outs[c0 + i].ptr, self.outs[c0 + i].ld
-                if plan.use_g2 and plan.shadow_wanted(self.outs[c0 + i]):
-                    G.out_h, G.ld_out_h = plan.shadow_view(self.outs[c0 + i])
-                    plan.mark_shadow(self.outs[c0 + i])
-                else:
-                    G.out_h = None
+                G.out_h, G.ld_out_h = plan.shadow_out(self.outs[c0 + i])
                 G.probs = self.probs[c0 + i].data_ptr()
                 self._sel(a, G, sel, t)
             self._keep.append(a)
@@ -1084,11 +1160,7 @@ class GatePool:
             else:
                 a.mask_relu, a.mask_scale = 0, 1.0
             a.accumulate = 1 if (acc or c0 > 0) else 0
-            if plan.use_g2 and plan.shadow_wanted(eg):       # the experts' grad-input / grad-weight read dZ through its shadow
-                a.d_experts_h, a.ld_dexp_h = plan.shadow_view(eg)
-                plan.mark_shadow(eg)
-            else:
-                a.d_experts_h = None
+            a.d_experts_h, a.ld_dexp_h = plan.shadow_out(eg)     # the experts' grad-input / grad-weight read dZ through its shadow
             for i, (lg, sel) in enumerate(chunk):
                 G = a.gate[i]
                 plan.ensure_grad(self.outs[c0 + i], gs)
@@ -1099,17 +1171,13 @@ class GatePool:
                 if gs.claim(lg):
                     raise RuntimeError("gate logits feed more than one consumer")
                 G.d_logits, G.ld_dlogits = lgg.ptr, lgg.ld
-                if plan.use_g2 and plan.shadow_wanted(lgg):
-                    G.d_logits_h, G.ld_dlogits_h = plan.shadow_view(lgg)
-                    plan.mark_shadow(lgg)
-                else:
-                    G.d_logits_h = None
+                G.d_logits_h, G.ld_dlogits_h = plan.shadow_out(lgg)
                 self._sel(a, G, sel, t)
             self._keep.append(a)
             plan.bwd_steps.append(plan.call(fn, C.byref(a)))
 
 
-class CGCMid:
+class CGCMid(Op):
     """The boundary between two extraction levels of PLE as ONE launch per direction (csrc/cgc.hip; model/ple.py:54-57,96-125):
     GatePool(level k) -> GLinear(level k+1: single-layer experts + gates) -> GatePool(level k+1).  Built from the three ops the
     model described (it takes their place in plan.ops and uses their buffers): the pooled level-k vectors exist only as bf16
@@ -1119,10 +1187,6 @@ class CGCMid:
     H1, H2 = 128, 64                      # the widths csrc/cgc.hip is instantiated for (config.py:39-42: ((256,128),(64,)))
     enabled = True                        # tests set this to False to build the three launches per direction at a matching shape
     MAX_B = 8192                          # batch rows up to which the fused boundary beats the three launches (see match)
-
-    @staticmethod
-    def _same(a, b):
-        return a.root is b.root and a.col0 == b.col0 and a.cols == b.cols and a.rows == b.rows
 
     @classmethod
     def match(cls, plan, p1, lin, p2):
@@ -1151,7 +1215,7 @@ class CGCMid:
 
         def src_of(x):
             for i, o in enumerate(p1.outs):
-                if cls._same(o, x):
+                if o.same(x):
                     return i
             return None
         srcs = []
@@ -1163,7 +1227,7 @@ class CGCMid:
             srcs.append(src_of(g["x"]))
         for t, g in enumerate(lin.groups[ne2:]):
             lg, sel = p2.gates[t]
-            if not (cls._same(g["y"], lg) and g["act_cols"] == 0 and g["w"].shape[0] == len(sel) and g["w"].shape[1] == cls.H1 and
+            if not (g["y"].same(lg) and g["act_cols"] == 0 and g["w"].shape[0] == len(sel) and g["w"].shape[1] == cls.H1 and
                     isinstance(g["w"], torch.Tensor)):
                 return None
             srcs.append(src_of(g["x"]))
@@ -1177,6 +1241,7 @@ class CGCMid:
         return srcs
 
     def __init__(self, plan, p1, lin, p2, srcs):
+        super().__init__()
         self.p1, self.lin, self.p2, self.srcs = p1, lin, p2, srcs
         i = plan.ops.index(p1)
         assert plan.ops[i + 1] is lin and plan.ops[i + 2] is p2
@@ -1186,7 +1251,6 @@ class CGCMid:
         # dZ of both expert levels: bf16 alone (read by the grad-weight launches and the level-k grad-input launch)
         plan.make_grad_half_only(p1.experts)
         plan.make_grad_half_only(p2.experts)
-        self._keep = []
 
     def build_fwd(self, plan):
         p1, lin, p2 = self.p1, self.lin, self.p2
@@ -1203,9 +1267,7 @@ class CGCMid:
             G.probs = p1.probs[i].data_ptr()
             G.pooled_h, G.ld_pooled_h = plan.shadow_view(p1.outs[i])
             plan.mark_shadow(p1.outs[i])
-            G.n_sel = len(sel)
-            for j, e in enumerate(sel):
-                G.sel[j] = e
+            _fill_sel(G, sel)
         for e, g in enumerate(lin.groups[:ne2]):
             E = a.e2[e]
             wh, _ = plan.wshadow(g["w"])
@@ -1221,17 +1283,11 @@ class CGCMid:
             G.probs = p2.probs[t].data_ptr()
             o = p2.outs[t]
             G.out, G.ld_out = o.ptr, o.ld
-            if plan.shadow_wanted(o):
-                G.out_h, G.ld_out_h = plan.shadow_view(o)
-                plan.mark_shadow(o)
-            else:
-                G.out_h = None
-            G.src, G.n_sel = self.srcs[ne2 + t], len(sel)
-            for j, e in enumerate(sel):
-                G.sel[j] = e
+            G.out_h, G.ld_out_h = plan.shadow_out(o)
+            G.src = self.srcs[ne2 + t]
+            _fill_sel(G, sel)
         self._keep.append(a)
-        fl = sum(2.0 * plan.B * g["w"].shape[0] * g["w"].shape[1] for g in lin.groups)
-        plan.fwd_steps.append(plan.call("cdc_cgc_mid_fwd", C.byref(a), flops=fl))
+        plan.fwd_steps.append(plan.call("cdc_cgc_mid_fwd", C.byref(a), flops=_flops(plan.B, (g["w"] for g in lin.groups))))
 
     def build_bwd(self, plan, gs):
         p1, lin, p2 = self.p1, self.lin, self.p2
@@ -1261,18 +1317,12 @@ class CGCMid:
             if gs.claim(lg):
                 raise RuntimeError("gate logits feed more than one consumer")
             G.d_logits, G.ld_dlogits = lgg.ptr, lgg.ld
-            if plan.shadow_wanted(lgg):
-                G.d_logits_h, G.ld_dlogits_h = plan.shadow_view(lgg)
-                plan.mark_shadow(lgg)
-            else:
-                G.d_logits_h = None
+            G.d_logits_h, G.ld_dlogits_h = plan.shadow_out(lgg)
         for i, (lg, sel) in enumerate(p1.gates):
             G = a.g1[i]
             G.probs = p1.probs[i].data_ptr()
             fill_logit_grads(G, lg)
-            G.n_sel = len(sel)
-            for j, e in enumerate(sel):
-                G.sel[j] = e
+            _fill_sel(G, sel)
         for e, g in enumerate(lin.groups[:ne2]):
             _, wt = plan.wshadow(g["w"])
             a.e2[e].wt, a.e2[e].ldwt, a.e2[e].src = wt.data_ptr(), wt.stride(0), self.srcs[e]
@@ -1286,12 +1336,10 @@ class CGCMid:
             fill_logit_grads(G, lg)
             _, wt = plan.wshadow(g["w"])
             G.wt, G.ldwt = wt.data_ptr(), wt.stride(0)
-            G.src, G.n_sel = self.srcs[ne2 + t], len(sel)
-            for j, e in enumerate(sel):
-                G.sel[j] = e
+            G.src = self.srcs[ne2 + t]
+            _fill_sel(G, sel)
         self._keep.append(a)
-        fl = sum(2.0 * plan.B * g["w"].shape[0] * g["w"].shape[1] for g in lin.groups)
-        plan.bwd_steps.append(plan.call("cdc_cgc_mid_bwd", C.byref(a), flops=fl))
+        plan.bwd_steps.append(plan.call("cdc_cgc_mid_bwd", C.byref(a), flops=_flops(plan.B, (g["w"] for g in lin.groups))))
         # the level-k+1 grad-weight contractions stay with the batched launches at the end of backward
         lin.skip_bwd_x = True
         lin.build_bwd(plan, gs)
@@ -1300,20 +1348,10 @@ class CGCMid:
 def fuse_cgc_mid(plan):
     """Replaces every (GatePool, GLinear, GatePool) run of plan.ops that is a PLE level boundary of the instantiated shape by ONE
     CGCMid op.  Called by the model that KNOWS the pooled level-k vectors have no other reader (model/ple.py: ple_inputs)."""
-    if not CGCMid.enabled:
-        return 0
-    n = 0
-    i = 0
-    while i + 2 < len(plan.ops):
-        srcs = CGCMid.match(plan, plan.ops[i], plan.ops[i + 1], plan.ops[i + 2])
-        if srcs is not None:
-            CGCMid(plan, plan.ops[i], plan.ops[i + 1], plan.ops[i + 2], srcs)
-            n += 1
-        i += 1
-    return n
+    return _fuse_runs(plan, CGCMid, 3) if CGCMid.enabled else 0
 
 
-class ExpertPair:
+class ExpertPair(Op):
     """Two consecutive BatchNorm-free expert layers — GLinear(x -> H1, ReLU, dropout; hidden kept as a bf16 shadow only) and
     GLinear(H1 -> H2, ReLU, dropout [+ gate projections of x riding along]) — as ONE forward launch (csrc/pair.hip; model/ple.py:83-94,
     model/layer.py:185-196).  Built from the two ops the model described (it takes their place in plan.ops and uses their buffers);
@@ -1338,22 +1376,20 @@ class ExpertPair:
             if not (isinstance(ga["w"], torch.Tensor) and isinstance(gb["w"], torch.Tensor) and tuple(ga["w"].shape) == (cls.H1, K) and
                     tuple(gb["w"].shape) == (cls.H2, cls.H1) and ga["act_cols"] == cls.H1 and gb["act_cols"] == cls.H2):
                 return False
-            if not (CGCMid._same(ga["y"], gb["x"]) and plan.is_half_only(ga["y"]) and not plan.is_half_only(ga["x"])):
+            if not (ga["y"].same(gb["x"]) and plan.is_half_only(ga["y"]) and not plan.is_half_only(ga["x"])):
                 return False
         for j, g in enumerate(lb.groups[n:]):                 # the riders: narrow, no activation, reading what expert j reads
             if not (isinstance(g["w"], torch.Tensor) and g["w"].shape[0] <= 16 and g["w"].shape[1] == K and g["act_cols"] == 0 and
-                    CGCMid._same(g["x"], la.groups[j]["x"]) and not plan.is_half_only(g["y"])):
+                    g["x"].same(la.groups[j]["x"]) and not plan.is_half_only(g["y"])):
                 return False
         return True
 
     def __init__(self, plan, la, lb):
+        super().__init__()
         self.la, self.lb = la, lb
         i = plan.ops.index(la)
         assert plan.ops[i + 1] is lb
         plan.ops[i:i + 2] = [self]
-        self._keep = []
-        for op in (la, lb):                                    # (their backward builders append argument blocks here)
-            op._keep = getattr(op, "_keep", [])
 
     def build_fwd(self, plan):
         la, lb = self.la, self.lb
@@ -1381,11 +1417,7 @@ class ExpertPair:
                 E.y = None
             else:
                 E.y, E.ldy = y.ptr, y.ld
-            if plan.shadow_wanted(y):
-                E.yh, E.ldyh = plan.shadow_view(y)
-                plan.mark_shadow(y)
-            else:
-                E.yh = None
+            E.yh, E.ldyh = plan.shadow_out(y)
             E.stream1, E.stream2 = i, i                        # the group's index in each of the two launches
             E.ws, E.ns = None, 0
         for j, g in enumerate(lb.groups[n:]):
@@ -1397,8 +1429,8 @@ class ExpertPair:
             if plan.shadow_wanted(g["y"]):
                 raise RuntimeError("ExpertPair: a rider's output is read by a bf16 contraction (no shadow is written for it)")
         self._keep.append(a)
-        fl = sum(2.0 * plan.B * g["w"].shape[0] * g["w"].shape[1] for g in la.groups + lb.groups)
-        plan.fwd_steps.append(plan.call("cdc_expert_pair_fwd", C.byref(a), what="cdc_glinear_pair_fwd", flops=fl))
+        plan.fwd_steps.append(plan.call("cdc_expert_pair_fwd", C.byref(a), what="cdc_glinear_pair_fwd",
+                                        flops=_flops(plan.B, (g["w"] for g in la.groups + lb.groups))))
 
     def build_bwd(self, plan, gs):
         self.lb.build_bwd(plan, gs)
@@ -1408,19 +1440,10 @@ class ExpertPair:
 def fuse_expert_pair(plan):
     """Replaces every (GLinear, GLinear) run of plan.ops that is the two layers of a level's experts in the instantiated shape by ONE
     ExpertPair op."""
-    if not ExpertPair.enabled:
-        return 0
-    n = 0
-    i = 0
-    while i + 1 < len(plan.ops):
-        if ExpertPair.match(plan, plan.ops[i], plan.ops[i + 1]):
-            ExpertPair(plan, plan.ops[i], plan.ops[i + 1])
-            n += 1
-        i += 1
-    return n
+    return _fuse_runs(plan, ExpertPair, 2) if ExpertPair.enabled else 0
 
 
-class BatchNorm:
+class BatchNorm(Op):
     """BatchNorm1d (+ReLU, +dropout) over column segments sharing one launch.
 
     segs: list of dicts {x: Buf, bn: module-like with weight/bias/running_mean/running_var/num_batches_tracked
@@ -1428,6 +1451,7 @@ class BatchNorm:
     """
 
     def __init__(self, plan, segs, relu=True, dropout=True, eps=1e-5, momentum=0.1, row_offsets=None, M=None, skip_le1=False):
+        super().__init__()
         self.segs = segs
         self.skip_le1 = skip_le1
         self.relu = relu
@@ -1448,7 +1472,6 @@ class BatchNorm:
             s["save_invstd"] = torch.ones(Cn, dtype=torch.float32, device=plan.device)
             self.outs.append(y)
             total_c += Cn
-        self._keep = []
         for c0 in range(0, len(segs), L.MAX_BN_SEGS):
             plan.need_bn_ws(self.M, sum(s["x"].cols for s in segs[c0:c0 + L.MAX_BN_SEGS]))
         plan.add(self)
@@ -1469,8 +1492,8 @@ class BatchNorm:
                 S.x, S.ldx = s["x"].ptr, s["x"].ld
                 S.y, S.ldy = s["y"].ptr, s["y"].ld
                 S.half = 0
-                prod = plan._lin_producer.get((id(s["x"].root), s["x"].col0, s["x"].cols))
-                s["_lin_g2"] = bool(prod is not None and getattr(prod["op"], "g2", False) and prod["G"].act_cols == 0)
+                prod = plan._lin_producer.get(s["x"].key)
+                s["_lin_g2"] = bool(prod is not None and prod["op"].g2 and prod["G"].act_cols == 0)
                 # the caller vouches (seg["half_only"]) that y is read by bf16 contractions only — and one did ask for the shadow:
                 # y then exists as bf16 alone (its sign is the relu/dropout mask of the backward)
                 if s.get("half_only") and plan.use_g2 and plan.shadow_wanted(s["y"]) and self.row_offsets is None:
@@ -1483,29 +1506,23 @@ class BatchNorm:
                 S.num_batches_tracked = None if nbt is None else nbt.data_ptr()
                 S.C = s["x"].cols
                 S.row_group = s.get("row_group", 0)
-                if plan.use_g2 and plan.shadow_wanted(s["y"]):
-                    S.yh, S.ldyh = plan.shadow_view(s["y"])
-                    plan.mark_shadow(s["y"])
-                else:
-                    S.yh = None
+                S.yh, S.ldyh = plan.shadow_out(s["y"])
             self._fuse_stats(plan, a, chunk)
-            self._keep.append(a)
-            if plan.dist is not None and plan.training:
-                # global-batch statistics: partial sums -> all-reduce -> normalise
-                total_c = sum(s["x"].cols for s in chunk)
-                ex = torch.zeros(2 * total_c + len(chunk), dtype=torch.float64, device=plan.device)
-                a.phase, a.exchange = 1, ex.data_ptr()
-                a2 = L.BnFwdArgs.from_buffer_copy(a)
-                a2.phase = 2
-                self._keep += [ex, a2]
-                plan.fwd_steps.append(plan.call("cdc_bn_fwd", C.byref(a), what="cdc_bn_fwd(stats)"))
-                plan.fwd_steps.append(plan.comm(lambda ex=ex: plan.dist.all_reduce_sum(ex)))
-                plan.fwd_steps.append(plan.call("cdc_bn_fwd", C.byref(a2), what="cdc_bn_fwd(apply)"))
-            else:
-                step = plan.call("cdc_bn_fwd", C.byref(a))
-                self._fwd_calls = getattr(self, "_fwd_calls", []) + [step]
-                plan.fwd_steps.append(step)
+            self._emit(plan, plan.fwd_steps, "cdc_bn_fwd", a, chunk)
             plan._last_bn_step = len(plan.fwd_steps)
+
+    def _emit(self, plan, steps, fn, a, chunk):
+        """one launch; data parallel, training: global-batch statistics — partial sums, all-reduce, then the launch that applies them"""
+        self._keep.append(a)
+        if plan.dist is None or not plan.training:
+            steps.append(plan.call(fn, C.byref(a)))
+            return
+        ex = torch.zeros(2 * sum(s["x"].cols for s in chunk) + len(chunk), dtype=torch.float64, device=plan.device)
+        a.phase, a.exchange = 1, ex.data_ptr()
+        a2 = type(a).from_buffer_copy(a)
+        a2.phase = 2
+        self._keep += [ex, a2]
+        plan.dp_phases(steps, [plan.call(fn, C.byref(a), what=fn + "(stats)"), plan.call(fn, C.byref(a2), what=fn + "(apply)")], [ex])
 
     def _fuse_stats(self, plan, a, chunk):
         """If every segment of this launch normalises the output of a plain linear launch (no activation, same rows, no
@@ -1517,7 +1534,7 @@ class BatchNorm:
         prods = []
         for s in chunk:
             x = s["x"]
-            p = plan._lin_producer.get((id(x.root), x.col0, x.cols))
+            p = plan._lin_producer.get(x.key)
             if (p is None or p["taken"] or p["op"].row_offsets is not None or p["op"].M != self.M or p["G"].act_cols != 0 or
                     p["step"] < plan._last_bn_step):
                 return
@@ -1533,14 +1550,13 @@ class BatchNorm:
     def build_bwd(self, plan, gs):
         # segments that normalise the SAME input over the same rows (STAR all-towers: every domain_norm reads the
         # embeddings) cannot write one gradient buffer concurrently: each writes its own slice, summed afterwards
-        keys = [(id(s["x"].root), s["x"].col0, s["x"].cols) for s in self.segs]
+        keys = [s["x"].key for s in self.segs]
         shared = self.row_offsets is None and len(set(keys)) < len(keys)
         fan_in = None
         if shared:
             assert len(set(keys)) == 1, "BatchNorm launch mixes shared and private inputs"
             x = self.segs[0]["x"]
             fan_in = plan.new(x.cols * len(self.segs), rows=x.rows)
-        ragged_acc = {}
         for c0 in range(0, len(self.segs), L.MAX_BN_SEGS):
             chunk = self.segs[c0:c0 + L.MAX_BN_SEGS]
             a = L.BnBwdArgs()
@@ -1570,21 +1586,13 @@ class BatchNorm:
                     S.dx, S.lddx = sl.ptr, sl.ld
                 else:
                     xg = s["x"].grad
-                    key = keys[c0 + i]
-                    if self.row_offsets is not None:
-                        if key not in ragged_acc:
-                            ragged_acc[key] = gs.claim(s["x"])
-                        S.accumulate_dx = 1 if ragged_acc[key] else 0
-                    elif gs.claim(s["x"]):
-                        S.accumulate_dx = 1
+                    S.accumulate_dx = 1 if (gs.claim(s["x"]) if self.row_offsets is None else gs.claim_once(s["x"], self)) else 0
                     S.dx, S.lddx = xg.ptr, xg.ld
-                    if plan.use_g2 and plan.shadow_wanted(xg):
-                        S.dxh, S.lddxh = plan.shadow_view(xg)
-                        plan.mark_shadow(xg)
-                        # x is the output of a bf16 linear launch whose backward reads dZ through the shadow only
-                        if s.get("_lin_g2") and not S.accumulate_dx and self.row_offsets is None:
-                            plan.make_grad_half_only(s["x"])
-                            S.dx = None
+                    S.dxh, S.lddxh = plan.shadow_out(xg)
+                    # x is the output of a bf16 linear launch whose backward reads dZ through the shadow only
+                    if S.dxh and s.get("_lin_g2") and not S.accumulate_dx and self.row_offsets is None:
+                        plan.make_grad_half_only(s["x"])
+                        S.dx = None
                 S.gamma = s["gamma"].data_ptr()
                 if plan.training:
                     S.save_mean, S.save_invstd = s["save_mean"].data_ptr(), s["save_invstd"].data_ptr()
@@ -1603,20 +1611,8 @@ class BatchNorm:
                     S.dbeta = None if s.get("dbeta") is None else s["dbeta"].data_ptr()
                 S.C = s["x"].cols
                 S.row_group = s.get("row_group", 0)
-            self._keep.append(a)
             plan.bwd_steps.extend(pre)
-            if plan.dist is not None and plan.training:
-                total_c = sum(s["x"].cols for s in chunk)
-                ex = torch.zeros(2 * total_c + len(chunk), dtype=torch.float64, device=plan.device)
-                a.phase, a.exchange = 1, ex.data_ptr()
-                a2 = L.BnBwdArgs.from_buffer_copy(a)
-                a2.phase = 2
-                self._keep += [ex, a2]
-                plan.bwd_steps.append(plan.call("cdc_bn_bwd", C.byref(a), what="cdc_bn_bwd(stats)"))
-                plan.bwd_steps.append(plan.comm(lambda ex=ex: plan.dist.all_reduce_sum(ex)))
-                plan.bwd_steps.append(plan.call("cdc_bn_bwd", C.byref(a2), what="cdc_bn_bwd(apply)"))
-            else:
-                plan.bwd_steps.append(plan.call("cdc_bn_bwd", C.byref(a)))
+            self._emit(plan, plan.bwd_steps, "cdc_bn_bwd", a, chunk)
         if fan_in is not None:
             x = self.segs[0]["x"]
             if x.mask is not None:
@@ -1627,7 +1623,7 @@ class BatchNorm:
                                             C.c_int64(x.rows), x.cols, len(self.segs), acc))
 
 
-class RowDot:
+class RowDot(Op):
     """out[b] = sigmoid?(x[b,:]·w + bias + sum addends[b])  for several groups (towers) in one launch.
 
     groups: list of dicts {x: Buf, w: Parameter [1,K] or [K], b: Parameter [1] or None, out: Buf [B,1]}
@@ -1635,6 +1631,7 @@ class RowDot:
     """
 
     def __init__(self, plan, groups, addends=(), sigmoid=False, row_offsets=None, M=None):
+        super().__init__()
         self.groups, self.addends, self.sigmoid = groups, list(addends), sigmoid
         self.row_offsets = row_offsets
         self.M = plan.B if M is None else M
@@ -1655,7 +1652,6 @@ class RowDot:
                 self.dlogit = [shared for _ in groups]
             else:
                 self.dlogit = [plan.new(1) for _ in groups]
-        self._keep = []
         plan.add(self)
 
     def build_fwd(self, plan):
@@ -1683,7 +1679,7 @@ class RowDot:
         # in successive launches; groups with private inputs (towers) share one
         waves = []
         for i, g in enumerate(self.groups):
-            key = (id(g["x"].root), g["x"].col0, g["x"].cols)
+            key = g["x"].key
             for w in waves:
                 if self.row_offsets is not None or key not in w["keys"]:
                     w["keys"].add(key)
@@ -1691,12 +1687,11 @@ class RowDot:
                     break
             else:
                 waves.append({"keys": {key}, "idx": [i]})
-        ragged_acc = {}
         for w in waves:
             for c0 in range(0, len(w["idx"]), L.MAX_GROUPS):
-                self._build_bwd_launch(plan, gs, w["idx"][c0:c0 + L.MAX_GROUPS], ragged_acc)
+                self._build_bwd_launch(plan, gs, w["idx"][c0:c0 + L.MAX_GROUPS])
 
-    def _build_bwd_launch(self, plan, gs, idxs, ragged_acc):
+    def _build_bwd_launch(self, plan, gs, idxs):
         a = L.RowdotBwdArgs()
         a.n_groups, a.sigmoid, a.M = len(idxs), 1 if self.sigmoid else 0, self.M
         first = idxs[0]
@@ -1721,13 +1716,7 @@ class RowDot:
                     raise RuntimeError("rowdot cannot consume an activation-fused linear output")
                 xg = g["x"].grad
                 G.dx, G.lddx = xg.ptr, xg.ld
-                if self.row_offsets is not None:
-                    key = (id(g["x"].root), g["x"].col0, g["x"].cols)
-                    if key not in ragged_acc:
-                        ragged_acc[key] = gs.claim(g["x"])
-                    G.accumulate_dx = 1 if ragged_acc[key] else 0
-                else:
-                    G.accumulate_dx = 1 if gs.claim(g["x"]) else 0
+                G.accumulate_dx = 1 if (gs.claim(g["x"]) if self.row_offsets is None else gs.claim_once(g["x"], self)) else 0
             gw = plan.param_grad(g["w"])
             if plan._claim_param(g["w"]):
                 # the same weight is used by an earlier-built op (CrossNetMix gates are shared by every layer):
@@ -1772,12 +1761,35 @@ class RowDot:
                 self._keep.append(n)
                 post.append(plan.call("cdc_add_n", C.byref(n)))
         self._keep.append(a)
-        self.bwd_args = getattr(self, "bwd_args", []) + [a]       # (trainer: the fused BCE is switched on in the head's launch)
+        self.bwd_args.append(a)                  # (trainer: the fused BCE is switched on in the head's launch)
         plan.bwd_steps.append(plan.call("cdc_rowdot_bwd", C.byref(a)))
         plan.bwd_steps.extend(post)
 
 
-class TowerHead:
+def _fill_wide(a, wide):
+    """the wide term of a head's argument block (HeadArgs / TowerArgs); wide: {x, w, b} or None"""
+    if wide is not None:
+        a.wide_x, a.ld_wide = wide["x"].ptr, wide["x"].ld
+        a.wide_w = wide["w"].data_ptr()
+        a.wide_bias = None if wide.get("b") is None else wide["b"].data_ptr()
+        a.wide_K = wide["w"].numel()
+
+
+def _fill_wide_bwd(a, wide, plan, gs):
+    if wide is None:
+        return
+    if wide["x"].mask is not None:
+        raise RuntimeError("the wide term cannot consume an activation-fused linear output")
+    xg = wide["x"].grad
+    a.accumulate_wide_dx = 1 if gs.claim(wide["x"]) else 0
+    a.wide_dx, a.ld_wide_dx = xg.ptr, xg.ld
+    if plan._claim_param(wide["w"]) or (wide.get("b") is not None and plan._claim_param(wide["b"])):
+        raise RuntimeError("the wide term's parameters are used twice in one plan")
+    a.wide_dw = plan.param_grad(wide["w"]).data_ptr()
+    a.wide_dbias = None if wide.get("b") is None else plan.param_grad(wide["b"]).data_ptr()
+
+
+class TowerHead(Op):
     """The tower head in one launch per direction (csrc/head.hip; model/layer.py:48-56): per tower the output Linear(->1), plus the
     wide term formed once per row, plus further [B,1] logits, sigmoid, column t of `out`.  The backward also forms the wide
     term's gradient (the sum of the towers' logit gradients) and, with the trainer's fused loss, BCELoss and its gradient.
@@ -1786,6 +1798,7 @@ class TowerHead:
     wide: dict {x: Buf [B,Kw], w, b} or None;  addends: Bufs [B,1]."""
 
     def __init__(self, plan, towers, out, wide=None, addends=(), sigmoid=True):
+        super().__init__()
         assert 0 < len(towers) <= L.HEAD_MAX_TOWERS and len(addends) <= 2 and out.cols == len(towers)
         self.towers, self.out, self.wide, self.addends, self.sigmoid = towers, out, wide, list(addends), sigmoid
         self.M = plan.B
@@ -1804,7 +1817,6 @@ class TowerHead:
                     raise RuntimeError("the tower head cannot take one input buffer twice (its gradients would need a fan-in add)")
         width = sum(t["w"].numel() + 1 for t in towers) + (wide["w"].numel() + 1 if wide is not None else 0)
         self.ws = torch.empty(L.ROWDOT_PARTS * width, dtype=torch.float32, device=plan.device)
-        self._keep = []
         plan.add(self)
 
     def _fill(self, a, plan):
@@ -1816,12 +1828,7 @@ class TowerHead:
             T.w = t["w"].data_ptr()
             T.bias = None if t.get("b") is None else t["b"].data_ptr()
             T.K = t["w"].numel()
-        if self.wide is not None:
-            w = self.wide
-            a.wide_x, a.ld_wide = w["x"].ptr, w["x"].ld
-            a.wide_w = w["w"].data_ptr()
-            a.wide_bias = None if w.get("b") is None else w["b"].data_ptr()
-            a.wide_K = w["w"].numel()
+        _fill_wide(a, self.wide)
         for i, ad in enumerate(self.addends):
             a.addend[i], a.ld_addend[i] = ad.ptr, ad.ld
 
@@ -1829,9 +1836,7 @@ class TowerHead:
         a = L.HeadArgs()
         self._fill(a, plan)
         self._keep.append(a)
-        step = plan.call("cdc_head_fwd", C.byref(a))
-        self._fwd_calls = [step]
-        plan.fwd_steps.append(step)
+        plan.fwd_steps.append(plan.call("cdc_head_fwd", C.byref(a)))
 
     def build_bwd(self, plan, gs):
         a = L.HeadArgs()
@@ -1848,28 +1853,18 @@ class TowerHead:
                 raise RuntimeError("a tower's output layer is used twice in one plan")
             T.dw = plan.param_grad(t["w"]).data_ptr()
             T.dbias = None if t.get("b") is None else plan.param_grad(t["b"]).data_ptr()
-        if self.wide is not None:
-            w = self.wide
-            if w["x"].mask is not None:
-                raise RuntimeError("the wide term cannot consume an activation-fused linear output")
-            xg = w["x"].grad
-            a.accumulate_wide_dx = 1 if gs.claim(w["x"]) else 0
-            a.wide_dx, a.ld_wide_dx = xg.ptr, xg.ld
-            if plan._claim_param(w["w"]) or (w.get("b") is not None and plan._claim_param(w["b"])):
-                raise RuntimeError("the wide term's parameters are used twice in one plan")
-            a.wide_dw = plan.param_grad(w["w"]).data_ptr()
-            a.wide_dbias = None if w.get("b") is None else plan.param_grad(w["b"]).data_ptr()
+        _fill_wide_bwd(a, self.wide, plan, gs)
         for i, ad in enumerate(self.addends):
             adg = ad.grad
             a.accumulate_d_addend[i] = 1 if gs.claim(ad) else 0
             a.d_addend[i], a.ld_d_addend[i] = adg.ptr, adg.ld
         a.workspace = self.ws.data_ptr()
         self._keep.append(a)
-        self.bwd_args = [a]                      # (trainer: the fused BCE is switched on in this launch)
+        self.bwd_args.append(a)                  # (trainer: the fused BCE is switched on in this launch)
         plan.bwd_steps.append(plan.call("cdc_head_bwd", C.byref(a)))
 
 
-class TowerChain:
+class TowerChain(Op):
     """The towers of a multi-tower model as ONE launch per direction (csrc/tower.hip; model/layer.py:35-56,178-206): built from
     the five ops the model described — GLinear, BatchNorm, GLinear, BatchNorm, TowerHead — where they have the instantiated
     shape; it takes their place in plan.ops and uses their buffers, seeds and parameters.  The grad-weight contractions of the two
@@ -1911,12 +1906,11 @@ class TowerChain:
         H2 = l2.groups[0]["w"].shape[0]
         if (H0, H1, H2) not in cls.SHAPES:
             return False
-        same = CGCMid._same
         for i in range(n):
             g1, g2, s1, s2, t = l1.groups[i], l2.groups[i], b1.segs[i], b2.segs[i], head.towers[i]
             if not (tuple(g1["w"].shape) == (H1, H0) and tuple(g2["w"].shape) == (H2, H1) and t["w"].numel() == H2):
                 return False
-            if not (same(g1["y"], s1["x"]) and same(s1["y"], g2["x"]) and same(g2["y"], s2["x"]) and same(s2["y"], t["x"])):
+            if not (g1["y"].same(s1["x"]) and s1["y"].same(g2["x"]) and g2["y"].same(s2["x"]) and s2["y"].same(t["x"])):
                 return False
         if head.wide is not None:
             w = head.wide
@@ -1926,6 +1920,7 @@ class TowerChain:
         return True
 
     def __init__(self, plan, l1, b1, l2, b2, head):
+        super().__init__()
         self.l1, self.b1, self.l2, self.b2, self.head = l1, b1, l2, b2, head
         i = plan.ops.index(l1)
         assert plan.ops[i:i + 5] == [l1, b1, l2, b2, head]
@@ -1936,9 +1931,7 @@ class TowerChain:
         self.H2 = l2.groups[0]["w"].shape[0]
         self.tmo_word = torch.zeros(1, dtype=torch.int32, device=plan.device)     # CDC_TOWER_ERR_TIMEOUT lands here (TrainStep.check_ids)
         self.ws = None
-        self._keep = []
-        for op in (l1, l2):
-            op._keep = getattr(op, "_keep", [])
+        self._ex = None                   # data parallel: the exchange buffers of the split form (_dp_buffers)
         # the hidden activation is read by the second contraction and the grad-weight launch only: bf16 alone
         for s in b1.segs:
             plan.want_shadow(s["y"])
@@ -1952,12 +1945,7 @@ class TowerChain:
         a.seed1, a.seed2 = self.b1.seed & 0xFFFFFFFFFFFFFFFF, self.b2.seed & 0xFFFFFFFFFFFFFFFF
         a.seed_offset_dev = plan.step_dev.data_ptr()
         a.out, a.ld_out = head.out.ptr, head.out.ld
-        if head.wide is not None:
-            w = head.wide
-            a.wide_x, a.ld_wide = w["x"].ptr, w["x"].ld
-            a.wide_w = w["w"].data_ptr()
-            a.wide_bias = None if w.get("b") is None else w["b"].data_ptr()
-            a.wide_K = w["w"].numel()
+        _fill_wide(a, head.wide)
         a.err = self.tmo_word.data_ptr()
         for i in range(self.n):
             T = a.t[i]
@@ -1992,7 +1980,7 @@ class TowerChain:
 
     def _dp_buffers(self, a, plan):
         """the split form's exchange buffers ([2 n C column sums | n row counts] doubles per exchange) and gradient scratch"""
-        if getattr(self, "_ex", None) is None:
+        if self._ex is None:
             n = self.n
             self._ex = [torch.zeros(2 * n * c + n, dtype=torch.float64, device=plan.device) for c in (self.H1, self.H2, self.H2, self.H1)]
             self._dy2, self._dy1 = plan.new(n * self.H2), plan.new(n * self.H1)
@@ -2004,11 +1992,8 @@ class TowerChain:
             T.dy2, T.lddy2, T.dy1, T.lddy1 = y2.ptr, y2.ld, y1.ptr, y1.ld
 
     def _dp_steps(self, plan, a, phases, exchanges, steps, flops):
-        for k, ph in enumerate(phases):
-            steps.append(plan.call("cdc_tower_dp", C.byref(a), ph, what=f"cdc_tower_dp({ph})", flops=flops if k == 0 else 0.0))
-            if k < len(exchanges):
-                ex = self._ex[exchanges[k]]
-                steps.append(plan.comm(lambda ex=ex: plan.dist.all_reduce_sum(ex)))
+        plan.dp_phases(steps, [plan.call("cdc_tower_dp", C.byref(a), ph, what=f"cdc_tower_dp({ph})", flops=flops if k == 0 else 0.0)
+                               for k, ph in enumerate(phases)], [self._ex[e] for e in exchanges])
 
     def build_fwd(self, plan):
         plan.ensure_shadows([g["x"] for g in self.l1.groups], plan.fwd_steps)
@@ -2017,7 +2002,7 @@ class TowerChain:
         for s in self.b1.segs:
             plan.mark_shadow(s["y"])
         self._keep.append(a)
-        fl = sum(2.0 * plan.B * g["w"].shape[0] * g["w"].shape[1] for g in self.l1.groups + self.l2.groups)
+        fl = _flops(plan.B, (g["w"] for g in self.l1.groups + self.l2.groups))
         if plan.dist is not None:
             # global-batch BatchNorm statistics: phases 1 | all-reduce | 2 | all-reduce | 3 (csrc/tower.hip cdc_tower_dp)
             self._dp_buffers(a, plan)
@@ -2028,7 +2013,6 @@ class TowerChain:
         def step(stream):
             if not self.one_launch:               # (one_launch: both directions go out where the backward stands, cdc_tower_step)
                 fwd(stream)
-        self._fwd_calls = [step]
         plan.fwd_steps.append(step)
 
     def build_bwd(self, plan, gs):
@@ -2061,20 +2045,10 @@ class TowerChain:
             if plan.is_half_only(xg):
                 raise RuntimeError("TowerChain: the tower input's gradient is kept as bf16 only")
             T.dx, T.lddx = xg.ptr, xg.ld
-        if head.wide is not None:
-            w = head.wide
-            if w["x"].mask is not None:
-                raise RuntimeError("the wide term cannot consume an activation-fused linear output")
-            xg = w["x"].grad
-            a.accumulate_wide_dx = 1 if gs.claim(w["x"]) else 0
-            a.wide_dx, a.ld_wide_dx = xg.ptr, xg.ld
-            if plan._claim_param(w["w"]) or (w.get("b") is not None and plan._claim_param(w["b"])):
-                raise RuntimeError("the wide term's parameters are used twice in one plan")
-            a.wide_dw = plan.param_grad(w["w"]).data_ptr()
-            a.wide_dbias = None if w.get("b") is None else plan.param_grad(w["b"]).data_ptr()
+        _fill_wide_bwd(a, head.wide, plan, gs)
         self._keep.append(a)
-        self.bwd_args = [a]                      # (trainer: the fused BCE is switched on in this launch)
-        fl = sum(2.0 * plan.B * g["w"].shape[0] * g["w"].shape[1] for g in self.l1.groups + self.l2.groups)
+        self.bwd_args.append(a)                  # (trainer: the fused BCE is switched on in this launch)
+        fl = _flops(plan.B, (g["w"] for g in self.l1.groups + self.l2.groups))
         if plan.dist is not None:
             self._dp_buffers(a, plan)
             self._dp_steps(plan, a, (4, 5, 6), (2, 3), plan.bwd_steps, fl)
@@ -2095,16 +2069,7 @@ def fuse_tower(plan, enable=True):
     """Replaces the run (GLinear, BatchNorm, GLinear, BatchNorm, TowerHead) of plan.ops that is the towers of a multi-tower model in
     the instantiated shape by ONE TowerChain op (training plans on one GPU; every other shape, precision or mode keeps the five
     ops)."""
-    if not (enable and TowerChain.enabled):
-        return 0
-    n = 0
-    i = 0
-    while i + 4 < len(plan.ops):
-        if TowerChain.match(plan, *plan.ops[i:i + 5]):
-            TowerChain(plan, *plan.ops[i:i + 5])
-            n += 1
-        i += 1
-    return n
+    return _fuse_runs(plan, TowerChain, 5) if (enable and TowerChain.enabled) else 0
 
 
 class CrossLayer:
@@ -2377,11 +2342,12 @@ class FMInteraction:
                                         C.c_int64(xg.ld), C.c_int64(self.x.rows), self.F, self.D, 1 if acc else 0))
 
 
-class MatmulRight:
+class MatmulRight(Op):
     """y_g = x_g @ M_g with M_g stored [K, N] row-major (CrossNetMix's V: model/layer.py:384 `v_list[i][k].t() @ x`).
     The three contractions reuse the grouped-linear kernels with the operand roles rotated."""
 
     def __init__(self, plan, groups):
+        super().__init__()
         self.groups = groups
         self.M = plan.B
         assert len(groups) <= L.MAX_GROUPS
@@ -2391,7 +2357,6 @@ class MatmulRight:
             if g.get("out") is None:
                 g["out"] = plan.new(N)
         self.outs = [g["out"] for g in groups]
-        self._keep = []
         plan.add(self)
 
     def build_fwd(self, plan):
@@ -2409,7 +2374,7 @@ class MatmulRight:
             S.w, S.ldw = g["m"].data_ptr(), N
             S.N, S.out = K, i
         self._keep.append(a)
-        fl = sum(2.0 * self.M * g["m"].shape[0] * g["m"].shape[1] for g in self.groups)
+        fl = _flops(self.M, (g["m"] for g in self.groups))
         plan.fwd_steps.append(plan.call("cdc_glinear_bwd_x", C.byref(a), plan.prec, what="cdc_glinear_bwd_x(matmul_right fwd)", flops=fl))
 
     def build_bwd(self, plan, gs):
@@ -2533,12 +2498,13 @@ class AddOut:
                                             C.c_int64(plan.B), t.cols, acc))
 
 
-class StarFuse:
+class StarFuse(Op):
     """out_g = a_g (*|+) s for every domain g in one launch (model/star.py:90-93,100-102,169-176).
     a: list of per-domain Parameters, s: the shared Parameter; outputs live in one [n, ...] scratch tensor whose
     per-domain slices are handed to the consumers as TViews (their gradients come back through the same scratch)."""
 
     def __init__(self, plan, a_list, s, op):
+        super().__init__()
         assert op in ("mul", "add")
         self.a_list, self.s, self.op = a_list, s, 0 if op == "mul" else 1
         n = len(a_list)
@@ -2546,7 +2512,6 @@ class StarFuse:
         self.out = torch.empty((n,) + shape, dtype=torch.float32, device=plan.device)
         self.d_out = torch.zeros((n,) + shape, dtype=torch.float32, device=plan.device)
         self.views = [TView(self.out[g], self.d_out[g]) for g in range(n)]
-        self._keep = []
         plan.add(self)
 
     def _args(self, c0, chunk, backward, plan):

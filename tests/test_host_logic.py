@@ -127,3 +127,26 @@ def test_plan_gradient_interval_bookkeeping():
     # activation mask geometry of slices: columns [0,20) masked
     whole.mask = (1.25, 20)
     assert whole.slice(0, 8).mask == (1.25, 8) and whole.slice(16, 32).mask == (1.25, 4) and whole.slice(24, 32).mask is None
+
+
+def test_plan_interval_table_merges_and_removes():
+    """the table behind the gradient bookkeeping and the bf16-shadow bookkeeping (which columns are wanted / current)"""
+    from cdcmdr_amd.plan import Buf, _Intervals
+    whole, other = Buf(torch.zeros(4, 32), 4, 32), Buf(torch.zeros(4, 32), 4, 32)
+    t = _Intervals()
+    t.add(whole.slice(0, 8))
+    t.add(whole.slice(4, 12))                                                # overlapping adds merge ...
+    assert t.covers(whole.slice(0, 12)) and t.covers(whole.slice(2, 10)) and not t.covers(whole.slice(0, 13))
+    t.add(whole.slice(20, 24))
+    assert not t.covers(whole.slice(8, 24)) and t.overlaps(whole.slice(11, 21)) == (0, 12)
+    assert t.overlaps(whole.slice(12, 20)) is None                           # half-open: touching is not overlapping
+    t.add(whole.slice(10, 22))                                               # ... also across a gap, into one interval
+    assert t.iv[id(whole.root)] == [(0, 24)]
+    assert not t.covers(other.slice(0, 4)) and t.overlaps(other) is None     # per root tensor
+    t.add(whole.slice(28, 32))
+    t.remove_overlapping(whole.slice(24, 28))                                # between the two: nothing goes
+    assert t.iv[id(whole.root)] == [(0, 24), (28, 32)]
+    t.remove_overlapping(whole.slice(23, 25))                                # one shared column: the WHOLE interval goes
+    assert t.iv[id(whole.root)] == [(28, 32)] and not t.covers(whole.slice(0, 4))
+    t.remove_overlapping(other)                                              # a root the table has never seen
+    assert t.covers(whole.slice(28, 32))
