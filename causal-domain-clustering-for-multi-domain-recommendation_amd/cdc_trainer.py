@@ -22,6 +22,7 @@ import torch
 import torch.nn.functional as F
 
 from .evaluate import eval_metrics
+from .probe import ROWS_CAP, ProbeEval
 from .trainer import TrainStep
 
 
@@ -29,10 +30,14 @@ class CDCTrainer:
     MAX_STEPS = 16      # resident TrainSteps (one per batch size x flavour); least recently used ones are rebuilt on demand
 
     def __init__(self, model, optimizer, batch_size, train_loaders, n_domain, domain_cnt_weight, train_domain_batch_seq,
-                 warmup_step=200, update_matrix_step=2, update_interval=1000, n_causal_mask=None, log=None):
+                 warmup_step=200, update_matrix_step=2, update_interval=1000, n_causal_mask=None, log=None,
+                 batched_probe=False, probe_rows_cap=ROWS_CAP):
         """model: cdcmdr_amd.model.cdc.CDC on the GPU; optimizer: FusedAdam(model.base_model_instance);
         train_loaders {domain: DeviceLoader of (X, y)} and train_domain_batch_seq from data.make_domain_loaders;
-        the three step counts are the reference's config values (config.py:57-59), rescaled like run.py:601-604."""
+        the three step counts are the reference's config values (config.py:57-59), rescaled like run.py:601-604.
+        batched_probe: the matrix update scores every domain's batch in ONE eval forward and one segmented metric launch
+        (probe.ProbeEval, at most probe_rows_cap rows per pass) instead of one forward and one metric call per domain; the same
+        batches are drawn in the same order, so the training steps of the probes are unchanged."""
         self.model, self.opt, self.bs = model, optimizer, int(batch_size)
         self.base = model.base_model_instance
         self.loaders = train_loaders
@@ -49,6 +54,7 @@ class CDCTrainer:
         self._gen = {}
         self._steps = {}
         self.domain2group_list = list(model.domain2group_list)
+        self._probe = ProbeEval(self.base, self.n_cluster, probe_rows_cap) if batched_probe else None
 
     # ---- run.py:499-526 ------------------------------------------------------------------------------------
     def get_domain_data(self, d):
@@ -106,6 +112,10 @@ class CDCTrainer:
         self.training = False
         self.model.eval()
         self.opt.flush_table()                                        # the eval forward reads the table directly
+        if self._probe is not None:                                   # the same draws, one per domain in order; one forward
+            batches = [self.get_domain_data(d) for d in range(self.n_domain)]
+            metric = 'loss' if self.model.use_metric == 'loss' else 'auc'            # as the loop below reads use_metric
+            return self._probe.run(batches, [int(g) for g in self.model.domain2group_list], metric)
         row = torch.zeros(self.n_domain, dtype=torch.float32, device=self.device)
         with torch.no_grad():
             for d in range(self.n_domain):
@@ -129,7 +139,7 @@ class CDCTrainer:
         self.opt.flush_table()
         self.model.load_model_state()
         if self.opt.table_mode == "lazy":                             # the restored rows ARE the current values
-            self.opt.table_last.fill_(int(self.opt.step_dev.item()))
+            self.opt.table_last.copy_(self.opt.step_dev.expand_as(self.opt.table_last))      # no read-back of the counter
 
     def update_matrix(self):
         m, n, k = self.model, self.n_domain, self.update_matrix_step

@@ -476,3 +476,69 @@ extern "C" int cdc_eval_gauc(const float* pred, const int16_t* label, const int3
     CDC_LAUNCH_CHECK("eval_gauc(final)");
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Per-segment BCE of CDC's probe evaluation (run.py:549-558): every domain's batch went through ONE eval forward, its rows
+// form a contiguous segment of the [rows, n_cols] tower probabilities, and segment s is scored by column seg_col[s].  One
+// workgroup per segment; the per-element loss is the expression of the step's BCE kernels (rowops.hip k_bce: ATen's, pinned
+// by golden g7) in fp32, widened to double; a thread adds its strided share, a wave butterfly and a serial pass over the
+// waves' sums follow — no atomics on the way to a result, the same inputs give the same bits.  A thread's loads of a round
+// are issued before its logarithms.  Rows at or past seg_start[n_seg] belong to no workgroup and are never touched.
+#define SEGS_THREADS 256
+#define SEGS_RB 4
+
+__global__ void __launch_bounds__(SEGS_THREADS) k_eval_segments(const float* __restrict__ probs, int64_t ld, const int16_t* __restrict__ label,
+                                                                const int32_t* __restrict__ seg_start, const int32_t* __restrict__ seg_col,
+                                                                double* __restrict__ loss, float* __restrict__ sel_pred,
+                                                                int32_t* __restrict__ seg_of_row, int32_t* __restrict__ err, int64_t rows,
+                                                                int32_t n_cols) {
+    __shared__ double sh[SEGS_THREADS / 64];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    // the bounds come from device memory: whatever they hold, no access leaves [0, rows) x [0, n_cols)
+    int64_t s0 = seg_start[s], s1 = seg_start[s + 1];
+    s0 = s0 < 0 ? 0 : (s0 > rows ? rows : s0);
+    s1 = s1 < s0 ? s0 : (s1 > rows ? rows : s1);
+    int32_t col = seg_col ? seg_col[s] : 0;
+    col = col < 0 ? 0 : (col >= n_cols ? n_cols - 1 : col);
+    double acc = 0.0;
+    for (int64_t i0 = s0 + tid; i0 < s1; i0 += (int64_t)SEGS_RB * SEGS_THREADS) {
+        float x[SEGS_RB];
+        int16_t y[SEGS_RB];
+#pragma unroll
+        for (int q = 0; q < SEGS_RB; ++q) {
+            const int64_t i = i0 + (int64_t)q * SEGS_THREADS;
+            x[q] = i < s1 ? probs[i * ld + col] : 0.5f;
+            y[q] = i < s1 ? label[i] : (int16_t)0;
+        }
+#pragma unroll
+        for (int q = 0; q < SEGS_RB; ++q) {
+            const int64_t i = i0 + (int64_t)q * SEGS_THREADS;
+            if (i >= s1) continue;
+            const float t = (float)y[q];
+            acc += (double)((t - 1.f) * fmaxf(log1pf(-x[q]), -100.f) - t * fmaxf(logf(x[q]), -100.f));
+            if (err && (x[q] != x[q] || (y[q] != 0 && y[q] != 1))) atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
+            if (sel_pred) sel_pred[i] = x[q];
+            if (seg_of_row) seg_of_row[i] = s;
+        }
+    }
+    acc = wave_sum_d(acc);
+    if ((tid & 63) == 0) sh[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        double sum = 0.0;
+        for (int w = 0; w < SEGS_THREADS / 64; ++w) sum += sh[w];
+        loss[s] = s1 > s0 ? sum / (double)(s1 - s0) : __longlong_as_double(0x7ff8000000000000ll);   // torch's mean of nothing
+    }
+}
+
+extern "C" int cdc_eval_segments(const float* probs, int64_t ld_probs, const int16_t* label, const int32_t* seg_start, int32_t n_seg,
+                                 const int32_t* seg_col, double* loss, float* sel_pred, int32_t* seg_of_row, int32_t* err_flag,
+                                 int64_t rows, int32_t n_cols, void* stream) {
+    CDC_CHECK_ARG(probs && label && seg_start && loss, CDC_E_BADARG, "eval_segments: null pointer");
+    CDC_CHECK_ARG(n_seg > 0 && n_cols > 0 && ld_probs >= n_cols && rows >= 0 && rows < (1ll << 31), CDC_E_BADARG,
+                  "eval_segments: bad sizes n_seg=%d n_cols=%d ld_probs=%ld rows=%ld", n_seg, n_cols, (long)ld_probs, (long)rows);
+    hipLaunchKernelGGL(k_eval_segments, dim3(n_seg), dim3(SEGS_THREADS), 0, (hipStream_t)stream, probs, ld_probs, label, seg_start,
+                       seg_col, loss, sel_pred, seg_of_row, err_flag, rows, n_cols);
+    CDC_LAUNCH_CHECK("eval_segments");
+    return 0;
+}

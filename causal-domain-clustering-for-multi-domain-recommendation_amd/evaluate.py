@@ -10,6 +10,9 @@ synchronisation is reading the result.
 With a user column configured the same pass also yields GAUC — the reference's `gauc_score` (base.py:33-64): the AUC of every
 user's rows, averaged over the users that have both classes, weighted by their row count or a given weight — from one more
 C-ABI call (`cdc_eval_gauc`) on the same device-resident predictions.
+
+`eval_segments` serves CDC's matrix update (run.py:549-558) instead: the metric of every contiguous row segment of ONE forward's
+raw output, each segment scored by its own tower column (`cdc_eval_segments`; probe.py lays the domains' batches out that way).
 """
 import ctypes as C
 import math
@@ -55,6 +58,64 @@ def eval_metrics(pred, label, domain=None, n_domain=1):
               counts.data_ptr(), err.data_ptr(), ws.data_ptr(), nbytes), C.c_void_p(torch.cuda.current_stream().cuda_stream))
     eval_metrics.last_err = err
     return out[:seg], out[seg:], counts[:seg], counts[seg:]
+
+
+def eval_segments(probs, label, seg_sizes, seg_col=None, metric="loss"):
+    """Per-segment metric of CDC's probe evaluation: probs f32 [rows, n_cols] (a model's raw output, every tower's probability; a
+    row-strided view is read in place), label int16 [rows] (0/1); seg_sizes: host sequence of row counts of consecutive row
+    segments (rows past their sum are padding and never looked at); seg_col: host sequence, the column segment s is scored by
+    (None = column 0).  metric "loss": the mean BCE of every segment (F.binary_cross_entropy's arithmetic), NaN for an empty one —
+    ONE launch (`cdc_eval_segments`); "auc": the same launch hands every row's selected probability and segment to
+    `cdc_eval_metrics`, NaN for an empty or single-class segment.  Returns a device float32 [n_seg] tensor; nothing is read back:
+    the error word (1 + a row inside a segment with a NaN probability or a label outside {0, 1}) is kept as
+    `eval_segments.last_err`."""
+    if metric not in ("loss", "auc"):
+        raise ValueError(f"metric must be 'loss' or 'auc', not {metric!r}")
+    lib = L.load()
+    if not probs.is_cuda:
+        raise L.HipExtensionError("eval_segments needs device tensors; there is no CPU fallback")
+    if probs.dim() == 1:
+        probs = probs.reshape(-1, 1)
+    if probs.dim() != 2:
+        raise ValueError("probs must be [rows, n_cols]")
+    rows, n_cols = probs.shape
+    if probs.dtype != torch.float32 or (n_cols > 1 and probs.stride(1) != 1) or (rows > 1 and probs.stride(0) < n_cols):
+        probs = probs.to(torch.float32).contiguous()
+    ld = max(probs.stride(0), n_cols)
+    label = label.reshape(-1).to(torch.int16).contiguous()
+    if label.numel() != rows:
+        raise ValueError(f"{rows} rows of probabilities but {label.numel()} labels")
+    sizes = [int(s) for s in seg_sizes]
+    n_seg = len(sizes)
+    if n_seg == 0 or min(sizes) < 0:
+        raise ValueError("seg_sizes must hold at least one segment and no negative size")
+    starts = [0]
+    for s in sizes:
+        starts.append(starts[-1] + s)
+    n = starts[-1]
+    if n > rows:
+        raise ValueError(f"the segments hold {n} rows, probs only {rows}")
+    cols = [0] * n_seg if seg_col is None else [int(c) for c in seg_col]
+    if len(cols) != n_seg or min(cols) < 0 or max(cols) >= n_cols:
+        raise ValueError(f"seg_col must hold one column in [0, {n_cols}) per segment")
+    dev = probs.device
+    # bounds and columns travel in one copy from pinned memory: stream-ordered, the host does not wait for the device
+    meta = torch.tensor(starts + cols, dtype=torch.int32, pin_memory=True).to(dev, non_blocking=True)
+    loss = torch.empty(n_seg, dtype=torch.float64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    want_auc = metric == "auc" and n > 0
+    sel = torch.empty(n, dtype=torch.float32, device=dev) if want_auc else None
+    seg = torch.empty(n, dtype=torch.int32, device=dev) if want_auc else None
+    L.launch("cdc_eval_segments", lib.cdc_eval_segments,
+             (probs.data_ptr(), ld, label.data_ptr(), meta.data_ptr(), n_seg, meta[n_seg + 1:].data_ptr(), loss.data_ptr(),
+              None if sel is None else sel.data_ptr(), None if seg is None else seg.data_ptr(), err.data_ptr(), rows, n_cols),
+             C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    eval_segments.last_err = err
+    if metric == "loss":
+        return loss.to(torch.float32)
+    if not want_auc:
+        return torch.full((n_seg,), math.nan, dtype=torch.float32, device=dev)
+    return eval_metrics(sel, label[:n], seg, n_seg)[0][:n_seg].to(torch.float32)
 
 
 def _id_column(col, n, what):

@@ -1156,6 +1156,23 @@ int cdc_eval_gauc(const float* pred, const int16_t* label, const int32_t* user, 
                   const int32_t* domain, int64_t ld_domain, int32_t n_domain, const double* user_weight, int64_t n,
                   double* out, int64_t* counts, int32_t* err_flag, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Per-segment BCE of CDC's probe evaluation (run.py:549-558): one batch of every domain went through ONE eval
+ * forward; segment s is the rows [seg_start[s], seg_start[s+1]) of probs [rows, n_cols] (row stride ld_probs: all towers'
+ * probabilities) and is scored by column seg_col[s] (NULL = column 0).  seg_start [n_seg+1] is non-decreasing; rows at or past
+ * seg_start[n_seg] are padding: never read into a result, never written.
+ *   loss       [n_seg] doubles: the mean over the segment of (t-1)*max(log1p(-p), -100) - t*max(log(p), -100), each element in
+ *              fp32 (cdc_bce_fwd_bwd's expression, ATen's binary_cross_entropy) and added in double; NaN for an empty segment.
+ *   sel_pred   (optional) [rows] floats: the selected probability of every segment row;
+ *   seg_of_row (optional) [rows] int32: its segment — together the input of cdc_eval_metrics for a per-segment AUC.
+ *   err_flag   (optional): 1 + the largest index of a row INSIDE a segment with a NaN probability or a label other than 0/1.
+ * One workgroup per segment, sums in a fixed order and no atomics: the same inputs give the same bits.  Bounds and columns read
+ * from the device are clamped into [0, rows] / [0, n_cols), so no access leaves the arrays whatever they hold.  Null pointers,
+ * n_seg <= 0, n_cols <= 0, ld_probs < n_cols, rows < 0 or rows >= 2^31: CDC_E_BADARG before anything is launched.  Stream-ordered:
+ * no allocation, no synchronisation, no state kept; the launch dimensions depend on (rows, n_seg) alone. */
+int cdc_eval_segments(const float* probs, int64_t ld_probs, const int16_t* label, const int32_t* seg_start, int32_t n_seg,
+                      const int32_t* seg_col, double* loss, float* sel_pred, int32_t* seg_of_row, int32_t* err_flag, int64_t rows,
+                      int32_t n_cols, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
