@@ -209,6 +209,17 @@ __device__ __forceinline__ void sort_begin_step(const SortSrc& s, int tid) {
         if (tid < s.n_acc) s.acc[tid] = 0.0;
     }
 }
+// what both bitonic kernels open with: keys[0, n_pad) = (row << 32 | batch position) of the rows [r0, r0 + n) of field f, then
+// the step's opening work and the barrier the sort starts behind
+__device__ __forceinline__ void load_sort_keys(const SortSrc& src, uint64_t* keys, int r0, int n, int n_pad, int f, int F, int tid) {
+    for (int i = tid; i < n_pad; i += SORT_THREADS) {
+        uint64_t k = ~0ull;                                               // padding sorts last
+        if (i < n) k = ((uint64_t)sort_row(src, r0 + i, f, F) << 32) | (uint32_t)(r0 + i);
+        keys[i] = k;
+    }
+    sort_begin_step(src, tid);
+    __syncthreads();
+}
 
 // B <= 1024 (and SORT_RADIX_MAX < B <= SORT_CHUNK when no scratch buffer is given): sort + dedupe in one workgroup per field
 __global__ void __launch_bounds__(SORT_THREADS) k_sort_dedupe(const SortSrc src, int32_t* __restrict__ uniq_row,
@@ -220,13 +231,7 @@ __global__ void __launch_bounds__(SORT_THREADS) k_sort_dedupe(const SortSrc src,
     int32_t* scan = reinterpret_cast<int32_t*>(keys + n_pad);            // SORT_THREADS entries
     const int f = blockIdx.x;
     const int tid = threadIdx.x;
-    for (int i = tid; i < n_pad; i += SORT_THREADS) {
-        uint64_t k = ~0ull;                                               // padding sorts last
-        if (i < B) k = ((uint64_t)sort_row(src, i, f, F) << 32) | (uint32_t)i;
-        keys[i] = k;
-    }
-    sort_begin_step(src, tid);
-    __syncthreads();
+    load_sort_keys(src, keys, 0, B, n_pad, f, F, tid);
     lds_bitonic_sort(keys, n_pad, tid);
     dedupe_sorted(keys, B, scan, uniq_row + (int64_t)f * B, seg_start + (int64_t)f * (B + 1), perm + (int64_t)f * B, uniq_cnt + f, tid);
 }
@@ -399,22 +404,32 @@ __global__ void __launch_bounds__(SORT_THREADS) k_sort_chunk(const SortSrc src, 
     const int f = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
     const int r0 = c * chunk;
     const int n = min(chunk, B - r0);
-    for (int i = tid; i < chunk; i += SORT_THREADS) {
-        uint64_t k = ~0ull;
-        if (i < n) k = ((uint64_t)sort_row(src, r0 + i, f, F) << 32) | (uint32_t)(r0 + i);
-        keys[i] = k;
-    }
-    sort_begin_step(src, tid);
-    __syncthreads();
+    load_sort_keys(src, keys, r0, n, chunk, f, F, tid);
     lds_bitonic_sort(keys, chunk, tid);
     uint64_t* out = runs + (int64_t)f * B + r0;
     for (int i = tid; i < n; i += SORT_THREADS) out[i] = keys[i];
 }
-// P (a power of two >= n_runs, <= 16) neighbouring lanes share one key: lane q counts the smaller keys of run q with its own
-// binary search (the searches of a key run side by side instead of one after the other), a butterfly adds the counts
+// The rank merge: P (a power of two >= n_runs, <= 64) neighbouring lanes share one key: lane q counts the smaller keys of run q
+// with its own binary search (the searches of a key run side by side instead of one after the other), a butterfly adds the
+// counts — every lane of the wave calls this.  The key is entry `own` of run r; at(q, i) reads entry i of run q.  TIES: the
+// keys are bare rows, equal keys of an EARLIER run count as smaller (otherwise the keys are unique: the batch position is
+// part of them).
 __device__ __forceinline__ int group_sum(int v, int P) {
     for (int off = 1; off < P; off <<= 1) v += __shfl_xor(v, off, 64);
     return v;
+}
+template <bool TIES, typename K, typename At>
+__device__ __forceinline__ int merge_rank(const K key, int r, int own, int q, bool valid, int n_runs, int run_len, int B, int P, At at) {
+    int lo = 0;
+    if (valid && q < n_runs) {
+        if (q == r) lo = own;
+        else {
+            int hi = min(run_len, B - q * run_len);                // number of keys of run q that are smaller
+            if (TIES && q < r) { while (lo < hi) { const int mid = (lo + hi) >> 1; if (at(q, mid) <= key) lo = mid + 1; else hi = mid; } }
+            else               { while (lo < hi) { const int mid = (lo + hi) >> 1; if (at(q, mid) <  key) lo = mid + 1; else hi = mid; } }
+        }
+    }
+    return group_sum(lo, P);
 }
 __global__ void __launch_bounds__(256) k_merge_runs(const uint64_t* __restrict__ runs, uint64_t* __restrict__ merged, int32_t B,
                                                     int32_t F, int32_t chunk, int32_t n_runs, int32_t P) {
@@ -427,19 +442,8 @@ __global__ void __launch_bounds__(256) k_merge_runs(const uint64_t* __restrict__
     const uint64_t* a = runs + (int64_t)f * B;
     const uint64_t key = a[i];
     const int r = i / chunk;
-    int lo = 0;
-    if (valid && q < n_runs) {
-        if (q == r) lo = i - r * chunk;
-        else {
-            const uint64_t* other = a + (int64_t)q * chunk;
-            int hi = min(chunk, B - q * chunk);                    // number of keys of run q that are smaller
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (other[mid] < key) lo = mid + 1; else hi = mid;
-            }
-        }
-    }
-    const int pos = group_sum(lo, P);
+    const int pos = merge_rank<false>(key, r, i - r * chunk, q, valid, n_runs, chunk, B, P,
+                                      [&](int q2, int mid) { return a[(int64_t)q2 * chunk + mid]; });
     if (valid && q == 0) merged[(int64_t)f * B + pos] = key;
 }
 // The same rank merge with the field's keys staged in LDS: one workgroup per (field, run) loads all runs of its field once
@@ -468,17 +472,8 @@ __global__ void __launch_bounds__(SORT_THREADS) k_merge_lds(const void* __restri
         const int item = t / P, q = t - item * P;
         const bool valid = item < n_r;
         const K key = keys[valid ? base + item : base];
-        int lo = 0;
-        if (valid && q < n_runs) {
-            if (q == r) lo = item;
-            else {
-                const K* other = keys + q * run_len;
-                int hi = min(run_len, B - q * run_len);
-                if (IDX && q < r) { while (lo < hi) { const int mid = (lo + hi) >> 1; if (other[mid] <= key) lo = mid + 1; else hi = mid; } }
-                else              { while (lo < hi) { const int mid = (lo + hi) >> 1; if (other[mid] <  key) lo = mid + 1; else hi = mid; } }
-            }
-        }
-        const int pos = group_sum(lo, P);
+        const int pos = merge_rank<IDX>(key, r, item, q, valid, n_runs, run_len, B, P,
+                                        [&](int q2, int mid) { return keys[q2 * run_len + mid]; });
         if (valid && q == 0)
             merged[(int64_t)f * B + pos] = IDX ? (((uint64_t)key << 32) | (uint32_t)(base + item)) : (uint64_t)key;
     }
@@ -493,6 +488,35 @@ __global__ void __launch_bounds__(SORT_THREADS) k_dedupe_merged(const uint64_t* 
                   uniq_cnt + f, threadIdx.x);
 }
 
+// host side shared by cdc_embed_sort_dedupe* and cdc_embed_merge_dedupe (`who` prefixes their messages)
+// the kernels that keep a field's keys in dynamic LDS ask for more than the default 64 KB: the limit is raised once for all four
+static int sort_raise_lds_limit(const char* who) {
+    static bool attr_set = false;
+    if (attr_set) return 0;
+    const void* const kernels[] = {(const void*)k_sort_dedupe, (const void*)k_sort_chunk, (const void*)k_merge_lds<uint64_t, false>,
+                                   (const void*)k_merge_lds<uint32_t, true>};
+    for (const void* k : kernels) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) { cdc_set_error("%s: cannot raise LDS limit: %s", who, hipGetErrorString(e)); return (int)e; }
+    }
+    attr_set = true;
+    return 0;
+}
+// lanes that share a key in the rank merge: the next power of two >= n_runs, inside one wave
+static int merge_lanes(const char* who, int n_runs, int& P) {
+    P = 1;
+    while (P < n_runs) P <<= 1;
+    CDC_CHECK_ARG(P <= 64, CDC_E_TOOBIG, "%s: %d runs", who, n_runs);
+    return 0;
+}
+// what follows either merge: unique rows, segment starts and permutation from the merged keys
+static int dedupe_merged_launch(const uint64_t* merged, int32_t* uniq_row, int32_t* seg_start, int32_t* perm, int32_t* uniq_cnt, int64_t B,
+                                int32_t F, hipStream_t st) {
+    hipLaunchKernelGGL(k_dedupe_merged, dim3(F), dim3(SORT_THREADS), 0, st, merged, uniq_row, seg_start, perm, uniq_cnt, (int32_t)B, F);
+    CDC_LAUNCH_CHECK("embed_dedupe_merged");
+    return 0;
+}
+
 static int sort_dedupe_launch(const SortSrc& src, int32_t* uniq_row, int32_t* seg_start, int32_t* perm, int32_t* uniq_cnt,
                               uint64_t* scratch, int64_t B, int32_t F, void* stream) {
     const int32_t* idx = src.idx;
@@ -500,14 +524,7 @@ static int sort_dedupe_launch(const SortSrc& src, int32_t* uniq_row, int32_t* se
     CDC_CHECK_ARG(B > 0 && F > 0, CDC_E_BADARG, "embed_sort_dedupe: bad sizes");
     CDC_CHECK_ARG(B <= CDC_SORT_MAX_ROWS, CDC_E_TOOBIG, "embed_sort_dedupe: B=%ld exceeds %d", (long)B, CDC_SORT_MAX_ROWS);
     CDC_CHECK_ARG(scratch || B <= SORT_CHUNK, CDC_E_BADARG, "embed_sort_dedupe: B > %d needs a scratch buffer of 2*F*B uint64", SORT_CHUNK);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_sort_dedupe, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_sort_chunk, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_merge_lds<uint64_t, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { cdc_set_error("embed_sort_dedupe: cannot raise LDS limit: %s", hipGetErrorString(e)); return (int)e; }
-        attr_set = true;
-    }
+    if (const int rc = sort_raise_lds_limit("embed_sort_dedupe")) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (B > 1024 && B <= SORT_RADIX_MAX) {                  // `scratch` is not needed
         hipLaunchKernelGGL(k_sort_dedupe_radix, dim3(F), dim3(SORT_THREADS), 0, st, src, uniq_row, seg_start, perm, uniq_cnt, (int32_t)B, F);
@@ -529,9 +546,8 @@ static int sort_dedupe_launch(const SortSrc& src, int32_t* uniq_row, int32_t* se
     uint64_t* merged = scratch + (int64_t)F * B;
     hipLaunchKernelGGL(k_sort_chunk, dim3(F, n_runs), dim3(SORT_THREADS), (size_t)chunk * 8, st, src, runs, (int32_t)B, F, chunk);
     CDC_LAUNCH_CHECK("embed_sort_chunk");
-    int P = 1;
-    while (P < n_runs) P <<= 1;
-    CDC_CHECK_ARG(P <= 64, CDC_E_TOOBIG, "embed_sort_dedupe: %d runs", n_runs);
+    int P;
+    if (const int rc = merge_lanes("embed_sort_dedupe", n_runs, P)) return rc;
     if ((size_t)B * 8 <= MERGE_LDS_MAX) {
         hipLaunchKernelGGL((k_merge_lds<uint64_t, false>), dim3(F, n_runs), dim3(SORT_THREADS), (size_t)B * 8, st, runs, merged, (int32_t)B, F,
                            n_runs, chunk, P);
@@ -540,9 +556,7 @@ static int sort_dedupe_launch(const SortSrc& src, int32_t* uniq_row, int32_t* se
         hipLaunchKernelGGL(k_merge_runs, dim3((unsigned)blocks), dim3(256), 0, st, runs, merged, (int32_t)B, F, chunk, n_runs, P);
     }
     CDC_LAUNCH_CHECK("embed_merge_runs");
-    hipLaunchKernelGGL(k_dedupe_merged, dim3(F), dim3(SORT_THREADS), 0, st, merged, uniq_row, seg_start, perm, uniq_cnt, (int32_t)B, F);
-    CDC_LAUNCH_CHECK("embed_dedupe_merged");
-    return 0;
+    return dedupe_merged_launch(merged, uniq_row, seg_start, perm, uniq_cnt, B, F, st);
 }
 
 extern "C" int cdc_embed_sort_dedupe(const int32_t* idx, int32_t* uniq_row, int32_t* seg_start, int32_t* perm,
@@ -562,55 +576,87 @@ extern "C" int cdc_embed_sort_dedupe_ids(const int32_t* ids, const int32_t* offs
 // Same result as cdc_embed_sort_dedupe for a batch that already consists of n_runs runs of run_len rows, each ascending
 // per field (as unsigned: -1 padding last) — the row lists an owner receives from the ranks.  No sort: every key's final
 // position is the sum over the runs of the number of smaller keys (binary searches), then the usual dedupe.
-__global__ void __launch_bounds__(256) k_merge_n(const int32_t* __restrict__ idx, uint64_t* __restrict__ merged, int32_t B, int32_t F,
-                                                 int32_t n_runs, int32_t run_len, int32_t P) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t item = t / P;
-    const int q = (int)(t - item * P);
-    const bool valid = item < (int64_t)F * B;
-    const int f = valid ? (int)(item / B) : 0;
-    const int i = valid ? (int)(item - (int64_t)f * B) : 0;
-    const uint32_t row = (uint32_t)idx[(int64_t)i * F + f];
-    const int r = i / run_len;
-    int lo = 0;
-    if (valid && q < n_runs) {
-        if (q == r) lo = i - r * run_len;
-        else {
-            const int32_t* col = idx + (int64_t)q * run_len * F + f;
-            int hi = run_len;
-            if (q < r) { while (lo < hi) { const int mid = (lo + hi) >> 1; if ((uint32_t)col[(int64_t)mid * F] <= row) lo = mid + 1; else hi = mid; } }
-            else       { while (lo < hi) { const int mid = (lo + hi) >> 1; if ((uint32_t)col[(int64_t)mid * F] <  row) lo = mid + 1; else hi = mid; } }
-        }
-    }
-    const int pos = group_sum(lo, P);
-    if (valid && q == 0) merged[(int64_t)f * B + pos] = ((uint64_t)row << 32) | (uint32_t)i;
-}
 extern "C" int cdc_embed_merge_dedupe(const int32_t* idx, int32_t* uniq_row, int32_t* seg_start, int32_t* perm, int32_t* uniq_cnt,
                                       uint64_t* scratch, int64_t B, int32_t F, int32_t n_runs, void* stream) {
     CDC_CHECK_ARG(idx && uniq_row && seg_start && perm && uniq_cnt && scratch, CDC_E_BADARG, "embed_merge_dedupe: null pointer");
     CDC_CHECK_ARG(B > 0 && F > 0 && n_runs > 0 && B % n_runs == 0, CDC_E_BADARG, "embed_merge_dedupe: bad sizes");
     CDC_CHECK_ARG(B <= CDC_SORT_MAX_ROWS, CDC_E_TOOBIG, "embed_merge_dedupe: B=%ld exceeds %d", (long)B, CDC_SORT_MAX_ROWS);
     hipStream_t st = (hipStream_t)stream;
-    int P = 1;
-    while (P < n_runs) P <<= 1;
-    CDC_CHECK_ARG(P <= 64, CDC_E_TOOBIG, "embed_merge_dedupe: %d runs", n_runs);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_merge_lds<uint32_t, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { cdc_set_error("embed_merge_dedupe: cannot raise LDS limit: %s", hipGetErrorString(e)); return (int)e; }
-        attr_set = true;
-    }
-    if ((size_t)B * 4 <= MERGE_LDS_MAX) {
-        hipLaunchKernelGGL((k_merge_lds<uint32_t, true>), dim3(F, n_runs), dim3(SORT_THREADS), (size_t)B * 4, st, idx, scratch, (int32_t)B, F,
-                           n_runs, (int32_t)(B / n_runs), P);
-    } else {
-        const int64_t blocks = cdc_ceil_div((int64_t)F * B * P, 256);
-        hipLaunchKernelGGL(k_merge_n, dim3((unsigned)blocks), dim3(256), 0, st, idx, scratch, (int32_t)B, F, n_runs, (int32_t)(B / n_runs), P);
-    }
+    int P;
+    if (const int rc = merge_lanes("embed_merge_dedupe", n_runs, P)) return rc;
+    if (const int rc = sort_raise_lds_limit("embed_merge_dedupe")) return rc;
+    // every batch the check above admits keeps a field's uint32 rows in LDS: there is no global-memory form of this merge
+    static_assert((size_t)CDC_SORT_MAX_ROWS * 4 <= MERGE_LDS_MAX, "cdc_embed_merge_dedupe stages a whole field in LDS");
+    hipLaunchKernelGGL((k_merge_lds<uint32_t, true>), dim3(F, n_runs), dim3(SORT_THREADS), (size_t)B * 4, st, idx, scratch, (int32_t)B, F,
+                       n_runs, (int32_t)(B / n_runs), P);
     CDC_LAUNCH_CHECK("embed_merge_n");
-    hipLaunchKernelGGL(k_dedupe_merged, dim3(F), dim3(SORT_THREADS), 0, st, scratch, uniq_row, seg_start, perm, uniq_cnt, (int32_t)B, F);
-    CDC_LAUNCH_CHECK("embed_dedupe_merged");
-    return 0;
+    return dedupe_merged_launch(scratch, uniq_row, seg_start, perm, uniq_cnt, B, F, st);
+}
+
+// ------------------------------------------------------------------------------------------------
+// shared by the kernels below that give a thread one (unique row of the batch, chunk of VEC floats of that row)
+// ------------------------------------------------------------------------------------------------
+// work item i of F * B * chunks: slot = f * B + j of the sorted lists, d = first column of the chunk.  live: j is below the
+// field's unique count and row = uniq_row[slot] is no padding entry (< 0) — row is loaded only for j in range.  ROW = false:
+// the decode and the count test alone, uniq_row is not read
+struct RowItem {
+    int64_t slot, row;
+    int f, j, d;
+    bool live;
+};
+template <int VEC, bool ROW = true>
+__device__ __forceinline__ RowItem row_item(int64_t i, int chunks, int B, const int32_t* __restrict__ uniq_cnt,
+                                            const int32_t* __restrict__ uniq_row) {
+    RowItem it;
+    it.d = (int)(i % chunks) * VEC;
+    it.slot = i / chunks;
+    it.f = (int)(it.slot / B);
+    it.j = (int)(it.slot - (int64_t)it.f * B);
+    it.row = -1;
+    it.live = it.j < uniq_cnt[it.f];
+    if (ROW && it.live) {
+        it.row = uniq_row[it.slot];
+        it.live = it.row >= 0;
+    }
+    return it;
+}
+// the chunk of VEC floats at element e0 of w, m and v: one 16-byte access each (VEC == 4) or one float
+template <int VEC>
+__device__ __forceinline__ void load_wmv(const float* w, const float* m, const float* v, int64_t e0, float (&wv)[VEC], float (&mv)[VEC],
+                                         float (&vv)[VEC]) {
+    if (VEC == 4) {
+        const float4 a4 = *reinterpret_cast<const float4*>(w + e0), b4 = *reinterpret_cast<const float4*>(m + e0),
+                     c4 = *reinterpret_cast<const float4*>(v + e0);
+        wv[0] = a4.x; wv[1 % VEC] = a4.y; wv[2 % VEC] = a4.z; wv[3 % VEC] = a4.w;
+        mv[0] = b4.x; mv[1 % VEC] = b4.y; mv[2 % VEC] = b4.z; mv[3 % VEC] = b4.w;
+        vv[0] = c4.x; vv[1 % VEC] = c4.y; vv[2 % VEC] = c4.z; vv[3 % VEC] = c4.w;
+    } else {
+        wv[0] = w[e0]; mv[0] = m[e0]; vv[0] = v[e0];
+    }
+}
+template <int VEC>
+__device__ __forceinline__ void store_wmv(float* w, float* m, float* v, int64_t e0, const float (&wv)[VEC], const float (&mv)[VEC],
+                                          const float (&vv)[VEC]) {
+    if (VEC == 4) {
+        *reinterpret_cast<float4*>(w + e0) = make_float4(wv[0], wv[1 % VEC], wv[2 % VEC], wv[3 % VEC]);
+        *reinterpret_cast<float4*>(m + e0) = make_float4(mv[0], mv[1 % VEC], mv[2 % VEC], mv[3 % VEC]);
+        *reinterpret_cast<float4*>(v + e0) = make_float4(vv[0], vv[1 % VEC], vv[2 % VEC], vv[3 % VEC]);
+    } else {
+        w[e0] = wv[0]; m[e0] = mv[0]; v[e0] = vv[0];
+    }
+}
+// Adam step t of the lazy table for the chunk at column d0 of `row` with the summed gradient g (the row stands at t - 1); the
+// lane of the row's first chunk writes last[row] = t
+template <int VEC>
+__device__ __forceinline__ void row_adam_step(float* w, float* m, float* v, int32_t* last, int64_t row, int D, int d0, const float (&g)[VEC],
+                                              const AdamConsts& c, float step_size, float bc2s, int32_t t) {
+    const int64_t e0 = row * D + d0;
+    float wv[VEC], mv[VEC], vv[VEC];
+    load_wmv<VEC>(w, m, v, e0, wv, mv, vv);
+#pragma unroll
+    for (int q = 0; q < VEC; ++q) adam_elem(wv[q], mv[q], vv[q], g[q], c, step_size, bc2s);
+    store_wmv<VEC>(w, m, v, e0, wv, mv, vv);
+    if (d0 == 0) last[row] = t;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -652,27 +698,7 @@ __device__ __forceinline__ void seg_finish(const SegSink& k, int64_t slot, int D
     }
     const int64_t row = k.uniq_row[slot];
     if (row < 0) return;
-    const int64_t e0 = row * D + d0;
-    float wv[VEC], mv[VEC], vv[VEC];
-    if (VEC == 4) {
-        const float4 a4 = *reinterpret_cast<const float4*>(k.w + e0), b4 = *reinterpret_cast<const float4*>(k.m + e0),
-                     c4 = *reinterpret_cast<const float4*>(k.v + e0);
-        wv[0] = a4.x; wv[1 % VEC] = a4.y; wv[2 % VEC] = a4.z; wv[3 % VEC] = a4.w;
-        mv[0] = b4.x; mv[1 % VEC] = b4.y; mv[2 % VEC] = b4.z; mv[3 % VEC] = b4.w;
-        vv[0] = c4.x; vv[1 % VEC] = c4.y; vv[2 % VEC] = c4.z; vv[3 % VEC] = c4.w;
-    } else {
-        wv[0] = k.w[e0]; mv[0] = k.m[e0]; vv[0] = k.v[e0];
-    }
-#pragma unroll
-    for (int q = 0; q < VEC; ++q) adam_elem(wv[q], mv[q], vv[q], acc[q], k.c, k.step_size, k.bc2s);
-    if (VEC == 4) {
-        *reinterpret_cast<float4*>(k.w + e0) = make_float4(wv[0], wv[1 % VEC], wv[2 % VEC], wv[3 % VEC]);
-        *reinterpret_cast<float4*>(k.m + e0) = make_float4(mv[0], mv[1 % VEC], mv[2 % VEC], mv[3 % VEC]);
-        *reinterpret_cast<float4*>(k.v + e0) = make_float4(vv[0], vv[1 % VEC], vv[2 % VEC], vv[3 % VEC]);
-    } else {
-        k.w[e0] = wv[0]; k.m[e0] = mv[0]; k.v[e0] = vv[0];
-    }
-    if (d0 == 0) k.last[row] = k.t;
+    row_adam_step<VEC>(k.w, k.m, k.v, k.last, row, D, d0, acc, k.c, k.step_size, k.bc2s, k.t);
 }
 __device__ __forceinline__ SegSink seg_sink_store(float* rowgrad) {
     SegSink k = {};
@@ -691,12 +717,10 @@ __device__ __forceinline__ void seg_direct_body(int bid, int nblocks, const floa
     const int chunks = D / VEC;
     const int64_t total = (int64_t)F * B * chunks;
     for (int64_t i = (int64_t)bid * blockDim.x + threadIdx.x; i < total; i += (int64_t)nblocks * blockDim.x) {
-        const int c = (int)(i % chunks);
-        const int64_t slot = i / chunks;
-        const int f = (int)(slot / B);
-        const int j = (int)(slot - (int64_t)f * B);
-        if (j >= uniq_cnt[f]) continue;
-        if (uniq_row && uniq_row[slot] < 0) continue;
+        const RowItem it = row_item<VEC, false>(i, chunks, B, uniq_cnt, nullptr);
+        if (!it.live) continue;
+        if (uniq_row && uniq_row[it.slot] < 0) continue;
+        const int f = it.f, j = it.j;
         const int32_t* sst = seg_start + (int64_t)f * (B + 1);
         const int32_t* prm = perm + (int64_t)f * B;
         const int k0 = sst[j], k1 = sst[j + 1];
@@ -711,7 +735,7 @@ __device__ __forceinline__ void seg_direct_body(int bid, int nblocks, const floa
             for (int q = 0; q < 8; ++q) p[q] = (k + q < k1) ? prm[k + q] : -1;
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
-                const float* src = d_out + ((int64_t)(p[q] >= 0 ? p[q] : 0) * F + f) * D + c * VEC;
+                const float* src = d_out + ((int64_t)(p[q] >= 0 ? p[q] : 0) * F + f) * D + it.d;
                 if (p[q] >= 0) {
                     if (VEC == 4) {
                         const float4 t = *reinterpret_cast<const float4*>(src);
@@ -728,7 +752,7 @@ __device__ __forceinline__ void seg_direct_body(int bid, int nblocks, const floa
                     for (int e = 0; e < VEC; ++e) acc[e] = __fadd_rn(acc[e], v[q][e]);
                 }
         }
-        seg_finish<VEC>(sink, slot, D, c * VEC, acc);
+        seg_finish<VEC>(sink, it.slot, D, it.d, acc);
     }
 }
 template <int VEC>
@@ -943,6 +967,24 @@ __global__ void __launch_bounds__(256) k_segment_sum_short_sink(const float* __r
     seg_direct_body<VEC>(blockIdx.x, gridDim.x, d_out, seg_start, perm, uniq_cnt, sink.uniq_row, sink, B, F, D, 0);
 }
 
+// launch geometry of the three launchers below: 16-byte chunks when every buffer allows them, the workgroups of the short
+// segments, the parts a wave splits a long segment into, and the sink (rowgrad, or the lazy table's w, m, v, last)
+struct SegGeom {
+    bool vec;
+    int direct_blocks, subs;
+    SegSink sink;
+};
+static SegGeom seg_geometry(const float* d_out, float* rowgrad, float* w, float* m, float* v, int32_t* last, const int32_t* uniq_row,
+                            int64_t B, int32_t F, int32_t D) {
+    SegGeom g = {};
+    g.vec = (D % 4 == 0) && (((uintptr_t)d_out | (uintptr_t)rowgrad | (uintptr_t)w | (uintptr_t)m | (uintptr_t)v) % 16 == 0);
+    g.direct_blocks = (int)std::min<int64_t>(cdc_ceil_div((int64_t)F * B * (g.vec ? D / 4 : D), 256), 8192);
+    g.subs = (D <= 64 && 64 % D == 0) ? 64 / D : 1;
+    g.sink.rowgrad = rowgrad;
+    g.sink.w = w; g.sink.m = m; g.sink.v = v; g.sink.last = last; g.sink.uniq_row = uniq_row;
+    return g;
+}
+
 extern "C" int cdc_embed_segment_sum(const float* d_out, const int32_t* seg_start, const int32_t* perm,
                                      const int32_t* uniq_cnt, float* sorted_scratch, float* rowgrad, int64_t B, int32_t F,
                                      int32_t D, void* stream) {
@@ -950,14 +992,11 @@ extern "C" int cdc_embed_segment_sum(const float* d_out, const int32_t* seg_star
     CDC_CHECK_ARG(d_out && seg_start && perm && uniq_cnt && rowgrad, CDC_E_BADARG, "embed_segment_sum: null pointer");
     CDC_CHECK_ARG(B > 0 && F > 0 && D > 0 && B <= CDC_SORT_MAX_ROWS, CDC_E_BADARG, "embed_segment_sum: bad sizes");
     hipStream_t st = (hipStream_t)stream;
-    const bool vec = (D % 4 == 0) && (((uintptr_t)d_out | (uintptr_t)rowgrad) % 16 == 0);
-    const int blocks = (int)std::min<int64_t>(cdc_ceil_div((int64_t)F * B * (vec ? D / 4 : D), 256), 8192) + F * SEG_LONG_BLOCKS;
-    const int subs = (D <= 64 && 64 % D == 0) ? 64 / D : 1;
-    SegSink sink = {};
-    sink.rowgrad = rowgrad;
+    const SegGeom g = seg_geometry(d_out, rowgrad, nullptr, nullptr, nullptr, nullptr, nullptr, B, F, D);
+    const int blocks = g.direct_blocks + F * SEG_LONG_BLOCKS;
     const cdc_adam_hp no_hp = {};
-    if (vec) hipLaunchKernelGGL(k_segment_sum<4>, dim3(blocks), dim3(256), 0, st, d_out, seg_start, perm, uniq_cnt, sink, no_hp, nullptr, (int32_t)B, F, D, subs);
-    else     hipLaunchKernelGGL(k_segment_sum<1>, dim3(blocks), dim3(256), 0, st, d_out, seg_start, perm, uniq_cnt, sink, no_hp, nullptr, (int32_t)B, F, D, subs);
+    if (g.vec) hipLaunchKernelGGL(k_segment_sum<4>, dim3(blocks), dim3(256), 0, st, d_out, seg_start, perm, uniq_cnt, g.sink, no_hp, nullptr, (int32_t)B, F, D, g.subs);
+    else       hipLaunchKernelGGL(k_segment_sum<1>, dim3(blocks), dim3(256), 0, st, d_out, seg_start, perm, uniq_cnt, g.sink, no_hp, nullptr, (int32_t)B, F, D, g.subs);
     CDC_LAUNCH_CHECK("embed_segment_sum");
     return 0;
 }
@@ -971,18 +1010,14 @@ extern "C" int cdc_embed_segsum_lazy_update(const float* d_out, const int32_t* s
                       hp.n_scalars > 0, CDC_E_BADARG, "embed_segsum_lazy_update: null pointer");
     CDC_CHECK_ARG(B > 0 && F > 0 && D > 0 && B <= CDC_SORT_MAX_ROWS, CDC_E_BADARG, "embed_segsum_lazy_update: bad sizes");
     hipStream_t st = (hipStream_t)stream;
-    const bool vec = (D % 4 == 0) && ((((uintptr_t)d_out | (uintptr_t)w | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
-    SegSink sink = {};
-    sink.w = w; sink.m = m; sink.v = v; sink.last = last; sink.uniq_row = uniq_row;
-    const int direct_blocks = (int)std::min<int64_t>(cdc_ceil_div((int64_t)F * B * (vec ? D / 4 : D), 256), 8192);
+    const SegGeom g = seg_geometry(d_out, nullptr, w, m, v, last, uniq_row, B, F, D);
     if (short_only) {
-        if (vec) hipLaunchKernelGGL(k_segment_sum_short_sink<4>, dim3(direct_blocks), dim3(256), 0, st, d_out, seg_start, perm, uniq_cnt, sink, hp, step_dev, (int32_t)B, F, D);
-        else     hipLaunchKernelGGL(k_segment_sum_short_sink<1>, dim3(direct_blocks), dim3(256), 0, st, d_out, seg_start, perm, uniq_cnt, sink, hp, step_dev, (int32_t)B, F, D);
+        if (g.vec) hipLaunchKernelGGL(k_segment_sum_short_sink<4>, dim3(g.direct_blocks), dim3(256), 0, st, d_out, seg_start, perm, uniq_cnt, g.sink, hp, step_dev, (int32_t)B, F, D);
+        else       hipLaunchKernelGGL(k_segment_sum_short_sink<1>, dim3(g.direct_blocks), dim3(256), 0, st, d_out, seg_start, perm, uniq_cnt, g.sink, hp, step_dev, (int32_t)B, F, D);
     } else {
-        const int blocks = direct_blocks + F * SEG_LONG_BLOCKS;
-        const int subs = (D <= 64 && 64 % D == 0) ? 64 / D : 1;
-        if (vec) hipLaunchKernelGGL(k_segment_sum<4>, dim3(blocks), dim3(256), 0, st, d_out, seg_start, perm, uniq_cnt, sink, hp, step_dev, (int32_t)B, F, D, subs);
-        else     hipLaunchKernelGGL(k_segment_sum<1>, dim3(blocks), dim3(256), 0, st, d_out, seg_start, perm, uniq_cnt, sink, hp, step_dev, (int32_t)B, F, D, subs);
+        const int blocks = g.direct_blocks + F * SEG_LONG_BLOCKS;
+        if (g.vec) hipLaunchKernelGGL(k_segment_sum<4>, dim3(blocks), dim3(256), 0, st, d_out, seg_start, perm, uniq_cnt, g.sink, hp, step_dev, (int32_t)B, F, D, g.subs);
+        else       hipLaunchKernelGGL(k_segment_sum<1>, dim3(blocks), dim3(256), 0, st, d_out, seg_start, perm, uniq_cnt, g.sink, hp, step_dev, (int32_t)B, F, D, g.subs);
     }
     CDC_LAUNCH_CHECK("embed_segsum_lazy_update");
     return 0;
@@ -1001,18 +1036,14 @@ extern "C" int cdc_embed_segsum_lazy_update_dense(const float* d_out, const int3
                       dense->step_dev && dense->step_scalars && dense->n_scalars > 0, CDC_E_BADARG,
                   "embed_segsum_lazy_update_dense: the dense parameters' descriptor table (as for cdc_adam_multi_table) is missing");
     hipStream_t st = (hipStream_t)stream;
-    const bool vec = (D % 4 == 0) && ((((uintptr_t)d_out | (uintptr_t)w | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
-    SegSink sink = {};
-    sink.w = w; sink.m = m; sink.v = v; sink.last = last; sink.uniq_row = uniq_row;
-    const int direct_blocks = (int)std::min<int64_t>(cdc_ceil_div((int64_t)F * B * (vec ? D / 4 : D), 256), 8192);
-    const int blocks = direct_blocks + (short_only ? 0 : F * SEG_LONG_BLOCKS) + n_dense_workgroups;
-    const int subs = (D <= 64 && 64 % D == 0) ? 64 / D : 1;
+    const SegGeom g = seg_geometry(d_out, nullptr, w, m, v, last, uniq_row, B, F, D);
+    const int blocks = g.direct_blocks + (short_only ? 0 : F * SEG_LONG_BLOCKS) + n_dense_workgroups;
     const AdamHdr h = {dense->lerp_w, dense->beta2, dense->one_minus_beta2, dense->eps, dense->weight_decay, dense->grad_scale,
                        dense->step_scalars, dense->n_scalars, dense->step_dev, dense->reg_sum, dense->reg_seed};
-    if (vec) hipLaunchKernelGGL(k_segment_sum_dense<4>, dim3(blocks), dim3(256), 0, st, d_out, seg_start, perm, uniq_cnt, sink, hp, step_dev, (int32_t)B, F, D, subs,
-                                h, tensors_dev, wg_tensor_dev, wg_chunk_dev, n_dense_workgroups, short_only);
-    else     hipLaunchKernelGGL(k_segment_sum_dense<1>, dim3(blocks), dim3(256), 0, st, d_out, seg_start, perm, uniq_cnt, sink, hp, step_dev, (int32_t)B, F, D, subs,
-                                h, tensors_dev, wg_tensor_dev, wg_chunk_dev, n_dense_workgroups, short_only);
+    if (g.vec) hipLaunchKernelGGL(k_segment_sum_dense<4>, dim3(blocks), dim3(256), 0, st, d_out, seg_start, perm, uniq_cnt, g.sink, hp, step_dev, (int32_t)B, F, D, g.subs,
+                                  h, tensors_dev, wg_tensor_dev, wg_chunk_dev, n_dense_workgroups, short_only);
+    else       hipLaunchKernelGGL(k_segment_sum_dense<1>, dim3(blocks), dim3(256), 0, st, d_out, seg_start, perm, uniq_cnt, g.sink, hp, step_dev, (int32_t)B, F, D, g.subs,
+                                  h, tensors_dev, wg_tensor_dev, wg_chunk_dev, n_dense_workgroups, short_only);
     CDC_LAUNCH_CHECK("embed_segsum_lazy_update_dense");
     return 0;
 }
@@ -1025,14 +1056,9 @@ __global__ void __launch_bounds__(256) k_grad_dense(const float* __restrict__ ro
                                                     int32_t B, int32_t F, int32_t D, int64_t R) {
     const int64_t total = (int64_t)F * B * D;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int d = (int)(i % D);
-        const int64_t slot = i / D;
-        const int f = (int)(slot / B);
-        const int j = (int)(slot - (int64_t)f * B);
-        if (j >= uniq_cnt[f]) continue;
-        const int32_t row = uniq_row[slot];
-        if (row < 0 || (int64_t)row >= R) continue;
-        grad[(int64_t)row * D + d] += rowgrad[i];
+        const RowItem it = row_item<1>(i, D, B, uniq_cnt, uniq_row);
+        if (!it.live || it.row >= R) continue;
+        grad[it.row * D + it.d] += rowgrad[i];
     }
 }
 
@@ -1061,16 +1087,12 @@ __global__ void __launch_bounds__(256) k_adam_touched(const float* __restrict__ 
     step_scalars_at(hp.step_scalars, hp.n_scalars, *step_dev, step_size, bc2s);
     const int64_t total = (int64_t)F * B * D;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int d = (int)(i % D);
-        const int64_t slot = i / D;
-        const int f = (int)(slot / B);
-        const int j = (int)(slot - (int64_t)f * B);
-        if (j >= uniq_cnt[f]) continue;
-        const int64_t row = uniq_row[slot];
-        if (row < 0) continue;
-        float wv = w[row * D + d], mv = m[row * D + d], vv = v[row * D + d];
+        const RowItem it = row_item<1>(i, D, B, uniq_cnt, uniq_row);
+        if (!it.live) continue;
+        const int d = it.d;
+        float wv = w[it.row * D + d], mv = m[it.row * D + d], vv = v[it.row * D + d];
         adam_elem(wv, mv, vv, rowgrad[i], c, step_size, bc2s);
-        float* s = side + slot * 3 * D;
+        float* s = side + it.slot * 3 * D;
         s[d] = wv; s[D + d] = mv; s[2 * D + d] = vv;
     }
 }
@@ -1146,17 +1168,13 @@ __global__ void __launch_bounds__(256) k_adam_patch(const float* __restrict__ si
                                                     int32_t D) {
     const int64_t total = (int64_t)F * B * D;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int d = (int)(i % D);
-        const int64_t slot = i / D;
-        const int f = (int)(slot / B);
-        const int j = (int)(slot - (int64_t)f * B);
-        if (j >= uniq_cnt[f]) continue;
-        const int64_t row = uniq_row[(int64_t)f * B + j];
-        if (row < 0) continue;
-        const float* s = side + slot * 3 * D;
-        w[row * D + d] = s[d];
-        m[row * D + d] = s[D + d];
-        v[row * D + d] = s[2 * D + d];
+        const RowItem it = row_item<1>(i, D, B, uniq_cnt, uniq_row);
+        if (!it.live) continue;
+        const int d = it.d;
+        const float* s = side + it.slot * 3 * D;
+        w[it.row * D + d] = s[d];
+        m[it.row * D + d] = s[D + d];
+        v[it.row * D + d] = s[2 * D + d];
     }
 }
 
@@ -1194,13 +1212,10 @@ __global__ void __launch_bounds__(256) k_lazy_catchup(const int32_t* __restrict_
         int d = 0, from = target;
         int64_t row = -1;
         if (act) {
-            d = (int)(i % chunks) * VEC;
-            const int64_t slot = i / chunks;
-            const int f = (int)(slot / B);
-            const int j = (int)(slot - (int64_t)f * B);
-            act = j < uniq_cnt[f];
-            if (act) row = uniq_row[(int64_t)f * B + j];
-            act = act && row >= 0;                               // < 0: padding entry of an exchanged row list
+            const RowItem it = row_item<VEC>(i, chunks, B, uniq_cnt, uniq_row);
+            d = it.d;
+            row = it.row;
+            act = it.live;                                       // row < 0: padding entry of an exchanged row list
         }
         if (act) from = last[row];
         act = act && from < target;
@@ -1210,26 +1225,10 @@ __global__ void __launch_bounds__(256) k_lazy_catchup(const int32_t* __restrict_
         float wv[VEC], mv[VEC], vv[VEC];
 #pragma unroll
         for (int k = 0; k < VEC; ++k) { wv[k] = 0.f; mv[k] = 0.f; vv[k] = 1.f; }
-        if (act) {
-            if (VEC == 4) {
-                const float4 a4 = *reinterpret_cast<const float4*>(w + e0), b4 = *reinterpret_cast<const float4*>(m + e0),
-                             c4 = *reinterpret_cast<const float4*>(v + e0);
-                wv[0] = a4.x; wv[1] = a4.y; wv[2] = a4.z; wv[3] = a4.w;
-                mv[0] = b4.x; mv[1] = b4.y; mv[2] = b4.z; mv[3] = b4.w;
-                vv[0] = c4.x; vv[1] = c4.y; vv[2] = c4.z; vv[3] = c4.w;
-            } else {
-                wv[0] = w[e0]; mv[0] = m[e0]; vv[0] = v[e0];
-            }
-        }
+        if (act) load_wmv<VEC>(w, m, v, e0, wv, mv, vv);
         adam_replay_wave<FAST, VEC>(wv, mv, vv, from, target, c, hp);
         if (!act) continue;
-        if (VEC == 4) {
-            *reinterpret_cast<float4*>(w + e0) = make_float4(wv[0], wv[1], wv[2], wv[3]);
-            *reinterpret_cast<float4*>(m + e0) = make_float4(mv[0], mv[1], mv[2], mv[3]);
-            *reinterpret_cast<float4*>(v + e0) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-        } else {
-            w[e0] = wv[0]; m[e0] = mv[0]; v[e0] = vv[0];
-        }
+        store_wmv<VEC>(w, m, v, e0, wv, mv, vv);
         // every lane of the row has read last[row] above.  mark: the row's `chunks` lanes sit in ONE wave (chunks divides 64),
         // whose load of last[row] has completed for all of them before this later store issues — lane 0 of the row
         // advances it here; otherwise k_lazy_mark does it in a separate launch.
@@ -1242,12 +1241,9 @@ __global__ void __launch_bounds__(256) k_lazy_mark(const int32_t* __restrict__ u
     const int target = *step_dev - 1;
     const int64_t total = (int64_t)F * B;
     for (int64_t slot = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; slot < total; slot += (int64_t)gridDim.x * blockDim.x) {
-        const int f = (int)(slot / B);
-        const int j = (int)(slot - (int64_t)f * B);
-        if (j >= uniq_cnt[f]) continue;
-        const int64_t row = uniq_row[slot];
-        if (row < 0) continue;
-        if (last[row] < target) last[row] = target;
+        const RowItem it = row_item<1>(slot, 1, B, uniq_cnt, uniq_row);
+        if (!it.live) continue;
+        if (last[it.row] < target) last[it.row] = target;
     }
 }
 
@@ -1503,35 +1499,16 @@ __global__ void __launch_bounds__(256) k_lazy_update(const float* __restrict__ r
     const int chunks = D / VEC;
     const int64_t total = (int64_t)F * B * chunks;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int d = (int)(i % chunks) * VEC;
-        const int64_t slot = i / chunks;
-        const int f = (int)(slot / B);
-        const int j = (int)(slot - (int64_t)f * B);
-        if (j >= uniq_cnt[f]) continue;
-        const int64_t row = uniq_row[slot];
-        if (row < 0) continue;
-        const int64_t e0 = row * D + d;
-        float wv[VEC], mv[VEC], vv[VEC], gv[VEC];
+        const RowItem it = row_item<VEC>(i, chunks, B, uniq_cnt, uniq_row);
+        if (!it.live) continue;
+        float gv[VEC];
         if (VEC == 4) {
-            const float4 a4 = *reinterpret_cast<const float4*>(w + e0), b4 = *reinterpret_cast<const float4*>(m + e0),
-                         c4 = *reinterpret_cast<const float4*>(v + e0), g4 = *reinterpret_cast<const float4*>(rowgrad + slot * D + d);
-            wv[0] = a4.x; wv[1] = a4.y; wv[2] = a4.z; wv[3] = a4.w;
-            mv[0] = b4.x; mv[1] = b4.y; mv[2] = b4.z; mv[3] = b4.w;
-            vv[0] = c4.x; vv[1] = c4.y; vv[2] = c4.z; vv[3] = c4.w;
-            gv[0] = g4.x; gv[1] = g4.y; gv[2] = g4.z; gv[3] = g4.w;
+            const float4 g4 = *reinterpret_cast<const float4*>(rowgrad + it.slot * D + it.d);
+            gv[0] = g4.x; gv[1 % VEC] = g4.y; gv[2 % VEC] = g4.z; gv[3 % VEC] = g4.w;
         } else {
-            wv[0] = w[e0]; mv[0] = m[e0]; vv[0] = v[e0]; gv[0] = rowgrad[slot * D + d];
+            gv[0] = rowgrad[it.slot * D + it.d];
         }
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) adam_elem(wv[k], mv[k], vv[k], gv[k], c, step_size, bc2s);
-        if (VEC == 4) {
-            *reinterpret_cast<float4*>(w + e0) = make_float4(wv[0], wv[1], wv[2], wv[3]);
-            *reinterpret_cast<float4*>(m + e0) = make_float4(mv[0], mv[1], mv[2], mv[3]);
-            *reinterpret_cast<float4*>(v + e0) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-        } else {
-            w[e0] = wv[0]; m[e0] = mv[0]; v[e0] = vv[0];
-        }
-        if (d == 0) last[row] = t;
+        row_adam_step<VEC>(w, m, v, last, it.row, D, it.d, gv, c, step_size, bc2s, t);
     }
 }
 
@@ -1835,16 +1812,13 @@ __global__ void __launch_bounds__(256) k_shard_pack(const float* __restrict__ ro
     const int chunks = D / VEC;
     const int64_t total = (int64_t)F * B * chunks;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % chunks);
-        const int64_t slotj = i / chunks;
-        const int f = (int)(slotj / B);
-        const int j = (int)(slotj - (int64_t)f * B);
-        if (j >= uniq_cnt[f]) continue;
-        const int32_t row = uniq_row[slotj];
-        const int s_ = slot_of[slotj];
+        const RowItem it = row_item<VEC, false>(i, chunks, B, uniq_cnt, nullptr);     // (row and slot number are loaded side by side below)
+        if (!it.live) continue;
+        const int32_t row = uniq_row[it.slot];
+        const int s_ = slot_of[it.slot];
         if (row < 0 || s_ < 0) continue;
-        float* dst = send + ((((int64_t)(row % n_rank)) * cap + s_) * F + f) * D + c * VEC;
-        const float* src = rowgrad + slotj * D + c * VEC;
+        float* dst = send + ((((int64_t)(row % n_rank)) * cap + s_) * F + it.f) * D + it.d;
+        const float* src = rowgrad + it.slot * D + it.d;
         if (VEC == 4) *reinterpret_cast<float4*>(dst) = *reinterpret_cast<const float4*>(src);
         else dst[0] = src[0];
     }

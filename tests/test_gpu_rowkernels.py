@@ -3,7 +3,8 @@ float64 (or, where the operation is exact in fp32, bit for bit against the same 
 of tests/test_gpu_head.py: padded buffers (NaN in input padding, a sentinel that must survive in output padding), accumulate
 targets pre-filled with random values and plain stores with NaN, bounds derived from the float64 terms (helpers.sum_bound) and
 capped by the suite's present figures, cross-row sums run twice for bit equality.  Every kernel gets one shape whose element
-count passes its grid cap, so that the grid-stride loop makes a second trip."""
+count passes its grid cap, so that the grid-stride loop makes a second trip.  Last: csrc/embedding.hip's cdc_embed_lazy_update,
+which no other test calls, bit for bit against the fused launch that training uses."""
 import ctypes as C
 
 import numpy as np
@@ -508,3 +509,65 @@ def test_mul_bcast_rejects_ragged(cuda, lib):
     p = t.data_ptr()
     assert lib.cdc_mul_bcast(p, p, p, 10, 3, _stream()) == BADARG and b"mul_bcast: bad argument" in lib.cdc_last_error()
     assert lib.cdc_mul_bcast_bwd(p, p, p, p, p, 10, 3, _stream()) == BADARG and b"mul_bcast_bwd: bad argument" in lib.cdc_last_error()
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the lazy table's row update from stored gradient sums (csrc/embedding.hip): cdc_embed_lazy_update after cdc_embed_segment_sum
+# against the launch that forms a row's sum and uses it on the spot
+# ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("D", [16, 6], ids=["float4", "scalar"])
+def test_lazy_update_from_rowgrad_equals_segsum_lazy_update(cuda, lib, D):
+    """sort_dedupe -> segment_sum -> lazy_update against segsum_lazy_update (short_only = 0) from a copy of the same table: the same
+    arithmetic in the same order (segments under 64 entries are summed serially in ascending order by both), so w, m, v and last
+    are equal bit for bit, and rows outside the batch keep their values.  Vocabularies 4, 40 and 100000 give segments of about
+    24, of a few and of one entry; one id per field is -1 (a padding entry: skipped by both)."""
+    from cdcmdr_amd import _lib as L
+    from cdcmdr_amd.optim import step_scalar_table
+    B, F, t = 96, 3, 3
+    vocab = (4, 40, 100000)
+    offsets = np.concatenate([[0], np.cumsum(vocab)[:-1]])
+    R = int(np.sum(vocab))
+    rng = np.random.default_rng(7 + D)
+    idx = np.stack([offsets[f] + rng.integers(0, vocab[f], size=B) for f in range(F)], axis=1).astype(np.int32)
+    for f in range(F):
+        idx[11 * f + 5, f] = -1
+    w0, m0 = rnd(rng, R, D, scale=0.1), rnd(rng, R, D, scale=0.01)
+    v0 = f32(1e-4 * rng.random((R, D)))
+    d_out = _dev(cuda, rnd(rng, B, F * D, scale=0.05))
+    scalars = step_scalar_table(1e-3, 0.9, 0.99, n=16).to(cuda).contiguous()
+    hp = L.AdamHP()
+    hp.lerp_w, hp.beta2, hp.one_minus_beta2, hp.eps = (float(np.float32(x)) for x in (1 - 0.9, 0.99, 1 - 0.99, 1e-8))
+    hp.weight_decay, hp.l2_twice = float(np.float32(1e-8)), 2.0 * float(np.float32(1e-5))
+    hp.step_scalars, hp.n_scalars = scalars.data_ptr(), scalars.shape[0]
+    step_dev = torch.full((1,), t, dtype=torch.int32, device=cuda)
+    d_idx = _dev(cuda, idx)
+    uniq = torch.full((F, B), -7, dtype=torch.int32, device=cuda)
+    seg = torch.full((F, B + 1), -7, dtype=torch.int32, device=cuda)
+    perm = torch.full((F, B), -7, dtype=torch.int32, device=cuda)
+    cnt = torch.zeros(F, dtype=torch.int32, device=cuda)
+    call(lib, "cdc_embed_sort_dedupe", d_idx.data_ptr(), uniq.data_ptr(), seg.data_ptr(), perm.data_ptr(), cnt.data_ptr(), None, B, F)
+    lens = [np.diff(seg[f, :int(cnt[f]) + 1].cpu().numpy()) for f in range(F)]
+    assert 8 <= lens[0][:4].min() and lens[0][:4].max() < 64 and lens[2].max() <= 2          # the segment classes the docstring names
+
+    def table():
+        return [_dev(cuda, a) for a in (w0, m0, v0)] + [torch.full((R,), t - 1, dtype=torch.int32, device=cuda)]
+
+    wa, ma, va, la = table()
+    rowgrad = torch.full((F, B, D), float("nan"), device=cuda)
+    call(lib, "cdc_embed_segment_sum", d_out.data_ptr(), seg.data_ptr(), perm.data_ptr(), cnt.data_ptr(), None, rowgrad.data_ptr(), B, F, D)
+    call(lib, "cdc_embed_lazy_update", rowgrad.data_ptr(), uniq.data_ptr(), cnt.data_ptr(), wa.data_ptr(), ma.data_ptr(), va.data_ptr(),
+         la.data_ptr(), hp, step_dev.data_ptr(), None, 0, B, F, D)
+    wb, mb, vb, lb = table()
+    call(lib, "cdc_embed_segsum_lazy_update", d_out.data_ptr(), seg.data_ptr(), perm.data_ptr(), cnt.data_ptr(), uniq.data_ptr(),
+         wb.data_ptr(), mb.data_ptr(), vb.data_ptr(), lb.data_ptr(), hp, step_dev.data_ptr(), B, F, D, 0)
+    for a, b, nm in ((wa, wb, "w"), (ma, mb, "m"), (va, vb, "v")):
+        assert_bits_equal(a.cpu().numpy(), b.cpu().numpy(), f"lazy_update {nm}: rowgrad round trip against the sum used on the spot")
+    assert np.array_equal(la.cpu().numpy(), lb.cpu().numpy())
+    touched = np.zeros(R, dtype=bool)
+    touched[idx[idx >= 0]] = True
+    assert touched.sum() > F and not touched.all()
+    assert np.array_equal(la.cpu().numpy(), np.where(touched, t, t - 1).astype(np.int32))
+    for a, a0, nm in ((wa, w0, "w"), (ma, m0, "m"), (va, v0, "v")):
+        got = a.cpu().numpy()
+        assert_bits_equal(got[~touched], a0[~touched], f"lazy_update {nm}: rows outside the batch")
+        assert (got[touched] != a0[touched]).any(), f"lazy_update {nm}: the batch's rows moved"
