@@ -542,3 +542,344 @@ extern "C" int cdc_eval_segments(const float* probs, int64_t ld_probs, const int
     CDC_LAUNCH_CHECK("eval_segments");
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// DeLong variance of the AUC and of the difference of two AUCs on the same rows (DeLong, DeLong & Clarke-Pearson 1988).
+// Per segment (a domain's rows, or all rows) with positives x_1..x_P, negatives y_1..y_N and psi = 1 / 0.5 / 0 for > / = / <
+// in score_key's order, the INTEGER placements are
+//     a_i = 2 sum_j psi(x_i, y_j) in [0, 2N]          c_j = 2 sum_i psi(x_i, y_j) in [0, 2P]
+// and  auc = sum a / (2 P N),   S10 = [P sum a^2 - (sum a)^2] / [P (P-1) 4 N^2],   S01 = [N sum c^2 - (sum c)^2] / [N (N-1) 4 P^2],
+// var = S10 / P + S01 / N.  With a second score vector (placements b_i, e_j) the variance of auc_a - auc_b is the same formula
+// on d = a - b and f = c - e: formed from the differences, never as var_a + var_b - 2 cov, which cancels when the vectors are close.
+//
+//   keys    every row twice, as k_metric_keys does, payload = the copy index j in [0, 2n); one radix sort per score vector
+//   scan    (rocPRIM, elements formed on the fly) per sorted position: f = first position of its tie run, cp = positives at
+//           positions <= i (the label is fetched through the payload)
+//   runend  the last position of every tie run, stored at the run's first position
+//   place   a row's placement is a difference of cp's at the bounds of its tie run and of its segment.  The second vector's
+//           placements are scattered to pl_b[j]; the first vector's are formed where they are consumed
+//   reduce  a workgroup walks a fixed stretch of the first vector's sorted order, adds per (segment, class) sum a, sum a^2
+//           (low and high 32 bits of every square in separate 64-bit sums: a square is below 2^64, n of them below 2^95) and,
+//           paired, the same of b and of d, in registers and a shuffle tree, and hands each stretch's sums over with INTEGER
+//           atomic adds — associative, so the totals do not depend on any order
+//   final   a thread per segment forms the numerators (< 2^126) and denominators (< 2^124) exactly in 128-bit integers,
+//           converts each to double with ONE rounding, and divides
+// Same rows in any order: same bits.  Launch dimensions depend on (n, n_domain, paired) alone.
+#define DL_THREADS 256
+#define DL_ITEMS 16                     // sorted positions per thread of the reduce launch
+#define DL_NSUM 9                       // per class: (sum, low and high half of the sum of squares) of a, of b and of a - b
+typedef unsigned __int128 dl_u128;
+
+struct DlScan { uint32_t f, cp; };
+struct DlScanOp {
+    __host__ __device__ DlScan operator()(const DlScan& a, const DlScan& b) const {
+        DlScan r;
+        r.f = a.f > b.f ? a.f : b.f;
+        r.cp = a.cp + b.cp;
+        return r;
+    }
+};
+struct DlScanIn {                       // element i of the scan
+    const uint64_t* keys;
+    const uint32_t* idx;
+    const int16_t* label;
+    uint32_t n;
+    __host__ __device__ DlScan operator()(uint32_t i) const {
+        DlScan r;
+        r.f = (i && keys[i] != keys[i - 1]) ? i : 0u;
+        const uint32_t j = idx[i];
+        r.cp = label[j >= n ? j - n : j] != 0 ? 1u : 0u;
+        return r;
+    }
+};
+typedef rocprim::transform_iterator<rocprim::counting_iterator<uint32_t>, DlScanIn, DlScan> DlScanIt;
+
+__global__ void __launch_bounds__(MET_THREADS) k_delong_keys(const float* __restrict__ pred, const int16_t* __restrict__ label,
+                                                             const int32_t* __restrict__ domain, int64_t ld_domain, int64_t n,
+                                                             int32_t n_domain, uint64_t* __restrict__ keys,
+                                                             uint32_t* __restrict__ idx, int32_t* __restrict__ err) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float p = pred[i];
+        int32_t d = domain ? domain[i * ld_domain] : 0;
+        const int16_t y = label[i];
+        if (p != p || d < 0 || d >= n_domain || (y != 0 && y != 1)) {
+            if (err) atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
+            d = d < 0 ? 0 : (d >= n_domain ? n_domain - 1 : d);
+        }
+        const uint32_t sk = score_key(p);
+        keys[i] = ((uint64_t)(uint32_t)d << 32) | sk;
+        keys[n + i] = ((uint64_t)(uint32_t)n_domain << 32) | sk;
+        idx[i] = (uint32_t)i;
+        idx[n + i] = (uint32_t)(n + i);
+    }
+}
+
+// start[d] as k_metric_starts; with acc given, the segment's sums are cleared for the reduce launch
+__global__ void k_delong_starts(const uint64_t* __restrict__ keys, int64_t n2, int32_t n_seg, int64_t* __restrict__ start,
+                                unsigned long long* __restrict__ acc) {
+    const int d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d <= n_seg) start[d] = d == n_seg ? n2 : lower_bound_u64(keys, 0, n2, (uint64_t)(uint32_t)d << 32);
+    if (d < n_seg && acc)
+        for (int k = 0; k < 2 * DL_NSUM; ++k) acc[(int64_t)d * 2 * DL_NSUM + k] = 0ull;
+}
+
+__global__ void __launch_bounds__(MET_THREADS) k_delong_runend(const DlScan* __restrict__ sc, int64_t n2, uint32_t* __restrict__ runend) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (int64_t)gridDim.x * blockDim.x)
+        if (i + 1 == n2 || sc[i + 1].f == (uint32_t)(i + 1)) runend[sc[i].f] = (uint32_t)i;      // one writer per run
+}
+
+// placement of the row at sorted position i of the segment [s0, s1): a_i of a positive, c_j of a negative
+__device__ __forceinline__ uint32_t dl_placement(const DlScan* __restrict__ sc, const uint32_t* __restrict__ runend, uint32_t i,
+                                                 uint32_t s0, uint32_t s1, bool* positive) {
+    const DlScan e = sc[i];
+    const uint32_t f = e.f, l = runend[f];
+    const uint32_t cp_s0 = s0 ? sc[s0 - 1].cp : 0u, cp_f = f ? sc[f - 1].cp : 0u, cp_l = sc[l].cp;
+    const uint32_t pos_below = cp_f - cp_s0, pos_run = cp_l - cp_f;
+    *positive = e.cp != (i ? sc[i - 1].cp : 0u);
+    if (*positive) return 2u * ((f - s0) - pos_below) + ((l - f + 1u) - pos_run);       // negatives below the run twice + in it
+    const uint32_t P = sc[s1 - 1].cp - cp_s0;
+    return 2u * (P - pos_below - pos_run) + pos_run;                                    // positives above the run twice + in it
+}
+
+__global__ void __launch_bounds__(MET_THREADS) k_delong_place(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ idx,
+                                                              const DlScan* __restrict__ sc, const uint32_t* __restrict__ runend,
+                                                              const int64_t* __restrict__ start, int64_t n2, uint32_t* __restrict__ pl) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (int64_t)gridDim.x * blockDim.x) {
+        const int d = (int)(keys[i] >> 32);
+        bool positive;
+        pl[idx[i]] = dl_placement(sc, runend, (uint32_t)i, (uint32_t)start[d], (uint32_t)start[d + 1], &positive);
+    }
+}
+
+__device__ __forceinline__ unsigned long long dl_wave_sum(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// workgroup b owns the sorted positions [b, b + 1) * DL_THREADS * DL_ITEMS of the FIRST score vector and adds, segment by segment,
+// what they contribute to acc[segment][class: positive, negative][DL_NSUM]
+template <bool PAIRED>
+__global__ void __launch_bounds__(DL_THREADS) k_delong_reduce(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ idx,
+                                                              const DlScan* __restrict__ sc, const uint32_t* __restrict__ runend,
+                                                              const uint32_t* __restrict__ pl_b, const int64_t* __restrict__ start,
+                                                              int64_t n2, unsigned long long* __restrict__ acc) {
+    constexpr int NS = PAIRED ? DL_NSUM : 3;
+    __shared__ unsigned long long sh[DL_THREADS / 64][2 * DL_NSUM];
+    const int tid = threadIdx.x;
+    const int64_t c0 = (int64_t)blockIdx.x * (DL_THREADS * DL_ITEMS);
+    const int64_t c1 = c0 + DL_THREADS * DL_ITEMS < n2 ? c0 + DL_THREADS * DL_ITEMS : n2;
+    if (c0 >= c1) return;
+    const int d_first = (int)(keys[c0] >> 32), d_last = (int)(keys[c1 - 1] >> 32);
+    for (int d = d_first; d <= d_last; ++d) {                                   // uniform over the workgroup
+        const int64_t s0 = start[d], s1 = start[d + 1];
+        const int64_t lo = s0 > c0 ? s0 : c0, hi = s1 < c1 ? s1 : c1;
+        if (lo >= hi) continue;                                                 // an empty segment
+        unsigned long long s[2][NS];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) s[0][k] = s[1][k] = 0ull;
+        for (int64_t i = lo + tid; i < hi; i += DL_THREADS) {
+            bool positive;
+            const unsigned long long a = dl_placement(sc, runend, (uint32_t)i, (uint32_t)s0, (uint32_t)s1, &positive);
+            unsigned long long v[NS];
+            v[0] = a; v[1] = (a * a) & 0xffffffffull; v[2] = (a * a) >> 32;
+            if constexpr (PAIRED) {
+                const unsigned long long b = pl_b[idx[i]];
+                const unsigned long long df = a - b;                            // two's complement: the sum is read back signed
+                const unsigned long long ad = a > b ? a - b : b - a;            // |a - b| < 2^32: its square fits 64 bits
+                v[3] = b;  v[4] = (b * b) & 0xffffffffull;   v[5] = (b * b) >> 32;
+                v[6] = df; v[7] = (ad * ad) & 0xffffffffull; v[8] = (ad * ad) >> 32;
+            }
+            const unsigned long long mp = positive ? ~0ull : 0ull, mn = ~mp;
+#pragma unroll
+            for (int k = 0; k < NS; ++k) { s[0][k] += v[k] & mp; s[1][k] += v[k] & mn; }
+        }
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int k = 0; k < NS; ++k) {
+                const unsigned long long w = dl_wave_sum(s[c][k]);
+                if ((tid & 63) == 0) sh[tid >> 6][c * DL_NSUM + k] = w;
+            }
+        __syncthreads();
+        if (tid < 2 * DL_NSUM && (tid % DL_NSUM) < NS) {
+            unsigned long long w = 0ull;
+#pragma unroll
+            for (int q = 0; q < DL_THREADS / 64; ++q) w += sh[q][tid];
+            if (w) atomicAdd(&acc[(int64_t)d * 2 * DL_NSUM + tid], w);
+        }
+        __syncthreads();
+    }
+}
+
+// an unsigned 128-bit integer as the nearest double (ties to even): ONE rounding.  Above 64 bits the value is cut to its top 64
+// bits with everything below OR-ed into the lowest of them — 11 bits under the rounding position, so the cut decides nothing
+__device__ __forceinline__ double dl_to_double(dl_u128 v) {
+    const uint64_t hi = (uint64_t)(v >> 64);
+    if (hi == 0) return (double)(uint64_t)v;
+    const int s = 64 - __clzll((long long)hi);
+    uint64_t top = (uint64_t)(v >> s);
+    if ((v & ((((dl_u128)1) << s) - 1)) != 0) top |= 1ull;
+    return ldexp((double)top, s);
+}
+__device__ __forceinline__ dl_u128 dl_sum_sq(const unsigned long long* t) { return ((dl_u128)t[2] << 32) + (dl_u128)t[1]; }
+
+// S10 / P + S01 / N from the exact sums of one placement vector: t1 = |sum|, t2 = sum of squares, positives then negatives.
+// Roundings: numerator and denominator to double (1 each), their quotient (1), the division by P resp. N (1; P, N are exact) —
+// 4 per term, each term >= 0, and the addition: the result is within (1 + 2^-53)^5 of the exact value
+__device__ __forceinline__ double dl_var(uint64_t P, uint64_t N, uint64_t p1, dl_u128 p2, uint64_t n1, dl_u128 n2) {
+    if (P < 2 || N < 2) return __longlong_as_double(0x7ff8000000000000ll);
+    const dl_u128 num10 = (dl_u128)P * p2 - (dl_u128)p1 * (dl_u128)p1;                 // < 2^126; >= 0 (Cauchy-Schwarz)
+    const dl_u128 num01 = (dl_u128)N * n2 - (dl_u128)n1 * (dl_u128)n1;
+    const dl_u128 den10 = (dl_u128)(P * (P - 1)) * (dl_u128)(4 * N * N);               // each factor < 2^64
+    const dl_u128 den01 = (dl_u128)(N * (N - 1)) * (dl_u128)(4 * P * P);
+    const double t10 = dl_to_double(num10) / dl_to_double(den10) / (double)P;
+    const double t01 = dl_to_double(num01) / dl_to_double(den01) / (double)N;
+    return t10 + t01;
+}
+
+__global__ void k_delong_final(const int64_t* __restrict__ start, const DlScan* __restrict__ sc, const unsigned long long* __restrict__ acc,
+                               int32_t n_seg, int32_t paired, double* __restrict__ out, int64_t* __restrict__ counts) {
+    const int d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= n_seg) return;
+    const int64_t s0 = start[d], s1 = start[d + 1], rows = s1 - s0;
+    const uint64_t P = rows > 0 ? (uint64_t)(sc[s1 - 1].cp - (s0 ? sc[s0 - 1].cp : 0u)) : 0ull, N = (uint64_t)rows - P;
+    counts[d] = rows;
+    counts[n_seg + d] = (int64_t)P;
+    const unsigned long long* p = acc + (int64_t)d * 2 * DL_NSUM;
+    const unsigned long long* q = p + DL_NSUM;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const bool both = P > 0 && N > 0;
+    const double pn = (double)P * (double)N;
+    out[d] = both ? (double)p[0] * 0.5 / pn : nan;                                     // cdc_eval_metrics' expression
+    out[n_seg + d] = dl_var(P, N, p[0], dl_sum_sq(p), q[0], dl_sum_sq(q));
+    if (!paired) return;
+    out[2 * n_seg + d] = both ? (double)p[3] * 0.5 / pn : nan;
+    out[3 * n_seg + d] = dl_var(P, N, p[3], dl_sum_sq(p + 3), q[3], dl_sum_sq(q + 3));
+    const long long dp = (long long)p[6], dq = (long long)q[6];
+    out[4 * n_seg + d] = both ? (double)dp * 0.5 / pn : nan;                           // sum (a - b) / (2 P N): no cancellation of two rounded AUCs
+    out[5 * n_seg + d] = dl_var(P, N, (uint64_t)(dp < 0 ? -dp : dp), dl_sum_sq(p + 6), (uint64_t)(dq < 0 ? -dq : dq), dl_sum_sq(q + 6));
+}
+
+struct DelongLayout {
+    int64_t keys_in, keys_out, idx_in, idx_out, pl_b, start, acc, temp, temp_bytes, total;
+};
+// everything but rocPRIM's temporary storage: plain arithmetic (argument checks use it before any HIP or rocPRIM call)
+static void delong_fixed_layout(int64_t n, int32_t n_domain, int32_t paired, DelongLayout* L) {
+    const int64_t n2 = 2 * n, seg = (int64_t)n_domain + 1;
+    int64_t off = 0;
+    L->keys_in = off;  off += align_up(n2 * 8);               // after the sort: the scan's (f, cp)
+    L->keys_out = off; off += align_up(n2 * 8);
+    L->idx_in = off;   off += align_up(n2 * 4);               // after the sort: runend
+    L->idx_out = off;  off += align_up(n2 * 4);
+    L->pl_b = off;     off += paired ? align_up(n2 * 4) : 0;
+    L->start = off;    off += align_up((seg + 1) * 8);
+    L->acc = off;      off += align_up(seg * 2 * DL_NSUM * 8);
+    L->temp = off;
+    L->temp_bytes = 0;
+    L->total = off;
+}
+static int delong_layout(int64_t n, int32_t n_domain, int32_t paired, DelongLayout* L) {
+    delong_fixed_layout(n, n_domain, paired, L);
+    const size_t n2 = (size_t)(2 * n);
+    size_t t_sort = 0, t_scan = 0;
+    hipError_t e = rocprim::radix_sort_pairs(nullptr, t_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr,
+                                             (uint32_t*)nullptr, n2, 0, 64, (hipStream_t)0, false);
+    if (e == hipSuccess)
+        e = rocprim::inclusive_scan(nullptr, t_scan, DlScanIt(rocprim::counting_iterator<uint32_t>(0), DlScanIn{nullptr, nullptr, nullptr, 0u}),
+                                    (DlScan*)nullptr, n2, DlScanOp(), (hipStream_t)0, false);
+    if (e != hipSuccess) { cdc_set_error("eval_auc_delong: rocprim size query failed: %s", hipGetErrorString(e)); return (int)e; }
+    L->temp_bytes = (int64_t)std::max(t_sort, t_scan);        // the two run one after the other
+    L->total = L->temp + align_up(L->temp_bytes);
+    return 0;
+}
+static bool delong_sizes_ok(int64_t n, int32_t n_domain) { return n > 0 && n < (1ll << 31) && n_domain > 0 && n_domain < (1 << 20); }
+
+extern "C" int64_t cdc_eval_auc_delong_workspace_bytes(int64_t n, int32_t n_domain, int32_t paired) {
+    if (!delong_sizes_ok(n, n_domain)) return 0;
+    DelongLayout L;
+    if (delong_layout(n, n_domain, paired != 0, &L) != 0) return -1;
+    return L.total;
+}
+
+// sort one score vector's 2n keys, scan them, mark the tie runs' ends: leaves keys_out, idx_out, sc, runend and start describing it
+static int delong_order(const float* pred, const int16_t* label, const int32_t* domain, int64_t ld_domain, int64_t n, int32_t n_domain,
+                        int32_t* err_flag, char* base, const DelongLayout& L, unsigned long long* acc, hipStream_t st) {
+    uint64_t* keys_in = (uint64_t*)(base + L.keys_in);
+    uint64_t* keys_out = (uint64_t*)(base + L.keys_out);
+    uint32_t* idx_in = (uint32_t*)(base + L.idx_in);
+    uint32_t* idx_out = (uint32_t*)(base + L.idx_out);
+    DlScan* sc = (DlScan*)keys_in;                                  // the unsorted keys and payloads are dead once the sort has run
+    uint32_t* runend = idx_in;
+    int64_t* start = (int64_t*)(base + L.start);
+    const int64_t n2 = 2 * n;
+    const int seg = n_domain + 1;
+    int blocks = (int)std::min<int64_t>(cdc_ceil_div(n, MET_THREADS), 4096);
+    hipLaunchKernelGGL(k_delong_keys, dim3(blocks), dim3(MET_THREADS), 0, st, pred, label, domain, ld_domain, n, n_domain, keys_in, idx_in,
+                       err_flag);
+    CDC_LAUNCH_CHECK("eval_auc_delong(keys)");
+    int end_bit = 33;
+    while (end_bit < 64 && ((uint64_t)n_domain >> (end_bit - 32)) != 0) ++end_bit;
+    size_t temp_bytes = (size_t)L.temp_bytes;
+    hipError_t e = rocprim::radix_sort_pairs(base + L.temp, temp_bytes, (const uint64_t*)keys_in, keys_out, (const uint32_t*)idx_in, idx_out,
+                                             (size_t)n2, 0, end_bit, st, false);
+    if (e != hipSuccess) { cdc_set_error("eval_auc_delong: radix sort failed: %s", hipGetErrorString(e)); return (int)e; }
+    hipLaunchKernelGGL(k_delong_starts, dim3((int)cdc_ceil_div(seg + 1, 64)), dim3(64), 0, st, keys_out, n2, seg, start, acc);
+    CDC_LAUNCH_CHECK("eval_auc_delong(starts)");
+    temp_bytes = (size_t)L.temp_bytes;
+    e = rocprim::inclusive_scan(base + L.temp, temp_bytes,
+                                DlScanIt(rocprim::counting_iterator<uint32_t>(0), DlScanIn{keys_out, idx_out, label, (uint32_t)n}), sc,
+                                (size_t)n2, DlScanOp(), st, false);
+    if (e != hipSuccess) { cdc_set_error("eval_auc_delong: scan failed: %s", hipGetErrorString(e)); return (int)e; }
+    blocks = (int)std::min<int64_t>(cdc_ceil_div(n2, MET_THREADS), 8192);
+    hipLaunchKernelGGL(k_delong_runend, dim3(blocks), dim3(MET_THREADS), 0, st, sc, n2, runend);
+    CDC_LAUNCH_CHECK("eval_auc_delong(runend)");
+    return 0;
+}
+
+extern "C" int cdc_eval_auc_delong(const float* pred_a, const float* pred_b, const int16_t* label, const int32_t* domain, int64_t ld_domain,
+                                   int64_t n, int32_t n_domain, double* out, int64_t* counts, int32_t* err_flag, void* workspace,
+                                   int64_t workspace_bytes, void* stream) {
+    CDC_CHECK_ARG(pred_a && label && out && counts && workspace, CDC_E_BADARG, "eval_auc_delong: null pointer");
+    CDC_CHECK_ARG(n > 0 && n_domain > 0 && n_domain < (1 << 20) && ld_domain >= 0, CDC_E_BADARG,
+                  "eval_auc_delong: bad sizes n=%ld n_domain=%d ld_domain=%ld", (long)n, n_domain, (long)ld_domain);
+    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_auc_delong: n_domain=%d needs the domain column", n_domain);
+    CDC_CHECK_ARG(n < (1ll << 31), CDC_E_TOOBIG, "eval_auc_delong: n=%ld exceeds the 2^31 rows a placement counts in 32 bits", (long)n);
+    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_auc_delong: workspace must be 256-byte aligned");
+    const int32_t paired = pred_b != nullptr;
+    DelongLayout L;
+    delong_fixed_layout(n, n_domain, paired, &L);
+    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_auc_delong: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
+    int rc = delong_layout(n, n_domain, paired, &L);
+    if (rc != 0) return rc;
+    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_auc_delong: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
+    char* base = (char*)workspace;
+    const uint64_t* keys = (const uint64_t*)(base + L.keys_out);
+    const uint32_t* idx = (const uint32_t*)(base + L.idx_out);
+    const DlScan* sc = (const DlScan*)(base + L.keys_in);
+    const uint32_t* runend = (const uint32_t*)(base + L.idx_in);
+    uint32_t* pl_b = (uint32_t*)(base + L.pl_b);
+    const int64_t* start = (const int64_t*)(base + L.start);
+    unsigned long long* acc = (unsigned long long*)(base + L.acc);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n2 = 2 * n;
+    const int seg = n_domain + 1;
+    if (paired) {                                                   // the second vector first: its placements wait in pl_b
+        rc = delong_order(pred_b, label, domain, ld_domain, n, n_domain, err_flag, base, L, nullptr, st);
+        if (rc != 0) return rc;
+        const int blocks = (int)std::min<int64_t>(cdc_ceil_div(n2, MET_THREADS), 8192);
+        hipLaunchKernelGGL(k_delong_place, dim3(blocks), dim3(MET_THREADS), 0, st, keys, idx, sc, runend, start, n2, pl_b);
+        CDC_LAUNCH_CHECK("eval_auc_delong(place)");
+    }
+    rc = delong_order(pred_a, label, domain, ld_domain, n, n_domain, err_flag, base, L, acc, st);
+    if (rc != 0) return rc;
+    const int blocks = (int)cdc_ceil_div(n2, DL_THREADS * DL_ITEMS);
+    if (paired)
+        hipLaunchKernelGGL(k_delong_reduce<true>, dim3(blocks), dim3(DL_THREADS), 0, st, keys, idx, sc, runend, (const uint32_t*)pl_b, start, n2, acc);
+    else
+        hipLaunchKernelGGL(k_delong_reduce<false>, dim3(blocks), dim3(DL_THREADS), 0, st, keys, idx, sc, runend, (const uint32_t*)nullptr, start, n2, acc);
+    CDC_LAUNCH_CHECK("eval_auc_delong(reduce)");
+    hipLaunchKernelGGL(k_delong_final, dim3((int)cdc_ceil_div(seg, 64)), dim3(64), 0, st, start, sc, acc, seg, paired, out, counts);
+    CDC_LAUNCH_CHECK("eval_auc_delong(final)");
+    return 0;
+}

@@ -11,9 +11,14 @@ With a user column configured the same pass also yields GAUC — the reference's
 user's rows, averaged over the users that have both classes, weighted by their row count or a given weight — from one more
 C-ABI call (`cdc_eval_gauc`) on the same device-resident predictions.
 
+`eval_auc_ci` adds what an AUC needs to be judged: its DeLong standard error on this evaluation set, and for two prediction
+vectors over the same rows the difference of their AUCs with the standard error of that difference (`cdc_eval_auc_delong`);
+`Evaluator(auc_ci=True)` and `Evaluator.compare` report them.
+
 `eval_segments` serves CDC's matrix update (run.py:549-558) instead: the metric of every contiguous row segment of ONE forward's
 raw output, each segment scored by its own tower column (`cdc_eval_segments`; probe.py lays the domains' batches out that way).
 """
+import collections
 import ctypes as C
 import math
 
@@ -175,6 +180,71 @@ def eval_gauc(pred, label, user, n_user, domain=None, n_domain=1, user_weight=No
     return out, counts[:seg], counts[seg:]
 
 
+AucCI = collections.namedtuple("AucCI", "auc var rows positives")
+AucCIPaired = collections.namedtuple("AucCIPaired", "auc var rows positives auc_b var_b delta var_delta")
+
+
+def eval_auc_ci(pred, label, domain=None, n_domain=1, pred_b=None):
+    """AUC with its DeLong variance (DeLong, DeLong & Clarke-Pearson 1988) per domain and over all rows; inputs as `eval_metrics`
+    (domain: int32 [n] or a strided column view).  Returns a namedtuple of device tensors with n_domain + 1 entries each —
+    domains 0..n_domain-1, then ALL rows: `auc`, `var` (f64), `rows`, `positives` (i64); `auc` is `eval_metrics`' figure bit for
+    bit.  With `pred_b` (a second prediction vector over the same rows) also `auc_b`, `var_b`, `delta` = auc - auc_b and
+    `var_delta`, the variance of the PAIRED difference (formed from the rows' placement differences: far below var + var_b when
+    the two vectors are close).  A standard error is `var.sqrt()`.  `auc` / `delta` are NaN for an empty or single-class segment,
+    a variance is NaN when a class has fewer than two rows.  No host synchronisation; the error word (1 + a row with a NaN
+    prediction in either vector, a label outside {0, 1} or a domain outside range) is kept as `eval_auc_ci.last_err`."""
+    lib = L.load()
+    if not pred.is_cuda:
+        raise L.HipExtensionError("eval_auc_ci needs device tensors; there is no CPU fallback")
+    pred = pred.reshape(-1).to(torch.float32).contiguous()
+    label = label.reshape(-1).to(torch.int16).contiguous()
+    n = pred.numel()
+    if label.numel() != n:
+        raise ValueError(f"{n} predictions but {label.numel()} labels")
+    if pred_b is not None:
+        pred_b = pred_b.reshape(-1).to(device=pred.device, dtype=torch.float32).contiguous()
+        if pred_b.numel() != n:
+            raise ValueError(f"{n} predictions but {pred_b.numel()} in pred_b")
+    n_domain = int(n_domain)
+    ld = 0
+    if domain is not None:
+        domain, ld = _id_column(domain, n, "domain")
+    elif n_domain != 1:
+        raise ValueError("n_domain > 1 needs the domain column")
+    dev = pred.device
+    seg = n_domain + 1
+    paired = pred_b is not None
+    out = torch.empty((6 if paired else 2) * seg, dtype=torch.float64, device=dev)
+    counts = torch.empty(2 * seg, dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    nbytes = lib.cdc_eval_auc_delong_workspace_bytes(n, n_domain, int(paired))
+    if nbytes <= 0:
+        raise RuntimeError(f"cdc_eval_auc_delong_workspace_bytes refused n={n}, n_domain={n_domain}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    L.launch("cdc_eval_auc_delong", lib.cdc_eval_auc_delong,
+             (pred.data_ptr(), pred_b.data_ptr() if paired else None, label.data_ptr(), None if domain is None else domain.data_ptr(), ld,
+              n, n_domain, out.data_ptr(), counts.data_ptr(), err.data_ptr(), ws.data_ptr(), nbytes),
+             C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    eval_auc_ci.last_err = err
+    o = out.reshape(-1, seg)
+    if paired:
+        return AucCIPaired(o[0], o[1], counts[:seg], counts[seg:], o[2], o[3], o[4], o[5])
+    return AucCI(o[0], o[1], counts[:seg], counts[seg:])
+
+
+def _se(var):
+    return math.sqrt(var) if var == var else math.nan
+
+
+def _z(delta, se):
+    """delta / se; NaN for 0 / 0, +-inf for a non-zero delta over se 0"""
+    if se != se or delta != delta:
+        return math.nan
+    if se == 0:
+        return math.nan if delta == 0 else math.copysign(math.inf, delta)
+    return delta / se
+
+
 class Evaluator:
     """Mirror of Run.test (run.py:647-690): the CDC, multi-tower and single-tower branches.
 
@@ -186,11 +256,20 @@ class Evaluator:
     domain_cnt_weight: {domain: weight} or a sequence, as Run.domain_cnt_weight (mean_auc / mean_loss, run.py:706-707).
     user_idx: column of X that holds the user id (in [0, n_user)).  When set, test() adds GAUC (base.py:33-64): total_gauc, and
               with per-domain evaluation domain_gauc and mean_gauc.  user_weight: f64 [n_user] or {user: weight} (a user missing
-              from the dict weighs NaN: the reference raises KeyError for it), None = the user's row count."""
+              from the dict weighs NaN: the reference raises KeyError for it), None = the user's row count.
+    auc_ci: test() adds the DeLong standard errors of its AUCs (`eval_auc_ci`): total_auc_se, and with per-domain evaluation
+            domain_auc_se {d: value} and mean_auc_se = sqrt(sum_d w_d^2 var_d) over the domains mean_auc sums (disjoint row sets:
+            independent given the model).  Significance-aware early stopping and intervals for GAUC or log-loss are not offered.
+    precision: None, or "bf16" / "f32": the model is switched to it for the scoring pass and switched back afterwards, so two
+            evaluators around ONE module can score it under two precisions (`compare`)."""
 
     def __init__(self, model, mode="multi", domain_idx=None, n_domain=1, domain_cnt_weight=None, is_evaluate_multi_domain=True,
-                 user_idx=None, n_user=None, user_weight=None):
+                 user_idx=None, n_user=None, user_weight=None, auc_ci=False, precision=None):
         self.model, self.mode = model, mode
+        self.auc_ci = bool(auc_ci)
+        if precision not in (None, "bf16", "f32"):
+            raise ValueError(f"precision must be None, 'bf16' or 'f32', not {precision!r}")
+        self.precision = precision
         self.domain_idx, self.n_domain = domain_idx, int(n_domain)
         self.domain_cnt_weight = domain_cnt_weight
         self.is_evaluate_multi_domain = bool(is_evaluate_multi_domain) and domain_idx is not None
@@ -214,6 +293,10 @@ class Evaluator:
         model = self.model
         was_training = model.training
         model.eval()
+        was_precision = None
+        if self.precision is not None:
+            was_precision = getattr(model, "base_model_instance", model).precision
+            model.set_precision(self.precision)
         preds, labels, domains, users = [], [], [], []
         try:
             with torch.no_grad():
@@ -235,6 +318,8 @@ class Evaluator:
                         users.append(X[:, self.user_idx].to(torch.int32))
         finally:
             model.train(was_training)
+            if was_precision is not None and was_precision != self.precision:
+                model.set_precision(was_precision)
         if not preds:
             raise ValueError("empty evaluation set")
         return torch.cat(preds), torch.cat(labels), (torch.cat(domains) if domains else None), (torch.cat(users) if users else None)
@@ -257,12 +342,14 @@ class Evaluator:
 
     def test(self, data_loader):
         """The reference's result_dict: total_auc, total_loss (+ domain_auc, domain_loss, mean_auc, mean_loss); with user_idx also
-        total_gauc (+ domain_gauc, mean_gauc)."""
+        total_gauc (+ domain_gauc, mean_gauc); with auc_ci also total_auc_se (+ domain_auc_se, mean_auc_se)."""
         pred, label, domain, user = self._score(data_loader)
         multi = self.is_evaluate_multi_domain
         auc, loss, rows, pos = eval_metrics(pred, label, domain if multi else None, self.n_domain if multi else 1)
         if user is not None:                                   # queued behind the metrics: still nothing has been read back
             gauc = eval_gauc(pred, label, user, self.n_user, domain if multi else None, self.n_domain if multi else 1, self.user_weight)[0]
+        if self.auc_ci:                                        # likewise queued
+            ci_var = eval_auc_ci(pred, label, domain if multi else None, self.n_domain if multi else 1).var
         auc, loss, rows, pos = auc.cpu().tolist(), loss.cpu().tolist(), rows.cpu().tolist(), pos.cpu().tolist()   # the one sync
         bad = int(eval_metrics.last_err.item())
         if bad:
@@ -291,6 +378,45 @@ class Evaluator:
                 domain_gauc = {d: gauc[d] for d in range(self.n_domain) if rows[d] > 0}
                 result["domain_gauc"] = domain_gauc
                 result["mean_gauc"] = sum(self._weight(d) * v for d, v in domain_gauc.items())     # as mean_auc; NaN when a domain has no countable user
+        if self.auc_ci:
+            var = ci_var.cpu().tolist()
+            result["total_auc_se"] = _se(var[-1])
+            if multi:
+                present = [d for d in range(self.n_domain) if rows[d] > 0]
+                result["domain_auc_se"] = {d: _se(var[d]) for d in present}
+                result["mean_auc_se"] = _se(sum(self._weight(d) ** 2 * var[d] for d in present))   # NaN when a summed domain's variance is
+        return result
+
+    def compare(self, other, data_loader):
+        """Paired comparison of this evaluator's model with `other`'s (an Evaluator) on ONE evaluation set: the loader is scored
+        with self.model, then with other.model — `other` may wrap the same module under another `precision`; the passes run one
+        after the other.  Both passes must see the same labels and domain columns in the same order (ValueError otherwise: a
+        shuffling loader shows here).  Returns total_delta = AUC(self) - AUC(other), total_delta_se (DeLong's paired standard
+        error) and total_z = delta / se, and with per-domain evaluation domain_delta / domain_delta_se / domain_z {d: value} and
+        mean_delta / mean_delta_se / mean_z, weighted by domain_cnt_weight like mean_auc.  z is NaN for 0 / 0 (identical
+        predictions) and +-inf for a non-zero delta with se 0."""
+        pred_a, label, domain, _ = self._score(data_loader)
+        pred_b, label_b, domain_b, _ = other._score(data_loader)
+        if label.shape != label_b.shape or not torch.equal(label, label_b):
+            raise ValueError("the two scoring passes saw different labels: compare() needs a loader that yields the same rows in the same order")
+        if (domain is None) != (domain_b is None) or (domain is not None and not torch.equal(domain, domain_b)):
+            raise ValueError("the two scoring passes saw different domain columns: compare() needs a loader that yields the same rows in the same order")
+        multi = self.is_evaluate_multi_domain
+        ci = eval_auc_ci(pred_a, label, domain if multi else None, self.n_domain if multi else 1, pred_b=pred_b)
+        delta, var, rows = ci.delta.cpu().tolist(), ci.var_delta.cpu().tolist(), ci.rows.cpu().tolist()
+        bad = int(eval_auc_ci.last_err.item())
+        if bad:
+            raise ValueError(f"evaluation row {bad - 1}: NaN prediction, label outside {{0,1}} or domain outside [0, {self.n_domain})")
+        se = _se(var[-1])
+        result = {"total_delta": delta[-1], "total_delta_se": se, "total_z": _z(delta[-1], se)}
+        if multi:
+            present = [d for d in range(self.n_domain) if rows[d] > 0]
+            d_se = {d: _se(var[d]) for d in present}
+            mean_delta = sum(self._weight(d) * delta[d] for d in present)
+            mean_se = _se(sum(self._weight(d) ** 2 * var[d] for d in present))
+            result.update({"domain_delta": {d: delta[d] for d in present}, "domain_delta_se": d_se,
+                           "domain_z": {d: _z(delta[d], d_se[d]) for d in present},
+                           "mean_delta": mean_delta, "mean_delta_se": mean_se, "mean_z": _z(mean_delta, mean_se)})
         return result
 
     def _weight(self, d):

@@ -1156,6 +1156,34 @@ int cdc_eval_gauc(const float* pred, const int16_t* label, const int32_t* user, 
                   const int32_t* domain, int64_t ld_domain, int32_t n_domain, const double* user_weight, int64_t n,
                   double* out, int64_t* counts, int32_t* err_flag, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* DeLong standard errors (DeLong, DeLong & Clarke-Pearson 1988) of the AUCs cdc_eval_metrics reports, and the paired comparison of
+ * two score vectors on the same rows.  pred_a, label, domain, ld_domain, n_domain as for cdc_eval_metrics; pred_b f32 [n] or NULL
+ * (unpaired).  Per segment (domain 0..n_domain-1, then ALL rows) with positives x_1..x_P, negatives y_1..y_N, scores compared in
+ * cdc_eval_metrics' order (-0.0 ties with +0.0) and psi(x, y) = 1, 1/2, 0 for x >, =, < y:
+ *     a_i = 2 sum_j psi(x_i, y_j),  c_j = 2 sum_i psi(x_i, y_j)             (integer placements)
+ *     auc = sum a / (2 P N)
+ *     var = S10 / P + S01 / N,   S10 = [P sum a^2 - (sum a)^2] / [P (P-1) 4 N^2],   S01 = [N sum c^2 - (sum c)^2] / [N (N-1) 4 P^2]
+ * and, with b_i, e_j the placements under pred_b:  delta = auc_a - auc_b = sum (a - b) / (2 P N),  var_delta = the formula of var on
+ * d = a - b and f = c - e — formed from the differences themselves, not as var_a + var_b - 2 cov, which cancels when the two
+ * vectors are close.
+ *   out    [(pred_b ? 6 : 2) * (n_domain+1)] doubles: auc_a, var_a (and auc_b, var_b, delta, var_delta), each an array over the
+ *          segments.  auc and delta are NaN when P == 0 or N == 0, every variance when P < 2 or N < 2.  auc_a is formed by
+ *          cdc_eval_metrics' expression and equals its figure bit for bit (wherever sum a < 2^53).
+ *   counts [2*(n_domain+1)] int64: rows per segment, then positives per segment.
+ *   err_flag (optional): as cdc_eval_metrics — 1 + the index of a row with a NaN in pred_a or pred_b, a label other than 0/1 or a
+ *          domain outside [0, n_domain) (the largest such index).
+ * Every sum is an exact integer (squares below 2^64 are added as two 32-bit halves, with integer atomics), numerators (< 2^126)
+ * and denominators are formed in 128-bit integers and converted to double with one rounding each: the same rows in any order
+ * give the same bits, and a variance is within 5 roundings of the exact rational.  Limits: null pointers, n <= 0, n_domain outside
+ * [1, 2^20), a workspace too small or not 256-byte aligned: CDC_E_BADARG; n >= 2^31: CDC_E_TOOBIG — all before anything is
+ * launched.  Stream-ordered: no allocation, no synchronisation, no state kept; the launch dimensions depend on (n, n_domain,
+ * pred_b != NULL) alone, so the call can be captured in a graph.
+ * workspace: cdc_eval_auc_delong_workspace_bytes(n, n_domain, paired) bytes, 256-byte aligned; 0 for sizes the call refuses. */
+int64_t cdc_eval_auc_delong_workspace_bytes(int64_t n, int32_t n_domain, int32_t paired);
+int cdc_eval_auc_delong(const float* pred_a, const float* pred_b, const int16_t* label, const int32_t* domain, int64_t ld_domain,
+                        int64_t n, int32_t n_domain, double* out, int64_t* counts, int32_t* err_flag, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+
 /* Per-segment BCE of CDC's probe evaluation (run.py:549-558): one batch of every domain went through ONE eval
  * forward; segment s is the rows [seg_start[s], seg_start[s+1]) of probs [rows, n_cols] (row stride ld_probs: all towers'
  * probabilities) and is scored by column seg_col[s] (NULL = column 0).  seg_start [n_seg+1] is non-decreasing; rows at or past
