@@ -14,6 +14,7 @@ loss every step (run.py:489, model/layer.py:31,96-112).  So every table row move
 
 Dense parameters go through one multi-tensor kernel with the L2 gradient 2*l2*w folded in.
 """
+import collections
 import ctypes as C
 import math
 
@@ -38,6 +39,41 @@ def step_scalar_table(lr, beta1, beta2, n=4096, truncate=False):
     return tab
 
 
+def _f32(v):
+    return float(torch.tensor(v, dtype=torch.float64).to(torch.float32))
+
+
+ReplayConstants = collections.namedtuple("ReplayConstants", "inv_bc2 replay_tab k1 k2 ik1 ik2 k1_lo k2_lo")
+
+
+def replay_constants(tab, lerp_w, omb2, eps, wd, l2_table):
+    """What the lazy table's fast replay reads beside the step scalars `tab` (step_scalar_table, fp32 [n,2]), formed in double on
+    the CPU: inv_bc2 [n] = 1 / tab[:,1], and for the replay in scaled state (csrc/common.h adam_replay_wave_scaled) the per-step
+    table replay_tab [n,2] with its six scale constants.  lerp_w, omb2, eps, wd: the fp32 values the kernels get; l2_table: the
+    table's L2 coefficient.  Without a decay term (2*l2 + wd == 0, or a scale that underflows) there is no scaled form:
+    replay_tab is None and the constants are 0, which makes the kernels take the unscaled fast step."""
+    inv_bc2 = (1.0 / tab[:, 1].double()).to(torch.float32).contiguous()
+    k1 = k2 = ik1 = ik2 = k1_lo = k2_lo = 0.0
+    replay_tab = None
+    c = float(torch.tensor(2.0 * _f32(l2_table) + wd, dtype=torch.float64).to(torch.float32))
+    if c > 0.0:
+        k1r, k2r = _f32(lerp_w * c), _f32(omb2 * c * c)
+        if k1r > 0.0 and k2r > 0.0:
+            # the scales as the kernel applies them: in by the fp32 reciprocals ik, out by K = 1 / ik (as fp32 pair hi + lo), the
+            # per-step constants formed with the same K — in and out are inverses to 2^-48 (cdc_adam_hp)
+            ik1, ik2 = _f32(1.0 / k1r), _f32(1.0 / k2r)
+            K1, K2 = 1.0 / ik1, 1.0 / ik2
+            k1, k2 = _f32(K1), _f32(K2)
+            k1_lo, k2_lo = _f32(K1 - k1), _f32(K2 - k2)
+            t64 = tab.double()
+            A = t64[:, 0] * K1 * t64[:, 1] / math.sqrt(K2)
+            E = eps * t64[:, 1] / math.sqrt(K2)
+            A[0] = A[1]                                           # (row 0 = "step 0" is never replayed; keep it finite)
+            rt = torch.stack([-1.0 / A, -E / A], dim=1)           # C1 = -1/A_t, C2 = -E_t/A_t (csrc/common.h adam_scaled_step_pk)
+            replay_tab = rt.to(torch.float32).contiguous()
+    return ReplayConstants(inv_bc2, replay_tab, k1, k2, ik1, ik2, k1_lo, k2_lo)
+
+
 class FusedAdam:
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=1e-8, table_mode="dense", frozen=(),
                  fast_replay=True, flush_every=64):
@@ -59,7 +95,6 @@ class FusedAdam:
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)       # 1-based step of the current update
         tab = step_scalar_table(lr, betas[0], betas[1], n=65536, truncate=True)
         self.scalars = tab.to(dev).contiguous()
-        self.inv_bc2 = (1.0 / tab[:, 1].double()).to(torch.float32).to(dev).contiguous()
         self.fast_replay = bool(fast_replay) and table_mode == "lazy"
         self.flush_every = int(flush_every) if table_mode == "lazy" else 0
         self.reg_sum = torch.zeros(2, dtype=torch.float64, device=dev)       # [0] dense params (l2 applied), [1] table sum(w^2)
@@ -79,26 +114,14 @@ class FusedAdam:
             l2_of[id(p)] = l2_of.get(id(p), 0.0) + l2
         self._l2_of = l2_of
         self.l2_table = l2_of.get(id(self.table), 0.0)
-        # fast replay in scaled state (csrc/common.h adam_replay_wave_scaled): constants and the per-step table, in double
-        self._k1 = self._k2 = 0.0
+        # fast replay in scaled state (csrc/common.h adam_replay_wave_scaled): constants and the per-step table
+        rc = replay_constants(tab, self._lerp_w, self._omb2, self._eps, self._wd, self.l2_table)
+        self._k1 = self._k2 = self._ik1 = self._ik2 = self._k1_lo = self._k2_lo = 0.0
         self.replay_tab = None
-        c = float(torch.tensor(2.0 * f32(self.l2_table) + self._wd, dtype=torch.float64).to(torch.float32))
-        self._ik1 = self._ik2 = self._k1_lo = self._k2_lo = 0.0
-        if self.fast_replay and c > 0.0:
-            k1, k2 = f32(self._lerp_w * c), f32(self._omb2 * c * c)
-            if k1 > 0.0 and k2 > 0.0:
-                # the scales as the kernel applies them: in by the fp32 reciprocals ik, out by K = 1 / ik (as fp32 pair hi + lo), the
-                # per-step constants formed with the same K — in and out are inverses to 2^-48 (cdc_adam_hp)
-                self._ik1, self._ik2 = f32(1.0 / k1), f32(1.0 / k2)
-                K1, K2 = 1.0 / self._ik1, 1.0 / self._ik2
-                self._k1, self._k2 = f32(K1), f32(K2)
-                self._k1_lo, self._k2_lo = f32(K1 - self._k1), f32(K2 - self._k2)
-                t64 = tab.double()
-                A = t64[:, 0] * K1 * t64[:, 1] / math.sqrt(K2)
-                E = self._eps * t64[:, 1] / math.sqrt(K2)
-                A[0] = A[1]                                           # (row 0 = "step 0" is never replayed; keep it finite)
-                rt = torch.stack([-1.0 / A, -E / A], dim=1)           # C1 = -1/A_t, C2 = -E_t/A_t (csrc/common.h adam_scaled_step_pk)
-                self.replay_tab = rt.to(torch.float32).to(dev).contiguous()
+        if self.fast_replay and rc.replay_tab is not None:
+            self._k1, self._k2, self._ik1, self._ik2, self._k1_lo, self._k2_lo = rc.k1, rc.k2, rc.ik1, rc.ik2, rc.k1_lo, rc.k2_lo
+            self.replay_tab = rc.replay_tab.to(dev).contiguous()
+        self.inv_bc2 = rc.inv_bc2.to(dev).contiguous()
         self.state = {}                                                       # id(param) -> (m, v)
         self.table_m = torch.zeros_like(self.table.data)
         self.table_v = torch.zeros_like(self.table.data)
