@@ -370,6 +370,8 @@ _SIGNATURES = {
     "cdc_eval_gauc": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_i32, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p]),
     "cdc_eval_auc_delong_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
     "cdc_eval_auc_delong": (c_i32, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i32, c_p, c_p, c_p, c_p, c_i64, c_p]),
+    "cdc_eval_calibration_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
+    "cdc_eval_calibration": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
     "cdc_eval_segments": (c_i32, [c_p, c_i64, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_p]),
     "cdc_shard_bucket": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_p]),
     "cdc_shard_expand": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_p]),

@@ -883,3 +883,361 @@ extern "C" int cdc_eval_auc_delong(const float* pred_a, const float* pred_b, con
     CDC_LAUNCH_CHECK("eval_auc_delong(final)");
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Calibration per segment (a domain's rows, or all rows): mean prediction, CTR, predicted over observed CTR, Brier score, and a
+// reliability table with ECE / MCE for K equal-width and K equal-mass bins.  A prediction enters every sum as the INTEGER
+// q = rint(double(p) * 2^32) in [0, 2^32], so every sum is exact and no result depends on an order of accumulation.
+//
+//   keys    every row twice, as k_metric_keys does: key = segment << 33 | score_key << 1 | label.  Score and label come back out of
+//           the key, so the radix sort carries no payload; the label in the key makes rows that tie identical
+//   cells   a row's equal-width bin is min(K-1, floor(double(p) * K)) (exact for K <= 1024), its equal-mass bin follows from its rank r
+//           among its segment's m rows: floor(((r+1) K - 1) / m), the b with floor(b m / K) <= r < floor((b+1) m / K).  Both are
+//           non-decreasing along a segment; (segment, width bin, mass bin) is a row's CELL
+//   pass    a wave owns CAL_ROUNDS rounds of 64 * CAL_ITEMS consecutive sorted keys (a lane loads its CAL_ITEMS keys as 16-byte words).
+//           While a round lies inside the wave's open cell — its last key's segment and width bin match and it ends before the mass
+//           bin does: one comparison per round, a division only where a cell opens — every lane adds q, the label and the two
+//           halves of (q - y 2^32)^2 to registers.  Where the cell changes the wave adds the lanes' registers in a shuffle tree and
+//           one lane hands them over with INTEGER atomic adds; a round with a boundary inside is walked lane by lane
+//   final   a workgroup per segment, a thread per bin: bounds of a width bin by binary search on the bin index, of a mass bin by
+//           rank arithmetic, count = their difference, pred_min / pred_max = the scores at the bounds; ECE's numerator
+//           sum_b |sum q_b - positives_b 2^32| is one integer, added in a tree.  Every double is (numerator -> double) /
+//           (denominator -> double, exact): two roundings at the most
+// Same rows in any order: same bits.  Launch dimensions depend on (n, n_domain, n_bins) alone.
+#define CAL_THREADS 256
+#define CAL_ITEMS 4
+#define CAL_ROUNDS 8
+#define CAL_MAX_BINS 1024
+#define CAL_SEG_OUT 8                   // mean_pred, ctr, pcoc, brier, ece, mce, ece_q, mce_q
+
+__device__ __forceinline__ float cal_score(uint64_t key) { return key_score((uint32_t)(key >> 1)); }
+__device__ __forceinline__ unsigned long long cal_quant(float p) { return (unsigned long long)rint((double)p * 4294967296.0); }
+__device__ __forceinline__ int32_t cal_bin(float p, int32_t K) {
+    const int32_t b = (int32_t)((double)p * (double)K);                   // p in [0, 1]: truncation is floor
+    return b < K - 1 ? b : K - 1;
+}
+
+__global__ void __launch_bounds__(MET_THREADS) k_calib_keys(const float* __restrict__ pred, const int16_t* __restrict__ label,
+                                                            const int32_t* __restrict__ domain, int64_t ld_domain, int64_t n,
+                                                            int32_t n_domain, uint64_t* __restrict__ keys, int32_t* __restrict__ err) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float p = pred[i];
+        int32_t d = domain ? domain[i * ld_domain] : 0;
+        const int16_t y = label[i];
+        const bool bad_p = !(p >= 0.f && p <= 1.f);                       // a NaN too
+        if (bad_p || d < 0 || d >= n_domain || (y != 0 && y != 1)) {
+            if (err) atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
+            d = d < 0 ? 0 : (d >= n_domain ? n_domain - 1 : d);
+            if (bad_p) p = p > 1.f ? 1.f : 0.f;                           // the bins and q are only defined on [0, 1]
+        }
+        const uint64_t low = ((uint64_t)score_key(p) << 1) | (uint64_t)(y != 0);
+        keys[i] = ((uint64_t)(uint32_t)d << 33) | low;
+        keys[n + i] = ((uint64_t)(uint32_t)n_domain << 33) | low;
+    }
+}
+
+// start[d] as k_metric_starts; clears the cells' sums acc_w, acc_q [n_cells][2] and the segments' acc_seg [n_seg][2]
+__global__ void __launch_bounds__(MET_THREADS) k_calib_starts(const uint64_t* __restrict__ keys, int64_t n2, int32_t n_seg, int64_t n_cells,
+                                                              int64_t* __restrict__ start, unsigned long long* __restrict__ acc_w,
+                                                              unsigned long long* __restrict__ acc_q, unsigned long long* __restrict__ acc_seg) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t <= n_seg) start[t] = t == n_seg ? n2 : lower_bound_u64(keys, 0, n2, (uint64_t)t << 33);
+    if (t < n_seg) acc_seg[2 * t] = acc_seg[2 * t + 1] = 0ull;
+    if (t < n_cells) acc_w[2 * t] = acc_w[2 * t + 1] = acc_q[2 * t] = acc_q[2 * t + 1] = 0ull;
+}
+
+struct CalSums { unsigned long long q, pos, sq_lo, sq_hi; };
+struct CalCell { int32_t seg, bw, bq; int64_t q_end; };                   // q_end: the sorted position at which mass bin bq ends
+
+__device__ __forceinline__ void cal_add(CalSums& s, uint64_t key) {
+    const unsigned long long q = cal_quant(cal_score(key)), y = key & 1ull;
+    const unsigned long long e = y ? 4294967296ull - q : q;               // |q - y 2^32| <= 2^32
+    const unsigned long long e2 = e * e;                                  // wraps (to 0) for e = 2^32 alone: the high half is put back below
+    s.q += q;
+    s.pos += y;
+    s.sq_lo += e2 & 0xffffffffull;
+    s.sq_hi += (e2 >> 32) + ((e >> 32) << 32);
+}
+
+// the cell of the key at sorted position pos (which lies inside its segment: m >= 1)
+__device__ __forceinline__ CalCell cal_cell(uint64_t key, int64_t pos, const int64_t* __restrict__ start, int32_t K) {
+    CalCell c;
+    c.seg = (int32_t)(key >> 33);
+    const int64_t s0 = start[c.seg], m = start[c.seg + 1] - s0;
+    c.bw = cal_bin(cal_score(key), K);
+    c.bq = (int32_t)(((pos - s0 + 1) * K - 1) / m);                       // < 2^31 * 2^10
+    c.q_end = s0 + ((int64_t)(c.bq + 1) * m) / K;
+    return c;
+}
+
+__device__ __forceinline__ void cal_hand_over(const CalSums& s, const CalCell& c, int32_t K, unsigned long long* __restrict__ acc_w,
+                                              unsigned long long* __restrict__ acc_q, unsigned long long* __restrict__ acc_seg) {
+    const int64_t cw = ((int64_t)c.seg * K + c.bw) * 2, cq = ((int64_t)c.seg * K + c.bq) * 2;
+    atomicAdd(&acc_w[cw], s.q);
+    atomicAdd(&acc_q[cq], s.q);
+    if (s.pos) { atomicAdd(&acc_w[cw + 1], s.pos); atomicAdd(&acc_q[cq + 1], s.pos); }
+    atomicAdd(&acc_seg[2 * c.seg], s.sq_lo);
+    atomicAdd(&acc_seg[2 * c.seg + 1], s.sq_hi);
+}
+
+__global__ void __launch_bounds__(CAL_THREADS) k_calib_pass(const uint64_t* __restrict__ keys, int64_t n2, const int64_t* __restrict__ start,
+                                                            int32_t K, unsigned long long* __restrict__ acc_w,
+                                                            unsigned long long* __restrict__ acc_q, unsigned long long* __restrict__ acc_seg) {
+    constexpr int64_t ROUND = 64 * CAL_ITEMS;
+    const int lane = threadIdx.x & 63;
+    const int64_t w0 = ((int64_t)blockIdx.x * (CAL_THREADS / 64) + (threadIdx.x >> 6)) * (ROUND * CAL_ROUNDS);
+    CalSums s = {0ull, 0ull, 0ull, 0ull};
+    CalCell cur = {0, 0, 0, 0};                                           // the wave's open cell: the same in every lane
+    bool open = false;
+    for (int r = 0; r < CAL_ROUNDS; ++r) {
+        const int64_t c0 = w0 + (int64_t)r * ROUND, c1 = c0 + ROUND;
+        if (c0 >= n2) break;
+        const int64_t p0 = c0 + (int64_t)lane * CAL_ITEMS;
+        uint64_t k[CAL_ITEMS];
+        const bool full = c1 <= n2;
+        bool inside = false;
+        if (full) {
+            const ulonglong2* v = reinterpret_cast<const ulonglong2*>(keys + p0);      // 32-byte aligned: p0 is a multiple of CAL_ITEMS
+#pragma unroll
+            for (int j = 0; j < CAL_ITEMS / 2; ++j) { const ulonglong2 t = v[j]; k[2 * j] = t.x; k[2 * j + 1] = t.y; }
+            const uint64_t kl = (uint64_t)__shfl((unsigned long long)k[CAL_ITEMS - 1], 63, 64);
+            const int32_t seg_l = (int32_t)(kl >> 33), bw_l = cal_bin(cal_score(kl), K);
+            // the keys are sorted: a round whose LAST key is in the open cell lies inside it
+            inside = open && seg_l == cur.seg && bw_l == cur.bw && c1 <= cur.q_end;
+            if (!inside) {
+                if (open) {
+                    s.q = dl_wave_sum(s.q); s.pos = dl_wave_sum(s.pos); s.sq_lo = dl_wave_sum(s.sq_lo); s.sq_hi = dl_wave_sum(s.sq_hi);
+                    if (lane == 0) cal_hand_over(s, cur, K, acc_w, acc_q, acc_seg);
+                    open = false;
+                }
+                const uint64_t kf = (uint64_t)__shfl((unsigned long long)k[0], 0, 64);
+                const CalCell c = cal_cell(kf, c0, start, K);
+                if (seg_l == c.seg && bw_l == c.bw && c1 <= c.q_end) {   // the round opens a cell and stays in it
+                    cur = c;
+                    open = inside = true;
+                    s.q = s.pos = s.sq_lo = s.sq_hi = 0ull;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < CAL_ITEMS; ++j) k[j] = p0 + j < n2 ? keys[p0 + j] : 0ull;
+            if (open) {
+                s.q = dl_wave_sum(s.q); s.pos = dl_wave_sum(s.pos); s.sq_lo = dl_wave_sum(s.sq_lo); s.sq_hi = dl_wave_sum(s.sq_hi);
+                if (lane == 0) cal_hand_over(s, cur, K, acc_w, acc_q, acc_seg);
+                open = false;
+            }
+        }
+        if (inside) {
+#pragma unroll
+            for (int j = 0; j < CAL_ITEMS; ++j) cal_add(s, k[j]);
+            continue;
+        }
+        // a cell boundary inside the round (or the array's end): every lane walks its own keys
+        CalSums t = {0ull, 0ull, 0ull, 0ull};
+        CalCell c = {0, 0, 0, 0};
+        bool have = false;
+#pragma unroll
+        for (int j = 0; j < CAL_ITEMS; ++j) {
+            if (p0 + j >= n2) break;
+            const CalCell cj = cal_cell(k[j], p0 + j, start, K);
+            if (have && (cj.seg != c.seg || cj.bw != c.bw || cj.bq != c.bq)) {
+                cal_hand_over(t, c, K, acc_w, acc_q, acc_seg);
+                t.q = t.pos = t.sq_lo = t.sq_hi = 0ull;
+            }
+            c = cj;
+            have = true;
+            cal_add(t, k[j]);
+        }
+        if (have) cal_hand_over(t, c, K, acc_w, acc_q, acc_seg);
+    }
+    if (open) {
+        s.q = dl_wave_sum(s.q); s.pos = dl_wave_sum(s.pos); s.sq_lo = dl_wave_sum(s.sq_lo); s.sq_hi = dl_wave_sum(s.sq_hi);
+        if (lane == 0) cal_hand_over(s, cur, K, acc_w, acc_q, acc_seg);
+    }
+}
+
+// first position in [lo, hi) (one segment) whose width bin is >= b
+__device__ __forceinline__ int64_t cal_width_bound(const uint64_t* __restrict__ keys, int64_t lo, int64_t hi, int32_t b, int32_t K) {
+    if (b >= K) return hi;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (cal_bin(cal_score(keys[mid]), K) < b) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// tab_counts [2 binnings][count, positives][n_seg][K], tab_out [2][mean_pred, pos_rate][n_seg][K], tab_range [2][pred_min, pred_max][n_seg][K]
+__global__ void __launch_bounds__(CAL_THREADS) k_calib_final(const uint64_t* __restrict__ keys, const int64_t* __restrict__ start,
+                                                             const unsigned long long* __restrict__ acc_w,
+                                                             const unsigned long long* __restrict__ acc_q,
+                                                             const unsigned long long* __restrict__ acc_seg, int32_t n_seg, int32_t K,
+                                                             double* __restrict__ seg_out, int64_t* __restrict__ seg_counts,
+                                                             double* __restrict__ tab_out, int64_t* __restrict__ tab_counts,
+                                                             float* __restrict__ tab_range) {
+    __shared__ unsigned long long sh_u[4][CAL_THREADS];
+    __shared__ double sh_m[2][CAL_THREADS];
+    const int d = blockIdx.x, tid = threadIdx.x;
+    const int64_t s0 = start[d], s1 = start[d + 1], m = s1 - s0, cells = (int64_t)n_seg * K;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const float nanf = __uint_as_float(0x7fc00000u);
+    unsigned long long sum_q = 0ull, sum_p = 0ull, ece[2] = {0ull, 0ull};
+    double mce[2] = {-1.0, -1.0};
+    for (int b = tid; b < K; b += CAL_THREADS) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            int64_t lo, hi;
+            if (t == 0) {
+                lo = cal_width_bound(keys, s0, s1, b, K);
+                hi = cal_width_bound(keys, lo, s1, b + 1, K);
+            } else {
+                lo = s0 + ((int64_t)b * m) / K;
+                hi = s0 + ((int64_t)(b + 1) * m) / K;
+            }
+            const int64_t o = (int64_t)d * K + b, cnt = hi - lo;
+            const unsigned long long* a = (t ? acc_q : acc_w) + 2 * o;
+            const unsigned long long q = a[0], ps = a[1];
+            double mean = nan, rate = nan;
+            float mn = nanf, mx = nanf;
+            if (cnt > 0) {
+                const double den = (double)cnt * 4294967296.0;            // exact
+                mean = (double)q / den;
+                rate = (double)ps / (double)cnt;
+                mn = cal_score(keys[lo]);
+                mx = cal_score(keys[hi - 1]);
+                const unsigned long long obs = ps << 32, gap = q > obs ? q - obs : obs - q;
+                ece[t] += gap;
+                const double g = (double)gap / den;
+                mce[t] = g > mce[t] ? g : mce[t];
+                if (t == 0) { sum_q += q; sum_p += ps; }
+            }
+            tab_counts[(2 * t) * cells + o] = cnt;
+            tab_counts[(2 * t + 1) * cells + o] = (int64_t)ps;
+            tab_out[(2 * t) * cells + o] = mean;
+            tab_out[(2 * t + 1) * cells + o] = rate;
+            tab_range[(2 * t) * cells + o] = mn;
+            tab_range[(2 * t + 1) * cells + o] = mx;
+        }
+    }
+    sh_u[0][tid] = sum_q; sh_u[1][tid] = sum_p; sh_u[2][tid] = ece[0]; sh_u[3][tid] = ece[1];
+    sh_m[0][tid] = mce[0]; sh_m[1][tid] = mce[1];
+    __syncthreads();
+    for (int off = CAL_THREADS / 2; off > 0; off >>= 1) {
+        if (tid < off) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) sh_u[k][tid] += sh_u[k][tid + off];
+#pragma unroll
+            for (int k = 0; k < 2; ++k) sh_m[k][tid] = sh_m[k][tid + off] > sh_m[k][tid] ? sh_m[k][tid + off] : sh_m[k][tid];
+        }
+        __syncthreads();
+    }
+    if (tid != 0) return;
+    const unsigned long long Q = sh_u[0][0], P = sh_u[1][0];
+    seg_counts[d] = m;
+    seg_counts[n_seg + d] = (int64_t)P;
+    double o[CAL_SEG_OUT];
+#pragma unroll
+    for (int k = 0; k < CAL_SEG_OUT; ++k) o[k] = nan;
+    if (m > 0) {
+        const double den = (double)m * 4294967296.0;                      // exact
+        const dl_u128 sq = ((dl_u128)acc_seg[2 * d + 1] << 32) + (dl_u128)acc_seg[2 * d];           // < 2^95
+        o[0] = (double)Q / den;
+        o[1] = (double)P / (double)m;
+        if (P > 0) o[2] = (double)Q / ((double)P * 4294967296.0);
+        o[3] = dl_to_double(sq) / ((double)m * 18446744073709551616.0);
+        o[4] = (double)sh_u[2][0] / den;
+        o[5] = sh_m[0][0];
+        o[6] = (double)sh_u[3][0] / den;
+        o[7] = sh_m[1][0];
+    }
+#pragma unroll
+    for (int k = 0; k < CAL_SEG_OUT; ++k) seg_out[(int64_t)k * n_seg + d] = o[k];
+}
+
+struct CalibLayout {
+    int64_t keys_in, keys_out, start, acc_w, acc_q, acc_seg, temp, temp_bytes, total;
+};
+// everything but rocPRIM's temporary storage: plain arithmetic (argument checks use it before any HIP or rocPRIM call)
+static void calib_fixed_layout(int64_t n, int32_t n_domain, int32_t n_bins, CalibLayout* L) {
+    const int64_t n2 = 2 * n, seg = (int64_t)n_domain + 1;
+    int64_t off = 0;
+    L->keys_in = off;  off += align_up(n2 * 8);
+    L->keys_out = off; off += align_up(n2 * 8);
+    L->start = off;    off += align_up((seg + 1) * 8);
+    L->acc_w = off;    off += align_up(seg * n_bins * 16);
+    L->acc_q = off;    off += align_up(seg * n_bins * 16);
+    L->acc_seg = off;  off += align_up(seg * 16);
+    L->temp = off;
+    L->temp_bytes = 0;
+    L->total = off;
+}
+static int calib_layout(int64_t n, int32_t n_domain, int32_t n_bins, CalibLayout* L) {
+    calib_fixed_layout(n, n_domain, n_bins, L);
+    size_t t_sort = 0;
+    hipError_t e = rocprim::radix_sort_keys(nullptr, t_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr, (size_t)(2 * n), 0, 64,
+                                            (hipStream_t)0, false);
+    if (e != hipSuccess) { cdc_set_error("eval_calibration: rocprim size query failed: %s", hipGetErrorString(e)); return (int)e; }
+    L->temp_bytes = (int64_t)t_sort;
+    L->total = L->temp + align_up(L->temp_bytes);
+    return 0;
+}
+static bool calib_sizes_ok(int64_t n, int32_t n_domain, int32_t n_bins) {
+    return n > 0 && n < (1ll << 31) && n_domain > 0 && n_domain < (1 << 20) && n_bins >= 1 && n_bins <= CAL_MAX_BINS;
+}
+
+extern "C" int64_t cdc_eval_calibration_workspace_bytes(int64_t n, int32_t n_domain, int32_t n_bins) {
+    if (!calib_sizes_ok(n, n_domain, n_bins)) return 0;
+    CalibLayout L;
+    if (calib_layout(n, n_domain, n_bins, &L) != 0) return -1;
+    return L.total;
+}
+
+extern "C" int cdc_eval_calibration(const float* pred, const int16_t* label, const int32_t* domain, int64_t ld_domain, int64_t n,
+                                    int32_t n_domain, int32_t n_bins, double* seg_out, int64_t* seg_counts, double* tab_out,
+                                    int64_t* tab_counts, float* tab_range, int32_t* err_flag, void* workspace, int64_t workspace_bytes,
+                                    void* stream) {
+    CDC_CHECK_ARG(pred && label && seg_out && seg_counts && tab_out && tab_counts && tab_range && workspace, CDC_E_BADARG,
+                  "eval_calibration: null pointer");
+    CDC_CHECK_ARG(n > 0 && n_domain > 0 && n_domain < (1 << 20) && ld_domain >= 0, CDC_E_BADARG,
+                  "eval_calibration: bad sizes n=%ld n_domain=%d ld_domain=%ld", (long)n, n_domain, (long)ld_domain);
+    CDC_CHECK_ARG(n_bins >= 1 && n_bins <= CAL_MAX_BINS, CDC_E_BADARG, "eval_calibration: n_bins=%d outside [1, %d]", n_bins, CAL_MAX_BINS);
+    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_calibration: n_domain=%d needs the domain column", n_domain);
+    CDC_CHECK_ARG(n < (1ll << 31), CDC_E_TOOBIG, "eval_calibration: n=%ld exceeds the 2^31 rows whose sums fit 64 bits", (long)n);
+    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_calibration: workspace must be 256-byte aligned");
+    CalibLayout L;
+    calib_fixed_layout(n, n_domain, n_bins, &L);
+    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_calibration: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
+    int rc = calib_layout(n, n_domain, n_bins, &L);
+    if (rc != 0) return rc;
+    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_calibration: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
+    char* base = (char*)workspace;
+    uint64_t* keys_in = (uint64_t*)(base + L.keys_in);
+    uint64_t* keys_out = (uint64_t*)(base + L.keys_out);
+    int64_t* start = (int64_t*)(base + L.start);
+    unsigned long long* acc_w = (unsigned long long*)(base + L.acc_w);
+    unsigned long long* acc_q = (unsigned long long*)(base + L.acc_q);
+    unsigned long long* acc_seg = (unsigned long long*)(base + L.acc_seg);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n2 = 2 * n, cells = ((int64_t)n_domain + 1) * n_bins;
+    const int seg = n_domain + 1;
+    int blocks = (int)std::min<int64_t>(cdc_ceil_div(n, MET_THREADS), 4096);
+    hipLaunchKernelGGL(k_calib_keys, dim3(blocks), dim3(MET_THREADS), 0, st, pred, label, domain, ld_domain, n, n_domain, keys_in, err_flag);
+    CDC_LAUNCH_CHECK("eval_calibration(keys)");
+    // the sort only has to look at the bits a key can have: label + 32 score bits + the bits of n_domain
+    int end_bit = 34;
+    while (end_bit < 64 && ((uint64_t)n_domain >> (end_bit - 33)) != 0) ++end_bit;
+    size_t temp_bytes = (size_t)L.temp_bytes;
+    hipError_t e = rocprim::radix_sort_keys(base + L.temp, temp_bytes, (const uint64_t*)keys_in, keys_out, (size_t)n2, 0, end_bit, st, false);
+    if (e != hipSuccess) { cdc_set_error("eval_calibration: radix sort failed: %s", hipGetErrorString(e)); return (int)e; }
+    hipLaunchKernelGGL(k_calib_starts, dim3((int)cdc_ceil_div(std::max<int64_t>(seg + 1, cells), MET_THREADS)), dim3(MET_THREADS), 0, st,
+                       keys_out, n2, seg, cells, start, acc_w, acc_q, acc_seg);
+    CDC_LAUNCH_CHECK("eval_calibration(starts)");
+    blocks = (int)cdc_ceil_div(n2, (int64_t)CAL_THREADS * CAL_ITEMS * CAL_ROUNDS);
+    hipLaunchKernelGGL(k_calib_pass, dim3(blocks), dim3(CAL_THREADS), 0, st, (const uint64_t*)keys_out, n2, (const int64_t*)start, n_bins,
+                       acc_w, acc_q, acc_seg);
+    CDC_LAUNCH_CHECK("eval_calibration(pass)");
+    hipLaunchKernelGGL(k_calib_final, dim3(seg), dim3(CAL_THREADS), 0, st, (const uint64_t*)keys_out, (const int64_t*)start,
+                       (const unsigned long long*)acc_w, (const unsigned long long*)acc_q, (const unsigned long long*)acc_seg, seg, n_bins,
+                       seg_out, seg_counts, tab_out, tab_counts, tab_range);
+    CDC_LAUNCH_CHECK("eval_calibration(final)");
+    return 0;
+}

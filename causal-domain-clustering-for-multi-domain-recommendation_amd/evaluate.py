@@ -15,6 +15,10 @@ C-ABI call (`cdc_eval_gauc`) on the same device-resident predictions.
 vectors over the same rows the difference of their AUCs with the standard error of that difference (`cdc_eval_auc_delong`);
 `Evaluator(auc_ci=True)` and `Evaluator.compare` report them.
 
+`eval_calibration` reports whether the predicted probabilities are right, where the figures above only say how well they rank: per
+domain and over all rows the ratio of predicted to observed CTR, the Brier score, and a reliability table with ECE / MCE for
+equal-width and equal-mass bins (`cdc_eval_calibration`); `Evaluator(calibration=True)` and `Evaluator.calibration_table` report them.
+
 `eval_segments` serves CDC's matrix update (run.py:549-558) instead: the metric of every contiguous row segment of ONE forward's
 raw output, each segment scored by its own tower column (`cdc_eval_segments`; probe.py lays the domains' batches out that way).
 """
@@ -232,6 +236,62 @@ def eval_auc_ci(pred, label, domain=None, n_domain=1, pred_b=None):
     return AucCI(o[0], o[1], counts[:seg], counts[seg:])
 
 
+Calibration = collections.namedtuple("Calibration", "rows positives mean_pred ctr pcoc brier ece mce ece_q mce_q table table_q")
+CalibrationTable = collections.namedtuple("CalibrationTable", "count positives mean_pred pos_rate pred_min pred_max")
+MAX_CALIBRATION_BINS = 1024
+
+
+def eval_calibration(pred, label, domain=None, n_domain=1, n_bins=10):
+    """Calibration of probabilities per domain and over all rows; inputs as `eval_metrics` (domain: int32 [n] or a strided column
+    view), pred in [0, 1], 1 <= n_bins <= 1024.  A prediction enters every sum as the integer q = rint(p * 2^32), so the sums are
+    exact and the same rows in any order give the same bits.  Returns a namedtuple of device tensors.  Per segment (n_domain + 1
+    entries: domains 0..n_domain-1, then ALL rows): `rows`, `positives` (i64), `mean_pred`, `ctr`, `pcoc` = predicted over observed
+    CTR (NaN without positives), `brier`, and the expected / maximum calibration error over n_bins equal-width bins (`ece`, `mce`:
+    a row is in bin min(n_bins-1, floor(p * n_bins))) and over n_bins equal-mass bins (`ece_q`, `mce_q`: bin b holds the sorted
+    positions [floor(b m / n_bins), floor((b+1) m / n_bins)) of the segment's m rows in (score, label) order), all f64 and NaN for a
+    segment without rows.  `table` / `table_q`: the two reliability tables, namedtuples (count, positives i64; mean_pred, pos_rate
+    f64; pred_min, pred_max f32) of shape [n_domain + 1, n_bins]; an empty bin has count 0 and NaN in the floating-point fields.
+    No host synchronisation; the error word (1 + a row with a NaN prediction, a prediction outside [0, 1], a label outside {0, 1} or
+    a domain outside range) is kept as `eval_calibration.last_err`.
+    Not offered: selection or early stopping by a calibration figure in `Runner`, calibration deltas in `Evaluator.compare`, and
+    fitting a recalibration map (Platt scaling, isotonic regression)."""
+    lib = L.load()
+    n_domain, n_bins = int(n_domain), int(n_bins)
+    if not 1 <= n_bins <= MAX_CALIBRATION_BINS:
+        raise ValueError(f"n_bins={n_bins} must lie in [1, {MAX_CALIBRATION_BINS}]")
+    if not pred.is_cuda:
+        raise L.HipExtensionError("eval_calibration needs device tensors; there is no CPU fallback")
+    pred = pred.reshape(-1).to(torch.float32).contiguous()
+    label = label.reshape(-1).to(torch.int16).contiguous()
+    n = pred.numel()
+    if label.numel() != n:
+        raise ValueError(f"{n} predictions but {label.numel()} labels")
+    ld = 0
+    if domain is not None:
+        domain, ld = _id_column(domain, n, "domain")
+    elif n_domain != 1:
+        raise ValueError("n_domain > 1 needs the domain column")
+    dev = pred.device
+    seg = n_domain + 1
+    seg_out = torch.empty((8, seg), dtype=torch.float64, device=dev)
+    seg_counts = torch.empty((2, seg), dtype=torch.int64, device=dev)
+    tab_out = torch.empty((2, 2, seg, n_bins), dtype=torch.float64, device=dev)
+    tab_counts = torch.empty((2, 2, seg, n_bins), dtype=torch.int64, device=dev)
+    tab_range = torch.empty((2, 2, seg, n_bins), dtype=torch.float32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    nbytes = lib.cdc_eval_calibration_workspace_bytes(n, n_domain, n_bins)
+    if nbytes <= 0:
+        raise RuntimeError(f"cdc_eval_calibration_workspace_bytes refused n={n}, n_domain={n_domain}, n_bins={n_bins}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    L.launch("cdc_eval_calibration", lib.cdc_eval_calibration,
+             (pred.data_ptr(), label.data_ptr(), None if domain is None else domain.data_ptr(), ld, n, n_domain, n_bins, seg_out.data_ptr(),
+              seg_counts.data_ptr(), tab_out.data_ptr(), tab_counts.data_ptr(), tab_range.data_ptr(), err.data_ptr(), ws.data_ptr(), nbytes),
+             C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    eval_calibration.last_err = err
+    tables = [CalibrationTable(tab_counts[t, 0], tab_counts[t, 1], tab_out[t, 0], tab_out[t, 1], tab_range[t, 0], tab_range[t, 1]) for t in (0, 1)]
+    return Calibration(seg_counts[0], seg_counts[1], *seg_out.unbind(0), tables[0], tables[1])
+
+
 def _se(var):
     return math.sqrt(var) if var == var else math.nan
 
@@ -260,13 +320,21 @@ class Evaluator:
     auc_ci: test() adds the DeLong standard errors of its AUCs (`eval_auc_ci`): total_auc_se, and with per-domain evaluation
             domain_auc_se {d: value} and mean_auc_se = sqrt(sum_d w_d^2 var_d) over the domains mean_auc sums (disjoint row sets:
             independent given the model).  Significance-aware early stopping and intervals for GAUC or log-loss are not offered.
+    calibration: test() adds calibration figures (`eval_calibration`; True: 10 bins, an int: that many): total_pcoc (predicted over
+            observed CTR), total_brier, total_ece, total_ece_quantile, and with per-domain evaluation domain_pcoc / domain_brier /
+            domain_ece / domain_ece_quantile {d: value} and mean_pcoc / mean_brier / mean_ece / mean_ece_quantile, weighted like
+            mean_auc; `calibration_table` returns the reliability tables.  Selection or early stopping by a calibration figure,
+            calibration deltas in `compare` and fitting a recalibration map (Platt, isotonic) are not offered.
     precision: None, or "bf16" / "f32": the model is switched to it for the scoring pass and switched back afterwards, so two
             evaluators around ONE module can score it under two precisions (`compare`)."""
 
     def __init__(self, model, mode="multi", domain_idx=None, n_domain=1, domain_cnt_weight=None, is_evaluate_multi_domain=True,
-                 user_idx=None, n_user=None, user_weight=None, auc_ci=False, precision=None):
+                 user_idx=None, n_user=None, user_weight=None, auc_ci=False, precision=None, calibration=False):
         self.model, self.mode = model, mode
         self.auc_ci = bool(auc_ci)
+        self.calibration_bins = 0 if calibration is False else (10 if calibration is True else int(calibration))   # 0: off
+        if calibration is not False and not 1 <= self.calibration_bins <= MAX_CALIBRATION_BINS:
+            raise ValueError(f"calibration must be a bool or a number of bins in [1, {MAX_CALIBRATION_BINS}], not {calibration!r}")
         if precision not in (None, "bf16", "f32"):
             raise ValueError(f"precision must be None, 'bf16' or 'f32', not {precision!r}")
         self.precision = precision
@@ -342,7 +410,8 @@ class Evaluator:
 
     def test(self, data_loader):
         """The reference's result_dict: total_auc, total_loss (+ domain_auc, domain_loss, mean_auc, mean_loss); with user_idx also
-        total_gauc (+ domain_gauc, mean_gauc); with auc_ci also total_auc_se (+ domain_auc_se, mean_auc_se)."""
+        total_gauc (+ domain_gauc, mean_gauc); with auc_ci also total_auc_se (+ domain_auc_se, mean_auc_se); with calibration also
+        total_pcoc, total_brier, total_ece, total_ece_quantile (+ domain_* and mean_* of the four)."""
         pred, label, domain, user = self._score(data_loader)
         multi = self.is_evaluate_multi_domain
         auc, loss, rows, pos = eval_metrics(pred, label, domain if multi else None, self.n_domain if multi else 1)
@@ -350,6 +419,8 @@ class Evaluator:
             gauc = eval_gauc(pred, label, user, self.n_user, domain if multi else None, self.n_domain if multi else 1, self.user_weight)[0]
         if self.auc_ci:                                        # likewise queued
             ci_var = eval_auc_ci(pred, label, domain if multi else None, self.n_domain if multi else 1).var
+        if self.calibration_bins:                              # likewise queued
+            cal = eval_calibration(pred, label, domain if multi else None, self.n_domain if multi else 1, self.calibration_bins)
         auc, loss, rows, pos = auc.cpu().tolist(), loss.cpu().tolist(), rows.cpu().tolist(), pos.cpu().tolist()   # the one sync
         bad = int(eval_metrics.last_err.item())
         if bad:
@@ -385,7 +456,34 @@ class Evaluator:
                 present = [d for d in range(self.n_domain) if rows[d] > 0]
                 result["domain_auc_se"] = {d: _se(var[d]) for d in present}
                 result["mean_auc_se"] = _se(sum(self._weight(d) ** 2 * var[d] for d in present))   # NaN when a summed domain's variance is
+        if self.calibration_bins:
+            figures = {"pcoc": cal.pcoc, "brier": cal.brier, "ece": cal.ece, "ece_quantile": cal.ece_q}
+            figures = {k: v.cpu().tolist() for k, v in figures.items()}
+            bad = int(eval_calibration.last_err.item())
+            if bad:
+                raise ValueError(f"evaluation row {bad - 1}: prediction outside [0, 1]")
+            for k, v in figures.items():
+                result["total_" + k] = v[-1]
+                if multi:
+                    result["domain_" + k] = {d: v[d] for d in range(self.n_domain) if rows[d] > 0}
+                    result["mean_" + k] = sum(self._weight(d) * x for d, x in result["domain_" + k].items())     # as mean_auc
         return result
+
+    def calibration_table(self, data_loader):
+        """One scoring pass -> (table, table_q, segments): the equal-width and the equal-mass reliability table as
+        `CalibrationTable`s of host numpy arrays [len(segments), n_bins] (count, positives, mean_pred, pos_rate, pred_min, pred_max;
+        NaN in an empty bin), and `segments`, the row order: the domain ids 0..n_domain-1 with per-domain evaluation, then "all".
+        The bins are those of `calibration` (10 when it is off)."""
+        pred, label, domain, _ = self._score(data_loader)
+        multi = self.is_evaluate_multi_domain
+        cal = eval_calibration(pred, label, domain if multi else None, self.n_domain if multi else 1, self.calibration_bins or 10)
+        first = 0 if multi else 1                              # without per-domain evaluation the one domain IS "all"
+        table, table_q = (CalibrationTable(*(f[first:].cpu().numpy() for f in t)) for t in (cal.table, cal.table_q))
+        bad = int(eval_calibration.last_err.item())
+        if bad:
+            raise ValueError(f"evaluation row {bad - 1}: NaN prediction or prediction outside [0, 1], label outside {{0,1}} or domain "
+                             f"outside [0, {self.n_domain})")
+        return table, table_q, (list(range(self.n_domain)) if multi else []) + ["all"]
 
     def compare(self, other, data_loader):
         """Paired comparison of this evaluator's model with `other`'s (an Evaluator) on ONE evaluation set: the loader is scored

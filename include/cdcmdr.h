@@ -1184,6 +1184,38 @@ int cdc_eval_auc_delong(const float* pred_a, const float* pred_b, const int16_t*
                         int64_t n, int32_t n_domain, double* out, int64_t* counts, int32_t* err_flag, void* workspace,
                         int64_t workspace_bytes, void* stream);
 
+/* Calibration of the predictions cdc_eval_metrics ranks: per segment (domain 0..n_domain-1, then ALL rows) the mean prediction, the
+ * CTR, predicted over observed CTR, the Brier score, and a reliability table with ECE / MCE for n_bins = K equal-width and K
+ * equal-mass (quantile) bins.  pred, label, domain, ld_domain, n_domain as for cdc_eval_metrics; pred is a probability in [0, 1].
+ *     q = rint(double(p) * 2^32), an integer in [0, 2^32] (-0.0 counts as 0): every sum of predictions is a sum of q
+ *     mean_pred = sum q / (rows 2^32)   ctr = positives / rows   pcoc = sum q / (positives 2^32)   brier = sum (q - y 2^32)^2 / (rows 2^64)
+ *     equal-width bin of a row: min(K-1, floor(double(p) * K)) (the product is exact for K <= 1024)
+ *     equal-mass bin b of a segment of m rows: the sorted positions [floor(b m / K), floor((b+1) m / K)) in (score, label) order —
+ *         the label is part of the order, so rows that tie are identical and a tie run cut by a bound gives the same bins always
+ *     per bin: count, positives, mean_pred = sum q / (count 2^32), pos_rate = positives / count, pred_min, pred_max
+ *     ece = sum_b |sum q_b - positives_b 2^32| / (rows 2^32)      mce = max_b |sum q_b - positives_b 2^32| / (count_b 2^32), b non-empty
+ *   seg_out    [8*(n_domain+1)] doubles: mean_pred, ctr, pcoc, brier, ece, mce (equal-width), ece_q, mce_q (equal-mass), each an array
+ *              over the segments.  All NaN for a segment without rows; pcoc NaN without positives.
+ *   seg_counts [2*(n_domain+1)] int64: rows per segment, then positives per segment.
+ *   tab_counts [2][2][n_domain+1][K] int64: binning (0 equal-width, 1 equal-mass) x (count, positives) x segment x bin;
+ *   tab_out    [2][2][n_domain+1][K] doubles: binning x (mean_pred, pos_rate) x segment x bin;
+ *   tab_range  [2][2][n_domain+1][K] floats: binning x (pred_min, pred_max) x segment x bin.  An empty bin: counts 0, the rest NaN.
+ *   err_flag (optional): 1 + the largest index of a row with a NaN prediction, a prediction outside [0, 1], a label other than 0/1 or
+ *              a domain outside [0, n_domain); such a row is counted with the prediction clamped into [0, 1] (NaN: 0) and the domain
+ *              clamped into range.
+ * Every sum is an exact integer (squares as two 32-bit halves, handed over with integer atomics), every double is formed by one
+ * conversion of an integer numerator, an exact denominator and one division: the same rows in any order give the same bits.
+ * Limits: null pointers, n <= 0, n_domain outside [1, 2^20), n_bins outside [1, 1024], n_domain > 1 without the domain column, a
+ * workspace too small or not 256-byte aligned: CDC_E_BADARG; n >= 2^31: CDC_E_TOOBIG — all before anything is launched.
+ * Stream-ordered: no allocation, no synchronisation, no state kept; the launch dimensions depend on (n, n_domain, n_bins) alone, so
+ * the call can be captured in a graph.
+ * workspace: cdc_eval_calibration_workspace_bytes(n, n_domain, n_bins) bytes, 256-byte aligned; 0 for sizes the call refuses. */
+int64_t cdc_eval_calibration_workspace_bytes(int64_t n, int32_t n_domain, int32_t n_bins);
+int cdc_eval_calibration(const float* pred, const int16_t* label, const int32_t* domain, int64_t ld_domain, int64_t n,
+                         int32_t n_domain, int32_t n_bins, double* seg_out, int64_t* seg_counts, double* tab_out,
+                         int64_t* tab_counts, float* tab_range, int32_t* err_flag, void* workspace, int64_t workspace_bytes,
+                         void* stream);
+
 /* Per-segment BCE of CDC's probe evaluation (run.py:549-558): one batch of every domain went through ONE eval
  * forward; segment s is the rows [seg_start[s], seg_start[s+1]) of probs [rows, n_cols] (row stride ld_probs: all towers'
  * probabilities) and is scored by column seg_col[s] (NULL = column 0).  seg_start [n_seg+1] is non-decreasing; rows at or past
