@@ -861,7 +861,10 @@ __global__ void __launch_bounds__(ROW_THREADS) k_bn_bwd_stats_v4(const cdc_bn_bw
     const int c = t.c0 + cg * 4;
     const int r_begin = t.chunk * CDC_BN_ROWS_PER_BLOCK, r_end = min(r_begin + CDC_BN_ROWS_PER_BLOCK, t.M);
     double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
-    if (c < S.C && t.M != 1) {
+    // a one-row group is skipped (dx = dz, no parameter gradients) — unless this is phase 1: the group may have more rows on
+    // other ranks, and then this rank's row belongs in the exchanged sums and in its own dgamma / dbeta (apply ignores the sums
+    // when the GLOBAL count is one).  tests/test_gpu_batchnorm.py::test_bn_data_parallel_phases[1+5-*] showed the missing row.
+    if (c < S.C && (t.M != 1 || a.phase == 1)) {
         const bool masked = a.relu || a.mask_scale != 1.f;
         const bool xh = S.half & CDC_BN_X_BF16, yh = S.half & CDC_BN_Y_BF16, dyh = S.half & CDC_BN_DY_BF16;
         bn_f4 dv[G::ITER], yv[G::ITER], xv[G::ITER];
@@ -1087,7 +1090,7 @@ __global__ void __launch_bounds__(ROW_THREADS) k_bn_bwd_stats(const cdc_bn_bwd_a
     double s1 = 0.0, s2 = 0.0;
     const int r_begin = t.chunk * CDC_BN_ROWS_PER_BLOCK;
     const int r_end = min(r_begin + CDC_BN_ROWS_PER_BLOCK, t.M);
-    if (c < S.C && t.M != 1) {
+    if (c < S.C && (t.M != 1 || a.phase == 1)) {                        // (phase 1: see k_bn_bwd_stats_v4)
         const float mean = S.save_mean[c], invstd = S.save_invstd[c];
         constexpr int RPW = CDC_BN_ROWS_PER_BLOCK / WAVES_PER_BLOCK;
         const bool masked = a.relu || a.mask_scale != 1.f;

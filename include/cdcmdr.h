@@ -672,7 +672,11 @@ typedef struct {
                                          the caller all-reduces (SUM) `exchange` across ranks; 2 = normalise from `exchange` */
     int32_t stats_ready;              /* 1: the partial sums are already in `workspace` (written by the cdc_glinear_fwd epilogues
                                          that produced every segment's x, see cdc_lin_group.bn_partial): no statistics pass */
-    double* exchange;                 /* phases 1/2: [2*sum(C) column sums (x, x^2) | n_seg row counts] doubles */
+    double* exchange;                 /* phases 1/2: [2*sum(C) column sums (x, x^2) | n_seg row counts] doubles.  Phase 1 writes
+                                         every entry; a row group that is empty on this rank contributes zero sums and a zero
+                                         count.  A launch with M == 0 returns 0 and launches nothing, so it leaves `exchange`
+                                         as it was: callers never do that — every rank's launch covers its local batch (dist.py:
+                                         global batch = world_size x local batch, at least one row per rank) */
     cdc_bn_seg s[CDC_MAX_BN_SEGS];
 } cdc_bn_fwd_args;
 int cdc_bn_fwd(const cdc_bn_fwd_args* a, void* stream);
@@ -701,7 +705,9 @@ typedef struct {
     int64_t M;
     const int32_t* row_offsets;
     double* workspace;                /* >= 2 * ceil(M/64) * sum(C) doubles */
-    int32_t phase;                    /* as in cdc_bn_fwd_args; exchange = [2*sum(C) sums (dz, dz*xhat) | n_seg row counts] */
+    int32_t phase;                    /* as in cdc_bn_fwd_args; exchange = [2*sum(C) sums (dz, dz*xhat) | n_seg row counts].
+                                         A group with ONE local row is skipped in phase 0 only: in phase 1 its row goes into
+                                         the sums (other ranks may hold more rows of it), and phase 2 skips by the global count */
     int32_t pad_;
     double* exchange;
     cdc_bn_bseg s[CDC_MAX_BN_SEGS];
