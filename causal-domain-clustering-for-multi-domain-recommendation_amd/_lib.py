@@ -372,6 +372,10 @@ _SIGNATURES = {
     "cdc_eval_auc_delong": (c_i32, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i32, c_p, c_p, c_p, c_p, c_i64, c_p]),
     "cdc_eval_calibration_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
     "cdc_eval_calibration": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
+    "cdc_eval_isotonic_max_blocks": (c_i64, [c_i64, c_i32]),
+    "cdc_eval_isotonic_fit_workspace_bytes": (c_i64, [c_i64, c_i32]),
+    "cdc_eval_isotonic_fit": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p]),
+    "cdc_eval_isotonic_apply": (c_i32, [c_p, c_p, c_i64, c_i64, c_i32, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p]),
     "cdc_eval_segments": (c_i32, [c_p, c_i64, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_p]),
     "cdc_shard_bucket": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_p]),
     "cdc_shard_expand": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_p]),

@@ -1241,3 +1241,437 @@ extern "C" int cdc_eval_calibration(const float* pred, const int16_t* label, con
     CDC_LAUNCH_CHECK("eval_calibration(final)");
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Isotonic recalibration per segment (a domain's rows, or all rows): the non-decreasing least-squares fit of the 0/1 labels on
+// the score (pool-adjacent-violators), in canonical form — blocks in ascending score order with strictly increasing means — and
+// the map it defines (constant on a block, linear between blocks, clipped outside).  The fit is integer geometry: with the rows in
+// score order the block ends are the vertices of the LOWER CONVEX HULL of the points (rows so far, positives so far) taken at the
+// ends of the tie groups; two means are compared as integer products, nothing is rounded before the final division.
+//
+//   keys    every row twice, as k_calib_keys does (key = segment << 33 | score_key << 1 | label), any finite score; the same sort
+//   scan    (rocPRIM) cp = positives at sorted positions <= i.  POINT b in [0, 2n] sits in front of sorted position b and is
+//           (b, positives before b); it exists where key >> 1 changes (the end of a tie group), at 0 and at 2n
+//   order   all segments are ONE hull problem.  Lift segment s by a slope s * 2^33 (continuously): inside a segment nothing
+//           changes, every segment boundary becomes a strictly convex corner, and the lower hull of all points is the segments'
+//           hulls one after the other.  The lift is never formed: for points a < b < c the corner at b is strictly convex when b
+//           is a boundary, or a or c lies outside b's segment, else when (c.y - b.y)(b.x - a.x) > (b.y - a.y)(c.x - b.x) —
+//           factors below 2^31, products below 2^62.  A point carries its segment's bounds (lo = hi = x for a boundary)
+//   local   a workgroup owns ISO_CHUNK consecutive points and joins spans of 1, 2, 4, .. of them in LDS; a lane finds one join,
+//           all lanes copy
+//   merge   ceil(log2(chunks)) launches, a workgroup per pair of adjacent spans.  Joining two hulls keeps a PREFIX of the left
+//           vertex list and a SUFFIX of the right one, bridged by their common lower tangent: the last left vertex that stays a
+//           strict corner against its tangent point on the right (binary search; the tangent point by binary search per probe,
+//           the farther one where two are collinear, so collinear points go); a wave probes 64 candidates of either search at
+//           once.  The joined list is written compactly into the other of two buffers, so every level reads plain arrays
+//   emit    consecutive vertices are one block of the segment they lie in: x_lo / x_hi from the keys at its first / last
+//           position, count and positives as differences, value = positives / count; start[s] = the rank of segment s's first
+//           point among the vertices (every boundary is a vertex)
+// Same rows in any order: same bits.  Launch dimensions and the number of launches depend on (n, n_domain) alone; a lane's serial
+// work is two nested binary searches over vertex lists and its share of a copy.
+#define ISO_THREADS 256
+#define ISO_CHUNK 1024                  // points per workgroup of the local launch: a power of two
+#define ISO_CHUNK_LOG 10
+
+struct __attribute__((aligned(16))) IsoPt { uint32_t x, y, lo, hi; };
+
+struct IsoLabelIn {                     // element i of the scan: the label bit of the sorted key
+    const uint64_t* keys;
+    __host__ __device__ uint32_t operator()(uint32_t i) const { return (uint32_t)(keys[i] & 1ull); }
+};
+typedef rocprim::transform_iterator<rocprim::counting_iterator<uint32_t>, IsoLabelIn, uint32_t> IsoLabelIt;
+
+__global__ void __launch_bounds__(MET_THREADS) k_iso_keys(const float* __restrict__ pred, const int16_t* __restrict__ label,
+                                                          const int32_t* __restrict__ domain, int64_t ld_domain, int64_t n,
+                                                          int32_t n_domain, uint64_t* __restrict__ keys, int32_t* __restrict__ err) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float p = pred[i];
+        int32_t d = domain ? domain[i * ld_domain] : 0;
+        const int16_t y = label[i];
+        const bool bad_p = !(fabsf(p) <= 3.4028234663852886e38f);         // NaN, +inf, -inf
+        if (bad_p || d < 0 || d >= n_domain || (y != 0 && y != 1)) {
+            if (err) atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
+            d = d < 0 ? 0 : (d >= n_domain ? n_domain - 1 : d);
+            if (bad_p) p = 0.f;
+        }
+        const uint64_t low = ((uint64_t)score_key(p) << 1) | (uint64_t)(y != 0);
+        keys[i] = ((uint64_t)(uint32_t)d << 33) | low;
+        keys[n + i] = ((uint64_t)(uint32_t)n_domain << 33) | low;
+    }
+}
+
+// pos[s] = first sorted position of segment s, s in [0, n_seg]; pos[n_seg] = 2n
+__global__ void __launch_bounds__(MET_THREADS) k_iso_starts(const uint64_t* __restrict__ keys, int64_t n2, int32_t n_seg,
+                                                            int64_t* __restrict__ pos) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t <= n_seg) pos[t] = t == n_seg ? n2 : lower_bound_u64(keys, 0, n2, (uint64_t)t << 33);
+}
+
+// a < b < c by position: is the corner at b strictly convex (b stays a vertex between a and c)?
+__device__ __forceinline__ bool iso_convex(const IsoPt& a, const IsoPt& b, const IsoPt& c) {
+    if (a.x < b.lo || c.x > b.hi) return true;
+    return (uint64_t)(c.y - b.y) * (uint64_t)(b.x - a.x) > (uint64_t)(b.y - a.y) * (uint64_t)(c.x - b.x);
+}
+
+// the vertex of the convex chain R[0, nr) (nr >= 1) that the lower tangent from p, left of all of R, touches: the smallest j with
+// a strict corner at R[j] between p and R[j+1] — false, .., false, true, .., true along a convex chain — else the last vertex
+__device__ __forceinline__ uint32_t iso_tangent(const IsoPt& p, const IsoPt* R, uint32_t nr) {
+    uint32_t lo = 0, hi = nr - 1;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        const IsoPt r0 = R[mid], r1 = R[mid + 1];
+        if (iso_convex(p, r0, r1)) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+// joins the chains L[0, nl) and R[0, nr), L left of R: L[0, keep) and R[skip, nr) are the joined chain
+__device__ __forceinline__ void iso_bridge(const IsoPt* L, uint32_t nl, const IsoPt* R, uint32_t nr, uint32_t* keep, uint32_t* skip) {
+    if (nl == 0 || nr == 0) { *keep = nl; *skip = 0; return; }
+    uint32_t lo = 0, hi = nl - 1;                                         // L[i] stays: true, .., true, false, .., false; L[0] stays
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi + 1) >> 1;
+        const IsoPt p = L[mid], q = L[mid - 1];
+        const IsoPt r = R[iso_tangent(p, R, nr)];
+        if (iso_convex(q, p, r)) lo = mid; else hi = mid - 1;
+    }
+    const IsoPt p = L[lo];
+    *keep = lo + 1;
+    *skip = iso_tangent(p, R, nr);
+}
+
+// iso_bridge by a whole wave (all 64 lanes call it with the same arguments): both searches probe 64 evenly spaced candidates at once,
+// a lane finding its own candidate's tangent point, so lists of up to 4096 vertices take two rounds each instead of 12 halvings
+__device__ __forceinline__ void iso_bridge_wave(const IsoPt* L, uint32_t nl, const IsoPt* R, uint32_t nr, uint32_t* keep, uint32_t* skip) {
+    if (nl == 0 || nr == 0) { *keep = nl; *skip = 0; return; }
+    const uint32_t lane = threadIdx.x & 63;
+    uint32_t lo = 0, hi = nl - 1;                                         // L[lo] stays; nothing past hi does
+    while (lo < hi) {
+        const uint32_t step = (hi - lo + 63) >> 6, i = lo + (lane + 1) * step;
+        bool stays = false;
+        if (i <= hi) {
+            const IsoPt p = L[i], q = L[i - 1];
+            const IsoPt r = R[iso_tangent(p, R, nr)];
+            stays = iso_convex(q, p, r);
+        }
+        const unsigned long long gone = ~__ballot(stays);
+        const uint32_t c = gone ? (uint32_t)__ffsll((long long)gone) - 1u : 64u;      // the candidates that stay come first
+        const uint32_t top = lo + (c + 1) * step - 1;
+        lo += c * step;
+        hi = top < hi ? top : hi;
+    }
+    *keep = lo + 1;
+    const IsoPt p = L[lo];
+    uint32_t a = 0, b = nr - 1;                                           // the tangent point lies in [a, b]
+    while (a < b) {
+        const uint32_t step = (b - a + 63) >> 6, j = a + lane * step;     // candidate j: is the corner at R[j] strict? false, .., true, ..
+        bool strict = false;
+        if (j < b) {
+            const IsoPt r0 = R[j], r1 = R[j + 1];
+            strict = iso_convex(p, r0, r1);
+        }
+        const unsigned long long hit = __ballot(strict);
+        if (hit) {                                                        // the first strict candidate f: the answer is in (f - step, f]
+            const uint32_t f = (uint32_t)__ffsll((long long)hit) - 1u, at = a + f * step;
+            a = f ? at - step + 1 : at;
+            b = at;
+        } else {                                                          // none of the probed corners: behind the last candidate below b
+            const uint32_t last = (b - 1 - a) / step;
+            a = a + last * step + 1;
+        }
+    }
+    *skip = a;
+}
+
+__global__ void __launch_bounds__(ISO_THREADS) k_iso_local(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ cp,
+                                                           const int64_t* __restrict__ pos, int64_t n2, IsoPt* __restrict__ verts,
+                                                           uint32_t* __restrict__ cnt) {
+    __shared__ IsoPt s_v[2][ISO_CHUNK];
+    __shared__ uint32_t s_n[2][ISO_CHUNK];
+    __shared__ uint32_t s_keep[ISO_CHUNK / 2], s_skip[ISO_CHUNK / 2];
+    const int tid = threadIdx.x;
+    const int64_t base = (int64_t)blockIdx.x * ISO_CHUNK;
+    for (int t = tid; t < ISO_CHUNK; t += ISO_THREADS) {
+        const int64_t b = base + t;
+        IsoPt q = {0u, 0u, 0u, 0u};
+        bool is = false;
+        if (b <= n2) {
+            const uint64_t k1 = b < n2 ? keys[b] : 0ull, k0 = b > 0 ? keys[b - 1] : 0ull;
+            const bool boundary = b == 0 || b == n2 || (k0 >> 33) != (k1 >> 33);
+            is = boundary || (k0 >> 1) != (k1 >> 1);
+            if (is) {
+                q.x = (uint32_t)b;
+                q.y = b > 0 ? cp[b - 1] : 0u;
+                if (boundary) q.lo = q.hi = (uint32_t)b;
+                else { const int64_t s = (int64_t)(k1 >> 33); q.lo = (uint32_t)pos[s]; q.hi = (uint32_t)pos[s + 1]; }
+            }
+        }
+        s_v[0][t] = q;
+        s_n[0][t] = is ? 1u : 0u;
+    }
+    __syncthreads();
+    int cur = 0;
+    for (int k = 1; k <= ISO_CHUNK_LOG; ++k) {
+        const int span = 1 << k, half = span >> 1, merges = ISO_CHUNK >> k;
+        const IsoPt* src = s_v[cur];
+        IsoPt* dst = s_v[cur ^ 1];
+        const uint32_t* nsrc = s_n[cur];
+        uint32_t* ndst = s_n[cur ^ 1];
+        for (int m = tid; m < merges; m += ISO_THREADS) {
+            const uint32_t nl = nsrc[2 * m], nr = nsrc[2 * m + 1];
+            uint32_t keep, skip;
+            iso_bridge(src + m * span, nl, src + m * span + half, nr, &keep, &skip);
+            s_keep[m] = keep;
+            s_skip[m] = skip;
+            ndst[m] = keep + nr - skip;
+        }
+        __syncthreads();
+        for (int slot = tid; slot < ISO_CHUNK; slot += ISO_THREADS) {
+            const int m = slot >> k;
+            const uint32_t o = (uint32_t)(slot & (span - 1)), keep = s_keep[m], tot = ndst[m];
+            if (o < keep) dst[slot] = src[slot];
+            else if (o < tot) dst[slot] = src[m * span + half + s_skip[m] + (o - keep)];
+        }
+        __syncthreads();
+        cur ^= 1;
+    }
+    const uint32_t nv = s_n[cur][0];
+    for (uint32_t o = tid; o < nv; o += ISO_THREADS) verts[base + o] = s_v[cur][o];
+    if (tid == 0) cnt[blockIdx.x] = nv;
+}
+
+// workgroup m joins the spans 2m and 2m + 1 of src (slots entries apart, nsrc vertices each) into span m of dst
+__global__ void __launch_bounds__(ISO_THREADS) k_iso_merge(const IsoPt* __restrict__ src, const uint32_t* __restrict__ nsrc,
+                                                           IsoPt* __restrict__ dst, uint32_t* __restrict__ ndst, int64_t spans_in,
+                                                           int64_t slots) {
+    __shared__ uint32_t sh[2];
+    const int tid = threadIdx.x;
+    const int64_t m = blockIdx.x;
+    const IsoPt* L = src + 2 * m * slots;
+    const IsoPt* R = L + slots;
+    const uint32_t nl = nsrc[2 * m], nr = 2 * m + 1 < spans_in ? nsrc[2 * m + 1] : 0u;
+    if (tid < 64) {                                                       // the first wave searches, every wave copies
+        uint32_t keep, skip;
+        iso_bridge_wave(L, nl, R, nr, &keep, &skip);
+        if (tid == 0) {
+            sh[0] = keep;
+            sh[1] = skip;
+            ndst[m] = keep + nr - skip;
+        }
+    }
+    __syncthreads();
+    const uint32_t keep = sh[0], skip = sh[1];
+    IsoPt* out = dst + 2 * m * slots;
+    for (uint32_t o = tid; o < keep; o += ISO_THREADS) out[o] = L[o];
+    for (uint32_t o = tid; o < nr - skip; o += ISO_THREADS) out[keep + o] = R[skip + o];
+}
+
+__global__ void __launch_bounds__(MET_THREADS) k_iso_emit(const uint64_t* __restrict__ keys, const IsoPt* __restrict__ V,
+                                                          const uint32_t* __restrict__ nv, int64_t cap, float* __restrict__ x_lo,
+                                                          float* __restrict__ x_hi, int64_t* __restrict__ count,
+                                                          int64_t* __restrict__ positives, double* __restrict__ value) {
+    int64_t nb = (int64_t)nv[0] - 1;
+    nb = nb < cap ? nb : cap;
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nb; j += (int64_t)gridDim.x * blockDim.x) {
+        const IsoPt a = V[j], b = V[j + 1];
+        const int64_t c = (int64_t)(b.x - a.x), p = (int64_t)(b.y - a.y);
+        x_lo[j] = cal_score(keys[a.x]);
+        x_hi[j] = cal_score(keys[b.x - 1u]);
+        count[j] = c;
+        positives[j] = p;
+        value[j] = (double)p / (double)c;
+    }
+}
+
+// start[s] = the rank of segment s's first point among the vertices (= its first block), start[n_seg] = the number of blocks
+__global__ void __launch_bounds__(MET_THREADS) k_iso_segments(const IsoPt* __restrict__ V, const uint32_t* __restrict__ nv,
+                                                              const int64_t* __restrict__ pos, const uint32_t* __restrict__ cp,
+                                                              int32_t n_seg, int64_t* __restrict__ start, int64_t* __restrict__ seg_rows,
+                                                              int64_t* __restrict__ seg_positives) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s > n_seg) return;
+    const uint32_t x = (uint32_t)pos[s];
+    uint32_t lo = 0, hi = nv[0];
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (V[mid].x < x) lo = mid + 1; else hi = mid;
+    }
+    start[s] = (int64_t)lo;
+    if (s < n_seg) {
+        const int64_t p0 = pos[s], p1 = pos[s + 1];
+        seg_rows[s] = p1 - p0;
+        seg_positives[s] = (int64_t)(p1 > 0 ? cp[p1 - 1] : 0u) - (int64_t)(p0 > 0 ? cp[p0 - 1] : 0u);
+    }
+}
+
+struct IsoLayout {
+    int64_t keys_in, keys_out, cp, pos, verts_a, verts_b, cnt_a, cnt_b, temp, temp_bytes, total, chunks;
+};
+// everything but rocPRIM's temporary storage: plain arithmetic (argument checks use it before any HIP or rocPRIM call)
+static void iso_fixed_layout(int64_t n, int32_t n_domain, IsoLayout* L) {
+    const int64_t n2 = 2 * n, seg = (int64_t)n_domain + 1;
+    L->chunks = (n2 + 1 + ISO_CHUNK - 1) / ISO_CHUNK;                      // the points 0 .. 2n
+    int64_t off = 0;
+    L->keys_in = off;  off += align_up(n2 * 8);
+    L->keys_out = off; off += align_up(n2 * 8);
+    L->cp = off;       off += align_up(n2 * 4);
+    L->pos = off;      off += align_up((seg + 1) * 8);
+    L->verts_a = off;  off += align_up(L->chunks * ISO_CHUNK * (int64_t)sizeof(IsoPt));
+    L->verts_b = off;  off += align_up(L->chunks * ISO_CHUNK * (int64_t)sizeof(IsoPt));
+    L->cnt_a = off;    off += align_up(L->chunks * 4);
+    L->cnt_b = off;    off += align_up(L->chunks * 4);
+    L->temp = off;
+    L->temp_bytes = 0;
+    L->total = off;
+}
+static int iso_layout(int64_t n, int32_t n_domain, IsoLayout* L) {
+    iso_fixed_layout(n, n_domain, L);
+    const size_t n2 = (size_t)(2 * n);
+    size_t t_sort = 0, t_scan = 0;
+    hipError_t e = rocprim::radix_sort_keys(nullptr, t_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr, n2, 0, 64, (hipStream_t)0, false);
+    if (e == hipSuccess)
+        e = rocprim::inclusive_scan(nullptr, t_scan, IsoLabelIt(rocprim::counting_iterator<uint32_t>(0), IsoLabelIn{nullptr}),
+                                    (uint32_t*)nullptr, n2, rocprim::plus<uint32_t>(), (hipStream_t)0, false);
+    if (e != hipSuccess) { cdc_set_error("eval_isotonic_fit: rocprim size query failed: %s", hipGetErrorString(e)); return (int)e; }
+    L->temp_bytes = (int64_t)std::max(t_sort, t_scan);                     // the two run one after the other
+    L->total = L->temp + align_up(L->temp_bytes);
+    return 0;
+}
+static bool iso_sizes_ok(int64_t n, int32_t n_domain) { return n > 0 && n < (1ll << 31) && n_domain > 0 && n_domain < (1 << 20); }
+
+extern "C" int64_t cdc_eval_isotonic_max_blocks(int64_t n, int32_t n_domain) {
+    return iso_sizes_ok(n, n_domain) ? 2 * n : 0;
+}
+
+extern "C" int64_t cdc_eval_isotonic_fit_workspace_bytes(int64_t n, int32_t n_domain) {
+    if (!iso_sizes_ok(n, n_domain)) return 0;
+    IsoLayout L;
+    if (iso_layout(n, n_domain, &L) != 0) return -1;
+    return L.total;
+}
+
+extern "C" int cdc_eval_isotonic_fit(const float* pred, const int16_t* label, const int32_t* domain, int64_t ld_domain, int64_t n,
+                                     int32_t n_domain, int64_t* start, float* x_lo, float* x_hi, int64_t* count, int64_t* positives,
+                                     double* value, int64_t cap, int64_t* seg_rows, int64_t* seg_positives, int32_t* err_flag,
+                                     void* workspace, int64_t workspace_bytes, void* stream) {
+    CDC_CHECK_ARG(pred && label && start && x_lo && x_hi && count && positives && value && seg_rows && seg_positives && workspace,
+                  CDC_E_BADARG, "eval_isotonic_fit: null pointer");
+    CDC_CHECK_ARG(n > 0 && n_domain > 0 && n_domain < (1 << 20) && ld_domain >= 0, CDC_E_BADARG,
+                  "eval_isotonic_fit: bad sizes n=%ld n_domain=%d ld_domain=%ld", (long)n, n_domain, (long)ld_domain);
+    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_isotonic_fit: n_domain=%d needs the domain column", n_domain);
+    CDC_CHECK_ARG(n < (1ll << 31), CDC_E_TOOBIG, "eval_isotonic_fit: n=%ld exceeds the 2^31 rows whose products fit 64 bits", (long)n);
+    CDC_CHECK_ARG(cap >= 2 * n, CDC_E_BADARG, "eval_isotonic_fit: cap=%ld < 2n = %ld blocks", (long)cap, (long)(2 * n));
+    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_isotonic_fit: workspace must be 256-byte aligned");
+    IsoLayout L;
+    iso_fixed_layout(n, n_domain, &L);
+    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_isotonic_fit: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
+    int rc = iso_layout(n, n_domain, &L);
+    if (rc != 0) return rc;
+    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_isotonic_fit: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
+    char* base = (char*)workspace;
+    uint64_t* keys_in = (uint64_t*)(base + L.keys_in);
+    uint64_t* keys_out = (uint64_t*)(base + L.keys_out);
+    uint32_t* cp = (uint32_t*)(base + L.cp);
+    int64_t* pos = (int64_t*)(base + L.pos);
+    IsoPt* va = (IsoPt*)(base + L.verts_a);
+    IsoPt* vb = (IsoPt*)(base + L.verts_b);
+    uint32_t* na = (uint32_t*)(base + L.cnt_a);
+    uint32_t* nb = (uint32_t*)(base + L.cnt_b);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n2 = 2 * n;
+    const int seg = n_domain + 1;
+    int blocks = (int)std::min<int64_t>(cdc_ceil_div(n, MET_THREADS), 4096);
+    hipLaunchKernelGGL(k_iso_keys, dim3(blocks), dim3(MET_THREADS), 0, st, pred, label, domain, ld_domain, n, n_domain, keys_in, err_flag);
+    CDC_LAUNCH_CHECK("eval_isotonic_fit(keys)");
+    // the sort only has to look at the bits a key can have: label + 32 score bits + the bits of n_domain
+    int end_bit = 34;
+    while (end_bit < 64 && ((uint64_t)n_domain >> (end_bit - 33)) != 0) ++end_bit;
+    size_t temp_bytes = (size_t)L.temp_bytes;
+    hipError_t e = rocprim::radix_sort_keys(base + L.temp, temp_bytes, (const uint64_t*)keys_in, keys_out, (size_t)n2, 0, end_bit, st, false);
+    if (e != hipSuccess) { cdc_set_error("eval_isotonic_fit: radix sort failed: %s", hipGetErrorString(e)); return (int)e; }
+    temp_bytes = (size_t)L.temp_bytes;
+    e = rocprim::inclusive_scan(base + L.temp, temp_bytes, IsoLabelIt(rocprim::counting_iterator<uint32_t>(0), IsoLabelIn{keys_out}), cp,
+                                (size_t)n2, rocprim::plus<uint32_t>(), st, false);
+    if (e != hipSuccess) { cdc_set_error("eval_isotonic_fit: label scan failed: %s", hipGetErrorString(e)); return (int)e; }
+    hipLaunchKernelGGL(k_iso_starts, dim3((int)cdc_ceil_div(seg + 1, MET_THREADS)), dim3(MET_THREADS), 0, st, (const uint64_t*)keys_out, n2, seg, pos);
+    CDC_LAUNCH_CHECK("eval_isotonic_fit(starts)");
+    hipLaunchKernelGGL(k_iso_local, dim3((unsigned)L.chunks), dim3(ISO_THREADS), 0, st, (const uint64_t*)keys_out, (const uint32_t*)cp,
+                       (const int64_t*)pos, n2, va, na);
+    CDC_LAUNCH_CHECK("eval_isotonic_fit(local)");
+    int64_t slots = ISO_CHUNK;
+    for (int64_t spans = L.chunks; spans > 1; spans = (spans + 1) / 2, slots *= 2) {
+        hipLaunchKernelGGL(k_iso_merge, dim3((unsigned)((spans + 1) / 2)), dim3(ISO_THREADS), 0, st, (const IsoPt*)va, (const uint32_t*)na, vb,
+                           nb, spans, slots);
+        CDC_LAUNCH_CHECK("eval_isotonic_fit(merge)");
+        std::swap(va, vb);
+        std::swap(na, nb);
+    }
+    blocks = (int)std::min<int64_t>(cdc_ceil_div(n2, MET_THREADS), 4096);
+    hipLaunchKernelGGL(k_iso_emit, dim3(blocks), dim3(MET_THREADS), 0, st, (const uint64_t*)keys_out, (const IsoPt*)va, (const uint32_t*)na, cap,
+                       x_lo, x_hi, count, positives, value);
+    CDC_LAUNCH_CHECK("eval_isotonic_fit(emit)");
+    hipLaunchKernelGGL(k_iso_segments, dim3((int)cdc_ceil_div(seg + 1, MET_THREADS)), dim3(MET_THREADS), 0, st, (const IsoPt*)va,
+                       (const uint32_t*)na, (const int64_t*)pos, (const uint32_t*)cp, seg, start, seg_rows, seg_positives);
+    CDC_LAUNCH_CHECK("eval_isotonic_fit(segments)");
+    return 0;
+}
+
+// a thread per row: the row's segment is seg_of_domain[its domain]; binary search for the last block that starts at or below the score
+__global__ void __launch_bounds__(MET_THREADS) k_iso_apply(const float* __restrict__ pred, const int32_t* __restrict__ domain,
+                                                           int64_t ld_domain, int64_t n, int32_t n_domain,
+                                                           const int32_t* __restrict__ seg_of_domain, const int64_t* __restrict__ start,
+                                                           const float* __restrict__ x_lo, const float* __restrict__ x_hi,
+                                                           const double* __restrict__ value, float eps, float* __restrict__ out,
+                                                           int32_t* __restrict__ err) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float xf = pred[i];
+    const int32_t d = domain ? domain[i * ld_domain] : 0;
+    int64_t b0 = 0, b1 = 0;
+    if (xf == xf && d >= 0 && d < n_domain) {
+        const int32_t s = seg_of_domain[d];
+        if (s >= 0 && s <= n_domain) { b0 = start[s]; b1 = start[s + 1]; }
+    }
+    if (b1 <= b0) {                                                       // a NaN score, a domain outside range, a segment without blocks
+        if (err) atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
+        out[i] = __uint_as_float(0x7fc00000u);
+        return;
+    }
+    const double x = (double)xf;
+    double r;
+    if (x <= (double)x_lo[b0]) r = value[b0];
+    else if (x >= (double)x_hi[b1 - 1]) r = value[b1 - 1];
+    else {
+        int64_t lo = b0, hi = b1 - 1;                                     // the largest k with x_lo[k] <= x; x_lo[b0] < x
+        while (lo < hi) {
+            const int64_t mid = (lo + hi + 1) >> 1;
+            if ((double)x_lo[mid] <= x) lo = mid; else hi = mid - 1;
+        }
+        const double h = (double)x_hi[lo], v = value[lo];
+        if (x <= h) r = v;
+        else {
+            const double t = (x - h) / ((double)x_lo[lo + 1] - h);
+            r = v + t * (value[lo + 1] - v);
+        }
+    }
+    float o = (float)r;
+    if (eps > 0.f) {
+        const float top = __fsub_rn(1.0f, eps);
+        o = o < eps ? eps : (o > top ? top : o);
+    }
+    out[i] = o;
+}
+
+extern "C" int cdc_eval_isotonic_apply(const float* pred, const int32_t* domain, int64_t ld_domain, int64_t n, int32_t n_domain,
+                                       const int32_t* seg_of_domain, const int64_t* start, const float* x_lo, const float* x_hi,
+                                       const double* value, float eps, float* out, int32_t* err_flag, void* stream) {
+    CDC_CHECK_ARG(pred && seg_of_domain && start && x_lo && x_hi && value && out, CDC_E_BADARG, "eval_isotonic_apply: null pointer");
+    CDC_CHECK_ARG(n > 0 && n_domain > 0 && n_domain < (1 << 20) && ld_domain >= 0 && eps >= 0.f && eps <= 0.5f, CDC_E_BADARG,
+                  "eval_isotonic_apply: bad sizes n=%ld n_domain=%d ld_domain=%ld eps=%g", (long)n, n_domain, (long)ld_domain, (double)eps);
+    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_isotonic_apply: n_domain=%d needs the domain column", n_domain);
+    CDC_CHECK_ARG(n < (1ll << 31), CDC_E_TOOBIG, "eval_isotonic_apply: n=%ld exceeds 2^31 rows", (long)n);
+    hipLaunchKernelGGL(k_iso_apply, dim3((unsigned)cdc_ceil_div(n, MET_THREADS)), dim3(MET_THREADS), 0, (hipStream_t)stream, pred, domain,
+                       ld_domain, n, n_domain, seg_of_domain, start, x_lo, x_hi, value, eps, out, err_flag);
+    CDC_LAUNCH_CHECK("eval_isotonic_apply");
+    return 0;
+}

@@ -19,6 +19,11 @@ vectors over the same rows the difference of their AUCs with the standard error 
 domain and over all rows the ratio of predicted to observed CTR, the Brier score, and a reliability table with ECE / MCE for
 equal-width and equal-mass bins (`cdc_eval_calibration`); `Evaluator(calibration=True)` and `Evaluator.calibration_table` report them.
 
+`eval_isotonic_fit` / `eval_isotonic_apply` repair what `eval_calibration` measures: a monotone map per domain (isotonic regression of the
+labels on the score, fitted on the validation split: `cdc_eval_isotonic_fit`) that is applied to the predictions of the test split
+(`cdc_eval_isotonic_apply`); `Recalibration` holds a fitted map, `Evaluator.fit_recalibration` fits one and
+`Evaluator(recalibration=...)` reports the recalibrated model.
+
 `eval_segments` serves CDC's matrix update (run.py:549-558) instead: the metric of every contiguous row segment of ONE forward's
 raw output, each segment scored by its own tower column (`cdc_eval_segments`; probe.py lays the domains' batches out that way).
 """
@@ -253,8 +258,8 @@ def eval_calibration(pred, label, domain=None, n_domain=1, n_bins=10):
     f64; pred_min, pred_max f32) of shape [n_domain + 1, n_bins]; an empty bin has count 0 and NaN in the floating-point fields.
     No host synchronisation; the error word (1 + a row with a NaN prediction, a prediction outside [0, 1], a label outside {0, 1} or
     a domain outside range) is kept as `eval_calibration.last_err`.
-    Not offered: selection or early stopping by a calibration figure in `Runner`, calibration deltas in `Evaluator.compare`, and
-    fitting a recalibration map (Platt scaling, isotonic regression)."""
+    A recalibration map is fitted by `eval_isotonic_fit` / `Recalibration` (isotonic regression).  Not offered: selection or early
+    stopping by a calibration figure in `Runner`, calibration deltas in `Evaluator.compare`, Platt scaling."""
     lib = L.load()
     n_domain, n_bins = int(n_domain), int(n_bins)
     if not 1 <= n_bins <= MAX_CALIBRATION_BINS:
@@ -292,6 +297,161 @@ def eval_calibration(pred, label, domain=None, n_domain=1, n_bins=10):
     return Calibration(seg_counts[0], seg_counts[1], *seg_out.unbind(0), tables[0], tables[1])
 
 
+IsotonicFit = collections.namedtuple("IsotonicFit", "start x_lo x_hi count positives value rows seg_positives")
+
+
+def _iso_domain(domain, n, n_domain):
+    if domain is not None:
+        return _id_column(domain, n, "domain")
+    if n_domain != 1:
+        raise ValueError("n_domain > 1 needs the domain column")
+    return None, 0
+
+
+def eval_isotonic_fit(pred, label, domain=None, n_domain=1):
+    """Isotonic regression of the labels on the score per domain and over all rows; inputs as `eval_metrics` (domain: int32 [n] or a
+    strided column view), pred any finite float32 (logits are allowed; -0.0 and +0.0 are one score).  Returns the namedtuple
+    `IsotonicFit` of device tensors: `start` i64 [n_domain + 2] — the blocks of segment s (domains 0..n_domain-1, then ALL rows) are
+    [start[s], start[s+1]) — and per block, in ascending score order, `x_lo`, `x_hi` (f32: its smallest and largest score), `count`,
+    `positives` (i64) and `value` = positives / count (f64), strictly increasing along a segment; `rows`, `seg_positives` i64
+    [n_domain + 1].  The block tensors have the full capacity 2n, entries at or past start[-1] are not written.  The fit is exact
+    (integer comparisons until the one division), so the same rows in any order give the same bits.  No host synchronisation; the
+    error word (1 + a row with a NaN or infinite score, a label outside {0, 1} or a domain outside range) is kept as
+    `eval_isotonic_fit.last_err`."""
+    lib = L.load()
+    n_domain = int(n_domain)
+    if not pred.is_cuda:
+        raise L.HipExtensionError("eval_isotonic_fit needs device tensors; there is no CPU fallback")
+    pred = pred.reshape(-1).to(torch.float32).contiguous()
+    label = label.reshape(-1).to(torch.int16).contiguous()
+    n = pred.numel()
+    if label.numel() != n:
+        raise ValueError(f"{n} predictions but {label.numel()} labels")
+    domain, ld = _iso_domain(domain, n, n_domain)
+    dev = pred.device
+    seg = n_domain + 1
+    cap = lib.cdc_eval_isotonic_max_blocks(n, n_domain)
+    nbytes = lib.cdc_eval_isotonic_fit_workspace_bytes(n, n_domain)
+    if cap <= 0 or nbytes <= 0:
+        raise RuntimeError(f"cdc_eval_isotonic_fit_workspace_bytes refused n={n}, n_domain={n_domain}")
+    start = torch.empty(seg + 1, dtype=torch.int64, device=dev)
+    x = torch.empty((2, cap), dtype=torch.float32, device=dev)
+    cnt = torch.empty((2, cap), dtype=torch.int64, device=dev)
+    value = torch.empty(cap, dtype=torch.float64, device=dev)
+    seg_counts = torch.empty((2, seg), dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    L.launch("cdc_eval_isotonic_fit", lib.cdc_eval_isotonic_fit,
+             (pred.data_ptr(), label.data_ptr(), None if domain is None else domain.data_ptr(), ld, n, n_domain, start.data_ptr(),
+              x[0].data_ptr(), x[1].data_ptr(), cnt[0].data_ptr(), cnt[1].data_ptr(), value.data_ptr(), cap, seg_counts[0].data_ptr(),
+              seg_counts[1].data_ptr(), err.data_ptr(), ws.data_ptr(), nbytes), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    eval_isotonic_fit.last_err = err
+    return IsotonicFit(start, x[0], x[1], cnt[0], cnt[1], value, seg_counts[0], seg_counts[1])
+
+
+def eval_isotonic_apply(pred, fit_or_map, domain=None, n_domain=1, seg_of_domain=None, eps=0.0):
+    """The isotonic map of `fit_or_map` (an `IsotonicFit` or a `Recalibration`) at the scores pred f32 [n]: a row of domain d goes
+    through the blocks of segment seg_of_domain[d] (int32 [n_domain], entries in [0, n_domain]; None: the identity, or the
+    `Recalibration`'s own table) — constant on a block, linear between two blocks, the first / last value outside; float64
+    arithmetic, the result float32, clamped to [eps, 1 - eps] when eps > 0.  Returns float32 [n] on the device.  A NaN score, a domain
+    outside range or a segment without blocks gives NaN and sets the error word (1 + the row), kept as
+    `eval_isotonic_apply.last_err`.  No host synchronisation.  Not offered: a "step" interpolation, Platt scaling."""
+    lib = L.load()
+    n_domain = int(n_domain)
+    if not pred.is_cuda:
+        raise L.HipExtensionError("eval_isotonic_apply needs device tensors; there is no CPU fallback")
+    pred = pred.reshape(-1).to(torch.float32).contiguous()
+    n = pred.numel()
+    domain, ld = _iso_domain(domain, n, n_domain)
+    dev = pred.device
+    m = fit_or_map
+    if m.start.numel() != n_domain + 2:
+        raise ValueError(f"the map holds {m.start.numel() - 2} domains, not {n_domain}")
+    if seg_of_domain is None:
+        seg_of_domain = getattr(m, "seg_of_domain", None)
+    if seg_of_domain is None:
+        seg_of_domain = torch.arange(n_domain, dtype=torch.int32, device=dev)
+    seg_of_domain = torch.as_tensor(seg_of_domain).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    if seg_of_domain.numel() != n_domain:
+        raise ValueError(f"seg_of_domain holds {seg_of_domain.numel()} entries for {n_domain} domains")
+    if not 0.0 <= float(eps) <= 0.5:
+        raise ValueError(f"eps={eps} must lie in [0, 0.5]")
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    L.launch("cdc_eval_isotonic_apply", lib.cdc_eval_isotonic_apply,
+             (pred.data_ptr(), None if domain is None else domain.data_ptr(), ld, n, n_domain, seg_of_domain.data_ptr(), m.start.data_ptr(),
+              m.x_lo.data_ptr(), m.x_hi.data_ptr(), m.value.data_ptr(), float(eps), out.data_ptr(), err.data_ptr()),
+             C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    eval_isotonic_apply.last_err = err
+    return out
+
+
+IsotonicBlocks = collections.namedtuple("IsotonicBlocks", "x_lo x_hi count positives value")
+
+
+class Recalibration:
+    """A fitted per-domain isotonic map: the blocks of `eval_isotonic_fit` cut to their number, and `seg_of_domain`, the segment
+    every domain is sent through — its own, or "all" (index n_domain) for the domains of `fallback_domains`."""
+    _TENSORS = ("start", "x_lo", "x_hi", "count", "positives", "value", "rows", "seg_positives", "seg_of_domain")
+
+    def __init__(self):
+        self.n_domain = 0
+        self.fallback_domains = []
+        for k in self._TENSORS:
+            setattr(self, k, None)
+
+    @classmethod
+    def fit(cls, pred, label, domain=None, n_domain=1, min_rows=0, need_both_classes=True):
+        """Fits on (pred, label, domain) — the validation split's RAW predictions.  A domain without fit rows, with fewer than
+        min_rows, or (need_both_classes) with a single class has no map of its own worth using: it is sent through the map of all
+        rows and listed in `fallback_domains`.  One host synchronisation: start, rows, seg_positives and the error word are read
+        once.  A bad row (non-finite score, label outside {0, 1}, domain outside range) raises ValueError naming it."""
+        n_domain = int(n_domain)
+        f = eval_isotonic_fit(pred, label, domain, n_domain)
+        seg = n_domain + 1
+        host = torch.cat([f.start, f.rows, f.seg_positives, eval_isotonic_fit.last_err.to(torch.int64)]).cpu().tolist()   # the one sync
+        start, rows, pos, bad = host[:seg + 1], host[seg + 1:2 * seg + 1], host[2 * seg + 1:3 * seg + 1], host[-1]
+        if bad:
+            raise ValueError(f"recalibration row {bad - 1}: NaN or infinite score, label outside {{0,1}} or domain outside [0, {n_domain})")
+        r = cls()
+        r.n_domain = n_domain
+        nb = start[seg]
+        r.start, r.rows, r.seg_positives = f.start, f.rows, f.seg_positives
+        for k in ("x_lo", "x_hi", "count", "positives", "value"):
+            setattr(r, k, getattr(f, k)[:nb].clone())              # the full-capacity buffers go
+        r.fallback_domains = [d for d in range(n_domain)
+                              if rows[d] == 0 or rows[d] < min_rows or (need_both_classes and (pos[d] == 0 or pos[d] == rows[d]))]
+        table = [n_domain if d in set(r.fallback_domains) else d for d in range(n_domain)]
+        r.seg_of_domain = torch.tensor(table, dtype=torch.int32, device=f.start.device)
+        return r
+
+    def apply(self, pred, domain=None, eps=0.0):
+        """-> float32 [n] on the device: pred through the map of every row's domain (domain: as `eval_metrics`; None for a map over
+        one domain)."""
+        return eval_isotonic_apply(pred, self, domain, self.n_domain, self.seg_of_domain, eps)
+
+    def state_dict(self):
+        sd = {k: getattr(self, k) for k in self._TENSORS}
+        sd["fallback_domains"] = torch.tensor(self.fallback_domains, dtype=torch.int64)
+        return sd
+
+    def load_state_dict(self, sd, device=None):
+        for k in self._TENSORS:
+            t = sd[k]
+            setattr(self, k, t.to(device) if device is not None else t)
+        self.n_domain = self.seg_of_domain.numel()
+        self.fallback_domains = [int(d) for d in sd["fallback_domains"].tolist()]
+        return self
+
+    def blocks(self, segment):
+        """Host numpy arrays (x_lo, x_hi, count, positives, value) of a domain's own blocks, or of "all" (also: index n_domain)."""
+        s = self.n_domain if segment == "all" else int(segment)
+        if not 0 <= s <= self.n_domain:
+            raise ValueError(f"segment {segment!r} outside [0, {self.n_domain}] / 'all'")
+        b0, b1 = self.start[s:s + 2].cpu().tolist()
+        return IsotonicBlocks(*(getattr(self, k)[b0:b1].cpu().numpy() for k in IsotonicBlocks._fields))
+
+
 def _se(var):
     return math.sqrt(var) if var == var else math.nan
 
@@ -323,14 +483,26 @@ class Evaluator:
     calibration: test() adds calibration figures (`eval_calibration`; True: 10 bins, an int: that many): total_pcoc (predicted over
             observed CTR), total_brier, total_ece, total_ece_quantile, and with per-domain evaluation domain_pcoc / domain_brier /
             domain_ece / domain_ece_quantile {d: value} and mean_pcoc / mean_brier / mean_ece / mean_ece_quantile, weighted like
-            mean_auc; `calibration_table` returns the reliability tables.  Selection or early stopping by a calibration figure,
-            calibration deltas in `compare` and fitting a recalibration map (Platt, isotonic) are not offered.
+            mean_auc; `calibration_table` returns the reliability tables.  Selection or early stopping by a calibration figure
+            and calibration deltas in `compare` are not offered.
+    recalibration: a `Recalibration` (from `fit_recalibration` on the validation loader, or `Recalibration.fit`): every prediction goes
+            through its isotonic map, clamped to [recalibration_eps, 1 - recalibration_eps] when that is positive, before anything is
+            computed, so test(), calibration_table(), predict() and compare() report the recalibrated model under the same keys; raw
+            against recalibrated on one checkpoint: Evaluator(model, ..).compare(Evaluator(model, .., recalibration=r), loader).  A map
+            over more than one domain needs domain_idx.  Platt scaling, a "step" interpolation, selection by a calibration figure in
+            `Runner` and calibration deltas in `compare` are not offered.
     precision: None, or "bf16" / "f32": the model is switched to it for the scoring pass and switched back afterwards, so two
             evaluators around ONE module can score it under two precisions (`compare`)."""
 
     def __init__(self, model, mode="multi", domain_idx=None, n_domain=1, domain_cnt_weight=None, is_evaluate_multi_domain=True,
-                 user_idx=None, n_user=None, user_weight=None, auc_ci=False, precision=None, calibration=False):
+                 user_idx=None, n_user=None, user_weight=None, auc_ci=False, precision=None, calibration=False, recalibration=None,
+                 recalibration_eps=0.0):
         self.model, self.mode = model, mode
+        if recalibration is not None and recalibration.n_domain > 1 and domain_idx is None:
+            raise ValueError(f"a recalibration map over {recalibration.n_domain} domains needs domain_idx, the column that holds a row's domain")
+        if not 0.0 <= float(recalibration_eps) <= 0.5:
+            raise ValueError(f"recalibration_eps={recalibration_eps} must lie in [0, 0.5]")
+        self.recalibration, self.recalibration_eps = recalibration, float(recalibration_eps)
         self.auc_ci = bool(auc_ci)
         self.calibration_bins = 0 if calibration is False else (10 if calibration is True else int(calibration))   # 0: off
         if calibration is not False and not 1 <= self.calibration_bins <= MAX_CALIBRATION_BINS:
@@ -356,8 +528,18 @@ class Evaluator:
         """-> (pred f32 [n], label int16 [n], domain int32 [n] or None), all on the device."""
         return self._score(data_loader)[:3]
 
-    def _score(self, data_loader):
-        """predict() and the user column: -> (pred, label, domain or None, user int32 [n] or None)"""
+    def fit_recalibration(self, data_loader, **kw):
+        """One scoring pass over `data_loader` (the validation split) -> `Recalibration`: the isotonic map of every domain of the
+        domain column (of all rows without one) fitted on the model's RAW predictions; kw: `Recalibration.fit`'s min_rows,
+        need_both_classes."""
+        pred, label, domain, _ = self._score(data_loader, raw=True)
+        if domain is None:
+            return Recalibration.fit(pred, label, None, 1, **kw)
+        return Recalibration.fit(pred, label, domain, self.n_domain, **kw)
+
+    def _score(self, data_loader, raw=False):
+        """predict() and the user column: -> (pred, label, domain or None, user int32 [n] or None); with a recalibration map (and not
+        raw) pred has gone through it"""
         model = self.model
         was_training = model.training
         model.eval()
@@ -390,7 +572,10 @@ class Evaluator:
                 model.set_precision(was_precision)
         if not preds:
             raise ValueError("empty evaluation set")
-        return torch.cat(preds), torch.cat(labels), (torch.cat(domains) if domains else None), (torch.cat(users) if users else None)
+        pred, domain = torch.cat(preds), (torch.cat(domains) if domains else None)
+        if self.recalibration is not None and not raw:
+            pred = self.recalibration.apply(pred, domain if self.recalibration.n_domain > 1 else None, self.recalibration_eps)
+        return pred, torch.cat(labels), domain, (torch.cat(users) if users else None)
 
     @staticmethod
     def _domain_batches(loaders, domain_batch_seq):

@@ -1222,6 +1222,44 @@ int cdc_eval_calibration(const float* pred, const int16_t* label, const int32_t*
                          int64_t* tab_counts, float* tab_range, int32_t* err_flag, void* workspace, int64_t workspace_bytes,
                          void* stream);
 
+/* Isotonic recalibration: per segment (domain 0..n_domain-1, then ALL rows) the non-decreasing least-squares fit of the 0/1 labels
+ * on the score (pool-adjacent-violators), and the map it defines.  pred, label, domain, ld_domain, n_domain as for cdc_eval_metrics;
+ * pred is any finite float (-0.0 and +0.0 are one score, reported as +0.0).  Rows of one score are one point; the fit is delivered
+ * in canonical form, as BLOCKS in ascending score order: x_lo / x_hi the smallest / largest score of the block, count its rows,
+ * positives its positive rows, value = (double)positives / (double)count — strictly increasing along a segment (blocks of equal
+ * mean are one block).  The block ends are the vertices of the lower convex hull of (rows so far, positives so far) at the ends of
+ * the tie groups, collinear points left out; two means are compared as integer products below 2^62, so the result is exact and the
+ * same rows in any order give the same bits.
+ *   start         [n_domain+2] int64: the blocks of segment s are [start[s], start[s+1]); an empty segment has none.
+ *   x_lo, x_hi    [cap] floats, count, positives [cap] int64, value [cap] doubles: entries at or past start[n_domain+1] are not
+ *                 written.  cap >= cdc_eval_isotonic_max_blocks(n, n_domain) = 2n (every row lies in its domain and in ALL).
+ *   seg_rows, seg_positives [n_domain+1] int64.
+ *   err_flag (optional): 1 + the largest index of a row with a NaN or infinite score, a label other than 0/1 or a domain outside
+ *                 [0, n_domain); such a row is counted with score 0 and the domain clamped into range.
+ * Limits: null pointers, n <= 0, n_domain outside [1, 2^20), n_domain > 1 without the domain column, cap < 2n, a workspace too small
+ * or not 256-byte aligned: CDC_E_BADARG; n >= 2^31: CDC_E_TOOBIG — all before anything is launched.  Stream-ordered: no
+ * allocation, no synchronisation, no state kept; the launches and their dimensions depend on (n, n_domain) alone (one sort, one
+ * scan, five launches and ceil(log2(ceil((2n + 1) / 1024))) merge launches), so the call can be captured in a graph.
+ * workspace: cdc_eval_isotonic_fit_workspace_bytes(n, n_domain) bytes, 256-byte aligned; 0 for sizes the call refuses. */
+int64_t cdc_eval_isotonic_max_blocks(int64_t n, int32_t n_domain);
+int64_t cdc_eval_isotonic_fit_workspace_bytes(int64_t n, int32_t n_domain);
+int cdc_eval_isotonic_fit(const float* pred, const int16_t* label, const int32_t* domain, int64_t ld_domain, int64_t n,
+                          int32_t n_domain, int64_t* start, float* x_lo, float* x_hi, int64_t* count, int64_t* positives,
+                          double* value, int64_t cap, int64_t* seg_rows, int64_t* seg_positives, int32_t* err_flag,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+
+/* The map of a fit at n scores: row i of domain d uses the blocks b0 = start[s] .. b1 - 1 = start[s+1] - 1 of segment
+ * s = seg_of_domain[d] (device int32 [n_domain], entries in [0, n_domain]: a domain may be sent to another's map, or to ALL).  With
+ * X = (double)pred[i]:  X <= x_lo[b0] -> value[b0];  X >= x_hi[b1-1] -> value[b1-1];  else k = the largest index with x_lo[k] <= X:
+ * X <= x_hi[k] -> value[k], else t = (X - x_hi[k]) / (x_lo[k+1] - x_hi[k]) and value[k] + t * (value[k+1] - value[k]), float64
+ * operations in this order, unfused.  out[i] = (float) of that, then clamped to [eps, 1.0f - eps] in float32 when eps > 0.
+ * A NaN score, a domain outside [0, n_domain) or a segment without blocks writes NaN and sets err_flag (optional) to 1 + the largest
+ * such row.  domain == NULL needs n_domain == 1.  Null pointers, n <= 0, n_domain outside [1, 2^20), eps outside [0, 0.5]:
+ * CDC_E_BADARG; n >= 2^31: CDC_E_TOOBIG.  One launch, a thread per row; stream-ordered, no allocation, no synchronisation. */
+int cdc_eval_isotonic_apply(const float* pred, const int32_t* domain, int64_t ld_domain, int64_t n, int32_t n_domain,
+                            const int32_t* seg_of_domain, const int64_t* start, const float* x_lo, const float* x_hi,
+                            const double* value, float eps, float* out, int32_t* err_flag, void* stream);
+
 /* Per-segment BCE of CDC's probe evaluation (run.py:549-558): one batch of every domain went through ONE eval
  * forward; segment s is the rows [seg_start[s], seg_start[s+1]) of probs [rows, n_cols] (row stride ld_probs: all towers'
  * probabilities) and is scored by column seg_col[s] (NULL = column 0).  seg_start [n_seg+1] is non-decreasing; rows at or past
