@@ -23,6 +23,7 @@ PREC_BF16 = 0
 PREC_F32 = 1
 
 c_f = C.c_float
+c_d = C.c_double
 c_i32 = C.c_int32
 c_i64 = C.c_int64
 c_p = C.c_void_p
@@ -376,6 +377,10 @@ _SIGNATURES = {
     "cdc_eval_isotonic_fit_workspace_bytes": (c_i64, [c_i64, c_i32]),
     "cdc_eval_isotonic_fit": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p]),
     "cdc_eval_isotonic_apply": (c_i32, [c_p, c_p, c_i64, c_i64, c_i32, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p]),
+    "cdc_eval_platt_fit_workspace_bytes": (c_i64, [c_i64, c_i32]),
+    "cdc_eval_platt_fit": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i32, c_i32, c_i32, c_d, c_d, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                   c_p, c_i64, c_p]),
+    "cdc_eval_platt_apply": (c_i32, [c_p, c_p, c_i64, c_i64, c_i32, c_p, c_p, c_p, c_i32, c_d, c_f, c_p, c_p, c_p]),
     "cdc_eval_segments": (c_i32, [c_p, c_i64, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_p]),
     "cdc_shard_bucket": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_p]),
     "cdc_shard_expand": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_p]),

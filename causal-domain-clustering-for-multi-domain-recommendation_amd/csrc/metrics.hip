@@ -1675,3 +1675,467 @@ extern "C" int cdc_eval_isotonic_apply(const float* pred, const int32_t* domain,
     CDC_LAUNCH_CHECK("eval_isotonic_apply");
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Platt / temperature / bias scaling per segment (a domain's rows, or all rows): the map p' = sigmoid(a z + b) of the logit-scale
+// score z that minimises the cross-entropy against Platt's smoothed targets, found by Newton steps with a backtracking line search,
+// all of it on the device.
+//
+//   keys    every row twice, as k_calib_keys does (key = segment << 33 | score_key << 1 | label); the same sort, the same starts
+//   prep    per sorted position the score z (float64) and the label byte; the positives of a segment are counted with INTEGER atomics,
+//           one per chunk that lies inside one segment
+//   pass    max_iter + 1 identical launches.  Workgroup c owns the sorted positions [c, c + 1) * PL_CHUNK and walks the segments that
+//           cross them; a (chunk, segment) PIECE is reduced in a fixed order (a lane's items in order, a shuffle tree, the waves in
+//           order) to PL_NV sums: at each of the four trial points theta + lambda d, lambda = 1, 1/2, 1/4, 1/8, the objective F, its
+//           gradient, its Hessian and the plain cross-entropy.  A segment of one piece is finished by its workgroup; otherwise the
+//           piece's sums go to slot (chunk + segment) — distinct for distinct pieces — and the workgroup that arrives LAST at the
+//           segment's counter (release before the ticket, acquire after it; nobody waits for anybody) adds the slots in slot order.
+//           Whoever holds the segment's sums takes the first lambda that satisfies Armijo's condition, moves there, and solves the
+//           2x2 Newton system for the next direction, or, where none does, keeps the point and divides the direction by 16.  The
+//           first pass has d = 0: it evaluates the start (1, 0).  A converged segment's workgroups skip it
+//   final   a thread per segment writes the outputs
+// The piece a position falls into, the order inside a piece and the slot order depend on the sorted keys alone: same rows in any
+// order, same bits.  Launch dimensions and the number of launches depend on (n, n_domain, max_iter) alone.
+#define PL_THREADS 256
+#define PL_ITEMS 8
+#define PL_CHUNK (PL_THREADS * PL_ITEMS)          // sorted positions per workgroup
+#define PL_NT 4                                   // trial step lengths per pass
+#define PL_NQ 7                                   // F, g_a, g_b, H_aa, H_ab, H_bb, plain BCE
+#define PL_NV (PL_NT * PL_NQ)
+#define PL_GROUPS 8                               // the last arriver adds the slots j = g, g + 8, .. in group g, then the groups in order
+#define PL_CONVERGED 1
+#define PL_EMPTY 2
+#define PL_SLOPE_FIXED 4
+#define PL_STARTED 0x100                          // internal: the start has been evaluated
+#define PL_METHOD_PLATT 0
+#define PL_METHOD_TEMPERATURE 1
+#define PL_METHOD_BIAS 2
+#define PL_ARMIJO 1e-4
+#define PL_F_SLACK 1e-12                          // relative: below it a difference of two objective sums is rounding noise
+
+struct __attribute__((aligned(16))) PlattSeg {
+    double a, b, da, db;                          // the point and the direction tried from it
+    double F, gd;                                 // the objective (a sum, not a mean) at the point, gradient . direction
+    double bce, bce0, gnorm;                      // plain BCE sums at the point and at the start, inf-norm of the MEAN gradient
+    unsigned long long P;                         // positives
+    int32_t iters, status;
+};
+
+__device__ __forceinline__ double platt_z(float x, int32_t input, double Z) {
+    const double v = (double)x;
+    const double z = input == 0 ? log(v) - log1p(-v) : v;                 // x = 0: -inf, x = 1: +inf; both clamp
+    return z < -Z ? -Z : (z > Z ? Z : z);
+}
+
+__global__ void __launch_bounds__(MET_THREADS) k_platt_keys(const float* __restrict__ score, const int16_t* __restrict__ label,
+                                                            const int32_t* __restrict__ domain, int64_t ld_domain, int64_t n,
+                                                            int32_t n_domain, int32_t input, uint64_t* __restrict__ keys,
+                                                            int32_t* __restrict__ err) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float p = score[i];
+        int32_t d = domain ? domain[i * ld_domain] : 0;
+        const int16_t y = label[i];
+        bool positive = y == 1;
+        const bool bad_p = input == 0 ? !(p >= 0.f && p <= 1.f) : p != p;
+        if (bad_p || d < 0 || d >= n_domain || (y != 0 && y != 1)) {      // counted with z = 0, label 0, the domain clamped
+            if (err) atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
+            d = d < 0 ? 0 : (d >= n_domain ? n_domain - 1 : d);
+            p = input == 0 ? 0.5f : 0.f;
+            positive = false;
+        }
+        const uint64_t low = ((uint64_t)score_key(p) << 1) | (uint64_t)positive;
+        keys[i] = ((uint64_t)(uint32_t)d << 33) | low;
+        keys[n + i] = ((uint64_t)(uint32_t)n_domain << 33) | low;
+    }
+}
+
+// pos[s] = first sorted position of segment s, pos[n_seg] = 2n; every segment's state at the start (1, 0), its arrival counter at zero
+__global__ void __launch_bounds__(MET_THREADS) k_platt_starts(const uint64_t* __restrict__ keys, int64_t n2, int32_t n_seg,
+                                                              int64_t* __restrict__ pos, PlattSeg* __restrict__ st,
+                                                              uint32_t* __restrict__ cnt) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t > n_seg) return;
+    const int64_t p0 = t == n_seg ? n2 : lower_bound_u64(keys, 0, n2, (uint64_t)t << 33);
+    pos[t] = p0;
+    if (t == n_seg) return;
+    const int64_t p1 = t + 1 == n_seg ? n2 : lower_bound_u64(keys, p0, n2, (uint64_t)(t + 1) << 33);
+    PlattSeg c;
+    c.a = 1.0; c.b = 0.0; c.da = 0.0; c.db = 0.0; c.F = 0.0; c.gd = 0.0; c.bce = 0.0; c.bce0 = 0.0; c.gnorm = 0.0;
+    c.P = 0ull; c.iters = 0; c.status = p1 == p0 ? PL_EMPTY : 0;
+    st[t] = c;
+    cnt[t] = 0u;
+}
+
+// workgroup c writes z and the label byte of the sorted positions [c, c + 1) * PL_CHUNK and counts their positives: one integer
+// atomic per workgroup where the chunk lies inside one segment (one per positive row, on the row's own segment, in the few that do not)
+__global__ void __launch_bounds__(PL_THREADS) k_platt_prep(const uint64_t* __restrict__ keys, int64_t n2, int32_t input, double Z,
+                                                           double* __restrict__ zs, uint8_t* __restrict__ lab, PlattSeg* __restrict__ st) {
+    __shared__ uint32_t s_cnt[PL_THREADS / 64];
+    const int tid = threadIdx.x;
+    const int64_t lo = (int64_t)blockIdx.x * PL_CHUNK, hi = lo + PL_CHUNK < n2 ? lo + PL_CHUNK : n2;
+    const uint64_t seg_lo = keys[lo] >> 33;
+    const bool one = seg_lo == (keys[hi - 1] >> 33);
+    uint32_t mine = 0;
+    for (int it = 0; it < PL_ITEMS; ++it) {
+        const int64_t i = lo + (int64_t)it * PL_THREADS + tid;
+        if (i >= hi) break;
+        const uint64_t key = keys[i];
+        const bool y = (key & 1ull) != 0;
+        zs[i] = platt_z(cal_score(key), input, Z);
+        lab[i] = (uint8_t)y;
+        if (y) {
+            if (one) ++mine;
+            else atomicAdd(&st[key >> 33].P, 1ull);
+        }
+    }
+    if (!one) return;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+    if ((tid & 63) == 0) s_cnt[tid >> 6] = mine;
+    __syncthreads();
+    if (tid == 0) {
+        const uint32_t all = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        if (all) atomicAdd(&st[seg_lo].P, (unsigned long long)all);
+    }
+}
+
+__device__ __forceinline__ double pl_wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// one thread, holding the sums of a whole segment at the four trial points: the line search and the next Newton direction
+__device__ void platt_advance(PlattSeg* sp, const double* tot, const double* zs, int64_t s0, int64_t s1, int32_t method, double gtol) {
+    PlattSeg c = *sp;
+    const double m = (double)(s1 - s0);
+    const bool started = (c.status & PL_STARTED) != 0;
+    int k = -1;
+    if (!started) {                                                       // d = 0: the four trial points are the start itself
+        c.status |= PL_STARTED;
+        if (method == PL_METHOD_PLATT && zs[s0] == zs[s1 - 1]) c.status |= PL_SLOPE_FIXED;     // z ascends along a segment
+        c.bce0 = tot[PL_NQ - 1];
+        k = 0;
+    } else {
+        c.iters += 1;
+        const double slack = PL_F_SLACK * fabs(c.F);
+        double lam = 1.0;
+        for (int j = 0; j < PL_NT; ++j, lam *= 0.5)
+            if (tot[j * PL_NQ] <= c.F + PL_ARMIJO * lam * c.gd + slack) { k = j; break; }
+    }
+    if (k < 0) {                                                          // no trial length was good enough: a shorter direction
+        c.da *= 0.0625; c.db *= 0.0625; c.gd *= 0.0625;
+        *sp = c;
+        return;
+    }
+    const bool free_a = method == PL_METHOD_TEMPERATURE || (method == PL_METHOD_PLATT && !(c.status & PL_SLOPE_FIXED));
+    const bool free_b = method != PL_METHOD_TEMPERATURE;
+    const double lam = k == 0 ? 1.0 : (k == 1 ? 0.5 : (k == 2 ? 0.25 : 0.125));
+    const double* q = tot + k * PL_NQ;
+    c.a = c.a + lam * c.da;                                               // the expressions of k_platt_pass
+    c.b = c.b + lam * c.db;
+    c.F = q[0];
+    c.bce = q[6];
+    const double ga = free_a ? q[1] : 0.0, gb = free_b ? q[2] : 0.0;
+    const double haa = q[3], hab = q[4], hbb = q[5];
+    c.gnorm = fmax(fabs(ga), fabs(gb)) / m;
+    c.da = c.db = c.gd = 0.0;
+    if (c.gnorm <= gtol) {
+        c.status |= PL_CONVERGED;
+    } else {
+        const double det = haa * hbb - hab * hab;
+        if (free_a && free_b && det > 1e-13 * haa * hbb) {
+            c.da = -(hbb * ga - hab * gb) / det;
+            c.db = -(haa * gb - hab * ga) / det;
+        } else {                                                          // one free parameter, or a Hessian too close to singular
+            if (free_a && haa > 0.0) c.da = -ga / haa;
+            if (free_b && hbb > 0.0) c.db = -gb / hbb;
+        }
+        c.gd = ga * c.da + gb * c.db;
+    }
+    *sp = c;
+}
+
+// st, part and cnt are written and read across workgroups inside this launch: no const, no __restrict__ (they stay off the scalar path)
+__global__ void __launch_bounds__(PL_THREADS) k_platt_pass(const double* __restrict__ zs, const uint8_t* __restrict__ lab,
+                                                           const int64_t* __restrict__ pos, int64_t n2, int32_t n_seg, int32_t method,
+                                                           double gtol, PlattSeg* st, double* part, uint32_t* cnt) {
+    __shared__ double sh[PL_GROUPS][PL_NV];
+    __shared__ double tot[PL_NV];
+    __shared__ int s_last;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t chunk = blockIdx.x;
+    const int64_t lo = chunk * PL_CHUNK, hi = lo + PL_CHUNK < n2 ? lo + PL_CHUNK : n2;
+    int32_t s;
+    {                                                                     // the largest s with pos[s] <= lo: the segment that holds lo
+        int32_t x = 0, y = n_seg - 1;
+        while (x < y) {
+            const int32_t mid = (x + y + 1) >> 1;
+            if (pos[mid] <= lo) x = mid; else y = mid - 1;
+        }
+        s = x;
+    }
+    for (; s < n_seg; ++s) {
+        const int64_t s0 = pos[s], s1 = pos[s + 1];
+        if (s0 >= hi) break;
+        const int64_t p0 = s0 > lo ? s0 : lo, p1 = s1 < hi ? s1 : hi;
+        if (p1 <= p0) continue;                                           // an empty segment
+        const PlattSeg cur = st[s];                                       // written by an earlier launch; this launch writes it only
+        if (cur.status & PL_CONVERGED) continue;                          //   after every piece of the segment has arrived
+        const bool started = (cur.status & PL_STARTED) != 0;
+        const double P = (double)cur.P, N = (double)(s1 - s0) - P;
+        const double t_pos = (P + 1.0) / (P + 2.0), t_neg = 1.0 / (N + 2.0);
+        double ta[PL_NT], tb[PL_NT], acc[PL_NT][PL_NQ];
+        {
+            double lam = 1.0;
+#pragma unroll
+            for (int k = 0; k < PL_NT; ++k, lam *= 0.5) {
+                ta[k] = cur.a + lam * cur.da;
+                tb[k] = cur.b + lam * cur.db;
+#pragma unroll
+                for (int j = 0; j < PL_NQ; ++j) acc[k][j] = 0.0;
+            }
+        }
+        int64_t i = p0 + tid;
+        double z_next = 0.0;
+        uint8_t y_next = 0;
+        if (i < p1) { z_next = zs[i]; y_next = lab[i]; }
+#pragma unroll 1
+        for (int it = 0; it < PL_ITEMS && i < p1; ++it) {                 // the next item's loads fly while this one is evaluated
+            const double z = z_next;
+            const bool y = y_next != 0;
+            i += PL_THREADS;
+            if (i < p1) { z_next = zs[i]; y_next = lab[i]; }
+            const double t = y ? t_pos : t_neg;
+#pragma unroll
+            for (int k = 0; k < PL_NT; ++k) {
+                if (k == 0 || started) {                                  // the first pass has one point, four times
+                    const double u = ta[k] * z + tb[k];
+                    const double e = exp(-fabs(u));
+                    const double sp = fmax(u, 0.0) + log1p(e);            // softplus(u)
+                    const double p = (u >= 0.0 ? 1.0 : e) / (1.0 + e);    // sigmoid(u)
+                    const double r = p - t, w = p * (1.0 - p);
+                    acc[k][0] += sp - t * u;
+                    acc[k][1] += r * z;
+                    acc[k][2] += r;
+                    acc[k][3] += w * z * z;
+                    acc[k][4] += w * z;
+                    acc[k][5] += w;
+                    acc[k][6] += y ? sp - u : sp;
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < PL_NT; ++k)
+#pragma unroll
+            for (int j = 0; j < PL_NQ; ++j) {
+                const double v = pl_wave_sum(acc[k][j]);
+                if (lane == 0) sh[wave][k * PL_NQ + j] = v;
+            }
+        __syncthreads();
+        double mine = 0.0;
+        if (tid < PL_NV) mine = ((sh[0][tid] + sh[1][tid]) + sh[2][tid]) + sh[3][tid];
+        const int64_t c0 = s0 / PL_CHUNK, pieces = (s1 - 1) / PL_CHUNK - c0 + 1;
+        bool finish = true;
+        if (pieces > 1) {
+            if (tid < PL_NV) part[(chunk + s) * PL_NV + tid] = mine;
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // every storing wave, then the barrier, then ONE release
+            __syncthreads();
+            if (tid == 0) {
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                const uint32_t ticket = __hip_atomic_fetch_add(&cnt[s], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const int last = ticket == (uint32_t)(pieces - 1);
+                if (last) {
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                }
+                s_last = last;
+            }
+            __syncthreads();
+            finish = s_last != 0;
+            if (finish) {                                                 // the slots c0 + s .. c0 + s + pieces - 1, in a fixed order
+                const int j = tid & 31, g = tid >> 5;
+                if (j < PL_NV) {
+                    double v = 0.0;
+                    for (int64_t k = g; k < pieces; k += PL_GROUPS) v += part[(c0 + s + k) * PL_NV + j];
+                    sh[g][j] = v;
+                }
+                __syncthreads();
+                if (tid < PL_NV) {
+                    mine = 0.0;
+#pragma unroll
+                    for (int g2 = 0; g2 < PL_GROUPS; ++g2) mine += sh[g2][tid];
+                }
+            }
+        }
+        if (finish) {
+            if (tid < PL_NV) tot[tid] = mine;
+            __syncthreads();
+            if (tid == 0) {
+                platt_advance(&st[s], tot, zs, s0, s1, method, gtol);
+                cnt[s] = 0u;                                              // the next pass counts from zero
+            }
+        }
+        __syncthreads();                                                  // sh, tot and s_last are free for the next segment
+    }
+}
+
+__global__ void __launch_bounds__(MET_THREADS) k_platt_final(const PlattSeg* __restrict__ st, const int64_t* __restrict__ pos, int32_t n_seg,
+                                                             double* __restrict__ a, double* __restrict__ b, double* __restrict__ loss_before,
+                                                             double* __restrict__ loss_after, double* __restrict__ grad,
+                                                             int64_t* __restrict__ seg_rows, int64_t* __restrict__ seg_positives,
+                                                             int32_t* __restrict__ iterations, int32_t* __restrict__ status) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_seg) return;
+    const PlattSeg c = st[s];
+    const int64_t m = pos[s + 1] - pos[s];
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    a[s] = c.a;
+    b[s] = c.b;
+    loss_before[s] = m > 0 ? c.bce0 / (double)m : nan;
+    loss_after[s] = m > 0 ? c.bce / (double)m : nan;
+    grad[s] = m > 0 ? c.gnorm : nan;
+    seg_rows[s] = m;
+    seg_positives[s] = (int64_t)c.P;
+    iterations[s] = c.iters;
+    status[s] = c.status & (PL_CONVERGED | PL_EMPTY | PL_SLOPE_FIXED);
+}
+
+struct PlattLayout {
+    int64_t keys_in, keys_out, lab, pos, st, cnt, part, temp, temp_bytes, total, chunks;
+};
+static void platt_fixed_layout(int64_t n, int32_t n_domain, PlattLayout* L) {
+    const int64_t n2 = 2 * n, seg = (int64_t)n_domain + 1;
+    L->chunks = cdc_ceil_div(n2, PL_CHUNK);
+    int64_t off = 0;
+    L->keys_in = off;  off += align_up(n2 * 8);                // after the sort: z per sorted position
+    L->keys_out = off; off += align_up(n2 * 8);
+    L->lab = off;      off += align_up(n2);
+    L->pos = off;      off += align_up((seg + 1) * 8);
+    L->st = off;       off += align_up(seg * (int64_t)sizeof(PlattSeg));
+    L->cnt = off;      off += align_up(seg * 4);
+    L->part = off;     off += align_up((L->chunks + seg) * PL_NV * 8);    // slot = chunk + segment < chunks + seg
+    L->temp = off;
+    L->temp_bytes = 0;
+    L->total = off;
+}
+static int platt_layout(int64_t n, int32_t n_domain, PlattLayout* L) {
+    platt_fixed_layout(n, n_domain, L);
+    size_t t_sort = 0;
+    hipError_t e = rocprim::radix_sort_keys(nullptr, t_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr, (size_t)(2 * n), 0, 64, (hipStream_t)0, false);
+    if (e != hipSuccess) { cdc_set_error("eval_platt_fit: rocprim size query failed: %s", hipGetErrorString(e)); return (int)e; }
+    L->temp_bytes = (int64_t)t_sort;
+    L->total = L->temp + align_up(L->temp_bytes);
+    return 0;
+}
+static bool platt_clip_ok(double clip) { return clip >= 1e-12 && clip <= 0.25; }
+
+extern "C" int64_t cdc_eval_platt_fit_workspace_bytes(int64_t n, int32_t n_domain) {
+    if (!iso_sizes_ok(n, n_domain)) return 0;
+    PlattLayout L;
+    if (platt_layout(n, n_domain, &L) != 0) return -1;
+    return L.total;
+}
+
+extern "C" int cdc_eval_platt_fit(const float* score, const int16_t* label, const int32_t* domain, int64_t ld_domain, int64_t n,
+                                  int32_t n_domain, int32_t method, int32_t input, double clip, double gtol, int32_t max_iter, double* a,
+                                  double* b, double* loss_before, double* loss_after, double* grad, int64_t* seg_rows,
+                                  int64_t* seg_positives, int32_t* iterations, int32_t* status, int32_t* err_flag, void* workspace,
+                                  int64_t workspace_bytes, void* stream) {
+    CDC_CHECK_ARG(score && label && a && b && loss_before && loss_after && grad && seg_rows && seg_positives && iterations && status && workspace,
+                  CDC_E_BADARG, "eval_platt_fit: null pointer");
+    CDC_CHECK_ARG(n > 0 && n_domain > 0 && n_domain < (1 << 20) && ld_domain >= 0, CDC_E_BADARG,
+                  "eval_platt_fit: bad sizes n=%ld n_domain=%d ld_domain=%ld", (long)n, n_domain, (long)ld_domain);
+    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_platt_fit: n_domain=%d needs the domain column", n_domain);
+    CDC_CHECK_ARG(method >= PL_METHOD_PLATT && method <= PL_METHOD_BIAS, CDC_E_BADARG, "eval_platt_fit: unknown method %d", method);
+    CDC_CHECK_ARG(input == 0 || input == 1, CDC_E_BADARG, "eval_platt_fit: unknown input %d (0: probabilities, 1: logits)", input);
+    CDC_CHECK_ARG(platt_clip_ok(clip), CDC_E_BADARG, "eval_platt_fit: clip=%g outside [1e-12, 0.25]", clip);
+    CDC_CHECK_ARG(gtol > 0.0, CDC_E_BADARG, "eval_platt_fit: gtol=%g must be positive", gtol);
+    CDC_CHECK_ARG(max_iter >= 1 && max_iter <= 1024, CDC_E_BADARG, "eval_platt_fit: max_iter=%d outside [1, 1024]", max_iter);
+    CDC_CHECK_ARG(n < (1ll << 31), CDC_E_TOOBIG, "eval_platt_fit: n=%ld exceeds 2^31 rows", (long)n);
+    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_platt_fit: workspace must be 256-byte aligned");
+    PlattLayout L;
+    platt_fixed_layout(n, n_domain, &L);
+    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_platt_fit: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
+    int rc = platt_layout(n, n_domain, &L);
+    if (rc != 0) return rc;
+    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_platt_fit: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
+    char* base = (char*)workspace;
+    uint64_t* keys_in = (uint64_t*)(base + L.keys_in);
+    uint64_t* keys_out = (uint64_t*)(base + L.keys_out);
+    double* zs = (double*)(base + L.keys_in);                             // the unsorted keys are done with after the sort
+    uint8_t* lab = (uint8_t*)(base + L.lab);
+    int64_t* pos = (int64_t*)(base + L.pos);
+    PlattSeg* st = (PlattSeg*)(base + L.st);
+    double* part = (double*)(base + L.part);
+    uint32_t* cnt = (uint32_t*)(base + L.cnt);
+    hipStream_t sm = (hipStream_t)stream;
+    const int64_t n2 = 2 * n;
+    const int seg = n_domain + 1;
+    const double Z = log((1.0 - clip) / clip);
+    const int blocks = (int)std::min<int64_t>(cdc_ceil_div(n, MET_THREADS), 4096);
+    hipLaunchKernelGGL(k_platt_keys, dim3(blocks), dim3(MET_THREADS), 0, sm, score, label, domain, ld_domain, n, n_domain, input, keys_in, err_flag);
+    CDC_LAUNCH_CHECK("eval_platt_fit(keys)");
+    int end_bit = 34;
+    while (end_bit < 64 && ((uint64_t)n_domain >> (end_bit - 33)) != 0) ++end_bit;
+    size_t temp_bytes = (size_t)L.temp_bytes;
+    hipError_t e = rocprim::radix_sort_keys(base + L.temp, temp_bytes, (const uint64_t*)keys_in, keys_out, (size_t)n2, 0, end_bit, sm, false);
+    if (e != hipSuccess) { cdc_set_error("eval_platt_fit: radix sort failed: %s", hipGetErrorString(e)); return (int)e; }
+    hipLaunchKernelGGL(k_platt_starts, dim3((int)cdc_ceil_div(seg + 1, MET_THREADS)), dim3(MET_THREADS), 0, sm, (const uint64_t*)keys_out, n2, seg, pos, st, cnt);
+    CDC_LAUNCH_CHECK("eval_platt_fit(starts)");
+    hipLaunchKernelGGL(k_platt_prep, dim3((unsigned)L.chunks), dim3(PL_THREADS), 0, sm, (const uint64_t*)keys_out, n2, input, Z, zs, lab, st);
+    CDC_LAUNCH_CHECK("eval_platt_fit(prep)");
+    for (int it = 0; it <= max_iter; ++it) {                              // the start, then max_iter Newton steps
+        hipLaunchKernelGGL(k_platt_pass, dim3((unsigned)L.chunks), dim3(PL_THREADS), 0, sm, (const double*)zs, (const uint8_t*)lab,
+                           (const int64_t*)pos, n2, seg, method, gtol, st, part, cnt);
+        CDC_LAUNCH_CHECK("eval_platt_fit(pass)");
+    }
+    hipLaunchKernelGGL(k_platt_final, dim3((int)cdc_ceil_div(seg, MET_THREADS)), dim3(MET_THREADS), 0, sm, (const PlattSeg*)st, (const int64_t*)pos, seg,
+                       a, b, loss_before, loss_after, grad, seg_rows, seg_positives, iterations, status);
+    CDC_LAUNCH_CHECK("eval_platt_fit(final)");
+    return 0;
+}
+
+// a thread per row: out = sigmoid(a[s] z + b[s]) with s = seg_of_domain[the row's domain], float64 operations in this order, unfused
+__global__ void __launch_bounds__(MET_THREADS) k_platt_apply(const float* __restrict__ score, const int32_t* __restrict__ domain,
+                                                             int64_t ld_domain, int64_t n, int32_t n_domain,
+                                                             const int32_t* __restrict__ seg_of_domain, const double* __restrict__ a,
+                                                             const double* __restrict__ b, int32_t input, double Z, float eps,
+                                                             float* __restrict__ out, int32_t* __restrict__ err) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float x = score[i];
+    const int32_t d = domain ? domain[i * ld_domain] : 0;
+    int32_t s = -1;
+    if ((input == 0 ? (x >= 0.f && x <= 1.f) : x == x) && d >= 0 && d < n_domain) s = seg_of_domain[d];
+    if (s < 0 || s > n_domain) {                                          // a NaN score, a probability outside [0, 1], a domain or a segment outside range
+        if (err) atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
+        out[i] = __uint_as_float(0x7fc00000u);
+        return;
+    }
+    const double u = __dadd_rn(__dmul_rn(a[s], platt_z(x, input, Z)), b[s]);
+    float o = (float)(1.0 / (1.0 + exp(-u)));
+    if (eps > 0.f) {
+        const float top = __fsub_rn(1.0f, eps);
+        o = o < eps ? eps : (o > top ? top : o);
+    }
+    out[i] = o;
+}
+
+extern "C" int cdc_eval_platt_apply(const float* score, const int32_t* domain, int64_t ld_domain, int64_t n, int32_t n_domain,
+                                    const int32_t* seg_of_domain, const double* a, const double* b, int32_t input, double clip, float eps,
+                                    float* out, int32_t* err_flag, void* stream) {
+    CDC_CHECK_ARG(score && seg_of_domain && a && b && out, CDC_E_BADARG, "eval_platt_apply: null pointer");
+    CDC_CHECK_ARG(n > 0 && n_domain > 0 && n_domain < (1 << 20) && ld_domain >= 0, CDC_E_BADARG,
+                  "eval_platt_apply: bad sizes n=%ld n_domain=%d ld_domain=%ld", (long)n, n_domain, (long)ld_domain);
+    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_platt_apply: n_domain=%d needs the domain column", n_domain);
+    CDC_CHECK_ARG(input == 0 || input == 1, CDC_E_BADARG, "eval_platt_apply: unknown input %d (0: probabilities, 1: logits)", input);
+    CDC_CHECK_ARG(platt_clip_ok(clip), CDC_E_BADARG, "eval_platt_apply: clip=%g outside [1e-12, 0.25]", clip);
+    CDC_CHECK_ARG(eps >= 0.f && eps <= 0.5f, CDC_E_BADARG, "eval_platt_apply: eps=%g outside [0, 0.5]", (double)eps);
+    CDC_CHECK_ARG(n < (1ll << 31), CDC_E_TOOBIG, "eval_platt_apply: n=%ld exceeds 2^31 rows", (long)n);
+    hipLaunchKernelGGL(k_platt_apply, dim3((unsigned)cdc_ceil_div(n, MET_THREADS)), dim3(MET_THREADS), 0, (hipStream_t)stream, score, domain,
+                       ld_domain, n, n_domain, seg_of_domain, a, b, input, log((1.0 - clip) / clip), eps, out, err_flag);
+    CDC_LAUNCH_CHECK("eval_platt_apply");
+    return 0;
+}

@@ -22,7 +22,10 @@ equal-width and equal-mass bins (`cdc_eval_calibration`); `Evaluator(calibration
 `eval_isotonic_fit` / `eval_isotonic_apply` repair what `eval_calibration` measures: a monotone map per domain (isotonic regression of the
 labels on the score, fitted on the validation split: `cdc_eval_isotonic_fit`) that is applied to the predictions of the test split
 (`cdc_eval_isotonic_apply`); `Recalibration` holds a fitted map, `Evaluator.fit_recalibration` fits one and
-`Evaluator(recalibration=...)` reports the recalibrated model.
+`Evaluator(recalibration=...)` reports the recalibrated model.  `eval_platt_fit` / `eval_platt_apply` / `PlattRecalibration` are the
+parametric half: sigmoid(a z + b) of the logit-scale score per domain — Platt scaling, temperature scaling (a alone) and the bias
+shift (b alone) that undoes negative down-sampling — fitted by Newton steps on the device (`cdc_eval_platt_fit`), for domains too
+small for an isotonic map.
 
 `eval_segments` serves CDC's matrix update (run.py:549-558) instead: the metric of every contiguous row segment of ONE forward's
 raw output, each segment scored by its own tower column (`cdc_eval_segments`; probe.py lays the domains' batches out that way).
@@ -258,8 +261,9 @@ def eval_calibration(pred, label, domain=None, n_domain=1, n_bins=10):
     f64; pred_min, pred_max f32) of shape [n_domain + 1, n_bins]; an empty bin has count 0 and NaN in the floating-point fields.
     No host synchronisation; the error word (1 + a row with a NaN prediction, a prediction outside [0, 1], a label outside {0, 1} or
     a domain outside range) is kept as `eval_calibration.last_err`.
-    A recalibration map is fitted by `eval_isotonic_fit` / `Recalibration` (isotonic regression).  Not offered: selection or early
-    stopping by a calibration figure in `Runner`, calibration deltas in `Evaluator.compare`, Platt scaling."""
+    A recalibration map is fitted by `eval_isotonic_fit` / `Recalibration` (isotonic regression) or `eval_platt_fit` /
+    `PlattRecalibration` (Platt, temperature, bias scaling).  Not offered: selection or early stopping by a calibration figure in
+    `Runner`, calibration deltas in `Evaluator.compare`."""
     lib = L.load()
     n_domain, n_bins = int(n_domain), int(n_bins)
     if not 1 <= n_bins <= MAX_CALIBRATION_BINS:
@@ -355,7 +359,8 @@ def eval_isotonic_apply(pred, fit_or_map, domain=None, n_domain=1, seg_of_domain
     `Recalibration`'s own table) — constant on a block, linear between two blocks, the first / last value outside; float64
     arithmetic, the result float32, clamped to [eps, 1 - eps] when eps > 0.  Returns float32 [n] on the device.  A NaN score, a domain
     outside range or a segment without blocks gives NaN and sets the error word (1 + the row), kept as
-    `eval_isotonic_apply.last_err`.  No host synchronisation.  Not offered: a "step" interpolation, Platt scaling."""
+    `eval_isotonic_apply.last_err`.  No host synchronisation.  Not offered: a "step" interpolation (the parametric maps are
+    `eval_platt_fit` / `eval_platt_apply`)."""
     lib = L.load()
     n_domain = int(n_domain)
     if not pred.is_cuda:
@@ -452,6 +457,179 @@ class Recalibration:
         return IsotonicBlocks(*(getattr(self, k)[b0:b1].cpu().numpy() for k in IsotonicBlocks._fields))
 
 
+PlattFit = collections.namedtuple("PlattFit", "a b rows positives loss_before loss_after grad iterations status")
+PLATT_METHODS = {"platt": 0, "temperature": 1, "bias": 2}
+PLATT_INPUTS = {"prob": 0, "logit": 1}
+PLATT_CONVERGED, PLATT_EMPTY, PLATT_SLOPE_FIXED = 1, 2, 4
+
+
+def _platt_args(method, input, clip):
+    if method is not None and method not in PLATT_METHODS:
+        raise ValueError(f"method={method!r} is none of {sorted(PLATT_METHODS)}")
+    if input not in PLATT_INPUTS:
+        raise ValueError(f"input={input!r} is none of {sorted(PLATT_INPUTS)}")
+    if not 1e-12 <= float(clip) <= 0.25:
+        raise ValueError(f"clip={clip} must lie in [1e-12, 0.25]")
+
+
+def eval_platt_fit(pred, label, domain=None, n_domain=1, method="platt", input="prob", clip=1e-7, gtol=1e-10, max_iter=32):
+    """Platt scaling per domain and over all rows: the map sigmoid(a z + b) of the logit-scale score z that minimises the
+    cross-entropy against Platt's smoothed targets (P + 1) / (P + 2) and 1 / (N + 2); inputs as `eval_metrics`.  input "prob":
+    pred in [0, 1], z = log(p) - log1p(-p); "logit": z = pred; both clamped to +-log((1 - clip) / clip).  method "platt": a and b;
+    "temperature": a alone (b = 0); "bias": b alone (a = 1) — the exact repair of negative down-sampling.  Newton steps with a
+    backtracking line search from (1, 0) on the device, until the mean gradient's inf-norm is <= gtol or max_iter steps are spent.
+    Returns the namedtuple `PlattFit` of device tensors with n_domain + 1 entries (domains, then ALL rows): a, b (f64), rows,
+    positives (i64), loss_before, loss_after (the plain mean BCE of sigmoid(z) and of the map), grad (f64), iterations, status (i32:
+    PLATT_CONVERGED | PLATT_EMPTY | PLATT_SLOPE_FIXED — "platt" on a segment with a single z fits b alone).  The same rows in any
+    order give the same bits.  No host synchronisation; the error word (1 + a row with a NaN score, a probability outside [0, 1], a
+    label outside {0, 1} or a domain outside range; such a row counts with z = 0 and label 0) is kept as `eval_platt_fit.last_err`.
+    Not offered: beta calibration, vector or matrix scaling."""
+    lib = L.load()
+    n_domain, max_iter = int(n_domain), int(max_iter)
+    if not pred.is_cuda:
+        raise L.HipExtensionError("eval_platt_fit needs device tensors; there is no CPU fallback")
+    _platt_args(method, input, clip)
+    if not float(gtol) > 0.0:
+        raise ValueError(f"gtol={gtol} must be positive")
+    if not 1 <= max_iter <= 1024:
+        raise ValueError(f"max_iter={max_iter} must lie in [1, 1024]")
+    pred = pred.reshape(-1).to(torch.float32).contiguous()
+    label = label.reshape(-1).to(torch.int16).contiguous()
+    n = pred.numel()
+    if label.numel() != n:
+        raise ValueError(f"{n} predictions but {label.numel()} labels")
+    domain, ld = _iso_domain(domain, n, n_domain)
+    dev = pred.device
+    seg = n_domain + 1
+    nbytes = lib.cdc_eval_platt_fit_workspace_bytes(n, n_domain)
+    if nbytes <= 0:
+        raise RuntimeError(f"cdc_eval_platt_fit_workspace_bytes refused n={n}, n_domain={n_domain}")
+    f64 = torch.empty((5, seg), dtype=torch.float64, device=dev)
+    i64 = torch.empty((2, seg), dtype=torch.int64, device=dev)
+    i32 = torch.empty((2, seg), dtype=torch.int32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    L.launch("cdc_eval_platt_fit", lib.cdc_eval_platt_fit,
+             (pred.data_ptr(), label.data_ptr(), None if domain is None else domain.data_ptr(), ld, n, n_domain, PLATT_METHODS[method],
+              PLATT_INPUTS[input], float(clip), float(gtol), max_iter, f64[0].data_ptr(), f64[1].data_ptr(), f64[2].data_ptr(),
+              f64[3].data_ptr(), f64[4].data_ptr(), i64[0].data_ptr(), i64[1].data_ptr(), i32[0].data_ptr(), i32[1].data_ptr(),
+              err.data_ptr(), ws.data_ptr(), nbytes), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    eval_platt_fit.last_err = err
+    return PlattFit(f64[0], f64[1], i64[0], i64[1], f64[2], f64[3], f64[4], i32[0], i32[1])
+
+
+def eval_platt_apply(pred, fit_or_map, domain=None, n_domain=1, seg_of_domain=None, input="prob", clip=1e-7, eps=0.0):
+    """The map of `fit_or_map` (a `PlattFit` or a `PlattRecalibration`) at the scores pred f32 [n]: a row of domain d gets
+    sigmoid(a[s] z + b[s]) with s = seg_of_domain[d] (int32 [n_domain], entries in [0, n_domain]; None: the identity, or the
+    `PlattRecalibration`'s own table) and z as in `eval_platt_fit` — give the fit's `input` and `clip`; float64 arithmetic, the result
+    float32, clamped to [eps, 1 - eps] when eps > 0.  Returns float32 [n] on the device.  A NaN score, a probability outside [0, 1]
+    or a domain outside range gives NaN and sets the error word (1 + the row), kept as `eval_platt_apply.last_err`.  No host
+    synchronisation."""
+    lib = L.load()
+    n_domain = int(n_domain)
+    if not pred.is_cuda:
+        raise L.HipExtensionError("eval_platt_apply needs device tensors; there is no CPU fallback")
+    _platt_args(None, input, clip)
+    pred = pred.reshape(-1).to(torch.float32).contiguous()
+    n = pred.numel()
+    domain, ld = _iso_domain(domain, n, n_domain)
+    dev = pred.device
+    m = fit_or_map
+    if m.a.numel() != n_domain + 1:
+        raise ValueError(f"the map holds {m.a.numel() - 1} domains, not {n_domain}")
+    if seg_of_domain is None:
+        seg_of_domain = getattr(m, "seg_of_domain", None)
+    if seg_of_domain is None:
+        seg_of_domain = torch.arange(n_domain, dtype=torch.int32, device=dev)
+    seg_of_domain = torch.as_tensor(seg_of_domain).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    if seg_of_domain.numel() != n_domain:
+        raise ValueError(f"seg_of_domain holds {seg_of_domain.numel()} entries for {n_domain} domains")
+    if not 0.0 <= float(eps) <= 0.5:
+        raise ValueError(f"eps={eps} must lie in [0, 0.5]")
+    a = m.a.to(device=dev, dtype=torch.float64).contiguous()
+    b = m.b.to(device=dev, dtype=torch.float64).contiguous()
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    L.launch("cdc_eval_platt_apply", lib.cdc_eval_platt_apply,
+             (pred.data_ptr(), None if domain is None else domain.data_ptr(), ld, n, n_domain, seg_of_domain.data_ptr(), a.data_ptr(),
+              b.data_ptr(), PLATT_INPUTS[input], float(clip), float(eps), out.data_ptr(), err.data_ptr()),
+             C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    eval_platt_apply.last_err = err
+    return out
+
+
+class PlattRecalibration:
+    """A fitted per-domain map sigmoid(a z + b) (`eval_platt_fit`) and `seg_of_domain`, the segment every domain is sent through —
+    its own, or "all" (index n_domain) for the domains of `fallback_domains`.  The surface `Evaluator` uses is `Recalibration`'s."""
+    _TENSORS = ("a", "b", "rows", "positives", "loss_before", "loss_after", "grad", "iterations", "status", "seg_of_domain")
+
+    def __init__(self):
+        self.n_domain = 0
+        self.fallback_domains = []
+        self.method, self.input, self.clip = "platt", "prob", 1e-7
+        for k in self._TENSORS:
+            setattr(self, k, None)
+
+    @classmethod
+    def fit(cls, pred, label, domain=None, n_domain=1, method="platt", input="prob", clip=1e-7, gtol=1e-10, max_iter=32, min_rows=0,
+            need_both_classes=True, need_increasing=True):
+        """Fits on (pred, label, domain) — the validation split's RAW predictions.  A domain without fit rows, with fewer than
+        min_rows, (need_both_classes) with a single class, whose fit did not converge, or (need_increasing) with a <= 0 is sent
+        through the map of all rows and listed in `fallback_domains`.  One host synchronisation: a, rows, positives, status and the
+        error word are read once.  A bad row (NaN score, probability outside [0, 1], label outside {0, 1}, domain outside range)
+        raises ValueError naming it."""
+        n_domain = int(n_domain)
+        f = eval_platt_fit(pred, label, domain, n_domain, method, input, clip, gtol, max_iter)
+        seg = n_domain + 1
+        host = torch.cat([f.a, f.rows.to(torch.float64), f.positives.to(torch.float64), f.status.to(torch.float64),
+                          eval_platt_fit.last_err.to(torch.float64)]).cpu().tolist()                  # the one sync; counts < 2^53
+        a, rows, pos, status, bad = host[:seg], host[seg:2 * seg], host[2 * seg:3 * seg], host[3 * seg:4 * seg], int(host[-1])
+        if bad:
+            raise ValueError(f"recalibration row {bad - 1}: NaN score, probability outside [0, 1], label outside {{0,1}} or domain "
+                             f"outside [0, {n_domain})")
+        r = cls()
+        r.n_domain, r.method, r.input, r.clip = n_domain, method, input, float(clip)
+        for k in PlattFit._fields:
+            setattr(r, k, getattr(f, k))
+        r.fallback_domains = [d for d in range(n_domain)
+                              if rows[d] == 0 or rows[d] < min_rows or (need_both_classes and (pos[d] == 0 or pos[d] == rows[d]))
+                              or not int(status[d]) & PLATT_CONVERGED or (need_increasing and not a[d] > 0.0)]
+        back = set(r.fallback_domains)
+        r.seg_of_domain = torch.tensor([n_domain if d in back else d for d in range(n_domain)], dtype=torch.int32, device=f.a.device)
+        return r
+
+    def apply(self, pred, domain=None, eps=0.0):
+        """-> float32 [n] on the device: pred through the map of every row's domain (domain: as `eval_metrics`; None for a map over
+        one domain)."""
+        return eval_platt_apply(pred, self, domain, self.n_domain, self.seg_of_domain, self.input, self.clip, eps)
+
+    def params(self, segment):
+        """Host (a, b, status) of a domain's own fit, or of "all" (also: index n_domain)."""
+        s = self.n_domain if segment == "all" else int(segment)
+        if not 0 <= s <= self.n_domain:
+            raise ValueError(f"segment {segment!r} outside [0, {self.n_domain}] / 'all'")
+        return float(self.a[s].item()), float(self.b[s].item()), int(self.status[s].item())
+
+    def state_dict(self):
+        sd = {k: getattr(self, k) for k in self._TENSORS}
+        sd["fallback_domains"] = torch.tensor(self.fallback_domains, dtype=torch.int64)
+        sd["method"] = torch.tensor(PLATT_METHODS[self.method], dtype=torch.int64)
+        sd["input"] = torch.tensor(PLATT_INPUTS[self.input], dtype=torch.int64)
+        sd["clip"] = torch.tensor(self.clip, dtype=torch.float64)
+        return sd
+
+    def load_state_dict(self, sd, device=None):
+        for k in self._TENSORS:
+            t = sd[k]
+            setattr(self, k, t.to(device) if device is not None else t)
+        self.n_domain = self.seg_of_domain.numel()
+        self.fallback_domains = [int(d) for d in sd["fallback_domains"].tolist()]
+        self.method = {v: k for k, v in PLATT_METHODS.items()}[int(sd["method"])]
+        self.input = {v: k for k, v in PLATT_INPUTS.items()}[int(sd["input"])]
+        self.clip = float(sd["clip"])
+        return self
+
+
 def _se(var):
     return math.sqrt(var) if var == var else math.nan
 
@@ -485,12 +663,12 @@ class Evaluator:
             domain_ece / domain_ece_quantile {d: value} and mean_pcoc / mean_brier / mean_ece / mean_ece_quantile, weighted like
             mean_auc; `calibration_table` returns the reliability tables.  Selection or early stopping by a calibration figure
             and calibration deltas in `compare` are not offered.
-    recalibration: a `Recalibration` (from `fit_recalibration` on the validation loader, or `Recalibration.fit`): every prediction goes
-            through its isotonic map, clamped to [recalibration_eps, 1 - recalibration_eps] when that is positive, before anything is
+    recalibration: a `Recalibration` or a `PlattRecalibration` (from `fit_recalibration` on the validation loader, or the class's
+            `fit`): every prediction goes through its map, clamped to [recalibration_eps, 1 - recalibration_eps] when that is positive, before anything is
             computed, so test(), calibration_table(), predict() and compare() report the recalibrated model under the same keys; raw
             against recalibrated on one checkpoint: Evaluator(model, ..).compare(Evaluator(model, .., recalibration=r), loader).  A map
-            over more than one domain needs domain_idx.  Platt scaling, a "step" interpolation, selection by a calibration figure in
-            `Runner` and calibration deltas in `compare` are not offered.
+            over more than one domain needs domain_idx.  Beta calibration, vector or matrix scaling, a "step" interpolation,
+            selection by a calibration figure in `Runner` and calibration deltas in `compare` are not offered.
     precision: None, or "bf16" / "f32": the model is switched to it for the scoring pass and switched back afterwards, so two
             evaluators around ONE module can score it under two precisions (`compare`)."""
 
@@ -528,14 +706,18 @@ class Evaluator:
         """-> (pred f32 [n], label int16 [n], domain int32 [n] or None), all on the device."""
         return self._score(data_loader)[:3]
 
-    def fit_recalibration(self, data_loader, **kw):
-        """One scoring pass over `data_loader` (the validation split) -> `Recalibration`: the isotonic map of every domain of the
-        domain column (of all rows without one) fitted on the model's RAW predictions; kw: `Recalibration.fit`'s min_rows,
-        need_both_classes."""
+    def fit_recalibration(self, data_loader, method="isotonic", **kw):
+        """One scoring pass over `data_loader` (the validation split) -> the map of every domain of the domain column (of all rows
+        without one) fitted on the model's RAW predictions.  method "isotonic": a `Recalibration` (kw: `Recalibration.fit`'s
+        min_rows, need_both_classes); "platt", "temperature", "bias": a `PlattRecalibration` (kw: `PlattRecalibration.fit`'s input,
+        clip, gtol, max_iter, min_rows, need_both_classes, need_increasing)."""
+        if method != "isotonic" and method not in PLATT_METHODS:
+            raise ValueError(f"method={method!r} is none of {['isotonic'] + sorted(PLATT_METHODS)}")
         pred, label, domain, _ = self._score(data_loader, raw=True)
-        if domain is None:
-            return Recalibration.fit(pred, label, None, 1, **kw)
-        return Recalibration.fit(pred, label, domain, self.n_domain, **kw)
+        n_domain = 1 if domain is None else self.n_domain
+        if method == "isotonic":
+            return Recalibration.fit(pred, label, domain, n_domain, **kw)
+        return PlattRecalibration.fit(pred, label, domain, n_domain, method=method, **kw)
 
     def _score(self, data_loader, raw=False):
         """predict() and the user column: -> (pred, label, domain or None, user int32 [n] or None); with a recalibration map (and not

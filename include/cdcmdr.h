@@ -1260,6 +1260,59 @@ int cdc_eval_isotonic_apply(const float* pred, const int32_t* domain, int64_t ld
                             const int32_t* seg_of_domain, const int64_t* start, const float* x_lo, const float* x_hi,
                             const double* value, float eps, float* out, int32_t* err_flag, void* stream);
 
+/* Platt, temperature and bias scaling: per segment (domain 0..n_domain-1, then ALL rows) the map sigmoid(a z + b) of the
+ * logit-scale score z that minimises the cross-entropy against Platt's (1999) smoothed targets.  score, label, domain, ld_domain,
+ * n_domain as for cdc_eval_metrics.
+ *   z       Z = log((1 - clip) / clip), clip in [1e-12, 0.25].  input CDC_PLATT_INPUT_PROB: z = clamp(log(p) - log1p(-p), -Z, Z) in
+ *           float64 (p = 0 gives -Z, p = 1 gives +Z; a p outside [0, 1] is a bad row); CDC_PLATT_INPUT_LOGIT: z = clamp((double)score,
+ *           -Z, Z), infinities clamp.  A NaN score is a bad row in both.
+ *   fit     a segment of m rows, P positives, N = m - P: target t = (P + 1) / (P + 2) of a positive row, 1 / (N + 2) of a negative one;
+ *           F(a, b) = sum t softplus(-u) + (1 - t) softplus(u), u = a z + b.  method CDC_PLATT_PLATT: a and b free;
+ *           CDC_PLATT_TEMPERATURE: b = 0; CDC_PLATT_BIAS: a = 1.  a is not constrained and may come out <= 0 on tiny segments.
+ *           Newton steps from (1, 0), each tried at the lengths 1, 1/2, 1/4, 1/8 (Armijo, c = 1e-4; where none passes the direction
+ *           is divided by 16 for the next step), until the inf-norm of the MEAN gradient over the free parameters is <= gtol
+ *           or max_iter steps (in [1, 1024]) are spent.
+ *   outputs [n_domain+1] each: a, b; loss_before / loss_after = the plain mean BCE (0/1 labels) of sigmoid(z) / sigmoid(a z + b);
+ *           grad = the inf-norm of the mean gradient of F at (a, b); seg_rows, seg_positives; iterations = the Newton steps tried;
+ *           status = CDC_PLATT_CONVERGED | CDC_PLATT_EMPTY (no rows: a = 1, b = 0, NaN losses and grad) | CDC_PLATT_SLOPE_FIXED
+ *           (CDC_PLATT_PLATT on a segment whose z is a single value: the Hessian is singular, a is held at 1 and b is fitted).
+ *   err_flag (optional): 1 + the largest index of a bad row (a NaN score, a probability outside [0, 1], a label other than 0/1, a
+ *           domain outside [0, n_domain)); such a row is counted with z = 0, label 0 and the domain clamped into range.
+ * Every sum is taken over the sorted rows in a fixed order (no floating-point atomics): the same rows in any order, with a
+ * contiguous or a strided domain column, give the same bits in every output.
+ * Limits: null pointers, n <= 0, n_domain outside [1, 2^20), n_domain > 1 without the domain column, an unknown method or input, clip
+ * outside [1e-12, 0.25], gtol <= 0, max_iter outside [1, 1024], a workspace too small or not 256-byte aligned: CDC_E_BADARG;
+ * n >= 2^31: CDC_E_TOOBIG — all before anything is launched.  Stream-ordered: no allocation, no synchronisation, no state kept; the
+ * launches and their dimensions depend on (n, n_domain, max_iter) alone (one sort, four launches and max_iter + 1 pass launches of
+ * ceil(2n / 2048) workgroups; convergence is a flag per segment on the device, the workgroups of a converged segment return at
+ * once; no workgroup waits for another), so the call can be captured in a graph.
+ * workspace: cdc_eval_platt_fit_workspace_bytes(n, n_domain) bytes, 256-byte aligned; 0 for sizes the call refuses. */
+#define CDC_PLATT_PLATT 0
+#define CDC_PLATT_TEMPERATURE 1
+#define CDC_PLATT_BIAS 2
+#define CDC_PLATT_INPUT_PROB 0
+#define CDC_PLATT_INPUT_LOGIT 1
+#define CDC_PLATT_CONVERGED 1
+#define CDC_PLATT_EMPTY 2
+#define CDC_PLATT_SLOPE_FIXED 4
+int64_t cdc_eval_platt_fit_workspace_bytes(int64_t n, int32_t n_domain);
+int cdc_eval_platt_fit(const float* score, const int16_t* label, const int32_t* domain, int64_t ld_domain, int64_t n,
+                       int32_t n_domain, int32_t method, int32_t input, double clip, double gtol, int32_t max_iter, double* a,
+                       double* b, double* loss_before, double* loss_after, double* grad, int64_t* seg_rows, int64_t* seg_positives,
+                       int32_t* iterations, int32_t* status, int32_t* err_flag, void* workspace, int64_t workspace_bytes,
+                       void* stream);
+
+/* The map of a fit at n scores: out[i] = (float)(1 / (1 + exp(-(a[s] z + b[s])))) with s = seg_of_domain[domain[i]] (device int32
+ * [n_domain], entries in [0, n_domain]: a domain may be sent to another's map, or to ALL) and z as above; float64 operations in
+ * this order, unfused; then clamped to [eps, 1.0f - eps] in float32 when eps > 0.  A NaN score, a probability outside [0, 1], a
+ * domain outside [0, n_domain) or a segment outside [0, n_domain] writes NaN and sets err_flag (optional) to 1 + the largest such
+ * row.  domain == NULL needs n_domain == 1.  Null pointers, n <= 0, n_domain outside [1, 2^20), an unknown input, clip outside
+ * [1e-12, 0.25], eps outside [0, 0.5]: CDC_E_BADARG; n >= 2^31: CDC_E_TOOBIG.  One launch, a thread per row; stream-ordered, no
+ * allocation, no synchronisation. */
+int cdc_eval_platt_apply(const float* score, const int32_t* domain, int64_t ld_domain, int64_t n, int32_t n_domain,
+                         const int32_t* seg_of_domain, const double* a, const double* b, int32_t input, double clip, float eps,
+                         float* out, int32_t* err_flag, void* stream);
+
 /* Per-segment BCE of CDC's probe evaluation (run.py:549-558): one batch of every domain went through ONE eval
  * forward; segment s is the rows [seg_start[s], seg_start[s+1]) of probs [rows, n_cols] (row stride ld_probs: all towers'
  * probabilities) and is scored by column seg_col[s] (NULL = column 0).  seg_start [n_seg+1] is non-decreasing; rows at or past
