@@ -388,8 +388,8 @@ static void gauc_fixed_layout(int64_t n, int32_t n_domain, GaucLayout* L) {
     L->temp_bytes = 0;
     L->total = off;
 }
-static int gauc_layout(int64_t n, int32_t n_domain, GaucLayout* L) {
-    gauc_fixed_layout(n, n_domain, L);
+// rocPRIM's temporary storage for the sort and the two scans of 2n keys: the three run one after the other
+static int gauc_temp_bytes(int64_t n, const char* what, int64_t* bytes) {
     const size_t n2 = (size_t)(2 * n);
     size_t t_sort = 0, t_scan = 0, t_share = 0;
     hipError_t e = rocprim::radix_sort_pairs(nullptr, t_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint8_t*)nullptr,
@@ -400,8 +400,14 @@ static int gauc_layout(int64_t n, int32_t n_domain, GaucLayout* L) {
     if (e == hipSuccess)
         e = rocprim::inclusive_scan(nullptr, t_share, GaucShareIt(rocprim::counting_iterator<uint32_t>(0), GaucShareIn{nullptr, nullptr}),
                                     (unsigned long long*)nullptr, n2, rocprim::plus<unsigned long long>(), (hipStream_t)0, false);
-    if (e != hipSuccess) { cdc_set_error("eval_gauc: rocprim size query failed: %s", hipGetErrorString(e)); return (int)e; }
-    L->temp_bytes = (int64_t)std::max(t_sort, std::max(t_scan, t_share));     // the three run one after the other
+    if (e != hipSuccess) { cdc_set_error("%s: rocprim size query failed: %s", what, hipGetErrorString(e)); return (int)e; }
+    *bytes = (int64_t)std::max(t_sort, std::max(t_scan, t_share));
+    return 0;
+}
+static int gauc_layout(int64_t n, int32_t n_domain, GaucLayout* L) {
+    gauc_fixed_layout(n, n_domain, L);
+    const int rc = gauc_temp_bytes(n, "eval_gauc", &L->temp_bytes);
+    if (rc != 0) return rc;
     L->total = L->temp + align_up(L->temp_bytes);
     return 0;
 }
@@ -416,6 +422,44 @@ extern "C" int64_t cdc_eval_gauc_workspace_bytes(int64_t n, int32_t n_domain, in
     GaucLayout L;
     if (gauc_layout(n, n_domain, &L) != 0) return -1;
     return L.total;
+}
+
+// keys, sort, the two scans and the segment bounds of one score vector: leaves keys_out, sc and start describing its order and W, the
+// running sum of scan 2 (the caller says where: by default over the unsorted keys, dead once the sort has run)
+static int gauc_order(const float* pred, const int16_t* label, const int32_t* user, int64_t ld_user, int64_t n_user, const int32_t* domain,
+                      int64_t ld_domain, int32_t n_domain, int64_t n, int32_t* err_flag, char* base, const GaucLayout& L,
+                      unsigned long long* W, const char* what, hipStream_t st) {
+    uint64_t* keys_in = (uint64_t*)(base + L.keys_in);
+    uint64_t* keys_out = (uint64_t*)(base + L.keys_out);
+    uint8_t* vals_in = (uint8_t*)(base + L.vals_in);
+    uint8_t* vals_out = (uint8_t*)(base + L.vals_out);
+    GaucScan* sc = (GaucScan*)(base + L.scan);
+    int64_t* start = (int64_t*)(base + L.start);
+    const int64_t n2 = 2 * n;
+    const int seg = n_domain + 1;
+    const int blocks = (int)std::min<int64_t>(cdc_ceil_div(n, MET_THREADS), 4096);
+    hipLaunchKernelGGL(k_gauc_keys, dim3(blocks), dim3(MET_THREADS), 0, st, pred, label, user, ld_user, n_user, domain, ld_domain,
+                       n_domain, n, keys_in, vals_in, err_flag);
+    CDC_LAUNCH_CHECK("eval_gauc(keys)");
+    // the sort only has to look at the bits a key can have: 32 score bits + the bits of the largest group id
+    const uint64_t g_max = (uint64_t)seg * (uint64_t)n_user - 1;
+    int end_bit = 33;
+    while (end_bit < 64 && (g_max >> (end_bit - 32)) != 0) ++end_bit;
+    size_t temp_bytes = (size_t)L.temp_bytes;
+    hipError_t e = rocprim::radix_sort_pairs(base + L.temp, temp_bytes, (const uint64_t*)keys_in, keys_out, (const uint8_t*)vals_in,
+                                             vals_out, (size_t)n2, 0, end_bit, st, false);
+    if (e != hipSuccess) { cdc_set_error("%s: radix sort failed: %s", what, hipGetErrorString(e)); return (int)e; }
+    temp_bytes = (size_t)L.temp_bytes;
+    e = rocprim::inclusive_scan(base + L.temp, temp_bytes, GaucScanIt(rocprim::counting_iterator<uint32_t>(0), GaucScanIn{keys_out, vals_out}),
+                                sc, (size_t)n2, GaucScanOp(), st, false);
+    if (e != hipSuccess) { cdc_set_error("%s: group scan failed: %s", what, hipGetErrorString(e)); return (int)e; }
+    temp_bytes = (size_t)L.temp_bytes;
+    e = rocprim::inclusive_scan(base + L.temp, temp_bytes, GaucShareIt(rocprim::counting_iterator<uint32_t>(0), GaucShareIn{sc, vals_out}),
+                                W, (size_t)n2, rocprim::plus<unsigned long long>(), st, false);
+    if (e != hipSuccess) { cdc_set_error("%s: rank scan failed: %s", what, hipGetErrorString(e)); return (int)e; }
+    hipLaunchKernelGGL(k_gauc_starts, dim3((int)cdc_ceil_div(seg + 1, 64)), dim3(64), 0, st, keys_out, n2, seg, n_user, start);
+    CDC_LAUNCH_CHECK("eval_gauc(starts)");
+    return 0;
 }
 
 extern "C" int cdc_eval_gauc(const float* pred, const int16_t* label, const int32_t* user, int64_t ld_user, int64_t n_user,
@@ -435,40 +479,17 @@ extern "C" int cdc_eval_gauc(const float* pred, const int16_t* label, const int3
     if (rc != 0) return rc;
     CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_gauc: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
     char* base = (char*)workspace;
-    uint64_t* keys_in = (uint64_t*)(base + L.keys_in);
-    uint64_t* keys_out = (uint64_t*)(base + L.keys_out);
-    uint8_t* vals_in = (uint8_t*)(base + L.vals_in);
-    uint8_t* vals_out = (uint8_t*)(base + L.vals_out);
-    GaucScan* sc = (GaucScan*)(base + L.scan);
-    unsigned long long* W = (unsigned long long*)keys_in;          // the unsorted keys are dead once the sort has run
-    int64_t* start = (int64_t*)(base + L.start);
+    const uint64_t* keys_out = (const uint64_t*)(base + L.keys_out);
+    const GaucScan* sc = (const GaucScan*)(base + L.scan);
+    unsigned long long* W = (unsigned long long*)(base + L.keys_in);
+    const int64_t* start = (const int64_t*)(base + L.start);
     double* part = (double*)(base + L.part);
     int64_t* part_cnt = (int64_t*)(base + L.part_cnt);
     hipStream_t st = (hipStream_t)stream;
     const int64_t n2 = 2 * n;
     const int seg = n_domain + 1;
-    const int blocks = (int)std::min<int64_t>(cdc_ceil_div(n, MET_THREADS), 4096);
-    hipLaunchKernelGGL(k_gauc_keys, dim3(blocks), dim3(MET_THREADS), 0, st, pred, label, user, ld_user, n_user, domain, ld_domain,
-                       n_domain, n, keys_in, vals_in, err_flag);
-    CDC_LAUNCH_CHECK("eval_gauc(keys)");
-    // the sort only has to look at the bits a key can have: 32 score bits + the bits of the largest group id
-    const uint64_t g_max = (uint64_t)seg * (uint64_t)n_user - 1;
-    int end_bit = 33;
-    while (end_bit < 64 && (g_max >> (end_bit - 32)) != 0) ++end_bit;
-    size_t temp_bytes = (size_t)L.temp_bytes;
-    hipError_t e = rocprim::radix_sort_pairs(base + L.temp, temp_bytes, (const uint64_t*)keys_in, keys_out, (const uint8_t*)vals_in,
-                                             vals_out, (size_t)n2, 0, end_bit, st, false);
-    if (e != hipSuccess) { cdc_set_error("eval_gauc: radix sort failed: %s", hipGetErrorString(e)); return (int)e; }
-    temp_bytes = (size_t)L.temp_bytes;
-    e = rocprim::inclusive_scan(base + L.temp, temp_bytes, GaucScanIt(rocprim::counting_iterator<uint32_t>(0), GaucScanIn{keys_out, vals_out}),
-                                sc, (size_t)n2, GaucScanOp(), st, false);
-    if (e != hipSuccess) { cdc_set_error("eval_gauc: group scan failed: %s", hipGetErrorString(e)); return (int)e; }
-    temp_bytes = (size_t)L.temp_bytes;
-    e = rocprim::inclusive_scan(base + L.temp, temp_bytes, GaucShareIt(rocprim::counting_iterator<uint32_t>(0), GaucShareIn{sc, vals_out}),
-                                W, (size_t)n2, rocprim::plus<unsigned long long>(), st, false);
-    if (e != hipSuccess) { cdc_set_error("eval_gauc: rank scan failed: %s", hipGetErrorString(e)); return (int)e; }
-    hipLaunchKernelGGL(k_gauc_starts, dim3((int)cdc_ceil_div(seg + 1, 64)), dim3(64), 0, st, keys_out, n2, seg, n_user, start);
-    CDC_LAUNCH_CHECK("eval_gauc(starts)");
+    rc = gauc_order(pred, label, user, ld_user, n_user, domain, ld_domain, n_domain, n, err_flag, base, L, W, "eval_gauc", st);
+    if (rc != 0) return rc;
     hipLaunchKernelGGL(k_gauc_sum, dim3(seg, GAUC_SLICES), dim3(GAUC_THREADS), 0, st, keys_out, sc, W, start, user_weight, n_user, n2,
                        part, part_cnt);
     CDC_LAUNCH_CHECK("eval_gauc(sum)");
@@ -881,6 +902,406 @@ extern "C" int cdc_eval_auc_delong(const float* pred_a, const float* pred_b, con
     CDC_LAUNCH_CHECK("eval_auc_delong(reduce)");
     hipLaunchKernelGGL(k_delong_final, dim3((int)cdc_ceil_div(seg, 64)), dim3(64), 0, st, start, sc, acc, seg, paired, out, counts);
     CDC_LAUNCH_CHECK("eval_auc_delong(final)");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Standard error of the log-loss and of the difference of two log-losses on the same rows.  Per segment (a domain's rows, or all
+// rows) of m rows with l_i the per-row term of k_metric_loss:
+//     loss = sum l / m        var = sum (l_i - loss)^2 / (m (m - 1))        (rows taken as independent, as DeLong's variance does)
+// and with a second vector (terms k_i):  delta = loss_a - loss_b,  var_delta = the formula of var on d_i = l_i - k_i, centred on
+// sum d / m — formed from the differences, never as var_a + var_b - 2 cov, which cancels when the two vectors are close.
+//
+//   keys    every row twice, as k_metric_keys does, payload = the copy index j in [0, 2n): ONE stable radix sort of the first vector
+//           gives cdc_eval_metrics' order of the rows (tied keys keep their row order there too); label and pred_b of a sorted
+//           position are fetched through the payload
+//   pass    one workgroup per segment walks it twice in k_metric_loss' order (strided per thread, then a tree over the threads): first
+//           sum l (sum k, sum d) and the positives, then — with the means broadcast through shared memory — the centred squares.
+//           The first sum is k_metric_loss' sum addition for addition, so loss equals cdc_eval_metrics' figure bit for bit.  A
+//           thread keeps its terms in the workspace for its second walk: the logarithms are taken once
+// No floating-point atomics: every addition's order follows from the sorted order and the launch dimensions, and those depend on
+// (n, n_domain) alone.
+__global__ void __launch_bounds__(MET_THREADS) k_lossci_keys(const float* __restrict__ pred_a, const float* __restrict__ pred_b,
+                                                             const int16_t* __restrict__ label, const int32_t* __restrict__ domain,
+                                                             int64_t ld_domain, int64_t n, int32_t n_domain, uint64_t* __restrict__ keys,
+                                                             uint32_t* __restrict__ idx, int32_t* __restrict__ err) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float p = pred_a[i];
+        int32_t d = domain ? domain[i * ld_domain] : 0;
+        const int16_t y = label[i];
+        bool bad = !(p >= 0.f && p <= 1.f) || (y != 0 && y != 1);           // a NaN too
+        if (pred_b) { const float q = pred_b[i]; bad = bad || !(q >= 0.f && q <= 1.f); }
+        if (bad || d < 0 || d >= n_domain) {
+            if (err) atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
+            d = d < 0 ? 0 : (d >= n_domain ? n_domain - 1 : d);
+        }
+        const uint32_t sk = score_key(p);
+        keys[i] = ((uint64_t)(uint32_t)d << 32) | sk;
+        keys[n + i] = ((uint64_t)(uint32_t)n_domain << 32) | sk;
+        idx[i] = (uint32_t)i;
+        idx[n + i] = (uint32_t)(n + i);
+    }
+}
+
+// k_metric_loss' term: 1 - p and the clip in float32, the logarithm in double
+__device__ __forceinline__ double lossci_term(float p, bool positive) {
+    const float eps = 1.1920928955078125e-07f, hi = 1.0f - eps;            // numpy.finfo(float32).eps
+    float c = positive ? p : __fsub_rn(1.0f, p);
+    c = c < eps ? eps : (c > hi ? hi : c);
+    return -log((double)c);
+}
+
+// k_metric_loss' tree over the workgroup's threads; every thread gets the total
+__device__ __forceinline__ double lossci_tree(double v, double* part, int tid) {
+    part[tid] = v;
+    __syncthreads();
+    for (int off = MET_LOSS_THREADS / 2; off > 0; off >>= 1) {
+        if (tid < off) part[tid] += part[tid + off];
+        __syncthreads();
+    }
+    const double r = part[0];
+    __syncthreads();
+    return r;
+}
+
+template <bool PAIRED>
+__global__ void __launch_bounds__(MET_LOSS_THREADS) k_lossci(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ idx,
+                                                             const int16_t* __restrict__ label, const float* __restrict__ pred_b,
+                                                             const int64_t* __restrict__ start, int64_t n, int32_t n_seg,
+                                                             double* __restrict__ term_a, double* __restrict__ term_b,
+                                                             double* __restrict__ out, int64_t* __restrict__ counts) {
+    __shared__ double part[MET_LOSS_THREADS];
+    __shared__ unsigned long long s_pos;
+    const int d = blockIdx.x, tid = threadIdx.x;
+    const int64_t s0 = start[d], s1 = start[d + 1], rows = s1 - s0;
+    if (tid == 0) s_pos = 0ull;
+    double sa = 0.0, sb = 0.0, sd = 0.0;
+    unsigned long long npos = 0ull;
+    for (int64_t i = s0 + tid; i < s1; i += MET_LOSS_THREADS) {
+        const int64_t j = idx[i], row = j >= n ? j - n : j;
+        const bool positive = label[row] != 0;
+        const double la = lossci_term(key_score((uint32_t)keys[i]), positive);
+        sa += la;
+        term_a[i] = la;
+        if constexpr (PAIRED) {
+            const double lb = lossci_term(pred_b[row], positive);
+            sb += lb;
+            sd += la - lb;
+            term_b[i] = lb;
+        }
+        npos += positive ? 1ull : 0ull;
+    }
+    sa = lossci_tree(sa, part, tid);                                        // the sync inside also publishes s_pos = 0
+    if constexpr (PAIRED) { sb = lossci_tree(sb, part, tid); sd = lossci_tree(sd, part, tid); }
+    if (npos) atomicAdd(&s_pos, npos);                                      // an integer: no order to keep
+    const double m = (double)rows;
+    const double mean_a = sa / m, mean_b = sb / m, mean_d = sd / m;         // mean_a: k_metric_final's expression
+    double qa = 0.0, qb = 0.0, qd = 0.0;
+    for (int64_t i = s0 + tid; i < s1; i += MET_LOSS_THREADS) {           // the positions this thread wrote itself
+        const double la = term_a[i];
+        const double ca = la - mean_a;
+        qa += ca * ca;
+        if constexpr (PAIRED) {
+            const double lb = term_b[i];
+            const double cb = lb - mean_b, cd = (la - lb) - mean_d;
+            qb += cb * cb;
+            qd += cd * cd;
+        }
+    }
+    qa = lossci_tree(qa, part, tid);
+    if constexpr (PAIRED) { qb = lossci_tree(qb, part, tid); qd = lossci_tree(qd, part, tid); }
+    if (tid != 0) return;
+    const int64_t P = (int64_t)s_pos, N = rows - P;
+    counts[d] = rows;
+    counts[n_seg + d] = P;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const bool ok = rows > 0 && P > 0 && N > 0;                             // cdc_eval_metrics' rule; it implies rows >= 2
+    const double mm = m * (double)(rows - 1);
+    out[d] = ok ? mean_a : nan;
+    out[n_seg + d] = ok ? qa / mm : nan;
+    if constexpr (PAIRED) {
+        out[2 * n_seg + d] = ok ? mean_b : nan;
+        out[3 * n_seg + d] = ok ? qb / mm : nan;
+        out[4 * n_seg + d] = ok ? mean_a - mean_b : nan;
+        out[5 * n_seg + d] = ok ? qd / mm : nan;
+    }
+}
+
+struct LossCiLayout {
+    int64_t keys_in, keys_out, idx_in, idx_out, term_b, start, temp, temp_bytes, total;
+};
+// everything but rocPRIM's temporary storage: plain arithmetic (argument checks use it before any HIP or rocPRIM call)
+static void lossci_fixed_layout(int64_t n, int32_t n_domain, int32_t paired, LossCiLayout* L) {
+    const int64_t n2 = 2 * n, seg = (int64_t)n_domain + 1;
+    int64_t off = 0;
+    L->keys_in = off;  off += align_up(n2 * 8);               // after the sort: the first vector's terms
+    L->keys_out = off; off += align_up(n2 * 8);
+    L->idx_in = off;   off += align_up(n2 * 4);
+    L->idx_out = off;  off += align_up(n2 * 4);
+    L->term_b = off;   off += paired ? align_up(n2 * 8) : 0;
+    L->start = off;    off += align_up((seg + 1) * 8);
+    L->temp = off;
+    L->temp_bytes = 0;
+    L->total = off;
+}
+static int lossci_layout(int64_t n, int32_t n_domain, int32_t paired, LossCiLayout* L) {
+    lossci_fixed_layout(n, n_domain, paired, L);
+    size_t t_sort = 0;
+    hipError_t e = rocprim::radix_sort_pairs(nullptr, t_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr,
+                                             (uint32_t*)nullptr, (size_t)(2 * n), 0, 64, (hipStream_t)0, false);
+    if (e != hipSuccess) { cdc_set_error("eval_loss_ci: rocprim size query failed: %s", hipGetErrorString(e)); return (int)e; }
+    L->temp_bytes = (int64_t)t_sort;
+    L->total = L->temp + align_up(L->temp_bytes);
+    return 0;
+}
+
+extern "C" int64_t cdc_eval_loss_ci_workspace_bytes(int64_t n, int32_t n_domain, int32_t paired) {
+    if (!delong_sizes_ok(n, n_domain)) return 0;
+    LossCiLayout L;
+    if (lossci_layout(n, n_domain, paired != 0, &L) != 0) return -1;
+    return L.total;
+}
+
+extern "C" int cdc_eval_loss_ci(const float* pred_a, const float* pred_b, const int16_t* label, const int32_t* domain, int64_t ld_domain,
+                                int64_t n, int32_t n_domain, double* out, int64_t* counts, int32_t* err_flag, void* workspace,
+                                int64_t workspace_bytes, void* stream) {
+    CDC_CHECK_ARG(pred_a && label && out && counts && workspace, CDC_E_BADARG, "eval_loss_ci: null pointer");
+    CDC_CHECK_ARG(n > 0 && n_domain > 0 && n_domain < (1 << 20) && ld_domain >= 0, CDC_E_BADARG,
+                  "eval_loss_ci: bad sizes n=%ld n_domain=%d ld_domain=%ld", (long)n, n_domain, (long)ld_domain);
+    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_loss_ci: n_domain=%d needs the domain column", n_domain);
+    CDC_CHECK_ARG(n < (1ll << 31), CDC_E_TOOBIG, "eval_loss_ci: n=%ld exceeds the 2^31 rows a sorted position counts in 32 bits", (long)n);
+    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_loss_ci: workspace must be 256-byte aligned");
+    const int32_t paired = pred_b != nullptr;
+    LossCiLayout L;
+    lossci_fixed_layout(n, n_domain, paired, &L);
+    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_loss_ci: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
+    int rc = lossci_layout(n, n_domain, paired, &L);
+    if (rc != 0) return rc;
+    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_loss_ci: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
+    char* base = (char*)workspace;
+    uint64_t* keys_in = (uint64_t*)(base + L.keys_in);
+    uint64_t* keys_out = (uint64_t*)(base + L.keys_out);
+    uint32_t* idx_in = (uint32_t*)(base + L.idx_in);
+    uint32_t* idx_out = (uint32_t*)(base + L.idx_out);
+    double* term_a = (double*)keys_in;                              // the unsorted keys are dead once the sort has run
+    double* term_b = (double*)(base + L.term_b);
+    int64_t* start = (int64_t*)(base + L.start);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n2 = 2 * n;
+    const int seg = n_domain + 1;
+    const int blocks = (int)std::min<int64_t>(cdc_ceil_div(n, MET_THREADS), 4096);
+    hipLaunchKernelGGL(k_lossci_keys, dim3(blocks), dim3(MET_THREADS), 0, st, pred_a, pred_b, label, domain, ld_domain, n, n_domain, keys_in,
+                       idx_in, err_flag);
+    CDC_LAUNCH_CHECK("eval_loss_ci(keys)");
+    int end_bit = 33;
+    while (end_bit < 64 && ((uint64_t)n_domain >> (end_bit - 32)) != 0) ++end_bit;
+    size_t temp_bytes = (size_t)L.temp_bytes;
+    hipError_t e = rocprim::radix_sort_pairs(base + L.temp, temp_bytes, (const uint64_t*)keys_in, keys_out, (const uint32_t*)idx_in, idx_out,
+                                             (size_t)n2, 0, end_bit, st, false);
+    if (e != hipSuccess) { cdc_set_error("eval_loss_ci: radix sort failed: %s", hipGetErrorString(e)); return (int)e; }
+    hipLaunchKernelGGL(k_delong_starts, dim3((int)cdc_ceil_div(seg + 1, 64)), dim3(64), 0, st, (const uint64_t*)keys_out, n2, seg, start,
+                       (unsigned long long*)nullptr);
+    CDC_LAUNCH_CHECK("eval_loss_ci(starts)");
+    if (paired)
+        hipLaunchKernelGGL(k_lossci<true>, dim3(seg), dim3(MET_LOSS_THREADS), 0, st, (const uint64_t*)keys_out, (const uint32_t*)idx_out, label,
+                           pred_b, (const int64_t*)start, n, seg, term_a, term_b, out, counts);
+    else
+        hipLaunchKernelGGL(k_lossci<false>, dim3(seg), dim3(MET_LOSS_THREADS), 0, st, (const uint64_t*)keys_out, (const uint32_t*)idx_out, label,
+                           (const float*)nullptr, (const int64_t*)start, n, seg, term_a, (double*)nullptr, out, counts);
+    CDC_LAUNCH_CHECK("eval_loss_ci(pass)");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// User-clustered standard error of GAUC and of the difference of two GAUCs on the same rows.  The sampling unit is the user: per
+// segment, over the K counted groups with weight w_g and AUC A_g, G = sum w A / sum w is a ratio of two sums over users, and its
+// linearised variance with clusters = users is
+//     var = K / (K - 1) * sum_g (w_g (A_g - G))^2 / (sum_g w_g)^2
+// and, with B_g the groups' AUCs under a second vector:  delta = G_a - G_b,  var_delta = the same formula on (A_g - B_g) - delta.
+//
+//   order   cdc_eval_gauc's keys, sort and two scans, once per vector.  The upper key halves of the two vectors are the same multiset,
+//           so a group occupies the SAME sorted positions in both orders, with the same h and cn at its ends: of the second vector's
+//           order only W, the running sum of scan 2, is kept
+//   pass 1  k_gauc_sum / k_gauc_final as cdc_eval_gauc launches them, once per vector (the second with its own W): G and G_b, the
+//           first cdc_eval_gauc's figure bit for bit
+//   pass 2  the same slices: the workgroup that finds a group's last row reads (W_a, W_b) there, forms A_g (B_g, A_g - B_g), reads G
+//           from device memory and adds the centred squares strided per thread, then in a tree; a last launch adds the slices' sums
+//           (and, again, the slices' sum w) in a tree and forms the variances
+// No per-group array, nothing indexed by a user id, no atomics on the way to a result: the order of every addition is a function of
+// the sorted keys alone — same rows, same bits.  The launch dimensions depend on (n, n_domain, paired) alone.
+template <bool PAIRED>
+__global__ void __launch_bounds__(GAUC_THREADS) k_gauc_ci_sq(const uint64_t* __restrict__ keys, const GaucScan* __restrict__ sc,
+                                                             const unsigned long long* __restrict__ W,
+                                                             const unsigned long long* __restrict__ W_b, const int64_t* __restrict__ start,
+                                                             const double* __restrict__ user_weight, int64_t n_user, int64_t n2,
+                                                             int32_t n_seg, const double* __restrict__ out, double* __restrict__ part_sq) {
+    __shared__ double s_sq[3][GAUC_THREADS];
+    const int d = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
+    const int64_t s0 = start[d], s1 = start[d + 1];
+    const int64_t per = (s1 - s0 + GAUC_SLICES - 1) / GAUC_SLICES;
+    const int64_t a = s0 + (int64_t)sl * per, b = a + per < s1 ? a + per : s1;
+    const uint64_t base = (uint64_t)d * (uint64_t)n_user;
+    const double G = out[d], G_b = PAIRED ? out[2 * n_seg + d] : 0.0, delta = G - G_b;     // NaN when no group is counted: then none is added
+    double qa = 0.0, qb = 0.0, qd = 0.0;
+    for (int64_t i = a + tid; i < b; i += GAUC_THREADS) {
+        const uint64_t g = keys[i] >> 32;
+        if (i + 1 < n2 && (keys[i + 1] >> 32) == g) continue;              // not the last row of its group
+        const GaucScan e = sc[i];
+        const int64_t h = e.h;
+        const int64_t rows = i - h + 1;
+        const int64_t N = (int64_t)(e.cn - (h ? sc[h - 1].cn : 0u)), P = rows - N;
+        if (P == 0 || N == 0) continue;
+        const double pn2 = 2.0 * (double)P * (double)N;
+        const double w = user_weight ? user_weight[g - base] : (double)rows;
+        const double auc = (double)(W[i] - (h ? W[h - 1] : 0ull)) / pn2;    // k_gauc_sum's expression
+        const double ta = w * (auc - G);
+        qa += ta * ta;
+        if constexpr (PAIRED) {
+            const double auc_b = (double)(W_b[i] - (h ? W_b[h - 1] : 0ull)) / pn2;
+            const double tb = w * (auc_b - G_b), td = w * ((auc - auc_b) - delta);
+            qb += tb * tb;
+            qd += td * td;
+        }
+    }
+    s_sq[0][tid] = qa; s_sq[1][tid] = qb; s_sq[2][tid] = qd;
+    __syncthreads();
+    for (int off = GAUC_THREADS / 2; off > 0; off >>= 1) {
+        if (tid < off) {
+            s_sq[0][tid] += s_sq[0][tid + off];
+            if constexpr (PAIRED) { s_sq[1][tid] += s_sq[1][tid + off]; s_sq[2][tid] += s_sq[2][tid + off]; }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const int64_t o = ((int64_t)d * GAUC_SLICES + sl) * 3;
+        part_sq[o] = s_sq[0][0]; part_sq[o + 1] = s_sq[1][0]; part_sq[o + 2] = s_sq[2][0];
+    }
+}
+
+// out: gauc, var (paired: gauc_b, var_b, delta, var_delta), each [n_seg]; gauc and gauc_b are in place (k_gauc_final wrote them)
+__global__ void __launch_bounds__(GAUC_SLICES) k_gauc_ci_final(const double* __restrict__ part, const int64_t* __restrict__ part_cnt,
+                                                               const double* __restrict__ part_sq, int32_t n_seg, int32_t paired,
+                                                               double* __restrict__ out) {
+    __shared__ double s_den[GAUC_SLICES], s_sq[3][GAUC_SLICES];
+    __shared__ int64_t s_in[GAUC_SLICES];
+    const int d = blockIdx.x, tid = threadIdx.x;
+    const int64_t o = (int64_t)d * GAUC_SLICES + tid;
+    s_den[tid] = part[2 * o + 1];
+    s_in[tid] = part_cnt[2 * o];
+    for (int k = 0; k < 3; ++k) s_sq[k][tid] = part_sq[3 * o + k];
+    __syncthreads();
+    for (int off = GAUC_SLICES / 2; off > 0; off >>= 1) {
+        if (tid < off) {
+            s_den[tid] += s_den[tid + off];
+            s_in[tid] += s_in[tid + off];
+            for (int k = 0; k < 3; ++k) s_sq[k][tid] += s_sq[k][tid + off];
+        }
+        __syncthreads();
+    }
+    if (tid != 0) return;
+    const int64_t K = s_in[0];
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const double scale = K >= 2 ? (double)K / (double)(K - 1) / (s_den[0] * s_den[0]) : nan;
+    out[n_seg + d] = K >= 2 ? scale * s_sq[0][0] : nan;
+    if (!paired) return;
+    out[3 * n_seg + d] = K >= 2 ? scale * s_sq[1][0] : nan;
+    out[4 * n_seg + d] = out[d] - out[2 * n_seg + d];                       // NaN - NaN when no group is counted
+    out[5 * n_seg + d] = K >= 2 ? scale * s_sq[2][0] : nan;
+}
+
+struct GaucCiLayout {
+    GaucLayout g;                       // cdc_eval_gauc's arrays; g.temp / g.total lie behind the ones below
+    int64_t w_b, part_b, part_cnt_b, counts_b, part_sq;
+};
+static void gauc_ci_fixed_layout(int64_t n, int32_t n_domain, int32_t paired, GaucCiLayout* L) {
+    const int64_t n2 = 2 * n, seg = (int64_t)n_domain + 1;
+    gauc_fixed_layout(n, n_domain, &L->g);
+    int64_t off = L->g.temp;
+    L->w_b = off;        off += paired ? align_up(n2 * 8) : 0;
+    L->part_b = off;     off += paired ? align_up(seg * GAUC_SLICES * 2 * 8) : 0;
+    L->part_cnt_b = off; off += paired ? align_up(seg * GAUC_SLICES * 2 * 8) : 0;
+    L->counts_b = off;   off += paired ? align_up(seg * 2 * 8) : 0;
+    L->part_sq = off;    off += align_up(seg * GAUC_SLICES * 3 * 8);
+    L->g.temp = off;
+    L->g.total = off;
+}
+static int gauc_ci_layout(int64_t n, int32_t n_domain, int32_t paired, GaucCiLayout* L) {
+    gauc_ci_fixed_layout(n, n_domain, paired, L);
+    const int rc = gauc_temp_bytes(n, "eval_gauc_ci", &L->g.temp_bytes);
+    if (rc != 0) return rc;
+    L->g.total = L->g.temp + align_up(L->g.temp_bytes);
+    return 0;
+}
+
+extern "C" int64_t cdc_eval_gauc_ci_workspace_bytes(int64_t n, int32_t n_domain, int64_t n_user, int32_t paired) {
+    if (!gauc_sizes_ok(n, n_domain, n_user)) return 0;
+    GaucCiLayout L;
+    if (gauc_ci_layout(n, n_domain, paired != 0, &L) != 0) return -1;
+    return L.g.total;
+}
+
+extern "C" int cdc_eval_gauc_ci(const float* pred_a, const float* pred_b, const int16_t* label, const int32_t* user, int64_t ld_user,
+                                int64_t n_user, const int32_t* domain, int64_t ld_domain, int32_t n_domain, const double* user_weight,
+                                int64_t n, double* out, int64_t* counts, int32_t* err_flag, void* workspace, int64_t workspace_bytes,
+                                void* stream) {
+    CDC_CHECK_ARG(pred_a && label && user && out && counts && workspace, CDC_E_BADARG, "eval_gauc_ci: null pointer");
+    CDC_CHECK_ARG(n > 0 && n_domain > 0 && n_domain < (1 << 20) && n_user > 0 && ld_user >= 0 && ld_domain >= 0, CDC_E_BADARG,
+                  "eval_gauc_ci: bad sizes n=%ld n_domain=%d n_user=%ld", (long)n, n_domain, (long)n_user);
+    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_gauc_ci: n_domain=%d needs the domain column", n_domain);
+    CDC_CHECK_ARG(n < (1ll << 31), CDC_E_TOOBIG, "eval_gauc_ci: n=%ld exceeds the 2^31 rows a sorted position counts in 32 bits", (long)n);
+    CDC_CHECK_ARG(gauc_sizes_ok(n, n_domain, n_user), CDC_E_BADARG,
+                  "eval_gauc_ci: (n_domain + 1) * n_user = %ld * %ld group ids exceed 2^32", (long)n_domain + 1, (long)n_user);
+    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_gauc_ci: workspace must be 256-byte aligned");
+    const int32_t paired = pred_b != nullptr;
+    GaucCiLayout L;
+    gauc_ci_fixed_layout(n, n_domain, paired, &L);
+    CDC_CHECK_ARG(workspace_bytes >= L.g.total, CDC_E_BADARG, "eval_gauc_ci: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.g.total);
+    int rc = gauc_ci_layout(n, n_domain, paired, &L);
+    if (rc != 0) return rc;
+    CDC_CHECK_ARG(workspace_bytes >= L.g.total, CDC_E_BADARG, "eval_gauc_ci: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.g.total);
+    char* base = (char*)workspace;
+    const uint64_t* keys = (const uint64_t*)(base + L.g.keys_out);
+    const GaucScan* sc = (const GaucScan*)(base + L.g.scan);
+    unsigned long long* W = (unsigned long long*)(base + L.g.keys_in);
+    unsigned long long* W_b = (unsigned long long*)(base + L.w_b);
+    const int64_t* start = (const int64_t*)(base + L.g.start);
+    double* part = (double*)(base + L.g.part);
+    int64_t* part_cnt = (int64_t*)(base + L.g.part_cnt);
+    double* part_b = (double*)(base + L.part_b);
+    int64_t* part_cnt_b = (int64_t*)(base + L.part_cnt_b);
+    int64_t* counts_b = (int64_t*)(base + L.counts_b);
+    double* part_sq = (double*)(base + L.part_sq);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n2 = 2 * n;
+    const int seg = n_domain + 1;
+    if (paired) {                                                   // the second vector first: of its order only W_b stays
+        rc = gauc_order(pred_b, label, user, ld_user, n_user, domain, ld_domain, n_domain, n, err_flag, base, L.g, W_b, "eval_gauc_ci", st);
+        if (rc != 0) return rc;
+    }
+    rc = gauc_order(pred_a, label, user, ld_user, n_user, domain, ld_domain, n_domain, n, err_flag, base, L.g, W, "eval_gauc_ci", st);
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(k_gauc_sum, dim3(seg, GAUC_SLICES), dim3(GAUC_THREADS), 0, st, keys, sc, (const unsigned long long*)W, start,
+                       user_weight, n_user, n2, part, part_cnt);
+    CDC_LAUNCH_CHECK("eval_gauc_ci(sum)");
+    hipLaunchKernelGGL(k_gauc_final, dim3(seg), dim3(GAUC_SLICES), 0, st, (const double*)part, (const int64_t*)part_cnt, seg, out, counts);
+    CDC_LAUNCH_CHECK("eval_gauc_ci(final)");
+    if (paired) {                                                   // the counts follow from the labels alone: the second set is dropped
+        hipLaunchKernelGGL(k_gauc_sum, dim3(seg, GAUC_SLICES), dim3(GAUC_THREADS), 0, st, keys, sc, (const unsigned long long*)W_b, start,
+                           user_weight, n_user, n2, part_b, part_cnt_b);
+        CDC_LAUNCH_CHECK("eval_gauc_ci(sum b)");
+        hipLaunchKernelGGL(k_gauc_final, dim3(seg), dim3(GAUC_SLICES), 0, st, (const double*)part_b, (const int64_t*)part_cnt_b, seg,
+                           out + 2 * seg, counts_b);
+        CDC_LAUNCH_CHECK("eval_gauc_ci(final b)");
+        hipLaunchKernelGGL(k_gauc_ci_sq<true>, dim3(seg, GAUC_SLICES), dim3(GAUC_THREADS), 0, st, keys, sc, (const unsigned long long*)W,
+                           (const unsigned long long*)W_b, start, user_weight, n_user, n2, seg, (const double*)out, part_sq);
+    } else {
+        hipLaunchKernelGGL(k_gauc_ci_sq<false>, dim3(seg, GAUC_SLICES), dim3(GAUC_THREADS), 0, st, keys, sc, (const unsigned long long*)W,
+                           (const unsigned long long*)nullptr, start, user_weight, n_user, n2, seg, (const double*)out, part_sq);
+    }
+    CDC_LAUNCH_CHECK("eval_gauc_ci(squares)");
+    hipLaunchKernelGGL(k_gauc_ci_final, dim3(seg), dim3(GAUC_SLICES), 0, st, (const double*)part, (const int64_t*)part_cnt,
+                       (const double*)part_sq, seg, paired, out);
+    CDC_LAUNCH_CHECK("eval_gauc_ci(variances)");
     return 0;
 }
 

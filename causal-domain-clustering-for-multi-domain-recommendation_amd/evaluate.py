@@ -15,6 +15,12 @@ C-ABI call (`cdc_eval_gauc`) on the same device-resident predictions.
 vectors over the same rows the difference of their AUCs with the standard error of that difference (`cdc_eval_auc_delong`);
 `Evaluator(auc_ci=True)` and `Evaluator.compare` report them.
 
+`eval_loss_ci` and `eval_gauc_ci` do the same for the other two headline figures: the log-loss with the standard error of its mean
+(rows taken as independent) and GAUC with a user-clustered standard error (the linearised ratio estimator, clusters = users), and
+for two prediction vectors over the same rows the paired difference with its standard error (`cdc_eval_loss_ci`,
+`cdc_eval_gauc_ci`); `Evaluator(loss_ci=True, gauc_ci=True)` and `Evaluator.compare` report them — the log-loss delta is the one
+figure that moves when a model is recalibrated.
+
 `eval_calibration` reports whether the predicted probabilities are right, where the figures above only say how well they rank: per
 domain and over all rows the ratio of predicted to observed CTR, the Brier score, and a reliability table with ECE / MCE for
 equal-width and equal-mass bins (`cdc_eval_calibration`); `Evaluator(calibration=True)` and `Evaluator.calibration_table` report them.
@@ -242,6 +248,123 @@ def eval_auc_ci(pred, label, domain=None, n_domain=1, pred_b=None):
     if paired:
         return AucCIPaired(o[0], o[1], counts[:seg], counts[seg:], o[2], o[3], o[4], o[5])
     return AucCI(o[0], o[1], counts[:seg], counts[seg:])
+
+
+LossCI = collections.namedtuple("LossCI", "loss var rows positives")
+LossCIPaired = collections.namedtuple("LossCIPaired", "loss var rows positives loss_b var_b delta var_delta")
+
+
+def eval_loss_ci(pred, label, domain=None, n_domain=1, pred_b=None):
+    """Log-loss with the variance of its mean per domain and over all rows; inputs as `eval_metrics` (domain: int32 [n] or a strided
+    column view), pred in [0, 1].  Returns a namedtuple of device tensors with n_domain + 1 entries each — domains 0..n_domain-1,
+    then ALL rows: `loss`, `var` = sum (l_i - loss)^2 / (m (m - 1)) over the segment's m per-row terms l_i (f64), `rows`,
+    `positives` (i64); `loss` is `eval_metrics`' figure bit for bit.  Rows are taken as independent, as DeLong's variance takes them.
+    With `pred_b` (a second prediction vector over the same rows) also `loss_b`, `var_b`, `delta` = loss - loss_b and `var_delta`,
+    the variance of the PAIRED difference (formed from the rows' differences l_i(a) - l_i(b): far below var + var_b when the two
+    vectors are close).  A standard error is `var.sqrt()`.  Every figure is NaN for an empty or single-class segment, as
+    `eval_metrics`' loss is.  No host synchronisation; the error word (1 + a row with a NaN prediction or one outside [0, 1] in
+    either vector, a label outside {0, 1} or a domain outside range) is kept as `eval_loss_ci.last_err`.
+    Not offered: a user-clustered variance of the log-loss (`eval_gauc_ci` clusters by user; this does not)."""
+    lib = L.load()
+    if not pred.is_cuda:
+        raise L.HipExtensionError("eval_loss_ci needs device tensors; there is no CPU fallback")
+    pred = pred.reshape(-1).to(torch.float32).contiguous()
+    label = label.reshape(-1).to(torch.int16).contiguous()
+    n = pred.numel()
+    if label.numel() != n:
+        raise ValueError(f"{n} predictions but {label.numel()} labels")
+    if pred_b is not None:
+        pred_b = pred_b.reshape(-1).to(device=pred.device, dtype=torch.float32).contiguous()
+        if pred_b.numel() != n:
+            raise ValueError(f"{n} predictions but {pred_b.numel()} in pred_b")
+    n_domain = int(n_domain)
+    ld = 0
+    if domain is not None:
+        domain, ld = _id_column(domain, n, "domain")
+    elif n_domain != 1:
+        raise ValueError("n_domain > 1 needs the domain column")
+    dev = pred.device
+    seg = n_domain + 1
+    paired = pred_b is not None
+    out = torch.empty((6 if paired else 2) * seg, dtype=torch.float64, device=dev)
+    counts = torch.empty(2 * seg, dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    nbytes = lib.cdc_eval_loss_ci_workspace_bytes(n, n_domain, int(paired))
+    if nbytes <= 0:
+        raise RuntimeError(f"cdc_eval_loss_ci_workspace_bytes refused n={n}, n_domain={n_domain}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    L.launch("cdc_eval_loss_ci", lib.cdc_eval_loss_ci,
+             (pred.data_ptr(), pred_b.data_ptr() if paired else None, label.data_ptr(), None if domain is None else domain.data_ptr(), ld,
+              n, n_domain, out.data_ptr(), counts.data_ptr(), err.data_ptr(), ws.data_ptr(), nbytes),
+             C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    eval_loss_ci.last_err = err
+    o = out.reshape(-1, seg)
+    if paired:
+        return LossCIPaired(o[0], o[1], counts[:seg], counts[seg:], o[2], o[3], o[4], o[5])
+    return LossCI(o[0], o[1], counts[:seg], counts[seg:])
+
+
+GaucCI = collections.namedtuple("GaucCI", "gauc var counted left_out")
+GaucCIPaired = collections.namedtuple("GaucCIPaired", "gauc var counted left_out gauc_b var_b delta var_delta")
+
+
+def eval_gauc_ci(pred, label, user, n_user, domain=None, n_domain=1, user_weight=None, pred_b=None):
+    """GAUC with its user-clustered variance per domain and over all rows; inputs as `eval_gauc`.  The sampling unit is the user:
+    over a segment's K counted users with weight w_g and AUC A_g, `var` = K / (K - 1) * sum (w_g (A_g - gauc))^2 / (sum w_g)^2, the
+    linearised variance of the ratio gauc = sum w A / sum w.  Returns a namedtuple of device tensors with n_domain + 1 entries each
+    — domains 0..n_domain-1, then ALL rows: `gauc`, `var` (f64), `counted`, `left_out` (i64); `gauc` is `eval_gauc`'s figure bit
+    for bit.  With `pred_b` (a second prediction vector over the same rows) also `gauc_b`, `var_b`, `delta` = gauc - gauc_b and
+    `var_delta`, the variance of the PAIRED difference (the same formula on the users' differences (A_g - B_g) - delta).  A
+    standard error is `var.sqrt()`.  `gauc` / `delta` are NaN where no user is counted, a variance where fewer than two are.  The
+    same rows in any order give the same bits.  No host synchronisation; the error word (as `eval_gauc`'s, over both vectors) is
+    kept as `eval_gauc_ci.last_err`."""
+    lib = L.load()
+    n_user, n_domain = int(n_user), int(n_domain)
+    if n_user <= 0 or n_domain <= 0:
+        raise ValueError(f"n_user={n_user} and n_domain={n_domain} must be positive")
+    if (n_domain + 1) * n_user > 1 << 32:
+        raise ValueError(f"(n_domain + 1) * n_user = {(n_domain + 1) * n_user} group ids exceed 2^32, the upper half of a sort key")
+    if not pred.is_cuda:
+        raise L.HipExtensionError("eval_gauc_ci needs device tensors; there is no CPU fallback")
+    pred = pred.reshape(-1).to(torch.float32).contiguous()
+    label = label.reshape(-1).to(torch.int16).contiguous()
+    n = pred.numel()
+    if label.numel() != n:
+        raise ValueError(f"{n} predictions but {label.numel()} labels")
+    if pred_b is not None:
+        pred_b = pred_b.reshape(-1).to(device=pred.device, dtype=torch.float32).contiguous()
+        if pred_b.numel() != n:
+            raise ValueError(f"{n} predictions but {pred_b.numel()} in pred_b")
+    user, ld_user = _id_column(user, n, "user")
+    ld_domain = 0
+    if domain is not None:
+        domain, ld_domain = _id_column(domain, n, "domain")
+    elif n_domain != 1:
+        raise ValueError("n_domain > 1 needs the domain column")
+    dev = pred.device
+    if user_weight is not None:
+        user_weight = torch.as_tensor(user_weight, dtype=torch.float64).to(dev).reshape(-1).contiguous()
+        if user_weight.numel() != n_user:
+            raise ValueError(f"user_weight holds {user_weight.numel()} entries for {n_user} users")
+    seg = n_domain + 1
+    paired = pred_b is not None
+    out = torch.empty((6 if paired else 2) * seg, dtype=torch.float64, device=dev)
+    counts = torch.empty(2 * seg, dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    nbytes = lib.cdc_eval_gauc_ci_workspace_bytes(n, n_domain, n_user, int(paired))
+    if nbytes <= 0:
+        raise RuntimeError(f"cdc_eval_gauc_ci_workspace_bytes refused n={n}, n_domain={n_domain}, n_user={n_user}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    L.launch("cdc_eval_gauc_ci", lib.cdc_eval_gauc_ci,
+             (pred.data_ptr(), pred_b.data_ptr() if paired else None, label.data_ptr(), user.data_ptr(), ld_user, n_user,
+              None if domain is None else domain.data_ptr(), ld_domain, n_domain, None if user_weight is None else user_weight.data_ptr(),
+              n, out.data_ptr(), counts.data_ptr(), err.data_ptr(), ws.data_ptr(), nbytes),
+             C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    eval_gauc_ci.last_err = err
+    o = out.reshape(-1, seg)
+    if paired:
+        return GaucCIPaired(o[0], o[1], counts[:seg], counts[seg:], o[2], o[3], o[4], o[5])
+    return GaucCI(o[0], o[1], counts[:seg], counts[seg:])
 
 
 Calibration = collections.namedtuple("Calibration", "rows positives mean_pred ctr pcoc brier ece mce ece_q mce_q table table_q")
@@ -657,7 +780,16 @@ class Evaluator:
               from the dict weighs NaN: the reference raises KeyError for it), None = the user's row count.
     auc_ci: test() adds the DeLong standard errors of its AUCs (`eval_auc_ci`): total_auc_se, and with per-domain evaluation
             domain_auc_se {d: value} and mean_auc_se = sqrt(sum_d w_d^2 var_d) over the domains mean_auc sums (disjoint row sets:
-            independent given the model).  Significance-aware early stopping and intervals for GAUC or log-loss are not offered.
+            independent given the model).
+    loss_ci: test() adds the standard errors of its log-losses (`eval_loss_ci`; rows taken as independent): total_loss_se, and with
+            per-domain evaluation domain_loss_se {d: value} and mean_loss_se = sqrt(sum_d w_d^2 var_d), as mean_auc_se; compare()
+            adds total_loss_delta = loss(self) - loss(other), total_loss_delta_se (from the rows' paired differences) and
+            total_loss_z, and the domain_loss_* / mean_loss_* forms.
+    gauc_ci: (needs user_idx) test() adds the user-clustered standard errors of its GAUCs (`eval_gauc_ci`): total_gauc_se, and with
+            per-domain evaluation domain_gauc_se {d: value}.  mean_gauc_se is NOT offered: a user's rows span domains, so the
+            per-domain GAUCs are not independent and sqrt(sum_d w_d^2 var_d) would not be their mean's standard error.  compare()
+            adds total_gauc_delta, total_gauc_delta_se, total_gauc_z and the domain_gauc_* forms.
+            Not offered: significance-aware early stopping in `Runner`, mean_gauc_se, a user-clustered standard error of the log-loss.
     calibration: test() adds calibration figures (`eval_calibration`; True: 10 bins, an int: that many): total_pcoc (predicted over
             observed CTR), total_brier, total_ece, total_ece_quantile, and with per-domain evaluation domain_pcoc / domain_brier /
             domain_ece / domain_ece_quantile {d: value} and mean_pcoc / mean_brier / mean_ece / mean_ece_quantile, weighted like
@@ -674,7 +806,7 @@ class Evaluator:
 
     def __init__(self, model, mode="multi", domain_idx=None, n_domain=1, domain_cnt_weight=None, is_evaluate_multi_domain=True,
                  user_idx=None, n_user=None, user_weight=None, auc_ci=False, precision=None, calibration=False, recalibration=None,
-                 recalibration_eps=0.0):
+                 recalibration_eps=0.0, loss_ci=False, gauc_ci=False):
         self.model, self.mode = model, mode
         if recalibration is not None and recalibration.n_domain > 1 and domain_idx is None:
             raise ValueError(f"a recalibration map over {recalibration.n_domain} domains needs domain_idx, the column that holds a row's domain")
@@ -682,6 +814,9 @@ class Evaluator:
             raise ValueError(f"recalibration_eps={recalibration_eps} must lie in [0, 0.5]")
         self.recalibration, self.recalibration_eps = recalibration, float(recalibration_eps)
         self.auc_ci = bool(auc_ci)
+        self.loss_ci, self.gauc_ci = bool(loss_ci), bool(gauc_ci)
+        if self.gauc_ci and user_idx is None:
+            raise ValueError("gauc_ci needs user_idx, the column that holds a row's user: the standard error is clustered by user")
         self.calibration_bins = 0 if calibration is False else (10 if calibration is True else int(calibration))   # 0: off
         if calibration is not False and not 1 <= self.calibration_bins <= MAX_CALIBRATION_BINS:
             raise ValueError(f"calibration must be a bool or a number of bins in [1, {MAX_CALIBRATION_BINS}], not {calibration!r}")
@@ -778,7 +913,9 @@ class Evaluator:
     def test(self, data_loader):
         """The reference's result_dict: total_auc, total_loss (+ domain_auc, domain_loss, mean_auc, mean_loss); with user_idx also
         total_gauc (+ domain_gauc, mean_gauc); with auc_ci also total_auc_se (+ domain_auc_se, mean_auc_se); with calibration also
-        total_pcoc, total_brier, total_ece, total_ece_quantile (+ domain_* and mean_* of the four)."""
+        total_pcoc, total_brier, total_ece, total_ece_quantile (+ domain_* and mean_* of the four); with loss_ci also total_loss_se
+        (+ domain_loss_se, mean_loss_se); with gauc_ci also total_gauc_se (+ domain_gauc_se; no mean_gauc_se: the per-domain GAUCs
+        share users and are not independent)."""
         pred, label, domain, user = self._score(data_loader)
         multi = self.is_evaluate_multi_domain
         auc, loss, rows, pos = eval_metrics(pred, label, domain if multi else None, self.n_domain if multi else 1)
@@ -788,6 +925,11 @@ class Evaluator:
             ci_var = eval_auc_ci(pred, label, domain if multi else None, self.n_domain if multi else 1).var
         if self.calibration_bins:                              # likewise queued
             cal = eval_calibration(pred, label, domain if multi else None, self.n_domain if multi else 1, self.calibration_bins)
+        if self.loss_ci:                                       # likewise queued
+            loss_var = eval_loss_ci(pred, label, domain if multi else None, self.n_domain if multi else 1).var
+        if self.gauc_ci:                                       # likewise queued
+            gauc_var = eval_gauc_ci(pred, label, user, self.n_user, domain if multi else None, self.n_domain if multi else 1,
+                                    self.user_weight).var
         auc, loss, rows, pos = auc.cpu().tolist(), loss.cpu().tolist(), rows.cpu().tolist(), pos.cpu().tolist()   # the one sync
         bad = int(eval_metrics.last_err.item())
         if bad:
@@ -834,6 +976,21 @@ class Evaluator:
                 if multi:
                     result["domain_" + k] = {d: v[d] for d in range(self.n_domain) if rows[d] > 0}
                     result["mean_" + k] = sum(self._weight(d) * x for d, x in result["domain_" + k].items())     # as mean_auc
+        if self.loss_ci:
+            var = loss_var.cpu().tolist()
+            bad = int(eval_loss_ci.last_err.item())
+            if bad:
+                raise ValueError(f"evaluation row {bad - 1}: prediction outside [0, 1]")
+            result["total_loss_se"] = _se(var[-1])
+            if multi:
+                present = [d for d in range(self.n_domain) if rows[d] > 0]
+                result["domain_loss_se"] = {d: _se(var[d]) for d in present}
+                result["mean_loss_se"] = _se(sum(self._weight(d) ** 2 * var[d] for d in present))  # as mean_auc_se: disjoint row sets
+        if self.gauc_ci:
+            var = gauc_var.cpu().tolist()
+            result["total_gauc_se"] = _se(var[-1])
+            if multi:
+                result["domain_gauc_se"] = {d: _se(var[d]) for d in range(self.n_domain) if rows[d] > 0}
         return result
 
     def calibration_table(self, data_loader):
@@ -859,15 +1016,26 @@ class Evaluator:
         shuffling loader shows here).  Returns total_delta = AUC(self) - AUC(other), total_delta_se (DeLong's paired standard
         error) and total_z = delta / se, and with per-domain evaluation domain_delta / domain_delta_se / domain_z {d: value} and
         mean_delta / mean_delta_se / mean_z, weighted by domain_cnt_weight like mean_auc.  z is NaN for 0 / 0 (identical
-        predictions) and +-inf for a non-zero delta with se 0."""
-        pred_a, label, domain, _ = self._score(data_loader)
-        pred_b, label_b, domain_b, _ = other._score(data_loader)
+        predictions) and +-inf for a non-zero delta with se 0.  With loss_ci set on this evaluator the same nine keys for the log-loss
+        (total_loss_delta, total_loss_delta_se, total_loss_z, domain_loss_*, mean_loss_*: raw against recalibrated shows here, where
+        the AUC delta is 0); with gauc_ci set total_gauc_delta, total_gauc_delta_se, total_gauc_z and domain_gauc_* (no mean_gauc_*,
+        as in test()) — then both passes must also see the same user column."""
+        pred_a, label, domain, user = self._score(data_loader)
+        pred_b, label_b, domain_b, user_b = other._score(data_loader)
         if label.shape != label_b.shape or not torch.equal(label, label_b):
             raise ValueError("the two scoring passes saw different labels: compare() needs a loader that yields the same rows in the same order")
         if (domain is None) != (domain_b is None) or (domain is not None and not torch.equal(domain, domain_b)):
             raise ValueError("the two scoring passes saw different domain columns: compare() needs a loader that yields the same rows in the same order")
+        if self.gauc_ci and (user_b is None or not torch.equal(user, user_b)):
+            raise ValueError("the two scoring passes saw different user columns: compare() with gauc_ci needs the same user_idx in both "
+                             "evaluators and a loader that yields the same rows in the same order")
         multi = self.is_evaluate_multi_domain
         ci = eval_auc_ci(pred_a, label, domain if multi else None, self.n_domain if multi else 1, pred_b=pred_b)
+        if self.loss_ci:                                       # queued behind the AUC's: still nothing has been read back
+            lci = eval_loss_ci(pred_a, label, domain if multi else None, self.n_domain if multi else 1, pred_b=pred_b)
+        if self.gauc_ci:                                       # likewise queued
+            gci = eval_gauc_ci(pred_a, label, user, self.n_user, domain if multi else None, self.n_domain if multi else 1,
+                               self.user_weight, pred_b=pred_b)
         delta, var, rows = ci.delta.cpu().tolist(), ci.var_delta.cpu().tolist(), ci.rows.cpu().tolist()
         bad = int(eval_auc_ci.last_err.item())
         if bad:
@@ -882,6 +1050,31 @@ class Evaluator:
             result.update({"domain_delta": {d: delta[d] for d in present}, "domain_delta_se": d_se,
                            "domain_z": {d: _z(delta[d], d_se[d]) for d in present},
                            "mean_delta": mean_delta, "mean_delta_se": mean_se, "mean_z": _z(mean_delta, mean_se)})
+        if self.loss_ci:
+            delta, var = lci.delta.cpu().tolist(), lci.var_delta.cpu().tolist()
+            bad = int(eval_loss_ci.last_err.item())
+            if bad:
+                raise ValueError(f"evaluation row {bad - 1}: prediction outside [0, 1]")
+            se = _se(var[-1])
+            result.update({"total_loss_delta": delta[-1], "total_loss_delta_se": se, "total_loss_z": _z(delta[-1], se)})
+            if multi:
+                d_se = {d: _se(var[d]) for d in present}
+                mean_delta = sum(self._weight(d) * delta[d] for d in present)
+                mean_se = _se(sum(self._weight(d) ** 2 * var[d] for d in present))
+                result.update({"domain_loss_delta": {d: delta[d] for d in present}, "domain_loss_delta_se": d_se,
+                               "domain_loss_z": {d: _z(delta[d], d_se[d]) for d in present},
+                               "mean_loss_delta": mean_delta, "mean_loss_delta_se": mean_se, "mean_loss_z": _z(mean_delta, mean_se)})
+        if self.gauc_ci:
+            delta, var = gci.delta.cpu().tolist(), gci.var_delta.cpu().tolist()
+            bad = int(eval_gauc_ci.last_err.item())
+            if bad:
+                raise ValueError(f"evaluation row {bad - 1}: user outside [0, {self.n_user})")
+            se = _se(var[-1])
+            result.update({"total_gauc_delta": delta[-1], "total_gauc_delta_se": se, "total_gauc_z": _z(delta[-1], se)})
+            if multi:
+                d_se = {d: _se(var[d]) for d in present}
+                result.update({"domain_gauc_delta": {d: delta[d] for d in present}, "domain_gauc_delta_se": d_se,
+                               "domain_gauc_z": {d: _z(delta[d], d_se[d]) for d in present}})
         return result
 
     def _weight(self, d):

@@ -1190,6 +1190,59 @@ int cdc_eval_auc_delong(const float* pred_a, const float* pred_b, const int16_t*
                         int64_t n, int32_t n_domain, double* out, int64_t* counts, int32_t* err_flag, void* workspace,
                         int64_t workspace_bytes, void* stream);
 
+/* Standard error of the log-losses cdc_eval_metrics reports, and the paired comparison of two score vectors on the same rows.
+ * pred_a, label, domain, ld_domain, n_domain as for cdc_eval_metrics (probabilities in [0, 1]); pred_b f32 [n] or NULL (unpaired).
+ * Per segment (domain 0..n_domain-1, then ALL rows) of m rows, with l_i = -log(clip(y_i ? p_i : 1 - p_i)) cdc_eval_metrics' per-row
+ * term (1 - p and the clip to [eps32, 1 - eps32] in float32, the logarithm in double) and k_i the same of pred_b:
+ *     loss = sum l / m                    var = sum (l_i - loss)^2 / (m (m - 1))          (rows taken as independent, as DeLong does)
+ *     delta = loss - loss_b               var_delta = sum (d_i - sum d / m)^2 / (m (m - 1)),  d_i = l_i - k_i
+ * Every variance comes from a second, centred pass over the segment (never sum l^2 - m loss^2), var_delta from the per-row
+ * differences (never var + var_b - 2 cov, which cancels when the two vectors are close).
+ *   out    [(pred_b ? 6 : 2) * (n_domain+1)] doubles: loss, var (and loss_b, var_b, delta, var_delta), each an array over the
+ *          segments.  All NaN for a segment without rows or with a single class (where cdc_eval_metrics' loss is NaN; such a
+ *          segment includes every one of fewer than 2 rows).  loss is added in cdc_eval_metrics' order — the same sorted order of the
+ *          rows, the same 1024 strided partial sums, the same tree — and equals its figure bit for bit.
+ *   counts [2*(n_domain+1)] int64: rows per segment, then positives per segment.
+ *   err_flag (optional): 1 + the largest index of a row with a NaN or a value outside [0, 1] in pred_a or pred_b, a label other
+ *          than 0/1 or a domain outside [0, n_domain).
+ * No floating-point atomics: the order of every addition follows from the sorted order of (domain, score of pred_a, row) and the
+ * launch dimensions, which depend on (n, n_domain) alone; the same call gives the same bits, another row order gives sums that
+ * differ by rounding only.  Limits: null pointers, n <= 0, n_domain outside [1, 2^20), a workspace too small or not 256-byte
+ * aligned: CDC_E_BADARG; n >= 2^31: CDC_E_TOOBIG — all before anything is launched.  Stream-ordered: no allocation, no
+ * synchronisation, no state kept, nothing read back.
+ * workspace: cdc_eval_loss_ci_workspace_bytes(n, n_domain, paired) bytes (O(n): 48 B per row, 64 B paired, plus the sort's), 256-byte
+ * aligned; 0 for sizes the call refuses. */
+int64_t cdc_eval_loss_ci_workspace_bytes(int64_t n, int32_t n_domain, int32_t paired);
+int cdc_eval_loss_ci(const float* pred_a, const float* pred_b, const int16_t* label, const int32_t* domain, int64_t ld_domain,
+                     int64_t n, int32_t n_domain, double* out, int64_t* counts, int32_t* err_flag, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+
+/* User-clustered standard error of the GAUCs cdc_eval_gauc reports, and the paired comparison of two score vectors on the same
+ * rows.  label, user, ld_user, n_user, domain, ld_domain, n_domain, user_weight as for cdc_eval_gauc; pred_b f32 [n] or NULL.  The
+ * sampling unit is the user.  Per segment, over the K counted groups (both classes present) with weight w_g and AUC A_g (B_g under
+ * pred_b), G = sum w A / sum w and the linearised ratio estimator with clusters = users is
+ *     var = K / (K - 1) * sum_g (w_g (A_g - G))^2 / (sum_g w_g)^2
+ *     delta = G_a - G_b        var_delta = K / (K - 1) * sum_g (w_g ((A_g - B_g) - delta))^2 / (sum_g w_g)^2
+ * — var_delta from the per-group differences, never as var + var_b - 2 cov.
+ *   out    [(pred_b ? 6 : 2) * (n_domain+1)] doubles: gauc, var (and gauc_b, var_b, delta, var_delta), each an array over the
+ *          segments.  gauc, gauc_b and delta are NaN when K == 0, every variance when K < 2.  gauc is formed by cdc_eval_gauc's own
+ *          launches and equals its figure bit for bit.
+ *   counts [2*(n_domain+1)] int64: counted groups per (pseudo-)domain, then the groups left out (they follow from the labels alone).
+ *   err_flag (optional): as cdc_eval_gauc, over both vectors; a bad row is counted with its ids clamped into range.
+ * Two passes: the first gives G (and G_b), the second reads them from device memory and adds the centred squares in the same
+ * slice-then-tree order.  Each vector gets its own sort and two scans; a group occupies the same sorted positions in both orders, so
+ * both AUCs of a group are formed where its last row is found: no per-group array, nothing indexed by a user id, workspace O(n).
+ * The order of every addition is a function of the sorted keys alone: the same rows in any order give the same bits.  Limits:
+ * null pointers, bad sizes, (n_domain + 1) * n_user > 2^32, a workspace too small or not 256-byte aligned: CDC_E_BADARG; n >= 2^31:
+ * CDC_E_TOOBIG — all before anything is launched.  Stream-ordered: no allocation, no synchronisation, no state kept; the launch
+ * dimensions depend on (n, n_domain, pred_b != NULL) alone.
+ * workspace: cdc_eval_gauc_ci_workspace_bytes(n, n_domain, n_user, paired) bytes, 256-byte aligned; 0 for sizes the call refuses. */
+int64_t cdc_eval_gauc_ci_workspace_bytes(int64_t n, int32_t n_domain, int64_t n_user, int32_t paired);
+int cdc_eval_gauc_ci(const float* pred_a, const float* pred_b, const int16_t* label, const int32_t* user, int64_t ld_user,
+                     int64_t n_user, const int32_t* domain, int64_t ld_domain, int32_t n_domain, const double* user_weight,
+                     int64_t n, double* out, int64_t* counts, int32_t* err_flag, void* workspace, int64_t workspace_bytes,
+                     void* stream);
+
 /* Calibration of the predictions cdc_eval_metrics ranks: per segment (domain 0..n_domain-1, then ALL rows) the mean prediction, the
  * CTR, predicted over observed CTR, the Brier score, and a reliability table with ECE / MCE for n_bins = K equal-width and K
  * equal-mass (quantile) bins.  pred, label, domain, ld_domain, n_domain as for cdc_eval_metrics; pred is a probability in [0, 1].
