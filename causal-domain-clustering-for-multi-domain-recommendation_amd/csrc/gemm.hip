@@ -1177,9 +1177,10 @@ extern "C" int cdc_glinear_bwd_w_pair(const cdc_lin_bwdw_args* wide, const cdc_l
 // away: data parallelism all-reduces it; autograd hands it on) — two launches where cdc_glinear_bwd_w twice issues four
 extern "C" int cdc_glinear_bwd_w_pair_reduce(const cdc_lin_bwdw_args* wide, const cdc_lin_bwdw_args* narrow, const cdc_lin_bwdw_args* tabs_dev,
                                              void* stream) {
+    CDC_CHECK_ARG(wide && narrow && tabs_dev, CDC_E_BADARG, "glinear_bwd_w_pair_reduce: null argument");
+    CDC_CHECK_ARG(wide->split_k > 1 && narrow->split_k > 1, CDC_E_BADARG, "glinear_bwd_w_pair_reduce: both classes must be split (else cdc_glinear_bwd_w_pair)");
     const int rc = cdc_glinear_bwd_w_pair(wide, narrow, tabs_dev, stream);
     if (rc) return rc;
-    CDC_CHECK_ARG(wide->split_k > 1 && narrow->split_k > 1, CDC_E_BADARG, "glinear_bwd_w_pair_reduce: both classes must be split (else cdc_glinear_bwd_w_pair)");
     int64_t slab[2] = {0, 0};
     for (int w = 0; w < 2; ++w) {
         const cdc_lin_bwdw_args* a = w ? narrow : wide;
