@@ -2560,3 +2560,633 @@ extern "C" int cdc_eval_platt_apply(const float* score, const int32_t* domain, i
     CDC_LAUNCH_CHECK("eval_platt_apply");
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Clustered bootstrap of AUC, log-loss and GAUC.  Replicate r gives cluster c (a user, or a row when there is no cluster column)
+// the weight w(seed, r, c), a Poisson(1) variate capped at 12 that is a pure function of its three arguments: it is formed from a
+// hash wherever it is needed and never stored per row.  Every figure is recomputed with the row weight w_i = w(cluster of row i):
+//
+//   AUC   U2 / (2 Wp Wn) with U2 = sum over (positive i, negative j) of w_i w_j (2 [s_j < s_i] + [s_j = s_i]), Wp = sum w_i y_i,
+//         Wn = W - Wp, all in 64-bit integers (order-free), one conversion and one division at the end
+//   loss  sum w_i l_i / W with k_metric_loss's per-row term l_i, added in an order that the sorted keys alone decide
+//   GAUC  sum_g w_g omega_g A_g / sum_g w_g omega_g over cdc_eval_gauc's counted groups: the user's own AUC A_g does not move
+//
+//   keys    every row twice, key = segment << 33 | score_key << 1 | label, payload = the copy index; one radix sort.  The label
+//           bit puts a tie run's negatives in front of its positives, so for a positive at sorted position i
+//               w_i * (weighted negatives at positions < i  +  weighted negatives in front of i's tie run)
+//           is its share of U2 — counted over the WHOLE sorted array; a segment subtracts 2 Wp * (weighted negatives of the
+//           segments in front of it) in the last launch.  Unsigned 64-bit sums wrap and the difference is exact
+//   prep    once per sorted position: its cluster, its loss term and f, the first position of its tie run (replicate-free)
+//   totals  workgroup = BOOT_CHUNK sorted positions, read once; for every tile of BOOT_REP_TILE replicates the weights are formed in
+//           registers and the chunk's weighted negatives, and those of its LAST tie run, are summed
+//   scan    per replicate an exclusive sum of the chunks' totals
+//   pass    the same chunks: an in-chunk scan of the weighted negatives per replicate (two replicates to a 32-bit word), kept in
+//           LDS as 16-bit in-chunk prefixes.  A tie run that began in an earlier chunk p takes the prefix in front of it from
+//           off[p + 1] - tail[p].  Per segment present in the chunk the sums (W, Wp, U, loss) go through registers, a shuffle
+//           tree and the waves in order, and are written — not added — to the chunk's head or tail slot (first / last segment of
+//           the chunk) or to the segment's own slot (a segment inside one chunk)
+//   reduce  a thread per (segment, replicate) adds its chunks' slots in order; final: a thread per replicate walks the segments
+// No float atomics, nothing zeroed, no per-row weights in memory.  The launch count depends on (paired, gauc) alone: the replicate
+// tiles are a loop inside the grid.  Integer figures do not depend on the row order; the loss depends on it only through the
+// order of tied rows.
+#define BOOT_THREADS 256
+#define BOOT_ITEMS 4
+#define BOOT_CHUNK 1024                 // sorted positions per workgroup: BOOT_THREADS * BOOT_ITEMS (12 * BOOT_CHUNK < 2^16)
+#define BOOT_REP_TILE 8                 // replicates per pass over a chunk's registers: 8 weights of 4 bits to a word
+#define BOOT_MAX_REP 4096
+#define BOOT_WAVES (BOOT_THREADS / 64)
+static_assert(BOOT_CHUNK == BOOT_THREADS * BOOT_ITEMS && 12 * BOOT_CHUNK < 65536 && BOOT_REP_TILE == 8, "bootstrap tile arithmetic");
+
+__device__ __forceinline__ uint64_t boot_mix(uint64_t x) {                 // splitmix64's finaliser
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27; x *= 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    return x;
+}
+__device__ __forceinline__ uint64_t boot_rep_base(uint64_t seed, uint32_t r) {
+    return boot_mix(seed + 0x9E3779B97F4A7C15ull * (uint64_t)(r + 1u));
+}
+// #{k < 12 : u >= floor(2^32 e^-1 sum_{j <= k} 1/j!)}: Poisson(1) by inversion, capped at 12
+__device__ __forceinline__ uint32_t boot_weight(uint64_t base, uint32_t c) {
+    const uint32_t u = (uint32_t)(boot_mix(base + (uint64_t)c) >> 32);
+    uint32_t w = (u >= 0x5e2d58d8u) + (u >= 0xbc5ab1b1u) + (u >= 0xeb715e1du) + (u >= 0xfb239797u);
+    if (u >= 0xff1025f5u)
+        w += 1u + (u >= 0xffd90f3bu) + (u >= 0xfffa8b71u) + (u >= 0xffff540cu) + (u >= 0xffffed1fu) + (u >= 0xfffffe21u) +
+             (u >= 0xffffffd4u) + (u >= 0xfffffffcu);
+    return w;
+}
+__device__ __forceinline__ double boot_wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__global__ void __launch_bounds__(MET_THREADS) k_boot_keys(const float* __restrict__ pred, const int16_t* __restrict__ label,
+                                                           const int32_t* __restrict__ cluster, int64_t ld_cluster, int64_t n_cluster,
+                                                           const int32_t* __restrict__ domain, int64_t ld_domain, int64_t n,
+                                                           int32_t n_domain, uint64_t* __restrict__ keys, uint32_t* __restrict__ idx,
+                                                           int32_t* __restrict__ err) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float p = pred[i];
+        int32_t d = domain ? domain[i * ld_domain] : 0;
+        const int64_t u = cluster ? (int64_t)cluster[i * ld_cluster] : 0;
+        const int16_t y = label[i];
+        if (p != p || d < 0 || d >= n_domain || u < 0 || (cluster && u >= n_cluster) || (y != 0 && y != 1)) {
+            if (err) atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
+            d = d < 0 ? 0 : (d >= n_domain ? n_domain - 1 : d);
+        }
+        const uint64_t low = ((uint64_t)score_key(p) << 1) | (uint64_t)(y != 0);
+        keys[i] = ((uint64_t)(uint32_t)d << 33) | low;
+        keys[n + i] = ((uint64_t)(uint32_t)n_domain << 33) | low;
+        idx[i] = (uint32_t)i;
+        idx[n + i] = (uint32_t)(n + i);
+    }
+}
+
+__global__ void k_boot_starts(const uint64_t* __restrict__ keys, int64_t n2, int32_t n_seg, int64_t* __restrict__ start) {
+    const int d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d <= n_seg) start[d] = d == n_seg ? n2 : lower_bound_u64(keys, 0, n2, (uint64_t)(uint32_t)d << 33);
+}
+
+// what a sorted position carries into every replicate: cluster (clamped as k_gauc_keys clamps a user), loss term, tie-run start
+__global__ void __launch_bounds__(MET_THREADS) k_boot_prep(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ idx,
+                                                           const int32_t* __restrict__ cluster, int64_t ld_cluster, int64_t n_cluster,
+                                                           int64_t n, int64_t n2, uint32_t* __restrict__ cl, double* __restrict__ term,
+                                                           uint32_t* __restrict__ f) {
+    const float eps = 1.1920928955078125e-07f, hi = 1.0f - eps;            // k_metric_loss's clip
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t key = keys[i];
+        const int64_t j = idx[i], row = j >= n ? j - n : j;
+        int64_t u = row;
+        if (cluster) {
+            u = cluster[row * ld_cluster];
+            u = u < 0 ? 0 : (u >= n_cluster ? n_cluster - 1 : u);
+        }
+        cl[i] = (uint32_t)u;
+        const float p = key_score((uint32_t)(key >> 1));
+        float c = (key & 1ull) ? p : __fsub_rn(1.0f, p);
+        c = c < eps ? eps : (c > hi ? hi : c);
+        term[i] = -log((double)c);
+        f[i] = (uint32_t)lower_bound_u64(keys, 0, i + 1, key & ~1ull);
+    }
+}
+
+// ntot[r][c]: weighted negatives of chunk c; ntail[r][c]: those of them in the chunk's last tie run
+__global__ void __launch_bounds__(BOOT_THREADS) k_boot_totals(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ cl,
+                                                              const uint32_t* __restrict__ f, int64_t n2, int64_t nchunks,
+                                                              int32_t n_rep, uint64_t seed, uint32_t* __restrict__ ntot,
+                                                              uint32_t* __restrict__ ntail) {
+    __shared__ uint32_t sh[BOOT_WAVES][BOOT_REP_TILE];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t c = blockIdx.x, c0 = c * BOOT_CHUNK, c1 = c0 + BOOT_CHUNK < n2 ? c0 + BOOT_CHUNK : n2;
+    const int64_t tail_lo = (int64_t)f[c1 - 1] > c0 ? (int64_t)f[c1 - 1] : c0;
+    bool neg[BOOT_ITEMS], tail[BOOT_ITEMS];
+    uint32_t clu[BOOT_ITEMS];
+#pragma unroll
+    for (int k = 0; k < BOOT_ITEMS; ++k) {
+        const int64_t pos = c0 + tid * BOOT_ITEMS + k;
+        neg[k] = false; tail[k] = false; clu[k] = 0u;
+        if (pos < c1) {
+            neg[k] = (keys[pos] & 1ull) == 0ull;
+            clu[k] = cl[pos];
+            tail[k] = pos >= tail_lo;
+        }
+    }
+    const int ntiles = (n_rep + BOOT_REP_TILE - 1) / BOOT_REP_TILE;
+    for (int t = blockIdx.y; t < ntiles; t += gridDim.y) {
+        uint32_t v[BOOT_REP_TILE];
+#pragma unroll
+        for (int r = 0; r < BOOT_REP_TILE; ++r) {
+            const uint64_t base = boot_rep_base(seed, (uint32_t)(t * BOOT_REP_TILE + r));
+            uint32_t a = 0u;
+#pragma unroll
+            for (int k = 0; k < BOOT_ITEMS; ++k)
+                if (neg[k]) {
+                    const uint32_t w = boot_weight(base, clu[k]);
+                    a += tail[k] ? w * 0x10001u : w;                       // low half: the chunk, high half: its last run
+                }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+            v[r] = a;
+        }
+        if (lane == 0)
+            for (int r = 0; r < BOOT_REP_TILE; ++r) sh[wave][r] = v[r];
+        __syncthreads();
+        if (tid < BOOT_REP_TILE) {
+            uint32_t s = 0u;
+            for (int w = 0; w < BOOT_WAVES; ++w) s += sh[w][tid];
+            const int rr = t * BOOT_REP_TILE + tid;
+            if (rr < n_rep) {
+                ntot[(int64_t)rr * nchunks + c] = s & 0xffffu;
+                ntail[(int64_t)rr * nchunks + c] = s >> 16;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// off[r][c], c in [0, nchunks]: weighted negatives in front of chunk c.  One workgroup per replicate
+__global__ void __launch_bounds__(BOOT_THREADS) k_boot_scan(const uint32_t* __restrict__ ntot, int64_t nchunks,
+                                                            unsigned long long* __restrict__ off) {
+    __shared__ unsigned long long sh[BOOT_THREADS];
+    const int tid = threadIdx.x;
+    const int64_t r = blockIdx.x;
+    unsigned long long carry = 0ull;
+    for (int64_t b = 0; b < nchunks; b += BOOT_THREADS) {
+        const unsigned long long v = b + tid < nchunks ? (unsigned long long)ntot[r * nchunks + b + tid] : 0ull;
+        sh[tid] = v;
+        __syncthreads();
+        for (int o = 1; o < BOOT_THREADS; o <<= 1) {
+            const unsigned long long x = tid >= o ? sh[tid - o] : 0ull;
+            __syncthreads();
+            sh[tid] += x;
+            __syncthreads();
+        }
+        if (b + tid < nchunks) off[r * (nchunks + 1) + b + tid] = carry + sh[tid] - v;
+        carry += sh[BOOT_THREADS - 1];
+        __syncthreads();
+    }
+    if (tid == 0) off[r * (nchunks + 1) + nchunks] = carry;
+}
+
+// slot layout of one chunk / one segment: 3 words per replicate — (W | Wp << 32) of at most BOOT_CHUNK rows, U, the loss sum's bits
+__global__ void __launch_bounds__(BOOT_THREADS) k_boot_pass(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ cl,
+                                                            const double* __restrict__ term, const uint32_t* __restrict__ f,
+                                                            const int64_t* __restrict__ start, int64_t n2, int64_t nchunks,
+                                                            int32_t n_rep, uint64_t seed, const uint32_t* __restrict__ ntail,
+                                                            const unsigned long long* __restrict__ off,
+                                                            unsigned long long* __restrict__ parts,
+                                                            unsigned long long* __restrict__ direct) {
+    __shared__ uint16_t s_pre[BOOT_REP_TILE][BOOT_CHUNK];
+    __shared__ uint32_t s_scan[BOOT_WAVES][BOOT_REP_TILE / 2];
+    __shared__ unsigned long long s_off[BOOT_REP_TILE], s_head[BOOT_REP_TILE];
+    __shared__ unsigned long long s_red[BOOT_WAVES][BOOT_REP_TILE * 3];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t c = blockIdx.x, c0 = c * BOOT_CHUNK, c1 = c0 + BOOT_CHUNK < n2 ? c0 + BOOT_CHUNK : n2;
+    const int64_t d_first = (int64_t)(keys[c0] >> 33), d_last = (int64_t)(keys[c1 - 1] >> 33);
+    const int64_t f_head = f[c0];
+    const bool has_head = f_head < c0;                                     // the first tie run began in an earlier chunk
+    const int64_t c_head = f_head / BOOT_CHUNK;
+    bool ok[BOOT_ITEMS], posv[BOOT_ITEMS];
+    uint32_t clu[BOOT_ITEMS], fl[BOOT_ITEMS];
+    bool f_in[BOOT_ITEMS];
+    double trm[BOOT_ITEMS];
+#pragma unroll
+    for (int k = 0; k < BOOT_ITEMS; ++k) {
+        const int64_t pos = c0 + tid * BOOT_ITEMS + k;
+        ok[k] = pos < c1; posv[k] = false; clu[k] = 0u; fl[k] = 0u; f_in[k] = true; trm[k] = 0.0;
+        if (ok[k]) {
+            posv[k] = (keys[pos] & 1ull) != 0ull;
+            clu[k] = cl[pos];
+            trm[k] = term[pos];
+            const int64_t fk = f[pos];
+            f_in[k] = fk >= c0;
+            fl[k] = f_in[k] ? (uint32_t)(fk - c0) : 0u;
+        }
+    }
+    const int ntiles = (n_rep + BOOT_REP_TILE - 1) / BOOT_REP_TILE;
+    for (int t = blockIdx.y; t < ntiles; t += gridDim.y) {
+        if (tid < BOOT_REP_TILE) {
+            const int rr = t * BOOT_REP_TILE + tid < n_rep ? t * BOOT_REP_TILE + tid : n_rep - 1;
+            const unsigned long long* o = off + (int64_t)rr * (nchunks + 1);
+            s_off[tid] = o[c];
+            s_head[tid] = has_head ? o[c_head + 1] - (unsigned long long)ntail[(int64_t)rr * nchunks + c_head] : 0ull;
+        }
+        // the tile's weights, 4 bits each, and this thread's weighted negatives, two replicates to a word
+        uint32_t wpk[BOOT_ITEMS] = {0u, 0u, 0u, 0u};
+        uint32_t tn[BOOT_REP_TILE / 2] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int r = 0; r < BOOT_REP_TILE; ++r) {
+            const uint64_t base = boot_rep_base(seed, (uint32_t)(t * BOOT_REP_TILE + r));
+#pragma unroll
+            for (int k = 0; k < BOOT_ITEMS; ++k) {
+                const uint32_t w = ok[k] ? boot_weight(base, clu[k]) : 0u;
+                wpk[k] |= w << (4 * r);
+                if (!posv[k]) tn[r >> 1] += w << (16 * (r & 1));
+            }
+        }
+        uint32_t ex[BOOT_REP_TILE / 2];
+#pragma unroll
+        for (int j = 0; j < BOOT_REP_TILE / 2; ++j) {
+            uint32_t v = tn[j];
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint32_t x = __shfl_up(v, o, 64);
+                if (lane >= o) v += x;
+            }
+            if (lane == 63) s_scan[wave][j] = v;
+            ex[j] = v - tn[j];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < BOOT_REP_TILE / 2; ++j)
+            for (int w = 0; w < wave; ++w) ex[j] += s_scan[w][j];
+#pragma unroll
+        for (int r = 0; r < BOOT_REP_TILE; ++r) {
+            uint32_t e = (ex[r >> 1] >> (16 * (r & 1))) & 0xffffu;
+#pragma unroll
+            for (int k = 0; k < BOOT_ITEMS; ++k) {
+                s_pre[r][tid * BOOT_ITEMS + k] = (uint16_t)e;              // weighted negatives of the chunk in front of the item
+                if (!posv[k]) e += (wpk[k] >> (4 * r)) & 15u;
+            }
+        }
+        __syncthreads();
+        for (int64_t d = d_first; d <= d_last; ++d) {
+            int64_t lo = c0, hi = c1;
+            if (d_first != d_last) {
+                lo = start[d] > c0 ? start[d] : c0;
+                hi = start[d + 1] < c1 ? start[d + 1] : c1;
+                if (lo >= hi) continue;                                    // uniform: no row of d in this chunk
+            }
+            bool in[BOOT_ITEMS];
+#pragma unroll
+            for (int k = 0; k < BOOT_ITEMS; ++k) {
+                const int64_t pos = c0 + tid * BOOT_ITEMS + k;
+                in[k] = pos >= lo && pos < hi;
+            }
+#pragma unroll
+            for (int r = 0; r < BOOT_REP_TILE; ++r) {
+                unsigned long long aw = 0ull, au = 0ull;
+                double al = 0.0;
+                const unsigned long long o_r = s_off[r], h_r = s_head[r];
+#pragma unroll
+                for (int k = 0; k < BOOT_ITEMS; ++k) {
+                    const unsigned long long w = in[k] ? (wpk[k] >> (4 * r)) & 15u : 0u;
+                    if (w == 0ull) continue;
+                    al += (double)w * trm[k];
+                    aw += w;
+                    if (posv[k]) {
+                        aw += w << 32;
+                        const unsigned long long below = o_r + s_pre[r][tid * BOOT_ITEMS + k];
+                        const unsigned long long below_run = f_in[k] ? o_r + s_pre[r][fl[k]] : h_r;
+                        au += w * (below + below_run);
+                    }
+                }
+                aw = dl_wave_sum(aw);
+                au = dl_wave_sum(au);
+                al = boot_wave_sum_f64(al);
+                if (lane == 0) {
+                    s_red[wave][r * 3] = aw;
+                    s_red[wave][r * 3 + 1] = au;
+                    s_red[wave][r * 3 + 2] = (unsigned long long)__double_as_longlong(al);
+                }
+            }
+            __syncthreads();
+            if (tid < BOOT_REP_TILE * 3) {
+                const int r = tid / 3, q = tid - 3 * r, rr = t * BOOT_REP_TILE + r;
+                unsigned long long v;
+                if (q < 2) {
+                    v = 0ull;
+                    for (int w = 0; w < BOOT_WAVES; ++w) v += s_red[w][tid];
+                } else {
+                    double a = 0.0;
+                    for (int w = 0; w < BOOT_WAVES; ++w) a += __longlong_as_double((long long)s_red[w][tid]);
+                    v = (unsigned long long)__double_as_longlong(a);
+                }
+                if (rr < n_rep) {
+                    if (d == d_first) parts[((c * 2 + 0) * 3 + q) * n_rep + rr] = v;
+                    else if (d == d_last) parts[((c * 2 + 1) * 3 + q) * n_rep + rr] = v;
+                    else direct[(d * 3 + q) * n_rep + rr] = v;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// tot[d][4][r]: W, Wp, U (over the whole array's prefixes), loss sum — a thread per (segment, replicate), its chunks in order
+__global__ void __launch_bounds__(BOOT_THREADS) k_boot_reduce(const uint64_t* __restrict__ keys, const int64_t* __restrict__ start,
+                                                              int64_t n2, int32_t n_rep, int32_t n_seg,
+                                                              const unsigned long long* __restrict__ parts,
+                                                              const unsigned long long* __restrict__ direct,
+                                                              unsigned long long* __restrict__ tot) {
+    const int64_t id = (int64_t)blockIdx.x * BOOT_THREADS + threadIdx.x;
+    const int64_t d = id / n_rep, r = id - d * n_rep;
+    if (d >= n_seg) return;
+    const int64_t s0 = start[d], s1 = start[d + 1];
+    unsigned long long W = 0ull, Wp = 0ull, U = 0ull;
+    double Ls = 0.0;
+    if (s1 > s0) {
+        const int64_t ca = s0 / BOOT_CHUNK, cb = (s1 - 1) / BOOT_CHUNK;
+        for (int64_t c = ca; c <= cb; ++c) {
+            const int64_t c0 = c * BOOT_CHUNK, c1 = c0 + BOOT_CHUNK < n2 ? c0 + BOOT_CHUNK : n2;
+            const int64_t df = (int64_t)(keys[c0] >> 33), dl = (int64_t)(keys[c1 - 1] >> 33);
+            const unsigned long long* p = df == d ? parts + (c * 2 + 0) * 3 * n_rep : (dl == d ? parts + (c * 2 + 1) * 3 * n_rep
+                                                                                               : direct + d * 3 * n_rep);
+            const unsigned long long wv = p[r];
+            W += wv & 0xffffffffull;
+            Wp += wv >> 32;
+            U += p[n_rep + r];
+            Ls += __longlong_as_double((long long)p[2 * n_rep + r]);
+        }
+    }
+    unsigned long long* o = tot + d * 4 * n_rep;
+    o[r] = W; o[n_rep + r] = Wp; o[2 * n_rep + r] = U; o[3 * n_rep + r] = (unsigned long long)__double_as_longlong(Ls);
+}
+
+// out: auc [n_rep, n_seg], loss [n_rep, n_seg]; counts (when given): W, Wp.  A thread per replicate walks the segments in sorted order
+__global__ void __launch_bounds__(BOOT_THREADS) k_boot_final(const unsigned long long* __restrict__ tot, int32_t n_rep, int32_t n_seg,
+                                                             double* __restrict__ out, int64_t* __restrict__ counts) {
+    const int64_t r = (int64_t)blockIdx.x * BOOT_THREADS + threadIdx.x;
+    if (r >= n_rep) return;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    unsigned long long before = 0ull;                                      // weighted negatives of the segments in front
+    for (int64_t d = 0; d < n_seg; ++d) {
+        const unsigned long long* t = tot + d * 4 * n_rep;
+        const unsigned long long W = t[r], Wp = t[n_rep + r], Wn = W - Wp;
+        const unsigned long long U2 = t[2 * n_rep + r] - 2ull * Wp * before;
+        double auc = nan, loss = nan;
+        if (Wp > 0ull && Wn > 0ull) {
+            auc = (double)U2 / (double)(2ull * Wp * Wn);
+            loss = __longlong_as_double((long long)t[3 * n_rep + r]) / (double)W;
+        }
+        out[r * n_seg + d] = auc;
+        out[((int64_t)n_rep + r) * n_seg + d] = loss;
+        if (counts) {
+            counts[r * n_seg + d] = (int64_t)W;
+            counts[((int64_t)n_rep + r) * n_seg + d] = (int64_t)Wp;
+        }
+        before += Wn;
+    }
+}
+
+// k_gauc_sum under the replicates' weights: part[d][slice][r] = (sum w omega A, sum w omega), cnt = counted users with w > 0
+__global__ void __launch_bounds__(GAUC_THREADS) k_boot_gauc(const uint64_t* __restrict__ keys, const GaucScan* __restrict__ sc,
+                                                            const unsigned long long* __restrict__ W, const int64_t* __restrict__ start,
+                                                            const double* __restrict__ user_weight, int64_t n_user, int64_t n2,
+                                                            int32_t n_rep, uint64_t seed, double* __restrict__ part,
+                                                            int64_t* __restrict__ part_cnt) {
+    __shared__ double s_red[GAUC_THREADS / 64][BOOT_REP_TILE * 3];
+    const int d = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t s0 = start[d], s1 = start[d + 1];
+    const int64_t per = (s1 - s0 + GAUC_SLICES - 1) / GAUC_SLICES;
+    const int64_t a = s0 + (int64_t)sl * per, b = a + per < s1 ? a + per : s1;
+    const uint64_t gbase = (uint64_t)d * (uint64_t)n_user;
+    const int ntiles = (n_rep + BOOT_REP_TILE - 1) / BOOT_REP_TILE;
+    for (int t = blockIdx.z; t < ntiles; t += gridDim.z) {
+        uint64_t base[BOOT_REP_TILE];
+        double num[BOOT_REP_TILE], den[BOOT_REP_TILE], cnt[BOOT_REP_TILE];     // cnt: a count below 2^31, exact in a double
+#pragma unroll
+        for (int r = 0; r < BOOT_REP_TILE; ++r) {
+            base[r] = boot_rep_base(seed, (uint32_t)(t * BOOT_REP_TILE + r));
+            num[r] = 0.0; den[r] = 0.0; cnt[r] = 0.0;
+        }
+        for (int64_t i = a + tid; i < b; i += GAUC_THREADS) {
+            const uint64_t g = keys[i] >> 32;
+            if (i + 1 < n2 && (keys[i + 1] >> 32) == g) continue;          // not the last row of its group
+            const GaucScan e = sc[i];
+            const int64_t h = e.h;
+            const int64_t rows = i - h + 1;
+            const int64_t N = (int64_t)(e.cn - (h ? sc[h - 1].cn : 0u)), P = rows - N;
+            if (P == 0 || N == 0) continue;
+            const unsigned long long u2 = W[i] - (h ? W[h - 1] : 0ull);
+            const double auc = (double)u2 / (2.0 * (double)P * (double)N);  // k_gauc_sum's expression
+            const double w = user_weight ? user_weight[g - gbase] : (double)rows;
+            const uint32_t u = (uint32_t)(g - gbase);
+#pragma unroll
+            for (int r = 0; r < BOOT_REP_TILE; ++r) {
+                const uint32_t wt = boot_weight(base[r], u);
+                if (wt == 0u) continue;
+                const double ww = (double)wt * w;
+                num[r] += ww * auc;
+                den[r] += ww;
+                cnt[r] += 1.0;
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < BOOT_REP_TILE; ++r) {
+            const double x = boot_wave_sum_f64(num[r]), y = boot_wave_sum_f64(den[r]), z = boot_wave_sum_f64(cnt[r]);
+            if (lane == 0) { s_red[wave][r * 3] = x; s_red[wave][r * 3 + 1] = y; s_red[wave][r * 3 + 2] = z; }
+        }
+        __syncthreads();
+        if (tid < BOOT_REP_TILE * 3) {
+            const int r = tid / 3, q = tid - 3 * r, rr = t * BOOT_REP_TILE + r;
+            double v = 0.0;
+            for (int w = 0; w < GAUC_THREADS / 64; ++w) v += s_red[w][tid];
+            if (rr < n_rep) {
+                const int64_t o = ((int64_t)d * GAUC_SLICES + sl) * n_rep + rr;
+                if (q < 2) part[o * 2 + q] = v; else part_cnt[o] = (int64_t)v;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(BOOT_THREADS) k_boot_gauc_final(const double* __restrict__ part, const int64_t* __restrict__ part_cnt,
+                                                                  int32_t n_rep, int32_t n_seg, double* __restrict__ out) {
+    const int64_t id = (int64_t)blockIdx.x * BOOT_THREADS + threadIdx.x;
+    const int64_t d = id / n_rep, r = id - d * n_rep;
+    if (d >= n_seg) return;
+    double num = 0.0, den = 0.0;
+    int64_t cnt = 0;
+    for (int sl = 0; sl < GAUC_SLICES; ++sl) {
+        const int64_t o = (d * GAUC_SLICES + sl) * n_rep + r;
+        num += part[o * 2]; den += part[o * 2 + 1]; cnt += part_cnt[o];
+    }
+    out[r * n_seg + d] = cnt > 0 ? num / den : __longlong_as_double(0x7ff8000000000000ll);
+}
+
+struct BootLayout {
+    int64_t keys_in, keys_out, idx_in, idx_out, f, start, ntot, ntail, off, parts, direct, tot, gauc, gpart, gcnt, temp, temp_bytes, total;
+    int64_t nchunks;
+    GaucLayout g;                       // cdc_eval_gauc's arrays, offsets from `gauc`
+};
+// everything but rocPRIM's temporary storage: plain arithmetic (argument checks use it before any HIP or rocPRIM call)
+static void boot_fixed_layout(int64_t n, int32_t n_domain, int32_t n_rep, int32_t gauc, BootLayout* L) {
+    const int64_t n2 = 2 * n, seg = (int64_t)n_domain + 1, nc = cdc_ceil_div(n2, BOOT_CHUNK), R = n_rep;
+    int64_t off = 0;
+    L->nchunks = nc;
+    L->keys_in = off;  off += align_up(n2 * 8);               // after the sort: the loss terms
+    L->keys_out = off; off += align_up(n2 * 8);
+    L->idx_in = off;   off += align_up(n2 * 4);               // after the sort: the clusters
+    L->idx_out = off;  off += align_up(n2 * 4);
+    L->f = off;        off += align_up(n2 * 4);
+    L->start = off;    off += align_up((seg + 1) * 8);
+    L->ntot = off;     off += align_up(R * nc * 4);
+    L->ntail = off;    off += align_up(R * nc * 4);
+    L->off = off;      off += align_up(R * (nc + 1) * 8);
+    L->parts = off;    off += align_up(nc * 2 * 3 * R * 8);
+    L->direct = off;   off += align_up(seg * 3 * R * 8);
+    L->tot = off;      off += align_up(seg * 4 * R * 8);
+    L->gauc = off;
+    L->gpart = off; L->gcnt = off;
+    if (gauc) {
+        gauc_fixed_layout(n, n_domain, &L->g);
+        off += L->g.total;
+        L->gpart = off; off += align_up(seg * GAUC_SLICES * R * 2 * 8);
+        L->gcnt = off;  off += align_up(seg * GAUC_SLICES * R * 8);
+    }
+    L->temp = off;
+    L->temp_bytes = 0;
+    L->total = off;
+}
+static int boot_layout(int64_t n, int32_t n_domain, int32_t n_rep, int32_t gauc, BootLayout* L) {
+    boot_fixed_layout(n, n_domain, n_rep, gauc, L);
+    size_t t_sort = 0;
+    hipError_t e = rocprim::radix_sort_pairs(nullptr, t_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr,
+                                             (uint32_t*)nullptr, (size_t)(2 * n), 0, 64, (hipStream_t)0, false);
+    if (e != hipSuccess) { cdc_set_error("eval_bootstrap: rocprim size query failed: %s", hipGetErrorString(e)); return (int)e; }
+    int64_t t_gauc = 0;
+    if (gauc) {
+        const int rc = gauc_temp_bytes(n, "eval_bootstrap", &t_gauc);
+        if (rc != 0) return rc;
+    }
+    L->temp_bytes = std::max<int64_t>((int64_t)t_sort, t_gauc);             // the sorts and scans run one after the other
+    L->total = L->temp + align_up(L->temp_bytes);
+    if (gauc) {                                                             // as gauc_order reads them: from the sub-block's base
+        L->g.temp = L->temp - L->gauc;
+        L->g.temp_bytes = L->temp_bytes;
+    }
+    return 0;
+}
+// 72 n^2 bounds U2 and 2 Wp Wn (weights <= 12): it must fit 64 bits
+static bool boot_sizes_ok(int64_t n, int32_t n_domain, int32_t n_rep) {
+    return n > 0 && n < (1ll << 28) && n_domain > 0 && n_domain < (1 << 20) && n_rep >= 1 && n_rep <= BOOT_MAX_REP;
+}
+
+extern "C" int64_t cdc_eval_bootstrap_workspace_bytes(int64_t n, int32_t n_domain, int64_t n_cluster, int32_t n_rep, int32_t gauc) {
+    if (!boot_sizes_ok(n, n_domain, n_rep)) return 0;
+    if (gauc && !gauc_sizes_ok(n, n_domain, n_cluster)) return 0;
+    BootLayout L;
+    if (boot_layout(n, n_domain, n_rep, gauc != 0, &L) != 0) return -1;
+    return L.total;
+}
+
+extern "C" int cdc_eval_bootstrap(const float* pred_a, const float* pred_b, const int16_t* label, const int32_t* cluster, int64_t ld_cluster,
+                                  int64_t n_cluster, const int32_t* domain, int64_t ld_domain, int32_t n_domain, const double* user_weight,
+                                  int64_t n, int32_t n_rep, uint64_t seed, int32_t gauc, double* out, int64_t* counts, int32_t* err_flag,
+                                  void* workspace, int64_t workspace_bytes, void* stream) {
+    CDC_CHECK_ARG(pred_a && label && out && counts && workspace, CDC_E_BADARG, "eval_bootstrap: null pointer");
+    CDC_CHECK_ARG(n > 0 && n_domain > 0 && n_domain < (1 << 20) && ld_cluster >= 0 && ld_domain >= 0 && (!cluster || n_cluster > 0),
+                  CDC_E_BADARG, "eval_bootstrap: bad sizes n=%ld n_domain=%d n_cluster=%ld", (long)n, n_domain, (long)n_cluster);
+    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_bootstrap: n_domain=%d needs the domain column", n_domain);
+    CDC_CHECK_ARG(n_rep >= 1 && n_rep <= BOOT_MAX_REP, CDC_E_BADARG, "eval_bootstrap: n_rep=%d outside [1, %d]", n_rep, BOOT_MAX_REP);
+    CDC_CHECK_ARG(!gauc || cluster, CDC_E_BADARG, "eval_bootstrap: GAUC needs the cluster column (a row's user)");
+    CDC_CHECK_ARG(n < (1ll << 28), CDC_E_TOOBIG, "eval_bootstrap: n=%ld exceeds the 2^28 rows whose weighted pair count fits 64 bits", (long)n);
+    CDC_CHECK_ARG(!gauc || gauc_sizes_ok(n, n_domain, n_cluster), CDC_E_BADARG,
+                  "eval_bootstrap: (n_domain + 1) * n_cluster = %ld * %ld group ids exceed 2^32", (long)n_domain + 1, (long)n_cluster);
+    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_bootstrap: workspace must be 256-byte aligned");
+    gauc = gauc != 0;
+    const int32_t paired = pred_b != nullptr;
+    BootLayout L;
+    boot_fixed_layout(n, n_domain, n_rep, gauc, &L);
+    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_bootstrap: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
+    int rc = boot_layout(n, n_domain, n_rep, gauc, &L);
+    if (rc != 0) return rc;
+    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_bootstrap: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
+    char* base = (char*)workspace;
+    uint64_t* keys_in = (uint64_t*)(base + L.keys_in);
+    uint64_t* keys = (uint64_t*)(base + L.keys_out);
+    uint32_t* idx_in = (uint32_t*)(base + L.idx_in);
+    uint32_t* idx = (uint32_t*)(base + L.idx_out);
+    double* term = (double*)keys_in;                                // the unsorted keys and payloads are dead once the sort has run
+    uint32_t* cl = idx_in;
+    uint32_t* f = (uint32_t*)(base + L.f);
+    int64_t* start = (int64_t*)(base + L.start);
+    uint32_t* ntot = (uint32_t*)(base + L.ntot);
+    uint32_t* ntail = (uint32_t*)(base + L.ntail);
+    unsigned long long* off = (unsigned long long*)(base + L.off);
+    unsigned long long* parts = (unsigned long long*)(base + L.parts);
+    unsigned long long* direct = (unsigned long long*)(base + L.direct);
+    unsigned long long* tot = (unsigned long long*)(base + L.tot);
+    char* gbase = base + L.gauc;
+    double* gpart = (double*)(base + L.gpart);
+    int64_t* gcnt = (int64_t*)(base + L.gcnt);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n2 = 2 * n, nc = L.nchunks;
+    const int seg = n_domain + 1, n_stat = 2 + gauc;
+    const int ntiles = (n_rep + BOOT_REP_TILE - 1) / BOOT_REP_TILE;
+    // the chunk passes put replicate tiles side by side only while the grid is small: a chunk's rows are read once per workgroup.
+    // GAUC's slices are uneven ("all rows" holds half the positions in 64 of them), so there the tiles go side by side much longer
+    const int gy = (int)std::min<int64_t>(ntiles, std::max<int64_t>(1, 2048 / nc));
+    const int gz = (int)std::min<int64_t>(ntiles, std::max<int64_t>(1, 131072 / ((int64_t)seg * GAUC_SLICES)));
+    int end_bit = 34;
+    while (end_bit < 64 && ((uint64_t)n_domain >> (end_bit - 33)) != 0) ++end_bit;
+    for (int v = 0; v <= paired; ++v) {
+        const float* pred = v ? pred_b : pred_a;
+        double* o = out + (int64_t)v * n_stat * n_rep * seg;
+        int blocks = (int)std::min<int64_t>(cdc_ceil_div(n, MET_THREADS), 4096);
+        hipLaunchKernelGGL(k_boot_keys, dim3(blocks), dim3(MET_THREADS), 0, st, pred, label, cluster, ld_cluster, n_cluster, domain,
+                           ld_domain, n, n_domain, keys_in, idx_in, err_flag);
+        CDC_LAUNCH_CHECK("eval_bootstrap(keys)");
+        size_t temp_bytes = (size_t)L.temp_bytes;
+        hipError_t e = rocprim::radix_sort_pairs(base + L.temp, temp_bytes, (const uint64_t*)keys_in, keys, (const uint32_t*)idx_in, idx,
+                                                 (size_t)n2, 0, end_bit, st, false);
+        if (e != hipSuccess) { cdc_set_error("eval_bootstrap: radix sort failed: %s", hipGetErrorString(e)); return (int)e; }
+        hipLaunchKernelGGL(k_boot_starts, dim3((int)cdc_ceil_div(seg + 1, 64)), dim3(64), 0, st, (const uint64_t*)keys, n2, seg, start);
+        CDC_LAUNCH_CHECK("eval_bootstrap(starts)");
+        blocks = (int)std::min<int64_t>(cdc_ceil_div(n2, MET_THREADS), 8192);
+        hipLaunchKernelGGL(k_boot_prep, dim3(blocks), dim3(MET_THREADS), 0, st, (const uint64_t*)keys, (const uint32_t*)idx, cluster,
+                           ld_cluster, n_cluster, n, n2, cl, term, f);
+        CDC_LAUNCH_CHECK("eval_bootstrap(prep)");
+        hipLaunchKernelGGL(k_boot_totals, dim3((unsigned)nc, gy), dim3(BOOT_THREADS), 0, st, (const uint64_t*)keys, (const uint32_t*)cl,
+                           (const uint32_t*)f, n2, nc, n_rep, seed, ntot, ntail);
+        CDC_LAUNCH_CHECK("eval_bootstrap(totals)");
+        hipLaunchKernelGGL(k_boot_scan, dim3(n_rep), dim3(BOOT_THREADS), 0, st, (const uint32_t*)ntot, nc, off);
+        CDC_LAUNCH_CHECK("eval_bootstrap(scan)");
+        hipLaunchKernelGGL(k_boot_pass, dim3((unsigned)nc, gy), dim3(BOOT_THREADS), 0, st, (const uint64_t*)keys, (const uint32_t*)cl,
+                           (const double*)term, (const uint32_t*)f, (const int64_t*)start, n2, nc, n_rep, seed, (const uint32_t*)ntail,
+                           (const unsigned long long*)off, parts, direct);
+        CDC_LAUNCH_CHECK("eval_bootstrap(pass)");
+        hipLaunchKernelGGL(k_boot_reduce, dim3((unsigned)cdc_ceil_div((int64_t)seg * n_rep, BOOT_THREADS)), dim3(BOOT_THREADS), 0, st,
+                           (const uint64_t*)keys, (const int64_t*)start, n2, n_rep, seg, (const unsigned long long*)parts,
+                           (const unsigned long long*)direct, tot);
+        CDC_LAUNCH_CHECK("eval_bootstrap(reduce)");
+        hipLaunchKernelGGL(k_boot_final, dim3((unsigned)cdc_ceil_div(n_rep, BOOT_THREADS)), dim3(BOOT_THREADS), 0, st,
+                           (const unsigned long long*)tot, n_rep, seg, o, v ? (int64_t*)nullptr : counts);   // the counts follow from the
+        CDC_LAUNCH_CHECK("eval_bootstrap(final)");                                                         // labels and weights alone
+        if (!gauc) continue;
+        unsigned long long* Wg = (unsigned long long*)(gbase + L.g.keys_in);
+        rc = gauc_order(pred, label, cluster, ld_cluster, n_cluster, domain, ld_domain, n_domain, n, err_flag, gbase, L.g, Wg,
+                        "eval_bootstrap", st);
+        if (rc != 0) return rc;
+        hipLaunchKernelGGL(k_boot_gauc, dim3(seg, GAUC_SLICES, gz), dim3(GAUC_THREADS), 0, st, (const uint64_t*)(gbase + L.g.keys_out),
+                           (const GaucScan*)(gbase + L.g.scan), (const unsigned long long*)Wg, (const int64_t*)(gbase + L.g.start),
+                           user_weight, n_cluster, n2, n_rep, seed, gpart, gcnt);
+        CDC_LAUNCH_CHECK("eval_bootstrap(gauc)");
+        hipLaunchKernelGGL(k_boot_gauc_final, dim3((unsigned)cdc_ceil_div((int64_t)seg * n_rep, BOOT_THREADS)), dim3(BOOT_THREADS), 0, st,
+                           (const double*)gpart, (const int64_t*)gcnt, n_rep, seg, o + (int64_t)2 * n_rep * seg);
+        CDC_LAUNCH_CHECK("eval_bootstrap(gauc final)");
+    }
+    return 0;
+}

@@ -21,6 +21,13 @@ for two prediction vectors over the same rows the paired difference with its sta
 `cdc_eval_gauc_ci`); `Evaluator(loss_ci=True, gauc_ci=True)` and `Evaluator.compare` report them — the log-loss delta is the one
 figure that moves when a model is recalibrated.
 
+`eval_bootstrap` covers what those analytic errors leave out: DeLong's and the log-loss's take rows as independent, the per-domain
+figures share users, and so do two models on one evaluation set.  It resamples whole users — one weight per user and replicate,
+applied to all of the user's rows in every domain and under both prediction vectors — and recomputes AUC, log-loss and GAUC for every
+replicate on the device (`cdc_eval_bootstrap`: the rows are sorted once, the replicates reuse that order); `summarize_bootstrap`
+gives the standard error and the percentile interval, `Evaluator(bootstrap=R)` reports them, mean_gauc's and the deltas of
+`Evaluator.compare` included.
+
 `eval_calibration` reports whether the predicted probabilities are right, where the figures above only say how well they rank: per
 domain and over all rows the ratio of predicted to observed CTR, the Brier score, and a reliability table with ECE / MCE for
 equal-width and equal-mass bins (`cdc_eval_calibration`); `Evaluator(calibration=True)` and `Evaluator.calibration_table` report them.
@@ -264,7 +271,7 @@ def eval_loss_ci(pred, label, domain=None, n_domain=1, pred_b=None):
     vectors are close).  A standard error is `var.sqrt()`.  Every figure is NaN for an empty or single-class segment, as
     `eval_metrics`' loss is.  No host synchronisation; the error word (1 + a row with a NaN prediction or one outside [0, 1] in
     either vector, a label outside {0, 1} or a domain outside range) is kept as `eval_loss_ci.last_err`.
-    Not offered: a user-clustered variance of the log-loss (`eval_gauc_ci` clusters by user; this does not)."""
+    A user-clustered error of the log-loss comes from `eval_bootstrap` with the user column as its clusters, not from here."""
     lib = L.load()
     if not pred.is_cuda:
         raise L.HipExtensionError("eval_loss_ci needs device tensors; there is no CPU fallback")
@@ -365,6 +372,125 @@ def eval_gauc_ci(pred, label, user, n_user, domain=None, n_domain=1, user_weight
     if paired:
         return GaucCIPaired(o[0], o[1], counts[:seg], counts[seg:], o[2], o[3], o[4], o[5])
     return GaucCI(o[0], o[1], counts[:seg], counts[seg:])
+
+
+BOOT_CHUNK = 1024               # csrc/metrics.hip BOOT_CHUNK: sorted positions per workgroup of the bootstrap's passes
+BOOT_REP_TILE = 8               # csrc/metrics.hip BOOT_REP_TILE: replicates a workgroup forms weights for at a time
+BOOT_MAX_REP = 4096
+BOOT_MAX_ROWS = (1 << 28) - 1   # 72 n^2 bounds the weighted pair count and must fit 64 bits
+
+Bootstrap = collections.namedtuple("Bootstrap", "auc loss gauc w_rows w_pos auc_b loss_b gauc_b")
+
+
+def eval_bootstrap(pred, label, cluster=None, n_cluster=None, domain=None, n_domain=1, n_rep=200, seed=0, user_weight=None, gauc=None,
+                   pred_b=None):
+    """Clustered bootstrap replicates of AUC, log-loss and GAUC (`cdc_eval_bootstrap`).  pred, label, domain, n_domain, user_weight,
+    pred_b as `eval_gauc_ci`; `cluster` int32 [n] or a strided column view with ids in [0, n_cluster) — the user column — or None:
+    then every row is its own cluster, a plain row bootstrap.  Replicate r draws ONE weight per cluster, a Poisson(1) variate capped
+    at 12 that is a fixed function of (seed, r, cluster) (include/cdcmdr.h spells the hash out), and applies it to all of the
+    cluster's rows: in every domain, in the "all rows" column and under both prediction vectors.  Every figure is recomputed under
+    those weights, so the spread over replicates carries the correlations the analytic errors leave out: within a user, across
+    domains, between two models.  `gauc`: None = when a cluster column is given.
+    Returns a namedtuple `Bootstrap` of device tensors [n_rep, n_domain + 1] (domains 0..n_domain-1, then ALL rows): `auc`, `loss`,
+    `gauc` (f64; gauc None when not computed), `w_rows`, `w_pos` (i64: the weighted row and positive counts), and with `pred_b` also
+    `auc_b`, `loss_b`, `gauc_b` (else None) under the SAME weights: a delta's replicates are `auc - auc_b`.  auc and loss are NaN
+    where a replicate leaves a segment without a class, gauc where no counted user has a positive weight.  auc does not depend on
+    the row order, loss only within rounding.  At most 2^28 - 1 rows, n_rep in [1, 4096].  No host synchronisation; the error word
+    (1 + a row with a NaN prediction in either vector, a label outside {0, 1}, a domain or a cluster outside range) is kept as
+    `eval_bootstrap.last_err`.  `summarize_bootstrap` turns a replicate matrix into a standard error and a percentile interval.
+    Not offered: BCa or studentised intervals, a bootstrap of the calibration figures."""
+    lib = L.load()
+    n_domain, n_rep, seed = int(n_domain), int(n_rep), int(seed)
+    if n_domain <= 0:
+        raise ValueError(f"n_domain={n_domain} must be positive")
+    if not 1 <= n_rep <= BOOT_MAX_REP:
+        raise ValueError(f"n_rep={n_rep} must lie in [1, {BOOT_MAX_REP}]")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed={seed} must fit 64 unsigned bits")
+    if gauc is None:
+        gauc = cluster is not None
+    gauc = bool(gauc)
+    if gauc and cluster is None:
+        raise ValueError("gauc needs the cluster column: GAUC is the mean over a user's AUCs")
+    if cluster is not None:
+        if n_cluster is None:
+            raise ValueError("a cluster column needs n_cluster, the size of the id range")
+        n_cluster = int(n_cluster)
+        if n_cluster <= 0:
+            raise ValueError(f"n_cluster={n_cluster} must be positive")
+        if gauc and (n_domain + 1) * n_cluster > 1 << 32:
+            raise ValueError(f"(n_domain + 1) * n_cluster = {(n_domain + 1) * n_cluster} group ids exceed 2^32, the upper half of a sort key")
+    else:
+        n_cluster = 0
+    if not pred.is_cuda:
+        raise L.HipExtensionError("eval_bootstrap needs device tensors; there is no CPU fallback")
+    pred = pred.reshape(-1).to(torch.float32).contiguous()
+    label = label.reshape(-1).to(torch.int16).contiguous()
+    n = pred.numel()
+    if label.numel() != n:
+        raise ValueError(f"{n} predictions but {label.numel()} labels")
+    if n > BOOT_MAX_ROWS:
+        raise ValueError(f"{n} rows exceed the {BOOT_MAX_ROWS} whose weighted pair count fits 64 bits")
+    if pred_b is not None:
+        pred_b = pred_b.reshape(-1).to(device=pred.device, dtype=torch.float32).contiguous()
+        if pred_b.numel() != n:
+            raise ValueError(f"{n} predictions but {pred_b.numel()} in pred_b")
+    ld_cluster = 0
+    if cluster is not None:
+        cluster, ld_cluster = _id_column(cluster, n, "cluster")
+    ld_domain = 0
+    if domain is not None:
+        domain, ld_domain = _id_column(domain, n, "domain")
+    elif n_domain != 1:
+        raise ValueError("n_domain > 1 needs the domain column")
+    dev = pred.device
+    if user_weight is not None and gauc:
+        user_weight = torch.as_tensor(user_weight, dtype=torch.float64).to(dev).reshape(-1).contiguous()
+        if user_weight.numel() != n_cluster:
+            raise ValueError(f"user_weight holds {user_weight.numel()} entries for {n_cluster} clusters")
+    else:
+        user_weight = None
+    seg = n_domain + 1
+    paired = pred_b is not None
+    n_stat = (3 if gauc else 2) * (2 if paired else 1)
+    out = torch.empty((n_stat, n_rep, seg), dtype=torch.float64, device=dev)
+    counts = torch.empty((2, n_rep, seg), dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    nbytes = lib.cdc_eval_bootstrap_workspace_bytes(n, n_domain, n_cluster, n_rep, int(gauc))
+    if nbytes <= 0:
+        raise RuntimeError(f"cdc_eval_bootstrap_workspace_bytes refused n={n}, n_domain={n_domain}, n_cluster={n_cluster}, n_rep={n_rep}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    L.launch("cdc_eval_bootstrap", lib.cdc_eval_bootstrap,
+             (pred.data_ptr(), pred_b.data_ptr() if paired else None, label.data_ptr(), None if cluster is None else cluster.data_ptr(),
+              ld_cluster, n_cluster, None if domain is None else domain.data_ptr(), ld_domain, n_domain,
+              None if user_weight is None else user_weight.data_ptr(), n, n_rep, seed, int(gauc), out.data_ptr(), counts.data_ptr(),
+              err.data_ptr(), ws.data_ptr(), nbytes), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    eval_bootstrap.last_err = err
+    k = 3 if gauc else 2
+    return Bootstrap(out[0], out[1], out[2] if gauc else None, counts[0], counts[1], out[k] if paired else None,
+                     out[k + 1] if paired else None, out[k + 2] if paired and gauc else None)
+
+
+def summarize_bootstrap(reps, level=0.95):
+    """reps: a tensor [n_rep, ...] of bootstrap replicates (any device) -> (se, lo, hi, valid), each of reps' shape without its first
+    axis, on the same device: `se` the standard deviation (ddof 1) over the non-NaN replicates, `lo` / `hi` the percentile interval
+    at (1 -+ level) / 2 (`torch.nanquantile`, linear interpolation), `valid` (i64) the count of non-NaN replicates; se, lo and hi
+    are NaN where valid < 2.  No host synchronisation."""
+    if not 0.0 < float(level) < 1.0:
+        raise ValueError(f"level={level} must lie in (0, 1)")
+    reps = reps.to(torch.float64)
+    ok = ~torch.isnan(reps)
+    valid = ok.sum(0)
+    cnt = valid.to(torch.float64)
+    zero = torch.zeros((), dtype=torch.float64, device=reps.device)
+    mean = torch.where(ok, reps, zero).sum(0) / cnt
+    dev2 = torch.where(ok, (reps - mean) ** 2, zero).sum(0)
+    se = (dev2 / (cnt - 1)).sqrt()
+    q = torch.tensor([(1.0 - level) / 2, (1.0 + level) / 2], dtype=torch.float64, device=reps.device)
+    lo, hi = torch.nanquantile(reps, q, dim=0)
+    few = valid < 2
+    nan = torch.full((), math.nan, dtype=torch.float64, device=reps.device)
+    return torch.where(few, nan, se), torch.where(few, nan, lo), torch.where(few, nan, hi), valid
 
 
 Calibration = collections.namedtuple("Calibration", "rows positives mean_pred ctr pcoc brier ece mce ece_q mce_q table table_q")
@@ -789,7 +915,20 @@ class Evaluator:
             per-domain evaluation domain_gauc_se {d: value}.  mean_gauc_se is NOT offered: a user's rows span domains, so the
             per-domain GAUCs are not independent and sqrt(sum_d w_d^2 var_d) would not be their mean's standard error.  compare()
             adds total_gauc_delta, total_gauc_delta_se, total_gauc_z and the domain_gauc_* forms.
-            Not offered: significance-aware early stopping in `Runner`, mean_gauc_se, a user-clustered standard error of the log-loss.
+            mean_gauc's error and a user-clustered error of the log-loss come from `bootstrap` (mean_gauc_boot_se, *_loss_boot_se).
+    bootstrap: None (off: the result dictionaries and launches are exactly those without it) or the number of replicates of a
+            clustered bootstrap (`eval_bootstrap`; seed `bootstrap_seed`, interval level `bootstrap_level`).  Clusters are the users
+            when user_idx is set, otherwise rows.  test() adds, for auc and loss and with user_idx for gauc, total_*_boot_se,
+            total_*_boot_lo, total_*_boot_hi (standard deviation and percentile interval over the replicates) and with per-domain
+            evaluation domain_*_boot_se/lo/hi {d: value} and mean_*_boot_se/lo/hi — the mean formed PER REPLICATE, sum over the
+            present domains of weight(d) * figure_d, so mean_gauc_boot_se is valid where mean_gauc_se cannot be offered; a replicate
+            in which a present domain is NaN is left out of the mean's summary.  boot_valid is the smallest number of non-NaN
+            replicates behind any reported figure.  compare() adds total_delta_boot_se/lo/hi (+ domain_ / mean_ forms), with loss_ci
+            the *_loss_delta_boot_* forms and with gauc_ci the *_gauc_delta_boot_* forms (mean_gauc_delta_boot_* included), all from
+            per-replicate differences under shared weights.  The bootstrap launches are queued with the others, before the one
+            synchronisation.
+            Not offered: significance-aware early stopping in `Runner`, BCa or studentised intervals, a bootstrap of the calibration
+            figures.
     calibration: test() adds calibration figures (`eval_calibration`; True: 10 bins, an int: that many): total_pcoc (predicted over
             observed CTR), total_brier, total_ece, total_ece_quantile, and with per-domain evaluation domain_pcoc / domain_brier /
             domain_ece / domain_ece_quantile {d: value} and mean_pcoc / mean_brier / mean_ece / mean_ece_quantile, weighted like
@@ -806,8 +945,14 @@ class Evaluator:
 
     def __init__(self, model, mode="multi", domain_idx=None, n_domain=1, domain_cnt_weight=None, is_evaluate_multi_domain=True,
                  user_idx=None, n_user=None, user_weight=None, auc_ci=False, precision=None, calibration=False, recalibration=None,
-                 recalibration_eps=0.0, loss_ci=False, gauc_ci=False):
+                 recalibration_eps=0.0, loss_ci=False, gauc_ci=False, bootstrap=None, bootstrap_seed=0, bootstrap_level=0.95):
         self.model, self.mode = model, mode
+        self.bootstrap = 0 if bootstrap is None else int(bootstrap)         # 0: off
+        if bootstrap is not None and (isinstance(bootstrap, bool) or not 1 <= self.bootstrap <= BOOT_MAX_REP):
+            raise ValueError(f"bootstrap must be None or a number of replicates in [1, {BOOT_MAX_REP}], not {bootstrap!r}")
+        if not 0.0 < float(bootstrap_level) < 1.0:
+            raise ValueError(f"bootstrap_level={bootstrap_level} must lie in (0, 1)")
+        self.bootstrap_seed, self.bootstrap_level = int(bootstrap_seed), float(bootstrap_level)
         if recalibration is not None and recalibration.n_domain > 1 and domain_idx is None:
             raise ValueError(f"a recalibration map over {recalibration.n_domain} domains needs domain_idx, the column that holds a row's domain")
         if not 0.0 <= float(recalibration_eps) <= 0.5:
@@ -915,7 +1060,8 @@ class Evaluator:
         total_gauc (+ domain_gauc, mean_gauc); with auc_ci also total_auc_se (+ domain_auc_se, mean_auc_se); with calibration also
         total_pcoc, total_brier, total_ece, total_ece_quantile (+ domain_* and mean_* of the four); with loss_ci also total_loss_se
         (+ domain_loss_se, mean_loss_se); with gauc_ci also total_gauc_se (+ domain_gauc_se; no mean_gauc_se: the per-domain GAUCs
-        share users and are not independent)."""
+        share users and are not independent); with bootstrap also total_*_boot_se/lo/hi, domain_*_boot_*, mean_*_boot_* for auc, loss
+        and (with user_idx) gauc, and boot_valid."""
         pred, label, domain, user = self._score(data_loader)
         multi = self.is_evaluate_multi_domain
         auc, loss, rows, pos = eval_metrics(pred, label, domain if multi else None, self.n_domain if multi else 1)
@@ -930,6 +1076,12 @@ class Evaluator:
         if self.gauc_ci:                                       # likewise queued
             gauc_var = eval_gauc_ci(pred, label, user, self.n_user, domain if multi else None, self.n_domain if multi else 1,
                                     self.user_weight).var
+        if self.bootstrap:                                     # likewise queued, summaries included
+            boot = self._bootstrap(pred, label, domain, user, multi)
+            stats = {"auc": boot.auc, "loss": boot.loss}
+            if user is not None:
+                stats["gauc"] = boot.gauc
+            boot_sum = self._boot_summary(stats, rows, multi)
         auc, loss, rows, pos = auc.cpu().tolist(), loss.cpu().tolist(), rows.cpu().tolist(), pos.cpu().tolist()   # the one sync
         bad = int(eval_metrics.last_err.item())
         if bad:
@@ -991,7 +1143,54 @@ class Evaluator:
             result["total_gauc_se"] = _se(var[-1])
             if multi:
                 result["domain_gauc_se"] = {d: _se(var[d]) for d in range(self.n_domain) if rows[d] > 0}
+        if self.bootstrap:
+            self._boot_report(result, list(stats), boot_sum, rows, multi)
         return result
+
+    def _bootstrap(self, pred, label, domain, user, multi, pred_b=None, gauc=None):
+        """the replicates of one evaluation set: clusters are the users when user_idx is set, otherwise rows"""
+        return eval_bootstrap(pred, label, user, self.n_user if user is not None else None, domain if multi else None,
+                              self.n_domain if multi else 1, self.bootstrap, self.bootstrap_seed,
+                              self.user_weight if user is not None else None, gauc=gauc, pred_b=pred_b)
+
+    def _boot_summary(self, stats, rows, multi):
+        """stats {name: replicates [n_rep, seg]}, rows: eval's row counts [seg] (device) -> [len(stats), 4, seg + 1] f64 on the device:
+        (se, lo, hi, valid) of every column and, last, of the mean over the present domains, formed PER REPLICATE with mean_auc's
+        weights (a replicate in which a present domain is NaN gives a NaN mean and is left out).  Nothing is read back."""
+        out = []
+        for reps in stats.values():
+            if multi:
+                w = torch.tensor([self._weight(d) for d in range(self.n_domain)], dtype=torch.float64, device=reps.device)
+                present = rows[:self.n_domain] > 0
+                mean = torch.where(present, reps[:, :self.n_domain] * w, torch.zeros((), dtype=torch.float64, device=reps.device)).sum(1)
+            else:
+                mean = torch.full((reps.shape[0],), math.nan, dtype=torch.float64, device=reps.device)
+            se, lo, hi, valid = summarize_bootstrap(torch.cat([reps, mean[:, None]], 1), self.bootstrap_level)
+            out.append(torch.stack([se, lo, hi, valid.to(torch.float64)]))
+        return torch.stack(out)
+
+    def _boot_report(self, result, names, boot_sum, rows, multi):
+        """total_<name>_boot_se / _lo / _hi, with per-domain evaluation domain_<name>_boot_* {d: value} over the present domains and
+        mean_<name>_boot_*; boot_valid = the smallest number of valid replicates over everything reported (the mean's only when
+        domain_cnt_weight is set: without it every mean is NaN)"""
+        summ = boot_sum.cpu().tolist()
+        bad = int(eval_bootstrap.last_err.item())
+        if bad:
+            raise ValueError(f"evaluation row {bad - 1}: NaN prediction, label outside {{0,1}}, domain outside [0, {self.n_domain}) or "
+                             f"user outside range")
+        n_all = len(summ[0][0]) - 2                            # columns: the domains, ALL rows, the mean
+        present = [d for d in range(self.n_domain) if rows[d] > 0] if multi else []
+        valid = []
+        for name, s in zip(names, summ):
+            for k, what in enumerate(("se", "lo", "hi")):
+                result[f"total_{name}_boot_{what}"] = s[k][n_all]
+                if multi:
+                    result[f"domain_{name}_boot_{what}"] = {d: s[k][d] for d in present}
+                    result[f"mean_{name}_boot_{what}"] = s[k][n_all + 1]
+            valid += [s[3][n_all]] + [s[3][d] for d in present]
+            if multi and self.domain_cnt_weight is not None:
+                valid.append(s[3][n_all + 1])
+        result["boot_valid"] = int(min(valid))
 
     def calibration_table(self, data_loader):
         """One scoring pass -> (table, table_q, segments): the equal-width and the equal-mass reliability table as
@@ -1019,7 +1218,10 @@ class Evaluator:
         predictions) and +-inf for a non-zero delta with se 0.  With loss_ci set on this evaluator the same nine keys for the log-loss
         (total_loss_delta, total_loss_delta_se, total_loss_z, domain_loss_*, mean_loss_*: raw against recalibrated shows here, where
         the AUC delta is 0); with gauc_ci set total_gauc_delta, total_gauc_delta_se, total_gauc_z and domain_gauc_* (no mean_gauc_*,
-        as in test()) — then both passes must also see the same user column."""
+        as in test()) — then both passes must also see the same user column.  With bootstrap set total_delta_boot_se/lo/hi (+ domain_
+        and mean_ forms), the *_loss_delta_boot_* forms with loss_ci and the *_gauc_delta_boot_* forms with gauc_ci
+        (mean_gauc_delta_boot_* included), and boot_valid: the replicates weight both models' rows alike; with user_idx the users are
+        resampled and both passes must see the same user column."""
         pred_a, label, domain, user = self._score(data_loader)
         pred_b, label_b, domain_b, user_b = other._score(data_loader)
         if label.shape != label_b.shape or not torch.equal(label, label_b):
@@ -1029,6 +1231,9 @@ class Evaluator:
         if self.gauc_ci and (user_b is None or not torch.equal(user, user_b)):
             raise ValueError("the two scoring passes saw different user columns: compare() with gauc_ci needs the same user_idx in both "
                              "evaluators and a loader that yields the same rows in the same order")
+        if self.bootstrap and user is not None and (user_b is None or not torch.equal(user, user_b)):
+            raise ValueError("the two scoring passes saw different user columns: compare() with bootstrap resamples users and needs the "
+                             "same user_idx in both evaluators and a loader that yields the same rows in the same order")
         multi = self.is_evaluate_multi_domain
         ci = eval_auc_ci(pred_a, label, domain if multi else None, self.n_domain if multi else 1, pred_b=pred_b)
         if self.loss_ci:                                       # queued behind the AUC's: still nothing has been read back
@@ -1036,6 +1241,14 @@ class Evaluator:
         if self.gauc_ci:                                       # likewise queued
             gci = eval_gauc_ci(pred_a, label, user, self.n_user, domain if multi else None, self.n_domain if multi else 1,
                                self.user_weight, pred_b=pred_b)
+        if self.bootstrap:                                     # likewise queued: per-replicate differences under shared weights
+            boot = self._bootstrap(pred_a, label, domain, user, multi, pred_b=pred_b, gauc=self.gauc_ci)
+            stats = {"delta": boot.auc - boot.auc_b}
+            if self.loss_ci:
+                stats["loss_delta"] = boot.loss - boot.loss_b
+            if self.gauc_ci:
+                stats["gauc_delta"] = boot.gauc - boot.gauc_b
+            boot_sum = self._boot_summary(stats, ci.rows, multi)
         delta, var, rows = ci.delta.cpu().tolist(), ci.var_delta.cpu().tolist(), ci.rows.cpu().tolist()
         bad = int(eval_auc_ci.last_err.item())
         if bad:
@@ -1075,6 +1288,8 @@ class Evaluator:
                 d_se = {d: _se(var[d]) for d in present}
                 result.update({"domain_gauc_delta": {d: delta[d] for d in present}, "domain_gauc_delta_se": d_se,
                                "domain_gauc_z": {d: _z(delta[d], d_se[d]) for d in present}})
+        if self.bootstrap:
+            self._boot_report(result, list(stats), boot_sum, rows, multi)
         return result
 
     def _weight(self, d):

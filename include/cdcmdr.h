@@ -1243,6 +1243,40 @@ int cdc_eval_gauc_ci(const float* pred_a, const float* pred_b, const int16_t* la
                      int64_t n, double* out, int64_t* counts, int32_t* err_flag, void* workspace, int64_t workspace_bytes,
                      void* stream);
 
+/* Clustered bootstrap of AUC, log-loss and GAUC: n_rep replicates, each of which draws ONE weight per cluster (a user) and applies it
+ * to all of the cluster's rows, in every segment and under both score vectors.  pred_a, pred_b (or NULL), label, domain, ld_domain,
+ * n_domain, user_weight as for cdc_eval_gauc_ci; cluster int32 (element stride ld_cluster, ids in [0, n_cluster)) or NULL: then
+ * every row is its own cluster (c = the row index), a plain row bootstrap.  n_rep in [1, 4096]; gauc != 0 asks for GAUC, with the
+ * cluster column as cdc_eval_gauc's user column (it needs the column and (n_domain + 1) * n_cluster <= 2^32).
+ *   weight  all arithmetic mod 2^64: mix(x) { x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB;
+ *           x ^= x >> 31; }   h = mix(mix(seed + 0x9E3779B97F4A7C15 * (r + 1)) + c)   u = h >> 32
+ *           w(seed, r, c) = #{k < 12 : u >= T[k]},  T[k] = floor(2^32 e^-1 sum_{j <= k} 1/j!) — Poisson(1) capped at 12.  A weight
+ *           depends on (seed, r, c) alone and is recomputed wherever it is needed, never stored per row.
+ *   auc     U2 / (2 Wp Wn), U2 = sum over (positive i, negative j) of w_i w_j (2 [s_j < s_i] + [s_j = s_i]) (-0.0 ties +0.0),
+ *           Wp = sum w_i y_i, Wn = W - Wp: 64-bit integers, the quotient formed once in double (correctly rounded while
+ *           2 Wp Wn < 2^53); the same rows in any order give the same bits.  With all weights 1 it is cdc_eval_metrics' AUC.
+ *   loss    sum w_i l_i / W with cdc_eval_metrics' per-row term l_i; added in a fixed order, no float atomics: two runs on the
+ *           same input give the same bits, another row order may not.
+ *   gauc    sum_g w_g omega_g A_g / sum_g w_g omega_g over the groups cdc_eval_gauc counts in the segment (A_g its unweighted
+ *           AUC, omega_g its row count in the segment or user_weight[g]); NaN iff no counted group has w_g > 0.
+ *   auc and loss are NaN iff Wp == 0 or Wn == 0.
+ *   out    [n_stat, n_rep, n_domain + 1] doubles, statistics in the order auc, loss, (gauc,) and with pred_b auc_b, loss_b,
+ *          (gauc_b): n_stat = (2 + (gauc != 0)) * (1 + (pred_b != NULL)).  Deltas are the caller's differences of these figures.
+ *   counts [2, n_rep, n_domain + 1] int64: W and Wp.
+ *   err_flag (optional): as cdc_eval_gauc_ci with the cluster column as the user; a bad row is counted with its ids clamped.
+ * The sort by (segment, score), the tie runs and cdc_eval_gauc's order are formed once per vector; the replicates are tiles of a
+ * loop INSIDE a fixed number of launches (it depends on pred_b != NULL and gauc != 0 alone).  Limits: null pointers, bad sizes,
+ * n_domain > 1 without the domain column, n_rep outside [1, 4096], gauc without the cluster column, a workspace too small or not
+ * 256-byte aligned: CDC_E_BADARG; n >= 2^28 (72 n^2 must fit 64 bits): CDC_E_TOOBIG — all before anything is launched.
+ * Stream-ordered: no allocation, no synchronisation, no state kept.
+ * workspace: cdc_eval_bootstrap_workspace_bytes(n, n_domain, n_cluster, n_rep, gauc) bytes, 256-byte aligned; 0 for sizes the call
+ * refuses (n_cluster is read only when gauc != 0). */
+int64_t cdc_eval_bootstrap_workspace_bytes(int64_t n, int32_t n_domain, int64_t n_cluster, int32_t n_rep, int32_t gauc);
+int cdc_eval_bootstrap(const float* pred_a, const float* pred_b, const int16_t* label, const int32_t* cluster, int64_t ld_cluster,
+                       int64_t n_cluster, const int32_t* domain, int64_t ld_domain, int32_t n_domain, const double* user_weight,
+                       int64_t n, int32_t n_rep, uint64_t seed, int32_t gauc, double* out, int64_t* counts, int32_t* err_flag,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Calibration of the predictions cdc_eval_metrics ranks: per segment (domain 0..n_domain-1, then ALL rows) the mean prediction, the
  * CTR, predicted over observed CTR, the Brier score, and a reliability table with ECE / MCE for n_bins = K equal-width and K
  * equal-mass (quantile) bins.  pred, label, domain, ld_domain, n_domain as for cdc_eval_metrics; pred is a probability in [0, 1].
