@@ -378,6 +378,9 @@ _SIGNATURES = {
     "cdc_eval_bootstrap_workspace_bytes": (c_i64, [c_i64, c_i32, c_i64, c_i32, c_i32]),
     "cdc_eval_bootstrap": (c_i32, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_i32, c_p, c_i64, c_i32, C.c_uint64, c_i32, c_p, c_p, c_p,
                                    c_p, c_i64, c_p]),
+    "cdc_eval_calibration_bootstrap_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32, c_i32]),
+    "cdc_eval_calibration_bootstrap": (c_i32, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_i32, c_i32, c_i64, c_i32, C.c_uint64, c_p,
+                                               c_p, c_p, c_p, c_i64, c_p]),
     "cdc_eval_calibration_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
     "cdc_eval_calibration": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
     "cdc_eval_isotonic_max_blocks": (c_i64, [c_i64, c_i32]),

@@ -1487,6 +1487,20 @@ __device__ __forceinline__ int64_t cal_width_bound(const uint64_t* __restrict__ 
     return lo;
 }
 
+// pcoc, brier, ece and ece_q of a segment with m >= 1 (weighted) rows below 2^32 from its exact sums: P positives, Q = sum q, the
+// two halves of sum (q - y 2^32)^2 and the two binnings' sum_b |sum q_b - positives_b 2^32|.  pcoc is left alone when P == 0.
+// k_calib_final and the bootstrap's k_cboot_final both form their doubles here: equal sums give equal bits
+__device__ __forceinline__ void cal_seg_figures(unsigned long long m, unsigned long long P, unsigned long long Q, unsigned long long sq_lo,
+                                                unsigned long long sq_hi, unsigned long long gap_w, unsigned long long gap_q,
+                                                double* pcoc, double* brier, double* ece, double* ece_q) {
+    const double den = (double)m * 4294967296.0;                          // exact
+    const dl_u128 sq = ((dl_u128)sq_hi << 32) + (dl_u128)sq_lo;           // < 2^96
+    if (P > 0) *pcoc = (double)Q / ((double)P * 4294967296.0);
+    *brier = dl_to_double(sq) / ((double)m * 18446744073709551616.0);
+    *ece = (double)gap_w / den;
+    *ece_q = (double)gap_q / den;
+}
+
 // tab_counts [2 binnings][count, positives][n_seg][K], tab_out [2][mean_pred, pos_rate][n_seg][K], tab_range [2][pred_min, pred_max][n_seg][K]
 __global__ void __launch_bounds__(CAL_THREADS) k_calib_final(const uint64_t* __restrict__ keys, const int64_t* __restrict__ start,
                                                              const unsigned long long* __restrict__ acc_w,
@@ -1560,14 +1574,11 @@ __global__ void __launch_bounds__(CAL_THREADS) k_calib_final(const uint64_t* __r
     for (int k = 0; k < CAL_SEG_OUT; ++k) o[k] = nan;
     if (m > 0) {
         const double den = (double)m * 4294967296.0;                      // exact
-        const dl_u128 sq = ((dl_u128)acc_seg[2 * d + 1] << 32) + (dl_u128)acc_seg[2 * d];           // < 2^95
         o[0] = (double)Q / den;
         o[1] = (double)P / (double)m;
-        if (P > 0) o[2] = (double)Q / ((double)P * 4294967296.0);
-        o[3] = dl_to_double(sq) / ((double)m * 18446744073709551616.0);
-        o[4] = (double)sh_u[2][0] / den;
+        cal_seg_figures((unsigned long long)m, P, Q, acc_seg[2 * d], acc_seg[2 * d + 1], sh_u[2][0], sh_u[3][0], &o[2], &o[3], &o[4],
+                        &o[6]);
         o[5] = sh_m[0][0];
-        o[6] = (double)sh_u[3][0] / den;
         o[7] = sh_m[1][0];
     }
 #pragma unroll
@@ -3187,6 +3198,453 @@ extern "C" int cdc_eval_bootstrap(const float* pred_a, const float* pred_b, cons
         hipLaunchKernelGGL(k_boot_gauc_final, dim3((unsigned)cdc_ceil_div((int64_t)seg * n_rep, BOOT_THREADS)), dim3(BOOT_THREADS), 0, st,
                            (const double*)gpart, (const int64_t*)gcnt, n_rep, seg, o + (int64_t)2 * n_rep * seg);
         CDC_LAUNCH_CHECK("eval_bootstrap(gauc final)");
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Clustered bootstrap of the calibration figures: replicate r gives row i the weight w_i = boot_weight(boot_rep_base(seed, r),
+// cluster_i) — cdc_eval_bootstrap's weight — and its figures are cdc_eval_calibration's on the multiset that holds row i w_i times.
+// Per replicate and segment: W = sum w, Wp = sum w y, SQ = sum w q, the halves of sum w (q - y 2^32)^2, and per bin (sum w q,
+// sum w y) for the equal-width bins (a function of p alone) and the equal-mass bins: with the segment's rows in (score, label) order
+// row i holds the expanded positions [R_i, R_i + w_i), R_i the weight in front of it, and bin b the expanded positions
+// [floor(b W / K), floor((b+1) W / K)) — a row's copies may lie in several bins.
+//
+//   keys    k_calib_keys' keys (the prediction clamped into [0, 1]) with the copy index as payload; one radix sort
+//   prep    the cluster of every sorted position (replicate-free); q, the label and the width bin come back out of the key
+//   totals  workgroup = CALBOOT_CHUNK sorted positions: the chunk's weight per replicate;  scan: k_boot_scan's exclusive sums
+//   segoff  the weight in front of every segment's first position: the chunk's offset + the weights between the chunk's start and it
+//   pass    the same chunks, a wave owns 4 rounds of 64 consecutive positions.  Per replicate: a wave scan gives R_i; a lane adds
+//           (w q, w y) to its width cell, the Brier halves to its segment and (copies q, copies y) to every mass bin its copies lie
+//           in (bin of an expanded position e: floor(((e + 1) K - 1) / W), estimated in double and corrected by integer products).
+//           The lanes of one cell are added in a shuffle tree; the wave keeps ONE open cell per stream in registers across its
+//           rounds and hands it over, with integer atomic adds, where the cell changes
+//   final   a wave per (replicate, segment): sum_b |sum q_b - positives_b 2^32| over both binnings, then cal_seg_figures
+// All sums are exact integers: the same rows in any order give the same bits, and a replicate's doubles are k_calib_final's on the
+// expanded rows.  No per-row weights in memory, no workgroup waits for another; the launches depend on the sizes and pred_b alone.
+#define CALBOOT_THREADS 256
+#define CALBOOT_ROUNDS 4
+#define CALBOOT_CHUNK 1024              // sorted positions per workgroup: CALBOOT_THREADS * CALBOOT_ROUNDS (12 * CALBOOT_CHUNK < 2^16)
+#define CALBOOT_REP_TILE 8              // replicates whose weights a lane holds at a time: 8 weights of 4 bits to a word
+#define CALBOOT_MAX_CELLS (1 << 22)     // n_rep * (n_domain + 1) * n_bins
+#define CALBOOT_WAVES (CALBOOT_THREADS / 64)
+static_assert(CALBOOT_CHUNK == CALBOOT_THREADS * CALBOOT_ROUNDS && CALBOOT_CHUNK == BOOT_CHUNK && CALBOOT_REP_TILE == 8 &&
+              CALBOOT_THREADS == BOOT_THREADS, "k_boot_scan and the 4-bit weights serve both bootstraps");
+
+__global__ void __launch_bounds__(MET_THREADS) k_cboot_keys(const float* __restrict__ pred, const int16_t* __restrict__ label,
+                                                            const int32_t* __restrict__ cluster, int64_t ld_cluster, int64_t n_cluster,
+                                                            const int32_t* __restrict__ domain, int64_t ld_domain, int64_t n,
+                                                            int32_t n_domain, uint64_t* __restrict__ keys, uint32_t* __restrict__ idx,
+                                                            int32_t* __restrict__ err) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float p = pred[i];
+        int32_t d = domain ? domain[i * ld_domain] : 0;
+        const int64_t u = cluster ? (int64_t)cluster[i * ld_cluster] : 0;
+        const int16_t y = label[i];
+        const bool bad_p = !(p >= 0.f && p <= 1.f);                       // a NaN too
+        if (bad_p || d < 0 || d >= n_domain || u < 0 || (cluster && u >= n_cluster) || (y != 0 && y != 1)) {
+            if (err) atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
+            d = d < 0 ? 0 : (d >= n_domain ? n_domain - 1 : d);
+            if (bad_p) p = p > 1.f ? 1.f : 0.f;                           // as k_calib_keys clamps
+        }
+        const uint64_t low = ((uint64_t)score_key(p) << 1) | (uint64_t)(y != 0);
+        keys[i] = ((uint64_t)(uint32_t)d << 33) | low;
+        keys[n + i] = ((uint64_t)(uint32_t)n_domain << 33) | low;
+        idx[i] = (uint32_t)i;
+        idx[n + i] = (uint32_t)(n + i);
+    }
+}
+
+// the cluster of every sorted position (clamped as k_boot_prep clamps it); clears the n_acc sums of the pass
+__global__ void __launch_bounds__(MET_THREADS) k_cboot_prep(const uint32_t* __restrict__ idx, const int32_t* __restrict__ cluster,
+                                                            int64_t ld_cluster, int64_t n_cluster, int64_t n, int64_t n2,
+                                                            uint32_t* __restrict__ cl, unsigned long long* __restrict__ acc, int64_t n_acc) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += stride) {
+        const int64_t j = idx[i], row = j >= n ? j - n : j;
+        int64_t u = row;
+        if (cluster) {
+            u = cluster[row * ld_cluster];
+            u = u < 0 ? 0 : (u >= n_cluster ? n_cluster - 1 : u);
+        }
+        cl[i] = (uint32_t)u;
+    }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_acc; i += stride) acc[i] = 0ull;
+}
+
+// the weight of a range of at most CALBOOT_CHUNK sorted positions, per replicate.  SEG false: workgroup c sums chunk c into
+// ntot[r][c].  SEG true: workgroup d (d <= n_seg) sums the positions between the start of the chunk that holds start[d] and
+// start[d], and writes segoff[r][d] = the weight in front of start[d] (off[r][nchunks] for an end at n2 on a chunk boundary)
+template <bool SEG>
+__global__ void __launch_bounds__(CALBOOT_THREADS) k_cboot_sums(const uint32_t* __restrict__ cl, const int64_t* __restrict__ start,
+                                                                int64_t n2, int64_t nchunks, int32_t n_seg, int32_t n_rep, uint64_t seed,
+                                                                const unsigned long long* __restrict__ off, uint32_t* __restrict__ ntot,
+                                                                unsigned long long* __restrict__ segoff) {
+    __shared__ uint32_t sh[CALBOOT_WAVES][CALBOOT_REP_TILE];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int64_t c, lo, hi;
+    if (SEG) {
+        hi = start[blockIdx.x];
+        c = hi / CALBOOT_CHUNK;
+        lo = c * CALBOOT_CHUNK;
+    } else {
+        c = blockIdx.x;
+        lo = c * CALBOOT_CHUNK;
+        hi = lo + CALBOOT_CHUNK < n2 ? lo + CALBOOT_CHUNK : n2;
+    }
+    bool ok[CALBOOT_ROUNDS];
+    uint32_t clu[CALBOOT_ROUNDS];
+#pragma unroll
+    for (int k = 0; k < CALBOOT_ROUNDS; ++k) {
+        const int64_t pos = lo + (int64_t)k * CALBOOT_THREADS + tid;
+        ok[k] = pos < hi;
+        clu[k] = ok[k] ? cl[pos] : 0u;
+    }
+    const int ntiles = (n_rep + CALBOOT_REP_TILE - 1) / CALBOOT_REP_TILE;
+    for (int t = blockIdx.y; t < ntiles; t += gridDim.y) {
+        uint32_t v[CALBOOT_REP_TILE];
+#pragma unroll
+        for (int r = 0; r < CALBOOT_REP_TILE; ++r) {
+            const uint64_t base = boot_rep_base(seed, (uint32_t)(t * CALBOOT_REP_TILE + r));
+            uint32_t a = 0u;
+#pragma unroll
+            for (int k = 0; k < CALBOOT_ROUNDS; ++k)
+                if (ok[k]) a += boot_weight(base, clu[k]);
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+            v[r] = a;
+        }
+        if (lane == 0)
+            for (int r = 0; r < CALBOOT_REP_TILE; ++r) sh[wave][r] = v[r];
+        __syncthreads();
+        if (tid < CALBOOT_REP_TILE) {
+            uint32_t s = 0u;
+            for (int w = 0; w < CALBOOT_WAVES; ++w) s += sh[w][tid];
+            const int64_t rr = (int64_t)t * CALBOOT_REP_TILE + tid;
+            if (rr < n_rep) {
+                if (SEG) segoff[rr * (n_seg + 1) + blockIdx.x] = off[rr * (nchunks + 1) + c] + (unsigned long long)s;
+                else ntot[rr * nchunks + c] = s;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// floor(num / den) from the double estimate num * inv (inv close to 1 / den, num < 2^53), made exact by integer products
+__device__ __forceinline__ unsigned long long cboot_floor_div(unsigned long long num, unsigned long long den, double inv) {
+    unsigned long long v = (unsigned long long)((double)num * inv);
+    while (v > 0ull && v * den > num) --v;
+    while ((v + 1ull) * den <= num) ++v;
+    return v;
+}
+// the mass bin of expanded position e of a segment of weight W (e < W < 2^32, K <= 1024): the b with
+// floor(b W / K) <= e < floor((b+1) W / K), as cal_cell forms it from a rank
+__device__ __forceinline__ int32_t cboot_mass_bin(unsigned long long e, unsigned long long K, unsigned long long W, double inv_w) {
+    return (int32_t)cboot_floor_div((e + 1ull) * K - 1ull, W, inv_w);
+}
+
+// a stream's open cell: the same in every lane.  cell < 0: nothing open
+struct CbOpen { int32_t cell; unsigned long long a, b; };
+
+__device__ __forceinline__ void cboot_hand_over(const CbOpen& o, unsigned long long* __restrict__ acc, int lane) {
+    if (o.cell >= 0 && lane == 0) {
+        if (o.a) atomicAdd(&acc[2 * (int64_t)o.cell], o.a);
+        if (o.b) atomicAdd(&acc[2 * (int64_t)o.cell + 1], o.b);
+    }
+}
+// adds (a, b) of every active lane to acc[its cell]: the lanes of one cell through a shuffle tree into the open cell, which is
+// handed over when another cell comes.  The positions are sorted, so a cell's lanes are neighbours and a wave inside one cell
+// takes one turn of the loop; any order of cells gives the same sums
+__device__ __forceinline__ void cboot_feed(CbOpen& o, bool act, int32_t cell, unsigned long long a, unsigned long long b,
+                                           unsigned long long* __restrict__ acc, int lane) {
+    unsigned long long todo = __ballot(act);
+    while (todo) {
+        const int32_t c = __shfl(cell, __ffsll((unsigned long long)todo) - 1, 64);
+        const bool mine = act && cell == c;
+        const unsigned long long sa = dl_wave_sum(mine ? a : 0ull), sb = dl_wave_sum(mine ? b : 0ull);
+        if (c != o.cell) {
+            cboot_hand_over(o, acc, lane);
+            o.cell = c; o.a = 0ull; o.b = 0ull;
+        }
+        o.a += sa; o.b += sb;
+        todo &= ~__ballot(mine);
+    }
+}
+
+// acc_w, acc_q [n_rep][n_seg][K][sum w q, sum w y]; acc_seg [n_rep][n_seg][low, high half of sum w (q - y 2^32)^2]
+__global__ void __launch_bounds__(CALBOOT_THREADS) k_cboot_pass(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ cl,
+                                                                int64_t n2, int64_t nchunks, int32_t n_seg, int32_t K, int32_t n_rep,
+                                                                uint64_t seed, const unsigned long long* __restrict__ off,
+                                                                const unsigned long long* __restrict__ segoff,
+                                                                unsigned long long* __restrict__ acc_w,
+                                                                unsigned long long* __restrict__ acc_q,
+                                                                unsigned long long* __restrict__ acc_seg) {
+    __shared__ uint32_t s_wave[CALBOOT_WAVES][CALBOOT_REP_TILE / 2];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t c = blockIdx.x, c0 = c * CALBOOT_CHUNK, c1 = c0 + CALBOOT_CHUNK < n2 ? c0 + CALBOOT_CHUNK : n2;
+    const double inv_k = 1.0 / (double)K;
+    // round k of a wave: the 64 consecutive positions from c0 + (wave * CALBOOT_ROUNDS + k) * 64
+    bool ok[CALBOOT_ROUNDS], yv[CALBOOT_ROUNDS];
+    uint32_t clu[CALBOOT_ROUNDS];
+    int32_t seg[CALBOOT_ROUNDS], bw[CALBOOT_ROUNDS];
+    unsigned long long q[CALBOOT_ROUNDS];
+#pragma unroll
+    for (int k = 0; k < CALBOOT_ROUNDS; ++k) {
+        const int64_t pos = c0 + (int64_t)(wave * CALBOOT_ROUNDS + k) * 64 + lane;
+        ok[k] = pos < c1; yv[k] = false; clu[k] = 0u; seg[k] = 0; bw[k] = 0; q[k] = 0ull;
+        if (ok[k]) {
+            const uint64_t key = keys[pos];
+            const float p = cal_score(key);
+            yv[k] = (key & 1ull) != 0ull;
+            clu[k] = cl[pos];
+            seg[k] = (int32_t)(key >> 33);
+            bw[k] = cal_bin(p, K);
+            q[k] = cal_quant(p);
+        }
+    }
+    const int ntiles = (n_rep + CALBOOT_REP_TILE - 1) / CALBOOT_REP_TILE;
+    for (int t = blockIdx.y; t < ntiles; t += gridDim.y) {
+        // the tile's weights, 4 bits each, and the wave's weight per replicate, two replicates to a word (12 * 256 < 2^16)
+        uint32_t wpk[CALBOOT_ROUNDS] = {0u, 0u, 0u, 0u};
+        uint32_t tn[CALBOOT_REP_TILE / 2] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int r = 0; r < CALBOOT_REP_TILE; ++r) {
+            const uint64_t base = boot_rep_base(seed, (uint32_t)(t * CALBOOT_REP_TILE + r));
+#pragma unroll
+            for (int k = 0; k < CALBOOT_ROUNDS; ++k) {
+                const uint32_t w = ok[k] ? boot_weight(base, clu[k]) : 0u;
+                wpk[k] |= w << (4 * r);
+                tn[r >> 1] += w << (16 * (r & 1));
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < CALBOOT_REP_TILE / 2; ++j) {
+            uint32_t v = tn[j];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+            if (lane == 0) s_wave[wave][j] = v;
+        }
+        __syncthreads();
+        for (int r = 0; r < CALBOOT_REP_TILE; ++r) {
+            const int64_t rr = (int64_t)t * CALBOOT_REP_TILE + r;
+            if (rr >= n_rep) break;                                        // the same in every thread
+            unsigned long long front = off[rr * (nchunks + 1) + c];        // the weight in front of the wave's next round
+            for (int w = 0; w < wave; ++w) front += (s_wave[w][r >> 1] >> (16 * (r & 1))) & 0xffffu;
+            const unsigned long long* so = segoff + rr * (n_seg + 1);
+            const int32_t seg0 = (int32_t)rr * n_seg;
+            CbOpen ow = {-1, 0ull, 0ull}, oq = {-1, 0ull, 0ull}, os = {-1, 0ull, 0ull};
+#pragma unroll
+            for (int k = 0; k < CALBOOT_ROUNDS; ++k) {
+                const uint32_t w = (wpk[k] >> (4 * r)) & 15u;
+                uint32_t inc = w;
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {
+                    const uint32_t x = __shfl_up(inc, o, 64);
+                    if (lane >= o) inc += x;
+                }
+                const unsigned long long R = front + (unsigned long long)(inc - w);
+                front += (unsigned long long)__shfl(inc, 63, 64);
+                const bool act = w != 0u;
+                const int32_t sc = seg0 + seg[k];
+                const unsigned long long y = yv[k] ? 1ull : 0ull;
+                cboot_feed(ow, act, sc * K + bw[k], (unsigned long long)w * q[k], (unsigned long long)w * y, acc_w, lane);
+                const unsigned long long e = yv[k] ? 4294967296ull - q[k] : q[k], e2 = e * e;      // cal_add's halves
+                cboot_feed(os, act, sc, (unsigned long long)w * (e2 & 0xffffffffull),
+                           (unsigned long long)w * ((e2 >> 32) + ((e >> 32) << 32)), acc_seg, lane);
+                // the row's copies: expanded positions [pe, pe + rem) of its segment
+                unsigned long long pe = 0ull, W = 1ull;
+                if (act) {
+                    const unsigned long long s0 = so[seg[k]];
+                    W = so[seg[k] + 1] - s0;
+                    W = W ? W : 1ull;                                      // w > 0 is part of W
+                    pe = R - s0;
+                }
+                const double inv_w = __builtin_amdgcn_rcp((double)W);
+                uint32_t rem = w;
+                while (__ballot(rem != 0u)) {
+                    int32_t b = 0;
+                    uint32_t take = 0u;
+                    if (rem != 0u) {
+                        b = cboot_mass_bin(pe, (unsigned long long)K, W, inv_w);
+                        take = rem;
+                        if (rem > 1u && cboot_mass_bin(pe + rem - 1u, (unsigned long long)K, W, inv_w) != b)
+                            take = (uint32_t)(cboot_floor_div((unsigned long long)(b + 1) * W, (unsigned long long)K, inv_k) - pe);
+                        b = b < K - 1 ? b : K - 1;                         // pe < W: both hold by construction; they keep a
+                        take = take >= 1u && take <= rem ? take : rem;     // broken invariant from leaving the arrays or the loop
+                    }
+                    cboot_feed(oq, rem != 0u, sc * K + b, (unsigned long long)take * q[k], (unsigned long long)take * y, acc_q, lane);
+                    rem -= take;
+                    pe += take;
+                }
+            }
+            cboot_hand_over(ow, acc_w, lane);
+            cboot_hand_over(oq, acc_q, lane);
+            cboot_hand_over(os, acc_seg, lane);
+        }
+        __syncthreads();                                                   // s_wave is free for the next tile
+    }
+}
+
+// out [4][n_rep][n_seg]: pcoc, brier, ece, ece_q; counts (when given) [2][n_rep][n_seg]: W, Wp.  A wave per (replicate, segment)
+__global__ void __launch_bounds__(CALBOOT_THREADS) k_cboot_final(const unsigned long long* __restrict__ acc_w,
+                                                                 const unsigned long long* __restrict__ acc_q,
+                                                                 const unsigned long long* __restrict__ acc_seg,
+                                                                 const unsigned long long* __restrict__ segoff, int32_t n_rep,
+                                                                 int32_t n_seg, int32_t K, double* __restrict__ out,
+                                                                 int64_t* __restrict__ counts) {
+    const int lane = threadIdx.x & 63;
+    const int64_t id = (int64_t)blockIdx.x * CALBOOT_WAVES + (threadIdx.x >> 6), total = (int64_t)n_rep * n_seg;
+    if (id >= total) return;                                               // a whole wave
+    const int64_t rr = id / n_seg, d = id - rr * n_seg;
+    const unsigned long long W = segoff[rr * (n_seg + 1) + d + 1] - segoff[rr * (n_seg + 1) + d];
+    const unsigned long long* aw = acc_w + 2 * id * K;
+    const unsigned long long* aq = acc_q + 2 * id * K;
+    unsigned long long Q = 0ull, P = 0ull, gap_w = 0ull, gap_q = 0ull;
+    for (int b = lane; b < K; b += 64) {
+        unsigned long long s = aw[2 * b], ps = aw[2 * b + 1], obs = ps << 32;
+        Q += s; P += ps;
+        gap_w += s > obs ? s - obs : obs - s;
+        s = aq[2 * b]; obs = aq[2 * b + 1] << 32;
+        gap_q += s > obs ? s - obs : obs - s;
+    }
+    Q = dl_wave_sum(Q); P = dl_wave_sum(P); gap_w = dl_wave_sum(gap_w); gap_q = dl_wave_sum(gap_q);
+    if (lane != 0) return;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    double o[4] = {nan, nan, nan, nan};
+    if (W > 0ull) cal_seg_figures(W, P, Q, acc_seg[2 * id], acc_seg[2 * id + 1], gap_w, gap_q, &o[0], &o[1], &o[2], &o[3]);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) out[(int64_t)k * total + id] = o[k];
+    if (counts) {
+        counts[id] = (int64_t)W;
+        counts[total + id] = (int64_t)P;
+    }
+}
+
+struct CalBootLayout {
+    int64_t keys_in, keys_out, idx_in, idx_out, start, ntot, off, segoff, acc, acc_words, temp, temp_bytes, total;
+    int64_t nchunks, cells;
+};
+// plain arithmetic, rocPRIM's temporary storage included: the size query must answer where no device is present.  The sort gets
+// 16 bytes per key and 1 MiB — a second copy of keys and payloads (12 bytes per key), digit histograms and the look-back states of
+// its tiles; the call asks rocPRIM what it needs and refuses to run if that is ever more
+static void calboot_layout(int64_t n, int32_t n_domain, int32_t n_bins, int32_t n_rep, CalBootLayout* L) {
+    const int64_t n2 = 2 * n, seg = (int64_t)n_domain + 1, nc = cdc_ceil_div(n2, CALBOOT_CHUNK), R = n_rep;
+    int64_t off = 0;
+    L->nchunks = nc;
+    L->cells = R * seg * n_bins;
+    L->acc_words = 2 * (2 * L->cells + R * seg);               // acc_w, acc_q, acc_seg: one block, cleared together
+    L->keys_in = off;  off += align_up(n2 * 8);
+    L->keys_out = off; off += align_up(n2 * 8);
+    L->idx_in = off;   off += align_up(n2 * 4);                // after the sort: the clusters
+    L->idx_out = off;  off += align_up(n2 * 4);
+    L->start = off;    off += align_up((seg + 1) * 8);
+    L->ntot = off;     off += align_up(R * nc * 4);
+    L->off = off;      off += align_up(R * (nc + 1) * 8);
+    L->segoff = off;   off += align_up(R * (seg + 1) * 8);
+    L->acc = off;      off += align_up(L->acc_words * 8);
+    L->temp = off;
+    L->temp_bytes = n2 * 16 + (1 << 20);
+    L->total = L->temp + align_up(L->temp_bytes);
+}
+static bool calboot_sizes_ok(int64_t n, int32_t n_domain, int32_t n_bins, int32_t n_rep) {
+    return n > 0 && n < (1ll << 28) && n_domain > 0 && n_domain < (1 << 20) && n_bins >= 1 && n_bins <= CAL_MAX_BINS && n_rep >= 1 &&
+           n_rep <= BOOT_MAX_REP && (int64_t)n_rep * ((int64_t)n_domain + 1) * n_bins <= CALBOOT_MAX_CELLS;
+}
+
+extern "C" int64_t cdc_eval_calibration_bootstrap_workspace_bytes(int64_t n, int32_t n_domain, int32_t n_bins, int32_t n_rep,
+                                                                  int32_t paired) {
+    (void)paired;                                                          // the second vector reuses the first one's arrays
+    if (!calboot_sizes_ok(n, n_domain, n_bins, n_rep)) return 0;
+    CalBootLayout L;
+    calboot_layout(n, n_domain, n_bins, n_rep, &L);
+    return L.total;
+}
+
+extern "C" int cdc_eval_calibration_bootstrap(const float* pred_a, const float* pred_b, const int16_t* label, const int32_t* cluster,
+                                              int64_t ld_cluster, int64_t n_cluster, const int32_t* domain, int64_t ld_domain,
+                                              int32_t n_domain, int32_t n_bins, int64_t n, int32_t n_rep, uint64_t seed, double* out,
+                                              int64_t* counts, int32_t* err_flag, void* workspace, int64_t workspace_bytes,
+                                              void* stream) {
+    CDC_CHECK_ARG(pred_a && label && out && counts && workspace, CDC_E_BADARG, "eval_calibration_bootstrap: null pointer");
+    CDC_CHECK_ARG(n > 0 && n_domain > 0 && n_domain < (1 << 20) && ld_cluster >= 0 && ld_domain >= 0 && (!cluster || n_cluster > 0),
+                  CDC_E_BADARG, "eval_calibration_bootstrap: bad sizes n=%ld n_domain=%d n_cluster=%ld", (long)n, n_domain, (long)n_cluster);
+    CDC_CHECK_ARG(n_bins >= 1 && n_bins <= CAL_MAX_BINS, CDC_E_BADARG, "eval_calibration_bootstrap: n_bins=%d outside [1, %d]", n_bins,
+                  CAL_MAX_BINS);
+    CDC_CHECK_ARG(n_rep >= 1 && n_rep <= BOOT_MAX_REP, CDC_E_BADARG, "eval_calibration_bootstrap: n_rep=%d outside [1, %d]", n_rep,
+                  BOOT_MAX_REP);
+    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_calibration_bootstrap: n_domain=%d needs the domain column", n_domain);
+    CDC_CHECK_ARG(n < (1ll << 28), CDC_E_TOOBIG, "eval_calibration_bootstrap: n=%ld exceeds the 2^28 rows whose weighted sums fit 64 bits",
+                  (long)n);
+    CDC_CHECK_ARG((int64_t)n_rep * ((int64_t)n_domain + 1) * n_bins <= CALBOOT_MAX_CELLS, CDC_E_TOOBIG,
+                  "eval_calibration_bootstrap: n_rep * (n_domain + 1) * n_bins = %ld cells exceed 2^22",
+                  (long)((int64_t)n_rep * ((int64_t)n_domain + 1) * n_bins));
+    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_calibration_bootstrap: workspace must be 256-byte aligned");
+    const int32_t paired = pred_b != nullptr;
+    CalBootLayout L;
+    calboot_layout(n, n_domain, n_bins, n_rep, &L);
+    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_calibration_bootstrap: workspace %ld < %ld bytes", (long)workspace_bytes,
+                  (long)L.total);
+    size_t t_sort = 0;
+    hipError_t e = rocprim::radix_sort_pairs(nullptr, t_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr,
+                                             (uint32_t*)nullptr, (size_t)(2 * n), 0, 64, (hipStream_t)0, false);
+    if (e != hipSuccess) { cdc_set_error("eval_calibration_bootstrap: rocprim size query failed: %s", hipGetErrorString(e)); return (int)e; }
+    CDC_CHECK_ARG((int64_t)t_sort <= L.temp_bytes, CDC_E_BADARG, "eval_calibration_bootstrap: the sort needs %ld temporary bytes, %ld reserved",
+                  (long)t_sort, (long)L.temp_bytes);
+    char* base = (char*)workspace;
+    uint64_t* keys_in = (uint64_t*)(base + L.keys_in);
+    uint64_t* keys = (uint64_t*)(base + L.keys_out);
+    uint32_t* idx_in = (uint32_t*)(base + L.idx_in);
+    uint32_t* idx = (uint32_t*)(base + L.idx_out);
+    uint32_t* cl = idx_in;                                          // the unsorted payloads are dead once the sort has run
+    int64_t* start = (int64_t*)(base + L.start);
+    uint32_t* ntot = (uint32_t*)(base + L.ntot);
+    unsigned long long* off = (unsigned long long*)(base + L.off);
+    unsigned long long* segoff = (unsigned long long*)(base + L.segoff);
+    unsigned long long* acc_w = (unsigned long long*)(base + L.acc);
+    unsigned long long* acc_q = acc_w + 2 * L.cells;
+    unsigned long long* acc_seg = acc_q + 2 * L.cells;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n2 = 2 * n, nc = L.nchunks;
+    const int seg = n_domain + 1;
+    const int ntiles = (n_rep + CALBOOT_REP_TILE - 1) / CALBOOT_REP_TILE;
+    // replicate tiles go side by side only while the grid is small, as in cdc_eval_bootstrap
+    const int gy = (int)std::min<int64_t>(ntiles, std::max<int64_t>(1, 2048 / nc));
+    const int gy_seg = (int)std::min<int64_t>(ntiles, std::max<int64_t>(1, 2048 / (seg + 1)));
+    int end_bit = 34;
+    while (end_bit < 64 && ((uint64_t)n_domain >> (end_bit - 33)) != 0) ++end_bit;
+    for (int v = 0; v <= paired; ++v) {
+        const float* pred = v ? pred_b : pred_a;
+        int blocks = (int)std::min<int64_t>(cdc_ceil_div(n, MET_THREADS), 4096);
+        hipLaunchKernelGGL(k_cboot_keys, dim3(blocks), dim3(MET_THREADS), 0, st, pred, label, cluster, ld_cluster, n_cluster, domain,
+                           ld_domain, n, n_domain, keys_in, idx_in, err_flag);
+        CDC_LAUNCH_CHECK("eval_calibration_bootstrap(keys)");
+        size_t temp_bytes = (size_t)L.temp_bytes;
+        e = rocprim::radix_sort_pairs(base + L.temp, temp_bytes, (const uint64_t*)keys_in, keys, (const uint32_t*)idx_in, idx, (size_t)n2,
+                                      0, end_bit, st, false);
+        if (e != hipSuccess) { cdc_set_error("eval_calibration_bootstrap: radix sort failed: %s", hipGetErrorString(e)); return (int)e; }
+        hipLaunchKernelGGL(k_boot_starts, dim3((int)cdc_ceil_div(seg + 1, 64)), dim3(64), 0, st, (const uint64_t*)keys, n2, seg, start);
+        CDC_LAUNCH_CHECK("eval_calibration_bootstrap(starts)");
+        blocks = (int)std::min<int64_t>(cdc_ceil_div(std::max<int64_t>(n2, L.acc_words), MET_THREADS), 8192);
+        hipLaunchKernelGGL(k_cboot_prep, dim3(blocks), dim3(MET_THREADS), 0, st, (const uint32_t*)idx, cluster, ld_cluster, n_cluster, n, n2,
+                           cl, acc_w, L.acc_words);
+        CDC_LAUNCH_CHECK("eval_calibration_bootstrap(prep)");
+        hipLaunchKernelGGL(k_cboot_sums<false>, dim3((unsigned)nc, gy), dim3(CALBOOT_THREADS), 0, st, (const uint32_t*)cl,
+                           (const int64_t*)start, n2, nc, seg, n_rep, seed, (const unsigned long long*)off, ntot, segoff);
+        CDC_LAUNCH_CHECK("eval_calibration_bootstrap(totals)");
+        hipLaunchKernelGGL(k_boot_scan, dim3(n_rep), dim3(BOOT_THREADS), 0, st, (const uint32_t*)ntot, nc, off);
+        CDC_LAUNCH_CHECK("eval_calibration_bootstrap(scan)");
+        hipLaunchKernelGGL(k_cboot_sums<true>, dim3((unsigned)(seg + 1), gy_seg), dim3(CALBOOT_THREADS), 0, st, (const uint32_t*)cl,
+                           (const int64_t*)start, n2, nc, seg, n_rep, seed, (const unsigned long long*)off, ntot, segoff);
+        CDC_LAUNCH_CHECK("eval_calibration_bootstrap(segment offsets)");
+        hipLaunchKernelGGL(k_cboot_pass, dim3((unsigned)nc, gy), dim3(CALBOOT_THREADS), 0, st, (const uint64_t*)keys, (const uint32_t*)cl,
+                           n2, nc, seg, n_bins, n_rep, seed, (const unsigned long long*)off, (const unsigned long long*)segoff, acc_w,
+                           acc_q, acc_seg);
+        CDC_LAUNCH_CHECK("eval_calibration_bootstrap(pass)");
+        hipLaunchKernelGGL(k_cboot_final, dim3((unsigned)cdc_ceil_div((int64_t)n_rep * seg, CALBOOT_WAVES)), dim3(CALBOOT_THREADS), 0, st,
+                           (const unsigned long long*)acc_w, (const unsigned long long*)acc_q, (const unsigned long long*)acc_seg,
+                           (const unsigned long long*)segoff, n_rep, seg, n_bins, out + (int64_t)v * 4 * n_rep * seg,
+                           v ? (int64_t*)nullptr : counts);                 // the counts follow from the labels and weights alone
+        CDC_LAUNCH_CHECK("eval_calibration_bootstrap(final)");
     }
     return 0;
 }

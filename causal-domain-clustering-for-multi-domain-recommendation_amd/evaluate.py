@@ -26,7 +26,8 @@ figures share users, and so do two models on one evaluation set.  It resamples w
 applied to all of the user's rows in every domain and under both prediction vectors — and recomputes AUC, log-loss and GAUC for every
 replicate on the device (`cdc_eval_bootstrap`: the rows are sorted once, the replicates reuse that order); `summarize_bootstrap`
 gives the standard error and the percentile interval, `Evaluator(bootstrap=R)` reports them, mean_gauc's and the deltas of
-`Evaluator.compare` included.
+`Evaluator.compare` included.  `eval_calibration_bootstrap` does the same for the calibration figures (pcoc, brier, ece, ece_q:
+`cdc_eval_calibration_bootstrap`); `Evaluator(calibration_ci=True)` reports their intervals and the calibration deltas of `compare`.
 
 `eval_calibration` reports whether the predicted probabilities are right, where the figures above only say how well they rank: per
 domain and over all rows the ratio of predicted to observed CTR, the Brier score, and a reliability table with ECE / MCE for
@@ -398,7 +399,8 @@ def eval_bootstrap(pred, label, cluster=None, n_cluster=None, domain=None, n_dom
     the row order, loss only within rounding.  At most 2^28 - 1 rows, n_rep in [1, 4096].  No host synchronisation; the error word
     (1 + a row with a NaN prediction in either vector, a label outside {0, 1}, a domain or a cluster outside range) is kept as
     `eval_bootstrap.last_err`.  `summarize_bootstrap` turns a replicate matrix into a standard error and a percentile interval.
-    Not offered: BCa or studentised intervals, a bootstrap of the calibration figures."""
+    The calibration figures' replicates under the same weights come from `eval_calibration_bootstrap`.  Not offered: BCa or studentised
+    intervals."""
     lib = L.load()
     n_domain, n_rep, seed = int(n_domain), int(n_rep), int(seed)
     if n_domain <= 0:
@@ -511,8 +513,9 @@ def eval_calibration(pred, label, domain=None, n_domain=1, n_bins=10):
     No host synchronisation; the error word (1 + a row with a NaN prediction, a prediction outside [0, 1], a label outside {0, 1} or
     a domain outside range) is kept as `eval_calibration.last_err`.
     A recalibration map is fitted by `eval_isotonic_fit` / `Recalibration` (isotonic regression) or `eval_platt_fit` /
-    `PlattRecalibration` (Platt, temperature, bias scaling).  Not offered: selection or early stopping by a calibration figure in
-    `Runner`, calibration deltas in `Evaluator.compare`."""
+    `PlattRecalibration` (Platt, temperature, bias scaling); `eval_calibration_bootstrap` gives pcoc, brier, ece and ece_q their
+    bootstrap intervals, `Evaluator(calibration_ci=True)` reports them and the calibration deltas of `Evaluator.compare`.  Not
+    offered: selection or early stopping by a calibration figure in `Runner`."""
     lib = L.load()
     n_domain, n_bins = int(n_domain), int(n_bins)
     if not 1 <= n_bins <= MAX_CALIBRATION_BINS:
@@ -548,6 +551,95 @@ def eval_calibration(pred, label, domain=None, n_domain=1, n_bins=10):
     eval_calibration.last_err = err
     tables = [CalibrationTable(tab_counts[t, 0], tab_counts[t, 1], tab_out[t, 0], tab_out[t, 1], tab_range[t, 0], tab_range[t, 1]) for t in (0, 1)]
     return Calibration(seg_counts[0], seg_counts[1], *seg_out.unbind(0), tables[0], tables[1])
+
+
+CALBOOT_CHUNK = 1024            # csrc/metrics.hip CALBOOT_CHUNK: sorted positions per workgroup of the calibration bootstrap's passes
+CALBOOT_REP_TILE = 8            # csrc/metrics.hip CALBOOT_REP_TILE: replicates whose weights a lane holds at a time
+CALBOOT_MAX_CELLS = 1 << 22     # csrc/metrics.hip CALBOOT_MAX_CELLS: n_rep * (n_domain + 1) * n_bins
+
+CalibrationBootstrap = collections.namedtuple("CalibrationBootstrap", "pcoc brier ece ece_q w_rows w_pos pcoc_b brier_b ece_b ece_q_b")
+
+
+def eval_calibration_bootstrap(pred, label, cluster=None, n_cluster=None, domain=None, n_domain=1, n_bins=10, n_rep=200, seed=0,
+                               pred_b=None):
+    """Clustered bootstrap replicates of the calibration figures (`cdc_eval_calibration_bootstrap`).  pred, label, domain, n_domain,
+    n_bins as `eval_calibration`; cluster, n_cluster, n_rep, seed, pred_b as `eval_bootstrap`: replicate r gives every row the weight
+    `eval_bootstrap` gives it for the same (seed, r, cluster) — rows are their own clusters without a cluster column — and a
+    replicate's figures are BY DEFINITION `eval_calibration`'s on the rows repeated by their weights: pcoc, brier, ece over the
+    equal-width bins (a row's bin depends on its prediction alone) and ece_q over equal-mass bins of the REPEATED rows (a row's
+    copies may fall into several bins).  Returns the namedtuple `CalibrationBootstrap` of device tensors [n_rep, n_domain + 1]
+    (domains 0..n_domain-1, then ALL rows): `pcoc`, `brier`, `ece`, `ece_q` (f64), `w_rows`, `w_pos` (i64: the weighted row and
+    positive counts, `eval_bootstrap`'s integers), and with `pred_b` also `pcoc_b`, `brier_b`, `ece_b`, `ece_q_b` (else None) under
+    the SAME weights: a delta's replicates are `ece - ece_b`.  Every figure is NaN where a replicate leaves a segment without rows,
+    pcoc also where it leaves it without positives; a single-class segment still has brier and ece.  All sums are exact integers:
+    the same rows in any order give the same bits, and a replicate equals `eval_calibration` on the repeated rows bit for bit.  At
+    most 2^28 - 1 rows, n_rep in [1, 4096], n_rep * (n_domain + 1) * n_bins <= 2^22 cells.  No host synchronisation; the error word
+    (1 + a row with a prediction outside [0, 1] or NaN in either vector, a label outside {0, 1}, a domain or a cluster outside
+    range; the row is counted clamped) is kept as `eval_calibration_bootstrap.last_err`.  `summarize_bootstrap` applies unchanged.
+    ECE is biased upwards on small segments, replicates included: the interval of a delta is more trustworthy than that of a level.
+    Not offered: MCE replicates, per-bin reliability bands, BCa or studentised intervals, selection by a calibration figure in
+    `Runner`."""
+    lib = L.load()
+    n_domain, n_bins, n_rep, seed = int(n_domain), int(n_bins), int(n_rep), int(seed)
+    if n_domain <= 0:
+        raise ValueError(f"n_domain={n_domain} must be positive")
+    if not 1 <= n_bins <= MAX_CALIBRATION_BINS:
+        raise ValueError(f"n_bins={n_bins} must lie in [1, {MAX_CALIBRATION_BINS}]")
+    if not 1 <= n_rep <= BOOT_MAX_REP:
+        raise ValueError(f"n_rep={n_rep} must lie in [1, {BOOT_MAX_REP}]")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed={seed} must fit 64 unsigned bits")
+    if n_rep * (n_domain + 1) * n_bins > CALBOOT_MAX_CELLS:
+        raise ValueError(f"n_rep * (n_domain + 1) * n_bins = {n_rep * (n_domain + 1) * n_bins} cells exceed the cell cap "
+                         f"CALBOOT_MAX_CELLS = {CALBOOT_MAX_CELLS}")
+    if cluster is not None:
+        if n_cluster is None:
+            raise ValueError("a cluster column needs n_cluster, the size of the id range")
+        n_cluster = int(n_cluster)
+        if n_cluster <= 0:
+            raise ValueError(f"n_cluster={n_cluster} must be positive")
+    else:
+        n_cluster = 0
+    if not pred.is_cuda:
+        raise L.HipExtensionError("eval_calibration_bootstrap needs device tensors; there is no CPU fallback")
+    pred = pred.reshape(-1).to(torch.float32).contiguous()
+    label = label.reshape(-1).to(torch.int16).contiguous()
+    n = pred.numel()
+    if label.numel() != n:
+        raise ValueError(f"{n} predictions but {label.numel()} labels")
+    if n > BOOT_MAX_ROWS:
+        raise ValueError(f"{n} rows exceed the {BOOT_MAX_ROWS} whose weighted sums fit 64 bits")
+    if pred_b is not None:
+        pred_b = pred_b.reshape(-1).to(device=pred.device, dtype=torch.float32).contiguous()
+        if pred_b.numel() != n:
+            raise ValueError(f"{n} predictions but {pred_b.numel()} in pred_b")
+    ld_cluster = 0
+    if cluster is not None:
+        cluster, ld_cluster = _id_column(cluster, n, "cluster")
+    ld_domain = 0
+    if domain is not None:
+        domain, ld_domain = _id_column(domain, n, "domain")
+    elif n_domain != 1:
+        raise ValueError("n_domain > 1 needs the domain column")
+    dev = pred.device
+    seg = n_domain + 1
+    paired = pred_b is not None
+    out = torch.empty((8 if paired else 4, n_rep, seg), dtype=torch.float64, device=dev)
+    counts = torch.empty((2, n_rep, seg), dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    nbytes = lib.cdc_eval_calibration_bootstrap_workspace_bytes(n, n_domain, n_bins, n_rep, int(paired))
+    if nbytes <= 0:
+        raise RuntimeError(f"cdc_eval_calibration_bootstrap_workspace_bytes refused n={n}, n_domain={n_domain}, n_bins={n_bins}, "
+                           f"n_rep={n_rep}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    L.launch("cdc_eval_calibration_bootstrap", lib.cdc_eval_calibration_bootstrap,
+             (pred.data_ptr(), pred_b.data_ptr() if paired else None, label.data_ptr(), None if cluster is None else cluster.data_ptr(),
+              ld_cluster, n_cluster, None if domain is None else domain.data_ptr(), ld_domain, n_domain, n_bins, n, n_rep, seed,
+              out.data_ptr(), counts.data_ptr(), err.data_ptr(), ws.data_ptr(), nbytes),
+             C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    eval_calibration_bootstrap.last_err = err
+    second = tuple(out[4:]) if paired else (None,) * 4
+    return CalibrationBootstrap(out[0], out[1], out[2], out[3], counts[0], counts[1], *second)
 
 
 IsotonicFit = collections.namedtuple("IsotonicFit", "start x_lo x_hi count positives value rows seg_positives")
@@ -927,25 +1019,34 @@ class Evaluator:
             the *_loss_delta_boot_* forms and with gauc_ci the *_gauc_delta_boot_* forms (mean_gauc_delta_boot_* included), all from
             per-replicate differences under shared weights.  The bootstrap launches are queued with the others, before the one
             synchronisation.
-            Not offered: significance-aware early stopping in `Runner`, BCa or studentised intervals, a bootstrap of the calibration
-            figures.
+            Not offered: significance-aware early stopping in `Runner`, BCa or studentised intervals.
     calibration: test() adds calibration figures (`eval_calibration`; True: 10 bins, an int: that many): total_pcoc (predicted over
             observed CTR), total_brier, total_ece, total_ece_quantile, and with per-domain evaluation domain_pcoc / domain_brier /
             domain_ece / domain_ece_quantile {d: value} and mean_pcoc / mean_brier / mean_ece / mean_ece_quantile, weighted like
             mean_auc; `calibration_table` returns the reliability tables.  Selection or early stopping by a calibration figure
-            and calibration deltas in `compare` are not offered.
+            is not offered; intervals and the deltas of `compare` come with `calibration_ci`.
     recalibration: a `Recalibration` or a `PlattRecalibration` (from `fit_recalibration` on the validation loader, or the class's
             `fit`): every prediction goes through its map, clamped to [recalibration_eps, 1 - recalibration_eps] when that is positive, before anything is
             computed, so test(), calibration_table(), predict() and compare() report the recalibrated model under the same keys; raw
             against recalibrated on one checkpoint: Evaluator(model, ..).compare(Evaluator(model, .., recalibration=r), loader).  A map
-            over more than one domain needs domain_idx.  Beta calibration, vector or matrix scaling, a "step" interpolation,
-            selection by a calibration figure in `Runner` and calibration deltas in `compare` are not offered.
+            over more than one domain needs domain_idx.  Beta calibration, vector or matrix scaling, a "step" interpolation
+            and selection by a calibration figure in `Runner` are not offered.
     precision: None, or "bf16" / "f32": the model is switched to it for the scoring pass and switched back afterwards, so two
-            evaluators around ONE module can score it under two precisions (`compare`)."""
+            evaluators around ONE module can score it under two precisions (`compare`).
+    calibration_ci: (needs calibration and bootstrap both set; ValueError otherwise) the clustered bootstrap over the calibration
+            figures (`eval_calibration_bootstrap`: the evaluator's bins, replicate count, seed and level; clusters as `bootstrap`'s).
+            test() adds, for fig in pcoc, brier, ece, ece_quantile, total_<fig>_boot_se/lo/hi and with per-domain evaluation
+            domain_<fig>_boot_* {d: value} and mean_<fig>_boot_* (the mean formed per replicate); boot_valid covers them.  compare()
+            adds total_<fig>_delta = figure(self) - figure(other) (two `eval_calibration` calls), total_<fig>_delta_boot_se/lo/hi from
+            the per-replicate differences under shared weights, total_<fig>_z = delta / boot_se, and the domain_ and mean_ forms.
+            ECE is biased upwards on small domains, so the interval of a delta deserves more trust than that of a level.  Without
+            it every result dictionary and every launch is exactly as before.  Not offered: MCE replicates, per-bin reliability
+            bands, BCa or studentised intervals, selection by a calibration figure in `Runner`."""
 
     def __init__(self, model, mode="multi", domain_idx=None, n_domain=1, domain_cnt_weight=None, is_evaluate_multi_domain=True,
                  user_idx=None, n_user=None, user_weight=None, auc_ci=False, precision=None, calibration=False, recalibration=None,
-                 recalibration_eps=0.0, loss_ci=False, gauc_ci=False, bootstrap=None, bootstrap_seed=0, bootstrap_level=0.95):
+                 recalibration_eps=0.0, loss_ci=False, gauc_ci=False, bootstrap=None, bootstrap_seed=0, bootstrap_level=0.95,
+                 calibration_ci=False):
         self.model, self.mode = model, mode
         self.bootstrap = 0 if bootstrap is None else int(bootstrap)         # 0: off
         if bootstrap is not None and (isinstance(bootstrap, bool) or not 1 <= self.bootstrap <= BOOT_MAX_REP):
@@ -965,6 +1066,10 @@ class Evaluator:
         self.calibration_bins = 0 if calibration is False else (10 if calibration is True else int(calibration))   # 0: off
         if calibration is not False and not 1 <= self.calibration_bins <= MAX_CALIBRATION_BINS:
             raise ValueError(f"calibration must be a bool or a number of bins in [1, {MAX_CALIBRATION_BINS}], not {calibration!r}")
+        self.calibration_ci = bool(calibration_ci)
+        if self.calibration_ci and not (self.calibration_bins and self.bootstrap):
+            raise ValueError("calibration_ci needs calibration (the bins) and bootstrap (the replicates) both set: its intervals are "
+                             "the clustered bootstrap's over the calibration figures")
         if precision not in (None, "bf16", "f32"):
             raise ValueError(f"precision must be None, 'bf16' or 'f32', not {precision!r}")
         self.precision = precision
@@ -1061,7 +1166,7 @@ class Evaluator:
         total_pcoc, total_brier, total_ece, total_ece_quantile (+ domain_* and mean_* of the four); with loss_ci also total_loss_se
         (+ domain_loss_se, mean_loss_se); with gauc_ci also total_gauc_se (+ domain_gauc_se; no mean_gauc_se: the per-domain GAUCs
         share users and are not independent); with bootstrap also total_*_boot_se/lo/hi, domain_*_boot_*, mean_*_boot_* for auc, loss
-        and (with user_idx) gauc, and boot_valid."""
+        and (with user_idx) gauc, and boot_valid; with calibration_ci the same *_boot_* keys for pcoc, brier, ece and ece_quantile."""
         pred, label, domain, user = self._score(data_loader)
         multi = self.is_evaluate_multi_domain
         auc, loss, rows, pos = eval_metrics(pred, label, domain if multi else None, self.n_domain if multi else 1)
@@ -1081,6 +1186,9 @@ class Evaluator:
             stats = {"auc": boot.auc, "loss": boot.loss}
             if user is not None:
                 stats["gauc"] = boot.gauc
+            if self.calibration_ci:                            # likewise queued: the same weights over the calibration figures
+                cb = self._calibration_bootstrap(pred, label, domain, user, multi)
+                stats.update({"pcoc": cb.pcoc, "brier": cb.brier, "ece": cb.ece, "ece_quantile": cb.ece_q})
             boot_sum = self._boot_summary(stats, rows, multi)
         auc, loss, rows, pos = auc.cpu().tolist(), loss.cpu().tolist(), rows.cpu().tolist(), pos.cpu().tolist()   # the one sync
         bad = int(eval_metrics.last_err.item())
@@ -1153,6 +1261,12 @@ class Evaluator:
                               self.n_domain if multi else 1, self.bootstrap, self.bootstrap_seed,
                               self.user_weight if user is not None else None, gauc=gauc, pred_b=pred_b)
 
+    def _calibration_bootstrap(self, pred, label, domain, user, multi, pred_b=None):
+        """the calibration figures' replicates under `_bootstrap`'s clusters, replicate count and seed, over the evaluator's bins"""
+        return eval_calibration_bootstrap(pred, label, user, self.n_user if user is not None else None, domain if multi else None,
+                                          self.n_domain if multi else 1, self.calibration_bins, self.bootstrap, self.bootstrap_seed,
+                                          pred_b=pred_b)
+
     def _boot_summary(self, stats, rows, multi):
         """stats {name: replicates [n_rep, seg]}, rows: eval's row counts [seg] (device) -> [len(stats), 4, seg + 1] f64 on the device:
         (se, lo, hi, valid) of every column and, last, of the mean over the present domains, formed PER REPLICATE with mean_auc's
@@ -1172,12 +1286,17 @@ class Evaluator:
     def _boot_report(self, result, names, boot_sum, rows, multi):
         """total_<name>_boot_se / _lo / _hi, with per-domain evaluation domain_<name>_boot_* {d: value} over the present domains and
         mean_<name>_boot_*; boot_valid = the smallest number of valid replicates over everything reported (the mean's only when
-        domain_cnt_weight is set: without it every mean is NaN)"""
+        domain_cnt_weight is set: without it every mean is NaN).  -> {name: [se, lo, hi, valid] host lists over the columns (the
+        domains, ALL rows, the mean)}"""
         summ = boot_sum.cpu().tolist()
         bad = int(eval_bootstrap.last_err.item())
         if bad:
             raise ValueError(f"evaluation row {bad - 1}: NaN prediction, label outside {{0,1}}, domain outside [0, {self.n_domain}) or "
                              f"user outside range")
+        if self.calibration_ci:
+            bad = int(eval_calibration_bootstrap.last_err.item())
+            if bad:
+                raise ValueError(f"evaluation row {bad - 1}: prediction outside [0, 1]")
         n_all = len(summ[0][0]) - 2                            # columns: the domains, ALL rows, the mean
         present = [d for d in range(self.n_domain) if rows[d] > 0] if multi else []
         valid = []
@@ -1191,6 +1310,7 @@ class Evaluator:
             if multi and self.domain_cnt_weight is not None:
                 valid.append(s[3][n_all + 1])
         result["boot_valid"] = int(min(valid))
+        return dict(zip(names, summ))
 
     def calibration_table(self, data_loader):
         """One scoring pass -> (table, table_q, segments): the equal-width and the equal-mass reliability table as
@@ -1221,7 +1341,9 @@ class Evaluator:
         as in test()) — then both passes must also see the same user column.  With bootstrap set total_delta_boot_se/lo/hi (+ domain_
         and mean_ forms), the *_loss_delta_boot_* forms with loss_ci and the *_gauc_delta_boot_* forms with gauc_ci
         (mean_gauc_delta_boot_* included), and boot_valid: the replicates weight both models' rows alike; with user_idx the users are
-        resampled and both passes must see the same user column."""
+        resampled and both passes must see the same user column.  With calibration_ci, for fig in pcoc, brier, ece, ece_quantile:
+        total_<fig>_delta (figure(self) - figure(other), from two `eval_calibration` calls), total_<fig>_delta_boot_se/lo/hi,
+        total_<fig>_z = delta / boot_se by the rules above, and the domain_ and mean_ forms."""
         pred_a, label, domain, user = self._score(data_loader)
         pred_b, label_b, domain_b, user_b = other._score(data_loader)
         if label.shape != label_b.shape or not torch.equal(label, label_b):
@@ -1248,6 +1370,15 @@ class Evaluator:
                 stats["loss_delta"] = boot.loss - boot.loss_b
             if self.gauc_ci:
                 stats["gauc_delta"] = boot.gauc - boot.gauc_b
+            if self.calibration_ci:                            # likewise queued: both point figures and the shared-weight replicates
+                cal_a = eval_calibration(pred_a, label, domain if multi else None, self.n_domain if multi else 1, self.calibration_bins)
+                cal_err_a = eval_calibration.last_err
+                cal_b = eval_calibration(pred_b, label, domain if multi else None, self.n_domain if multi else 1, self.calibration_bins)
+                cb = self._calibration_bootstrap(pred_a, label, domain, user, multi, pred_b=pred_b)
+                cal_delta = {"pcoc": cal_a.pcoc - cal_b.pcoc, "brier": cal_a.brier - cal_b.brier, "ece": cal_a.ece - cal_b.ece,
+                             "ece_quantile": cal_a.ece_q - cal_b.ece_q}
+                stats.update({"pcoc_delta": cb.pcoc - cb.pcoc_b, "brier_delta": cb.brier - cb.brier_b, "ece_delta": cb.ece - cb.ece_b,
+                              "ece_quantile_delta": cb.ece_q - cb.ece_q_b})
             boot_sum = self._boot_summary(stats, ci.rows, multi)
         delta, var, rows = ci.delta.cpu().tolist(), ci.var_delta.cpu().tolist(), ci.rows.cpu().tolist()
         bad = int(eval_auc_ci.last_err.item())
@@ -1289,7 +1420,21 @@ class Evaluator:
                 result.update({"domain_gauc_delta": {d: delta[d] for d in present}, "domain_gauc_delta_se": d_se,
                                "domain_gauc_z": {d: _z(delta[d], d_se[d]) for d in present}})
         if self.bootstrap:
-            self._boot_report(result, list(stats), boot_sum, rows, multi)
+            summ = self._boot_report(result, list(stats), boot_sum, rows, multi)
+        if self.calibration_ci:
+            bad = max(int(cal_err_a.item()), int(eval_calibration.last_err.item()))
+            if bad:
+                raise ValueError(f"evaluation row {bad - 1}: prediction outside [0, 1]")
+            n_all = self.n_domain if multi else 1              # the "all rows" column; the mean's follows it
+            for k, v in cal_delta.items():
+                delta, se = v.cpu().tolist(), summ[k + "_delta"][0]
+                result[f"total_{k}_delta"] = delta[-1]
+                result[f"total_{k}_z"] = _z(delta[-1], se[n_all])
+                if multi:
+                    mean_delta = sum(self._weight(d) * delta[d] for d in present)
+                    result.update({f"domain_{k}_delta": {d: delta[d] for d in present},
+                                   f"domain_{k}_z": {d: _z(delta[d], se[d]) for d in present},
+                                   f"mean_{k}_delta": mean_delta, f"mean_{k}_z": _z(mean_delta, se[n_all + 1])})
         return result
 
     def _weight(self, d):

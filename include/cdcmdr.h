@@ -1309,6 +1309,43 @@ int cdc_eval_calibration(const float* pred, const int16_t* label, const int32_t*
                          int64_t* tab_counts, float* tab_range, int32_t* err_flag, void* workspace, int64_t workspace_bytes,
                          void* stream);
 
+/* Clustered bootstrap of the calibration figures: n_rep replicates of pcoc, brier, ece and ece_q (equal-mass bins) per segment
+ * (domain 0..n_domain-1, then ALL rows).  pred_a, pred_b (or NULL), label, cluster, ld_cluster, n_cluster, domain, ld_domain,
+ * n_domain, n_rep, seed as for cdc_eval_bootstrap; n_bins = K as for cdc_eval_calibration; predictions are probabilities in [0, 1].
+ * Replicate r gives row i the integer weight w_i = w(seed, r, cluster_i): cdc_eval_bootstrap's weight — the same hash, the same
+ * thresholds, cluster = the row index without a cluster column.  THE FIGURES OF A REPLICATE ARE cdc_eval_calibration's FIGURES ON
+ * THE MULTISET IN WHICH ROW i APPEARS w_i TIMES.  Per segment, with q = rint(double(p) * 2^32):
+ *     W = sum w_i   Wp = sum w_i y_i   SQ = sum w_i q_i   SE2 = sum w_i (q_i - y_i 2^32)^2
+ *     pcoc = SQ / (Wp 2^32)      brier = SE2 / (W 2^64)
+ *     equal-width bin of a row: min(K-1, floor(double(p) * K)), a function of p alone;  ece = sum_b |SQ_b - Wp_b 2^32| / (W 2^32)
+ *     equal-mass bins: with the segment's rows in (score, label) order row i occupies the expanded positions [R_i, R_i + w_i), R_i
+ *         the weight in front of it; bin b is the expanded positions [floor(b W / K), floor((b+1) W / K)).  A row gives each bin
+ *         as many copies as fall in it: one row's copies may be split over several bins; rows that tie in (score, label) are
+ *         identical, so their order does not matter.  ece_q is the same formula over these bins.
+ *     every figure is NaN iff W == 0; pcoc is also NaN iff Wp == 0.  A single-class segment still has brier, ece and ece_q.
+ *   out    [4 * (1 + (pred_b != NULL))][n_rep][n_domain + 1] doubles: pcoc, brier, ece, ece_q, then the four of pred_b under the
+ *          SAME weights (its equal-mass bins from its own order).  Deltas are the caller's per-replicate differences.
+ *   counts [2][n_rep][n_domain + 1] int64: W and Wp — the integers cdc_eval_bootstrap writes for the same (seed, r).
+ *   err_flag (optional): 1 + the largest index of a row with a prediction outside [0, 1] or NaN (either vector), a label other than
+ *          0/1, or a domain or cluster outside range; such a row is counted clamped, as cdc_eval_calibration and
+ *          cdc_eval_bootstrap clamp it.
+ * Every sum is an exact integer (below 2^64 for n < 2^28 and weights <= 12; squares as two 32-bit halves), handed over with integer
+ * atomic adds; every double is one integer numerator converted once, an exact denominator and one division, formed by the code
+ * cdc_eval_calibration uses: the same rows in any order give the same bits, and a replicate equals cdc_eval_calibration on the
+ * expanded rows bit for bit.  A weight is recomputed from (seed, r, cluster) wherever it is needed; no [row][replicate] array exists.
+ * Limits, all checked before anything is launched: null pointers, n_bins outside [1, 1024], n_rep outside [1, 4096], n_domain
+ * outside [1, 2^20), n_domain > 1 without the domain column, a workspace too small or not 256-byte aligned: CDC_E_BADARG; n >= 2^28,
+ * or n_rep * (n_domain + 1) * n_bins > 2^22 cells: CDC_E_TOOBIG.  Stream-ordered: no allocation, no synchronisation, no state kept;
+ * the number and dimensions of the launches depend on the sizes and on pred_b != NULL alone, never on the data.
+ * Not part of this call: MCE replicates, per-bin reliability bands, BCa or studentised intervals.
+ * workspace: cdc_eval_calibration_bootstrap_workspace_bytes(n, n_domain, n_bins, n_rep, paired) bytes, 256-byte aligned; 0 for
+ * sizes the call refuses. */
+int64_t cdc_eval_calibration_bootstrap_workspace_bytes(int64_t n, int32_t n_domain, int32_t n_bins, int32_t n_rep, int32_t paired);
+int cdc_eval_calibration_bootstrap(const float* pred_a, const float* pred_b, const int16_t* label, const int32_t* cluster,
+                                   int64_t ld_cluster, int64_t n_cluster, const int32_t* domain, int64_t ld_domain, int32_t n_domain,
+                                   int32_t n_bins, int64_t n, int32_t n_rep, uint64_t seed, double* out, int64_t* counts,
+                                   int32_t* err_flag, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Isotonic recalibration: per segment (domain 0..n_domain-1, then ALL rows) the non-decreasing least-squares fit of the 0/1 labels
  * on the score (pool-adjacent-violators), and the map it defines.  pred, label, domain, ld_domain, n_domain as for cdc_eval_metrics;
  * pred is any finite float (-0.0 and +0.0 are one score, reported as +0.0).  Rows of one score are one point; the fit is delivered
