@@ -915,8 +915,10 @@ int cdc_tower_step(const cdc_tower_args* a, void* stream);
  * end with the LOCAL column sums of the statistics the next phase needs in exchange[0..3] (the last workgroup of a tower to finish
  * adds the tower's partials up, in cdc_bn_fwd's order; nobody waits inside a launch); the caller sums each exchange buffer over
  * the ranks (all-reduce) before the next phase, which normalises with the GLOBAL sums and row count.  Parameter gradients stay
- * local sums (the data-parallel all-reduce of the gradient arena adds the ranks).  Same arithmetic as cdc_tower_fwd / _bwd;
- * a one-rank run gives their results.  M is this rank's row count (may differ between ranks). */
+ * local sums (the data-parallel all-reduce of the gradient arena adds the ranks).  Same arithmetic as cdc_tower_fwd / _bwd:
+ * a one-rank run (the exchange buffers left as written) gives their results bit for bit, except bce_loss, whose rows phase 4
+ * adds per block over all towers where cdc_tower_bwd adds per (tower, block) — the same double sum in another order.  bce_loss
+ * is this rank's LOCAL sum times bce_inv_count (1 / global batch).  M is this rank's row count (may differ between ranks). */
 int cdc_tower_dp(const cdc_tower_args* a, int32_t phase, void* stream);
 
 /* ------------------------------------------------------------------------------------------

@@ -353,11 +353,13 @@ def kernel_forward32(s, D):
 # ------------------------------------------------------------------------------------------------------------------------
 # backward: from the fp32 (or bf16) operands the kernel reads — x, the sign of y, dy, gamma, save_mean, save_invstd
 # ------------------------------------------------------------------------------------------------------------------------
-def ref_backward(s, D, Y, MEAN, INV, defect=None, parts=None):
+def ref_backward(s, D, Y, MEAN, INV, defect=None, parts=None, ddy=None, divisor=None):
     """Y[i]: the launch's y buffer [rows of the launch, C] (only its sign is used); MEAN[i] / INV[i]: the saved statistics (in
     eval the running mean and rsqrt(running_var + eps), as the header asks of the caller).  parts[i]: the segment's rows split
     over data-parallel ranks (index arrays into the group's rows): dx then uses the sums over all rows, and dgamma_r<k> /
-    dbeta_r<k> are rank k's local sums; without parts dgamma / dbeta are the sums over the group."""
+    dbeta_r<k> are rank k's local sums; without parts dgamma / dbeta are the sums over the group.
+    ddy[i]: the error the kernel's own dy already carries against D["dy"][i] (a fused launch forms dy itself: tests/tower_ref.py),
+    joined to every bound.  divisor[i]: per row, what a seeded defect divides the column sums by instead of the group's rows."""
     out = []
     ms_true = mask_scale(s)
     ms = 1.0 if defect == "no_mask_scale" else ms_true
@@ -372,6 +374,9 @@ def ref_backward(s, D, Y, MEAN, INV, defect=None, parts=None):
         sign = x if defect == "mask_from_x" else y
         dz = np.where(sign > 0, dy * ms, 0.0) if masked else dy
         ddz = U24 * np.abs(dz) if (masked and ms != 1.0) else np.zeros_like(dz)
+        if ddy is not None:
+            e = f64(ddy[i])[rows]
+            ddz = ddz + (np.where(sign > 0, e * abs(ms), 0.0) if masked else e)
         R = {}
         P = [np.arange(Mg)] if parts is None else parts[i]
         names = [("dgamma", "dbeta")] if parts is None else [(f"dgamma_r{k}", f"dbeta_r{k}") for k in range(len(P))]
@@ -398,6 +403,8 @@ def ref_backward(s, D, Y, MEAN, INV, defect=None, parts=None):
             gi = gam * inv
             if s["training"]:
                 Md = launch_rows(s) if defect == "launch_M" else Mg
+                if divisor is not None:
+                    Md = f64(divisor[i])[rows].reshape(-1, 1)
                 pq = xh * dg
                 ep = np.abs(xh) * bdg + np.abs(dg) * dxh + U24 * np.abs(pq)
                 q = db + pq

@@ -158,6 +158,34 @@ class PadBuf:
         return h[:, :self.cols].copy()
 
 
+class PadBufH:
+    """PadBuf for a [rows, cols] bf16 matrix (values given as fp32, rounded to nearest even): 0x7FC0 (NaN) in input padding, the
+    sentinel's bf16 bits in output padding.  `extra_rows` rows of padding follow the matrix (rows below M of an output)."""
+
+    def __init__(self, dev, values, out=False, pad=8, extra_rows=0):
+        from bn_ref import bf16_bits
+        values = np.asarray(values, dtype=np.float32)
+        self.rows, self.cols = values.shape
+        self.ld = self.cols + pad
+        fill = int(bf16_bits(np.array([OUT_SENTINEL], dtype=np.float32))[0]) if out else 0x7FC0
+        host = np.full((self.rows + extra_rows, self.ld), fill, dtype=np.uint16)
+        host[:self.rows, :self.cols] = bf16_bits(values).reshape(values.shape)
+        self.host0 = host
+        self.t = torch.from_numpy(host.view(np.int16).copy()).to(dev)
+
+    @property
+    def ptr(self):
+        return self.t.data_ptr()
+
+    def read(self, what="buffer"):
+        """the matrix as fp32 values; the padding must have come back bit-unchanged"""
+        from bn_ref import bf16_from_bits
+        h = self.t.cpu().numpy().view(np.uint16)
+        assert np.array_equal(h[:, self.cols:], self.host0[:, self.cols:]) and np.array_equal(h[self.rows:], self.host0[self.rows:]), \
+            f"{what}: padding written"
+        return bf16_from_bits(h[:self.rows, :self.cols]).reshape(self.rows, self.cols).copy()
+
+
 def nan_like(rows, cols):
     return np.full((rows, cols), np.nan, dtype=np.float32)
 
