@@ -541,13 +541,28 @@ __device__ __forceinline__ bf16x8_t g2_tr_fragment(const unsigned char* tile, in
     const int row = row_base + 4 * g + q;
     const int c = (col0 + 4 * p) >> 3;
     const unsigned char* a0 = tile + row * T::ROW_BYTES + ((c ^ T::swz(row)) << 4) + ((p & 1) << 3);
-    const unsigned char* a1 = a0 + 16 * T::ROW_BYTES;               // row + 16: the same (row & 7), the same swizzle
-    typedef g2_s16x4 __attribute__((address_space(3))) * lds_ptr;
-    const g2_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)a0);
-    const g2_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)a1);
+    // The two reads are inline assembly ON PURPOSE.  Through __builtin_amdgcn_ds_read_tr16_b64_v4i16 the compiler sees an LDS read
+    // that may alias the pending direct-to-LDS loads and puts `s_waitcnt vmcnt(0)` in front of the first fragment read of every
+    // slab: the slab issued a moment earlier had to land before the MFMAs of the current one could start, so the stages overlapped
+    // nothing, however many there were (profiles/round8/README.md).  Which slab has landed is the K loop's own counted wait +
+    // barrier; what the compiler no longer does for us is the wait for these reads themselves: g2_tr_wait, before their first use.
+    typedef __attribute__((address_space(3))) const unsigned char* lds_ptr;
+    const unsigned addr = (unsigned)(uintptr_t)(lds_ptr)a0;
+    g2_s16x4 lo, hi;
+    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo) : "v"(addr) : "memory");
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(addr), "n"(16 * T::ROW_BYTES) : "memory");   // row + 16: the same (row & 7), the same swizzle
     union { g2_s16x4 h[2]; bf16x8_t v; } u;
     u.h[0] = lo; u.h[1] = hi;
     return u.v;
+}
+// every fragment read issued so far has arrived; the fragments are operands of the wait, so no use of them can be scheduled above it
+template <int MT, int NT>
+__device__ __forceinline__ void g2_tr_wait(bf16x8_t (&fa)[MT], bf16x8_t (&fb)[NT]) {
+    static_assert(MT == NT && (MT == 2 || MT == 4), "wave tiles of 2 x 2 or 4 x 4 MFMA tiles");
+    if constexpr (MT == 4)
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa[0]), "+v"(fa[1]), "+v"(fa[2]), "+v"(fa[3]), "+v"(fb[0]), "+v"(fb[1]), "+v"(fb[2]), "+v"(fb[3])::"memory");
+    else
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa[0]), "+v"(fa[1]), "+v"(fb[0]), "+v"(fb[1])::"memory");
 }
 
 // (the body is a device function so that one launch can run two tile classes: k_g2_tn_dual below; `a` may live in the kernel
@@ -644,6 +659,7 @@ __device__ __forceinline__ void g2_tn_body(const cdc_lin_bwdw_args& a, const int
             for (int mt = 0; mt < MT; ++mt) fa[mt] = g2_tr_fragment<BMO>(As, ks * 32, wm + mt * 16, lane);
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) fb[nt] = g2_tr_fragment<BNO>(Bs, ks * 32, wn + nt * 16, lane);
+            g2_tr_wait(fa, fb);
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
