@@ -797,6 +797,8 @@ extern "C" int cdc_cgc_mid_bwd(const cdc_cgc_mid_bwd_args* a, void* stream) {
     CDC_CHECK_ARG((((uintptr_t)a->ex1 | (uintptr_t)a->ex2 | (uintptr_t)a->dz1_h) & 15) == 0 && (((uintptr_t)a->dz2_h) & 7) == 0 &&
                       a->ld_ex1 % 4 == 0 && a->ld_ex2 % 4 == 0 && a->ld_dz1_h % 8 == 0 && a->ld_dz2_h % 4 == 0, CDC_E_ALIGN,
                   "cgc_mid_bwd: misaligned expert buffers");
+    CDC_CHECK_ARG(a->ld_ex1 >= (int64_t)a->n_exp1 * a->H1 && a->ld_ex2 >= (int64_t)a->n_exp2 * a->H2, CDC_E_ALIGN,
+                  "cgc_mid_bwd: expert buffers must be wide enough (as cgc_mid_fwd asks)");
     for (int g = 0; g < a->n_gate1; ++g)
         CDC_CHECK_ARG(a->g1[g].probs && a->g1[g].d_logits && mid_check_sel(a->g1[g].sel, a->g1[g].n_sel, a->n_exp1), CDC_E_BADARG,
                       "cgc_mid_bwd: level-k gate %d malformed", g);
@@ -813,6 +815,8 @@ extern "C" int cdc_cgc_mid_bwd(const cdc_cgc_mid_bwd_args* a, void* stream) {
         int n = 0;
         for (int e = 0; e < a->n_exp2; ++e) n += a->e2[e].src == s ? a->H2 / 32 : 0;
         for (int g = 0; g < a->n_gate2; ++g) n += a->g2[g].src == s ? 1 : 0;
+        // a source nothing reads has no K step: the grad-input tile's clamp (sc = ns - 1) would index the step table at -1
+        CDC_CHECK_ARG(n > 0, CDC_E_BADARG, "cgc_mid_bwd: level-k output %d is read by no level-k+1 expert or gate", s);
         CDC_CHECK_ARG(n <= MID_MAXSTEP, CDC_E_TOOBIG, "cgc_mid_bwd: level-k output %d feeds %d K-steps of 32 (limit %d: two experts and a gate, or three experts)",
                       s, n, MID_MAXSTEP);
     }

@@ -262,9 +262,12 @@ __global__ void __launch_bounds__(ROW_THREADS) k_gate_pool_bwd_v4(const cdc_pool
 extern "C" int cdc_gate_pool_bwd(const cdc_pool_bwd_args* a, void* stream) {
     CDC_CHECK_ARG(a && a->n_gates > 0 && a->n_gates <= CDC_MAX_GATES && a->n_expert > 0 && a->n_expert <= 2 * CDC_MAX_SEL && a->H > 0 &&
                       a->B >= 0 && a->experts && a->d_experts, CDC_E_BADARG, "gate_pool_bwd: bad argument (n_expert <= 32)");
-    for (int g = 0; g < a->n_gates; ++g)
+    for (int g = 0; g < a->n_gates; ++g) {
         CDC_CHECK_ARG(a->gate[g].d_out && a->gate[g].probs && a->gate[g].d_logits && a->gate[g].n_sel > 0 &&
                           a->gate[g].n_sel <= CDC_MAX_SEL, CDC_E_BADARG, "gate_pool_bwd: gate %d malformed", g);
+        for (int j = 0; j < a->gate[g].n_sel; ++j)                     // (sel indexes the LDS accumulators)
+            CDC_CHECK_ARG(a->gate[g].sel[j] >= 0 && a->gate[g].sel[j] < a->n_expert, CDC_E_BADARG, "gate_pool_bwd: gate %d selects expert out of range", g);
+    }
     if (a->B == 0) return 0;
     if (pool_vec_ok(a->H, a->experts, a->ld_exp) && (((uintptr_t)a->d_experts & 15) == 0) && a->ld_dexp % 4 == 0 && a->n_expert <= 16 &&
         (!a->d_experts_h || ((((uintptr_t)a->d_experts_h & 7) == 0) && a->ld_dexp_h % 4 == 0))) {

@@ -398,7 +398,8 @@ int cdc_glinear_bwd_w_pair_reduce(const cdc_lin_bwdw_args* wide, const cdc_lin_b
 /* ------------------------------------------------------------------------------------------
  * Gate softmax + expert pooling (reference: model/ple.py:89-94,105-123; model/mmoe.py:37-40,58-60)
  *   p[b,g,:] = softmax(logits[b, gate g's columns]) ; out[g][b,:] = sum_j p[b,g,j] * experts[b, sel[g][j], :]
- * experts [B, n_expert, H] with row stride ld_exp (expert e at column e*H).
+ * experts [B, n_expert, H] with row stride ld_exp (expert e at column e*H).  Both directions return CDC_E_BADARG for a
+ * sel[j] outside [0, n_expert).
  * ---------------------------------------------------------------------------------------- */
 #define CDC_MAX_GATES 16
 #define CDC_MAX_SEL   16
@@ -509,6 +510,9 @@ int cdc_gate_pool_wide_bwd(const cdc_pool_wide_bwd_args* a, void* stream);
  * Widths are compile-time: (H1, H2) = (128, 64), the reference's expert_dims ((256,128),(64,)) (config.py:39-42); other
  * shapes take the three separate launches.  sel lists ascending.  What the backward needs is written: probabilities of both
  * levels, the level-k outputs' bf16 shadows (grad-weight operand), the level-k+1 expert activations (fp32).
+ * Both directions return CDC_E_ALIGN unless ld_ex1 >= n_exp1*H1 and ld_ex2 >= n_exp2*H2.  In the backward every level-k pooled
+ * output must be read by at least one level-k+1 expert or gate, and by at most 6 K steps of 32 (two per expert, one per gate):
+ * cdc_cgc_mid_bwd returns CDC_E_BADARG for an output nothing reads (the forward accepts it), CDC_E_TOOBIG beyond the 6.
  * ---------------------------------------------------------------------------------------- */
 #define CDC_MID_MAX_EXPERT 16
 #define CDC_MID_MAX_GATE 8

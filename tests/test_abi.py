@@ -209,6 +209,36 @@ def test_entry_points_reject_bad_arguments_without_touching_the_device():
     assert lib.cdc_cgc_mid_fits(8, 4, 8, 3) == 1 and lib.cdc_cgc_mid_fits(12, 6, 12, 5) == 1
     assert lib.cdc_cgc_mid_fits(14, 7, 14, 6) == 0 and lib.cdc_cgc_mid_fits(16, 8, 16, 7) == 0
     assert lib.cdc_cgc_mid_fits(0, 1, 1, 1) == -1 and lib.cdc_cgc_mid_fits(17, 1, 1, 1) == -1
+    # the boundary's backward: two level-k outputs, one level-k+1 expert and gate.  B = 0: every check runs, nothing is launched
+    b = _lib.CgcMidBwdArgs()
+    b.B, b.H1, b.H2, b.n_exp1, b.n_gate1, b.n_exp2, b.n_gate2 = 0, 128, 64, 1, 2, 1, 1
+    b.ex1 = b.ex2 = b.dz1_h = b.dz2_h = 16
+    b.ld_ex1, b.ld_dz1_h, b.ld_ex2, b.ld_dz2_h = 128, 128, 64, 64
+    for g in range(2):
+        b.g1[g].probs = b.g1[g].d_logits = 16
+        b.g1[g].n_sel = 1
+    b.e2[0].wt, b.e2[0].ldwt, b.e2[0].src = 16, 64, 0
+    G = b.g2[0]
+    G.d_out = G.probs = G.d_logits = G.wt = 16
+    G.ld_dout, G.ldwt, G.src, G.n_sel = 64, 32, 1, 1
+    assert lib.cdc_cgc_mid_bwd(C.byref(b), None) == 0
+    G.src = 0                                              # level-k output 1 is read by nothing: its grad-input tile has no K step
+    assert lib.cdc_cgc_mid_bwd(C.byref(b), None) == -1 and b"is read by no" in lib.cdc_last_error()
+    G.src = 1
+    for field, width in (("ld_ex1", 128), ("ld_ex2", 64)):  # narrower than the experts it holds: refused as the forward refuses it
+        setattr(b, field, width - 4)
+        assert lib.cdc_cgc_mid_bwd(C.byref(b), None) == -3 and b"wide enough" in lib.cdc_last_error()
+        setattr(b, field, width)
+    assert lib.cdc_cgc_mid_bwd(C.byref(b), None) == 0
+    # the narrow pool backward indexes its LDS accumulators with sel: out of range is refused, as in the forward
+    q = _lib.PoolBwdArgs()
+    q.n_gates, q.n_expert, q.H, q.B, q.experts, q.d_experts = 1, 4, 64, 0, 16, 16
+    q.gate[0].d_out = q.gate[0].probs = q.gate[0].d_logits = 16
+    q.gate[0].n_sel, q.gate[0].sel[0], q.gate[0].sel[1] = 2, 0, 3
+    assert lib.cdc_gate_pool_bwd(C.byref(q), None) == 0
+    for bad in (4, -1):
+        q.gate[0].sel[1] = bad
+        assert lib.cdc_gate_pool_bwd(C.byref(q), None) == -1 and b"out of range" in lib.cdc_last_error()
     with pytest.raises(RuntimeError):
         _lib.check(-1, "probe")
 
