@@ -14,7 +14,8 @@
 //     fragment is bank-conflict free;
 //   * two LDS stages: the loads of K-slab t+1 are in flight under the MFMAs of slab t, one barrier per slab.
 // K-slabs are whole: every operand row must be READABLE up to the next multiple of 64 elements and the padding of at
-// least one operand of each product must be zero (the shadows are allocated zero-padded for that).
+// least one operand of each product must be zero (the shadows are allocated zero-padded for that), the other's FINITE
+// (0 x NaN and 0 x Inf are NaN).
 #include "common.h"
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -264,15 +265,17 @@ __global__ void __launch_bounds__(G2_THREADS, (G2Cfg<BM, BN, NSTAGE>::BLOCKS_PER
     const bool vec_y = !O.y || (((((uintptr_t)O.y) & 15) == 0) && (O.ldy % 4 == 0));
     const bool vec_h = !O.yh || (((((uintptr_t)O.yh) & 15) == 0) && (O.ldyh % 8 == 0));
     const bool vec_m = !O.mask || (((((uintptr_t)O.mask) & 15) == 0) && (O.mask_bf16 ? (O.ldmask % 8 == 0) : (O.ldmask % 4 == 0)));
+    const bool vec_b = !(fwd && O.bias) || ((((uintptr_t)O.bias) & 15) == 0);     // (the header asks 4-byte alignment of a bias, no more)
     // per THREAD: its 8 columns are all inside the output and on one side of the activation boundary -> vector path;
-    // a piece that straddles N or act_cols (or unaligned destinations) -> element-wise path; pieces past N: nothing to do
+    // a piece that straddles N or act_cols (or unaligned destinations, or a bias off the 16-byte grid) -> element-wise path;
+    // pieces past N: nothing to do
     if (col >= N) return;
     const int row_end = min(G2_BM, M - i0);
     const bool act_all = col + 8 <= O.act_cols, act_none = col >= O.act_cols;
     float* const yp = O.y ? O.y + (int64_t)i0 * O.ldy + col : nullptr;
     __bf16* const hp = O.yh ? reinterpret_cast<__bf16*>(O.yh) + (int64_t)i0 * O.ldyh + col : nullptr;
 
-    if (col + 8 <= N && vec_y && vec_h && vec_m && (act_all || act_none)) {
+    if (col + 8 <= N && vec_y && vec_h && vec_m && vec_b && (act_all || act_none)) {
         // ---- fast path (every tile of a whole-slab problem): straight-line code, 8 columns per thread, all decisions uniform
         if (fwd) {
             f32x4_t b0 = {0.f, 0.f, 0.f, 0.f}, b1 = {0.f, 0.f, 0.f, 0.f};

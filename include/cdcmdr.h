@@ -300,8 +300,11 @@ int cdc_transpose_multi(const cdc_transpose_args* a, void* stream);
  *                        of the layer that produced x on columns [0,act_cols): d = (mask > 0) ? d * mask_scale : 0, then
  *                        optional += into the fp32 destination
  * Kr: the reduction length rounded UP to a multiple of 64; both operands' rows must be readable that far and the padding of
- * at least one of them must be zero (shadows are allocated zero-padded).  Operand pointers 16-byte aligned, row strides
- * multiples of 8 elements.  Every output may be written as fp32 (y), as its bf16 shadow (yh), or both. */
+ * at least one of them must be zero (shadows are allocated zero-padded) and the padding of the other FINITE: the padded
+ * products are formed (0 x NaN and 0 x Inf are NaN), finite garbage times zero adds nothing.  Nothing is read beyond Kr.
+ * Operand pointers 16-byte aligned, row strides multiples of 8 elements.  Every output may be written as fp32 (y), as its bf16
+ * shadow (yh), or both.  y, yh, mask and bias need only their element's alignment: destinations, masks or a bias off the
+ * 16-byte grid (or row strides that are no multiple of 16 bytes) take an element-wise epilogue with the same results. */
 #define CDC_G2_MAX_OUT 24
 #define CDC_G2_MAX_SEG 32
 typedef struct {
