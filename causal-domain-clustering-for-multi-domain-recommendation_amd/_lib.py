@@ -273,7 +273,7 @@ class RowdotBGroup(C.Structure):
 class RowdotBwdArgs(C.Structure):
     _fields_ = [("n_groups", c_i32), ("sigmoid", c_i32), ("M", c_i64), ("row_offsets", c_p), ("workspace", c_p),
                 ("bce_group", c_p), ("bce_y_i16", c_p), ("bce_y_f32", c_p), ("bce_loss", c_p), ("bce_partial", c_p),
-                ("bce_inv_count", c_f), ("pad_", c_i32), ("g", RowdotBGroup * MAX_GROUPS)]
+                ("bce_weight", c_p), ("bce_inv_count", c_f), ("pad_", c_i32), ("g", RowdotBGroup * MAX_GROUPS)]
 
 
 HEAD_MAX_TOWERS = 8
@@ -292,7 +292,7 @@ class HeadArgs(C.Structure):
                 ("addend", c_p * 2), ("ld_addend", c_i64 * 2), ("d_addend", c_p * 2), ("ld_d_addend", c_i64 * 2),
                 ("accumulate_d_addend", c_i32 * 2), ("workspace", c_p),
                 ("bce_group", c_p), ("bce_y_i16", c_p), ("bce_y_f32", c_p), ("bce_loss", c_p), ("bce_partial", c_p),
-                ("bce_inv_count", c_f), ("pad2_", c_i32), ("t", HeadTower * HEAD_MAX_TOWERS)]
+                ("bce_weight", c_p), ("bce_inv_count", c_f), ("pad2_", c_i32), ("t", HeadTower * HEAD_MAX_TOWERS)]
 
 
 TOWER_MAX = 4
@@ -314,12 +314,22 @@ class TowerDesc(C.Structure):
 
 class TowerArgs(C.Structure):
     _fields_ = [("n_tower", c_i32), ("H0", c_i32), ("H1", c_i32), ("H2", c_i32), ("M", c_i64), ("relu", c_i32), ("sigmoid", c_i32),
-                ("drop_p", c_f), ("eps", c_f), ("momentum", c_f), ("pad_", c_i32), ("seed1", C.c_uint64), ("seed2", C.c_uint64),
+                ("drop_p", c_f), ("eps", c_f), ("momentum", c_f), ("bce_weight_lo", C.c_uint32), ("seed1", C.c_uint64), ("seed2", C.c_uint64),
                 ("seed_offset_dev", c_p), ("out", c_p), ("ld_out", c_i64), ("d_out", c_p), ("ld_dout", c_i64),
                 ("wide_x", c_p), ("ld_wide", c_i64), ("wide_w", c_p), ("wide_bias", c_p), ("wide_dx", c_p), ("ld_wide_dx", c_i64),
                 ("wide_dw", c_p), ("wide_dbias", c_p), ("wide_K", c_i32), ("accumulate_wide_dx", c_i32),
-                ("bce_group", c_p), ("bce_y_i16", c_p), ("bce_y_f32", c_p), ("bce_loss", c_p), ("bce_inv_count", c_f), ("pad2_", c_i32),
+                ("bce_group", c_p), ("bce_y_i16", c_p), ("bce_y_f32", c_p), ("bce_loss", c_p), ("bce_inv_count", c_f), ("bce_weight_hi", C.c_uint32),
                 ("workspace", c_p), ("err", c_p), ("exchange", c_p * 4), ("t", TowerDesc * TOWER_MAX)]
+
+    # the address of the fused loss's row weights travels as two 32-bit words (include/cdcmdr.h: CDC_TOWER_SET_BCE_WEIGHT)
+    @property
+    def bce_weight(self):
+        return ((self.bce_weight_hi << 32) | self.bce_weight_lo) or None
+
+    @bce_weight.setter
+    def bce_weight(self, p):
+        p = int(p or 0)
+        self.bce_weight_lo, self.bce_weight_hi = p & 0xffffffff, p >> 32
 
 
 class StarFuseArgs(C.Structure):
@@ -439,6 +449,9 @@ _SIGNATURES = {
     "cdc_fm_fwd": (c_i32, [c_p, c_i64, c_p, c_i64, c_i64, c_i32, c_i32, c_p]),
     "cdc_fm_bwd": (c_i32, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_i32, c_i32, c_i32, c_p]),
     "cdc_bce_mean_fwd_bwd": (c_i32, [c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i32, c_f, c_p]),
+    "cdc_bce_weighted_fwd_bwd": (c_i32, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i32, c_f, c_p]),
+    "cdc_bce_mean_weighted_fwd_bwd": (c_i32, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i32, c_f, c_p]),
+    "cdc_stage_weights": (c_i32, [c_p, c_p, c_i64, c_i32, c_p, c_i32, c_p, c_f, c_p, c_i64, c_p]),
     "cdc_cross_fwd": (c_i32, [c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_i64, c_p, c_i64, c_i32, c_p]),
     "cdc_cross_bwd": (c_i32, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_i64, c_i32, c_p]),
     "cdc_tanh_fwd": (c_i32, [c_p, c_i64, c_p, c_i64, c_i64, c_i32, c_p]),

@@ -159,10 +159,11 @@ __global__ void __launch_bounds__(HEAD_BWD_WAVES * 64) k_head_bwd(const cdc_head
     for (int r = r_begin + wave; r < r_end; r += HEAD_BWD_WAVES) {
         const int64_t rr = r;
         int64_t c = 0;
-        float tgt = 0.f;
+        float tgt = 0.f, wrow = 1.f;
         if (bce) {
             c = a.bce_group ? a.bce_group[rr] : 0;
             tgt = a.bce_y_i16 ? (float)a.bce_y_i16[rr] : a.bce_y_f32[rr];
+            if (a.bce_weight) wrow = a.bce_weight[rr];                   // the row's loss weight (NULL: unweighted, the code as it was)
         }
         float o[NT], dout_in[NT];
 #pragma unroll
@@ -205,8 +206,10 @@ __global__ void __launch_bounds__(HEAD_BWD_WAVES * 64) k_head_bwd(const cdc_head
                 if (bce) {
                     // BCELoss(mean) on the row's own tower and its gradient (cdc_bce_fwd_bwd's arithmetic, operation for operation)
                     if (t == own) {
-                        loss_part += (double)((tgt - 1.f) * fmaxf(log1pf(-o[t]), -100.f) - tgt * fmaxf(logf(o[t]), -100.f));
+                        const double lp = (double)((tgt - 1.f) * fmaxf(log1pf(-o[t]), -100.f) - tgt * fmaxf(logf(o[t]), -100.f));
+                        loss_part += a.bce_weight ? lp * (double)wrow : lp;
                         dout = a.bce_inv_count * (o[t] - tgt) / fmaxf((1.f - o[t]) * o[t], 1e-12f);
+                        if (a.bce_weight) dout *= wrow;                  // the last factor of the finished unweighted gradient
                     } else dout = 0.f;
                 } else dout = dout_in[t];
                 d[t] = a.sigmoid ? dout * o[t] * (1.f - o[t]) : dout;
@@ -360,6 +363,7 @@ extern "C" int cdc_head_bwd(const cdc_head_args* a, void* stream) {
     CDC_CHECK_ARG(bce || a->d_out, CDC_E_BADARG, "head_bwd: needs the output gradient or the fused loss");
     CDC_CHECK_ARG(!bce || (a->sigmoid && a->bce_loss && a->bce_partial && a->bce_inv_count > 0.f), CDC_E_BADARG,
                   "head_bwd: the fused BCE needs sigmoid outputs, a loss pointer and the partial-sum buffer");
+    CDC_CHECK_ARG(bce || !a->bce_weight, CDC_E_BADARG, "head_bwd: bce_weight without the fused BCE's labels");
     for (int t = 0; t < a->n_tower; ++t)
         CDC_CHECK_ARG(a->t[t].x && a->t[t].w && a->t[t].K > 0, CDC_E_BADARG, "head_bwd: tower %d malformed", t);
     // every load of a row is issued before its first store, so an input gradient that two towers (or a tower and the wide term)

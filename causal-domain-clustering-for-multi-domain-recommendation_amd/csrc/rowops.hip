@@ -1292,7 +1292,7 @@ __global__ void __launch_bounds__(ROW_THREADS) k_rowdot_bwd(const cdc_rowdot_bwd
         int64_t gr[RB];
         if (bce) {
             // the loss and its gradient formed here instead of by a cdc_bce_fwd_bwd launch in between (same float operations)
-            float o[RB], t[RB];
+            float o[RB], t[RB], wv[RB];
             int64_t col[RB];
 #pragma unroll
             for (int q = 0; q < RB; ++q) {
@@ -1301,14 +1301,20 @@ __global__ void __launch_bounds__(ROW_THREADS) k_rowdot_bwd(const cdc_rowdot_bwd
                 o[q] = G.out[gr[q] * G.ld_out];
                 t[q] = a.bce_y_i16 ? (float)a.bce_y_i16[gr[q]] : a.bce_y_f32[gr[q]];
                 col[q] = a.bce_group ? a.bce_group[gr[q]] : 0;
+                if (a.bce_weight) wv[q] = a.bce_weight[gr[q]];
             }
 #pragma unroll
             for (int q = 0; q < RB; ++q) {
                 if (col[q] < 0 || col[q] >= a.n_groups) col[q] = 0;
                 const bool own = col[q] == g && r0 + q * WAVES_PER_BLOCK < r_end;
                 const float x = o[q];
-                if (own) loss_part += (double)((t[q] - 1.f) * fmaxf(log1pf(-x), -100.f) - t[q] * fmaxf(logf(x), -100.f));
-                const float dout = own ? a.bce_inv_count * (x - t[q]) / fmaxf((1.f - x) * x, 1e-12f) : 0.f;
+                // (bce_weight: the row's loss weight, the last factor of the finished loss term and gradient; NULL = the code as it was)
+                if (own) {
+                    const double lp = (double)((t[q] - 1.f) * fmaxf(log1pf(-x), -100.f) - t[q] * fmaxf(logf(x), -100.f));
+                    loss_part += a.bce_weight ? lp * (double)wv[q] : lp;
+                }
+                float dout = own ? a.bce_inv_count * (x - t[q]) / fmaxf((1.f - x) * x, 1e-12f) : 0.f;
+                if (a.bce_weight) dout *= wv[q];
                 d[q] = dout * x * (1.f - x);
             }
         } else {
@@ -1409,6 +1415,7 @@ extern "C" int cdc_rowdot_bwd(const cdc_rowdot_bwd_args* a, void* stream) {
         kmax = std::max(kmax, a->g[g].K);
     }
     CDC_CHECK_ARG((size_t)WAVES_PER_BLOCK * (kmax + 1) * 4 <= 64 * 1024, CDC_E_TOOBIG, "rowdot_bwd: K too large");
+    CDC_CHECK_ARG(!a->bce_weight || a->bce_y_i16 || a->bce_y_f32, CDC_E_BADARG, "rowdot_bwd: bce_weight without the fused BCE's labels");
     if (a->bce_y_i16 || a->bce_y_f32)
         CDC_CHECK_ARG(a->sigmoid && !a->row_offsets && a->bce_loss && a->bce_partial && a->bce_inv_count > 0.f, CDC_E_BADARG,
                       "rowdot_bwd: the fused BCE needs sigmoid outputs, dense rows, a loss pointer and the partial-sum buffer");
@@ -1425,17 +1432,20 @@ extern "C" int cdc_rowdot_bwd(const cdc_rowdot_bwd_args* a, void* stream) {
 // =================================================================================================
 // BCE on probabilities, mean reduction, + its gradient  (run.py:484,723; aten binary_cross_entropy)
 // =================================================================================================
+// WEIGHTED (cdc_bce_weighted_fwd_bwd): row b's loss term and gradient times weight[b] — the weight is the last fp32 factor of the
+// finished unweighted gradient, and the loss adds (double)l * (double)w.  The unweighted instantiation is the code as it was.
+template <bool WEIGHTED>
 __global__ void __launch_bounds__(1024) k_bce(const float* __restrict__ p, int64_t ldp, const int64_t* __restrict__ group,
                                               const int16_t* __restrict__ y_i16, const float* __restrict__ y_f32,
-                                              float* __restrict__ loss, float* __restrict__ dp, int64_t lddp, int64_t B,
-                                              int32_t n_col, float inv_count) {
+                                              const float* __restrict__ weight, float* __restrict__ loss, float* __restrict__ dp,
+                                              int64_t lddp, int64_t B, int32_t n_col, float inv_count) {
     double acc = 0.0;
     // one workgroup (the loss is one ordered sum), so the launch is as long as its chain of dependent loads: four rows per
     // thread and round, their tower indices fetched together, then their probabilities and labels
     constexpr int RB = 4;
     for (int64_t b0 = threadIdx.x; b0 < B; b0 += (int64_t)RB * blockDim.x) {
         int64_t col[RB];
-        float x[RB], t[RB];
+        float x[RB], t[RB], wv[RB];
 #pragma unroll
         for (int q = 0; q < RB; ++q) {
             const int64_t b = b0 + (int64_t)q * blockDim.x;
@@ -1447,16 +1457,19 @@ __global__ void __launch_bounds__(1024) k_bce(const float* __restrict__ p, int64
             const int64_t b = b0 + (int64_t)q * blockDim.x;
             x[q] = b < B ? p[b * ldp + col[q]] : 0.5f;
             t[q] = b < B ? (y_i16 ? (float)y_i16[b] : y_f32[b]) : 0.f;
+            if (WEIGHTED) wv[q] = b < B ? weight[b] : 0.f;
         }
 #pragma unroll
         for (int q = 0; q < RB; ++q) {
             const int64_t b = b0 + (int64_t)q * blockDim.x;
             if (b >= B) continue;
             const float l = (t[q] - 1.f) * fmaxf(log1pf(-x[q]), -100.f) - t[q] * fmaxf(logf(x[q]), -100.f);
-            acc += (double)l;
+            if (WEIGHTED) acc += (double)l * (double)wv[q];
+            else acc += (double)l;
             if (dp) {
                 for (int c = 0; c < n_col; ++c) dp[b * lddp + c] = 0.f;
-                dp[b * lddp + col[q]] = inv_count * (x[q] - t[q]) / fmaxf((1.f - x[q]) * x[q], 1e-12f);
+                const float g = inv_count * (x[q] - t[q]) / fmaxf((1.f - x[q]) * x[q], 1e-12f);
+                dp[b * lddp + col[q]] = WEIGHTED ? g * wv[q] : g;
             }
         }
     }
@@ -1475,16 +1488,30 @@ extern "C" int cdc_bce_fwd_bwd(const float* p, int64_t ldp, const int64_t* group
                                float* loss, float* dp, int64_t lddp, int64_t B, int32_t n_col, float inv_count, void* stream) {
     CDC_CHECK_ARG(p && loss && (y_i16 || y_f32) && B > 0 && n_col > 0 && ldp >= n_col && (!dp || lddp >= n_col), CDC_E_BADARG,
                   "bce_fwd_bwd: bad argument");
-    hipLaunchKernelGGL(k_bce, dim3(1), dim3(1024), 0, (hipStream_t)stream, p, ldp, group, y_i16, y_f32, loss, dp, lddp, B, n_col, inv_count);
+    hipLaunchKernelGGL(k_bce<false>, dim3(1), dim3(1024), 0, (hipStream_t)stream, p, ldp, group, y_i16, y_f32, nullptr, loss, dp, lddp, B,
+                       n_col, inv_count);
     CDC_LAUNCH_CHECK("bce_fwd_bwd");
+    return 0;
+}
+extern "C" int cdc_bce_weighted_fwd_bwd(const float* p, int64_t ldp, const int64_t* group, const int16_t* y_i16, const float* y_f32,
+                                        const float* weight, float* loss, float* dp, int64_t lddp, int64_t B, int32_t n_col,
+                                        float inv_count, void* stream) {
+    CDC_CHECK_ARG(p && loss && weight && (y_i16 || y_f32) && B > 0 && n_col > 0 && ldp >= n_col && (!dp || lddp >= n_col), CDC_E_BADARG,
+                  "bce_weighted_fwd_bwd: bad argument");
+    hipLaunchKernelGGL(k_bce<true>, dim3(1), dim3(1024), 0, (hipStream_t)stream, p, ldp, group, y_i16, y_f32, weight, loss, dp, lddp, B,
+                       n_col, inv_count);
+    CDC_LAUNCH_CHECK("bce_weighted_fwd_bwd");
     return 0;
 }
 
 // BCE on the MEAN of the tower probabilities (CDC warm-up, cdc.py:100-102 `torch.mean(y_cat, dim=1)` + run.py:616):
 // loss = mean_b bce(mean_c p[b,c], y[b]); d loss / d p[b,c] = bce'(mean) / n_col for every column.
+// WEIGHTED as in k_bce; the weight multiplies the finished gradient of the mean BEFORE the 1 / n_col.
+template <bool WEIGHTED>
 __global__ void __launch_bounds__(1024) k_bce_mean(const float* __restrict__ p, int64_t ldp, const int16_t* __restrict__ y_i16,
-                                                   const float* __restrict__ y_f32, float* __restrict__ loss, float* __restrict__ dp,
-                                                   int64_t lddp, int64_t B, int32_t n_col, float inv_count) {
+                                                   const float* __restrict__ y_f32, const float* __restrict__ weight,
+                                                   float* __restrict__ loss, float* __restrict__ dp, int64_t lddp, int64_t B,
+                                                   int32_t n_col, float inv_count) {
     double acc = 0.0;
     const float inv_c = 1.f / (float)n_col;
     for (int64_t b = threadIdx.x; b < B; b += blockDim.x) {
@@ -1493,9 +1520,13 @@ __global__ void __launch_bounds__(1024) k_bce_mean(const float* __restrict__ p, 
         const float x = sum / (float)n_col;
         const float t = y_i16 ? (float)y_i16[b] : y_f32[b];
         const float l = (t - 1.f) * fmaxf(log1pf(-x), -100.f) - t * fmaxf(logf(x), -100.f);
-        acc += (double)l;
+        float wv = 1.f;
+        if (WEIGHTED) wv = weight[b];
+        if (WEIGHTED) acc += (double)l * (double)wv;
+        else acc += (double)l;
         if (dp) {
-            const float g = inv_count * (x - t) / fmaxf((1.f - x) * x, 1e-12f) * inv_c;
+            const float g = WEIGHTED ? inv_count * (x - t) / fmaxf((1.f - x) * x, 1e-12f) * wv * inv_c
+                                     : inv_count * (x - t) / fmaxf((1.f - x) * x, 1e-12f) * inv_c;
             for (int c = 0; c < n_col; ++c) dp[b * lddp + c] = g;
         }
     }
@@ -1513,8 +1544,65 @@ extern "C" int cdc_bce_mean_fwd_bwd(const float* p, int64_t ldp, const int16_t* 
                                     int64_t lddp, int64_t B, int32_t n_col, float inv_count, void* stream) {
     CDC_CHECK_ARG(p && loss && (y_i16 || y_f32) && B > 0 && n_col > 0 && ldp >= n_col && (!dp || lddp >= n_col), CDC_E_BADARG,
                   "bce_mean_fwd_bwd: bad argument");
-    hipLaunchKernelGGL(k_bce_mean, dim3(1), dim3(1024), 0, (hipStream_t)stream, p, ldp, y_i16, y_f32, loss, dp, lddp, B, n_col, inv_count);
+    hipLaunchKernelGGL(k_bce_mean<false>, dim3(1), dim3(1024), 0, (hipStream_t)stream, p, ldp, y_i16, y_f32, nullptr, loss, dp, lddp, B,
+                       n_col, inv_count);
     CDC_LAUNCH_CHECK("bce_mean_fwd_bwd");
+    return 0;
+}
+extern "C" int cdc_bce_mean_weighted_fwd_bwd(const float* p, int64_t ldp, const int16_t* y_i16, const float* y_f32, const float* weight,
+                                             float* loss, float* dp, int64_t lddp, int64_t B, int32_t n_col, float inv_count,
+                                             void* stream) {
+    CDC_CHECK_ARG(p && loss && weight && (y_i16 || y_f32) && B > 0 && n_col > 0 && ldp >= n_col && (!dp || lddp >= n_col), CDC_E_BADARG,
+                  "bce_mean_weighted_fwd_bwd: bad argument");
+    hipLaunchKernelGGL(k_bce_mean<true>, dim3(1), dim3(1024), 0, (hipStream_t)stream, p, ldp, y_i16, y_f32, weight, loss, dp, lddp, B,
+                       n_col, inv_count);
+    CDC_LAUNCH_CHECK("bce_mean_weighted_fwd_bwd");
+    return 0;
+}
+
+// The step's effective loss weight, formed once per step in fp32 and in this order: w[b] = (row[b] * dom[b]) * pos[b] with
+// row = row_w[b] (1 without row_w), dom = domain_w[ids[b, domain_col]] (1 without domain_w, 0 for an id outside the table) and
+// pos = pos_weight where y[b] > 0, else 1 (1 without labels).  Elements past B are not touched.
+__global__ void __launch_bounds__(256) k_stage_weights(const float* __restrict__ row_w, const int32_t* __restrict__ ids, int64_t ld_ids,
+                                                       int32_t domain_col, const float* __restrict__ domain_w, int32_t n_domain_w,
+                                                       const int16_t* __restrict__ y_i16, float pos_weight, float* __restrict__ w_out,
+                                                       int64_t B) {
+    // four consecutive rows per thread and trip: their loads go out together, one 16-byte store where the rows are all there
+    const bool vec = (reinterpret_cast<uintptr_t>(w_out) & 15) == 0;
+    const int64_t n4 = (B + 3) / 4;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t b0 = 4 * i;
+        float w[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t b = b0 + q < B ? b0 + q : B - 1;         // (rows past B: the last row again, not stored)
+            const float row = row_w ? row_w[b] : 1.f;
+            float dom = 1.f;
+            if (domain_w) {
+                const int32_t id = ids[b * ld_ids + domain_col];
+                dom = (id >= 0 && id < n_domain_w) ? domain_w[id] : 0.f;
+            }
+            const float pos = (y_i16 && y_i16[b] > 0) ? pos_weight : 1.f;
+            w[q] = (row * dom) * pos;
+        }
+        if (vec && b0 + 4 <= B) *reinterpret_cast<float4*>(w_out + b0) = make_float4(w[0], w[1], w[2], w[3]);
+        else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (b0 + q < B) w_out[b0 + q] = w[q];
+        }
+    }
+}
+extern "C" int cdc_stage_weights(const float* row_w, const int32_t* ids, int64_t ld_ids, int32_t domain_col, const float* domain_w,
+                                 int32_t n_domain_w, const int16_t* y_i16, float pos_weight, float* w_out, int64_t B, void* stream) {
+    CDC_CHECK_ARG(w_out && B > 0 && std::isfinite(pos_weight) && (y_i16 || pos_weight == 1.f), CDC_E_BADARG,
+                  "stage_weights: bad argument");
+    CDC_CHECK_ARG(!domain_w || (ids && n_domain_w > 0 && domain_col >= 0 && ld_ids > domain_col), CDC_E_BADARG,
+                  "stage_weights: the domain table needs the ids, its column inside a row and its length");
+    int blocks = (int)std::min<int64_t>(cdc_ceil_div(cdc_ceil_div(B, 4), 256), 1024);
+    hipLaunchKernelGGL(k_stage_weights, dim3(blocks), dim3(256), 0, (hipStream_t)stream, row_w, ids, ld_ids, domain_col, domain_w, n_domain_w,
+                       y_i16, pos_weight, w_out, B);
+    CDC_LAUNCH_CHECK("stage_weights");
     return 0;
 }
 

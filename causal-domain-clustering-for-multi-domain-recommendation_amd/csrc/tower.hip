@@ -434,13 +434,14 @@ __device__ __forceinline__ void tw_fwd_body(const TW_KARG cdc_tower_args& a, uns
 
     // cdc_tower_step: the head thread of a row (tid = 2 row) fetches the row's tower column and label now, for the loss at the end
     int k_own = 0;
-    float k_tgt = 0.f;
+    float k_tgt = 0.f, k_w = 1.f;                                        // (k_w: the row's loss weight, read only where bce_weight is set)
     if (keep && (tid & 1) == 0 && (tid >> 1) < rows) {
         const int64_t r = row0 + (tid >> 1);
         int64_t c = a.bce_group ? a.bce_group[r] : 0;
         if (c < 0 || c >= n_tower) c = 0;
         k_own = (int)c;
         k_tgt = a.bce_y_i16 ? (float)a.bce_y_i16[r] : a.bce_y_f32[r];
+        if (const float* bce_w = CDC_TOWER_BCE_WEIGHT(&a)) k_w = bce_w[r];
     }
 
     // ---- operands of both contractions: global -> LDS, all in flight at once
@@ -655,7 +656,8 @@ __device__ __forceinline__ void tw_fwd_body(const TW_KARG cdc_tower_args& a, uns
             if (lr < rows && k_own == t) {
                 const float o = acc, tgt = k_tgt;
                 lp = (double)((tgt - 1.f) * fmaxf(log1pf(-o), -100.f) - tgt * fmaxf(logf(o), -100.f));
-                const float dout = a.bce_inv_count * (o - tgt) / fmaxf((1.f - o) * o, 1e-12f);
+                float dout = a.bce_inv_count * (o - tgt) / fmaxf((1.f - o) * o, 1e-12f);
+                if (CDC_TOWER_BCE_WEIGHT(&a)) { lp *= (double)k_w; dout *= k_w; }    // (the keep buffer hands the weighted values to the backward)
                 d_t = a.sigmoid ? dout * o * (1.f - o) : dout;
                 mine = 1;
             }
@@ -890,7 +892,11 @@ __device__ __forceinline__ void tw_bwd_body(const TW_KARG cdc_tower_args& a, uns
                 if (own == t) {
                     const float o = a.out[r * a.ld_out + t];
                     lp = (double)((tgt - 1.f) * fmaxf(log1pf(-o), -100.f) - tgt * fmaxf(logf(o), -100.f));
-                    const float dout = a.bce_inv_count * (o - tgt) / fmaxf((1.f - o) * o, 1e-12f);
+                    float dout = a.bce_inv_count * (o - tgt) / fmaxf((1.f - o) * o, 1e-12f);
+                    if (const float* bce_w = CDC_TOWER_BCE_WEIGHT(&a)) { // the row's loss weight: last factor of the finished term and gradient
+                        const float w = bce_w[r];
+                        lp *= (double)w; dout *= w;
+                    }
                     d_t = a.sigmoid ? dout * o * (1.f - o) : dout;
                     dsum = d_t;
                 }
@@ -1575,6 +1581,7 @@ __global__ void __launch_bounds__(TW_THREADS) k_tower_dp(const cdc_tower_args a_
                 const int64_t r = row0 + tid;
                 int own = 0;
                 float tgt = 0.f;
+                const float* bce_w = CDC_TOWER_BCE_WEIGHT(&a);
                 if (bce) {
                     int64_t c = a.bce_group ? a.bce_group[r] : 0;
                     if (c < 0 || c >= n_tower) c = 0;
@@ -1588,10 +1595,17 @@ __global__ void __launch_bounds__(TW_THREADS) k_tower_dp(const cdc_tower_args a_
                         if (tt == own) {
                             lp = (double)((tgt - 1.f) * fmaxf(log1pf(-o), -100.f) - tgt * fmaxf(logf(o), -100.f));
                             dout = a.bce_inv_count * (o - tgt) / fmaxf((1.f - o) * o, 1e-12f);
+                            if (bce_w) {
+                                const float w = bce_w[r];
+                                lp *= (double)w; dout *= w;
+                            }
                         } else dout = 0.f;
                     } else dout = a.d_out[r * a.ld_dout + tt];
                     const float d = a.sigmoid ? dout * o * (1.f - o) : dout;
-                    dsum += d;
+                    // weighted loss: the own tower's d alone, as tw_bwd_body takes it — adding the other towers' zeros changes nothing
+                    // but the sign of a zero, and a row of weight 0 has d = -0 wherever o < t (unweighted: the sum as it always was)
+                    if (!(bce && bce_w)) dsum += d;
+                    else if (tt == own) dsum = d;
                     if (tt == t) d_t = d;
                 }
                 mine = (bce ? own : (int)(r % n_tower)) == t;
@@ -1972,6 +1986,7 @@ extern "C" int cdc_tower_bwd(const cdc_tower_args* a, void* stream) {
     const bool bce = a->bce_y_i16 || a->bce_y_f32;
     CDC_CHECK_ARG(bce || a->d_out, CDC_E_BADARG, "tower_bwd: needs the output gradient or the fused loss");
     CDC_CHECK_ARG(!bce || (a->sigmoid && a->bce_loss && a->bce_inv_count > 0.f), CDC_E_BADARG, "tower_bwd: the fused BCE needs sigmoid outputs and a loss pointer");
+    CDC_CHECK_ARG(bce || !CDC_TOWER_BCE_WEIGHT(a), CDC_E_BADARG, "tower_bwd: bce_weight without the fused BCE's labels");
     const unsigned grid = (unsigned)(a->n_tower * cdc_ceil_div(a->M, TW_ROWS));
     static bool attr_done = false;
     if (!attr_done) {
@@ -2026,6 +2041,7 @@ extern "C" int cdc_tower_dp(const cdc_tower_args* a, int32_t phase, void* stream
         const bool bce = a->bce_y_i16 || a->bce_y_f32;
         CDC_CHECK_ARG(bce || a->d_out, CDC_E_BADARG, "tower_dp: needs the output gradient or the fused loss");
         CDC_CHECK_ARG(!bce || (a->sigmoid && a->bce_loss && a->bce_inv_count > 0.f), CDC_E_BADARG, "tower_dp: the fused BCE needs sigmoid outputs and a loss pointer");
+        CDC_CHECK_ARG(bce || !CDC_TOWER_BCE_WEIGHT(a), CDC_E_BADARG, "tower_dp: bce_weight without the fused BCE's labels");
         for (int t = 0; t < a->n_tower; ++t)
             CDC_CHECK_ARG(a->t[t].dy2 && a->t[t].dy1 && (((uintptr_t)a->t[t].dy2 | (uintptr_t)a->t[t].dy1) & 15) == 0 && a->t[t].lddy2 % 4 == 0 &&
                               a->t[t].lddy1 % 4 == 0, CDC_E_BADARG, "tower_dp: tower %d gradient scratch", t);

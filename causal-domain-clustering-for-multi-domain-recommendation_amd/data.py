@@ -48,6 +48,7 @@ class DeviceLoader:
         self.n = n
         self.dropped_rows = 0             # data parallel: rows of a last global batch with fewer rows than ranks (not trained on)
         self.last_global_rows = 0         # data parallel: true size of the ragged last global batch this epoch yielded shares of
+        self.has_weight = False           # make_loader(row_weight=): the LAST tensor of every batch is the rows' loss weight
 
     def __len__(self):
         g = self.batch_size * self.world
@@ -104,14 +105,24 @@ class DeviceLoader:
                 yield tuple(t.index_select(0, idx) for t in self.tensors)
 
 
-def make_loader(X, y, batch_size, device, domain_idx=None, domain2group=None, domain_filter=None, shuffle=True, rank=0, world=1):
+def make_loader(X, y, batch_size, device, domain_idx=None, domain2group=None, domain_filter=None, shuffle=True, rank=0, world=1,
+                row_weight=None):
     """run.py:208-250 `convert2data_loader` after the tensors are loaded: optional domain filter, the tower index
     `group = domain2group[X[:, domain_idx]]` for multi-tower models, `domain_cnt_weight` (relative domain frequencies, used
-    by evaluate_multi_domain), everything moved to `device`.  Returns (loader, domain_cnt_weight)."""
+    by evaluate_multi_domain), everything moved to `device`.  Returns (loader, domain_cnt_weight).
+    row_weight (optional, one fp32 weight per row of X): the rows' loss weights travel as the LAST tensor of every batch tuple —
+    filtered, shuffled, sharded by rank and cut at the ragged tail like y — and the loader is marked `has_weight`; train_epoch hands
+    them to a TrainStep built with LossWeights(row=True) as `weight=`."""
     X, y = X.to(torch.int32), y.to(torch.int16).reshape(-1, 1)
+    if row_weight is not None:
+        row_weight = torch.as_tensor(row_weight).to(torch.float32).reshape(-1, 1)
+        if row_weight.shape[0] != X.shape[0]:
+            raise ValueError(f"row_weight holds {row_weight.shape[0]} weights for {X.shape[0]} rows")
     if domain_filter is not None:
         mask = torch.isin(X[:, domain_idx], torch.as_tensor(list(domain_filter), dtype=X.dtype))
         X, y = X[mask], y[mask]
+        if row_weight is not None:
+            row_weight = row_weight[mask.to(row_weight.device)]
     weight = None
     if domain_idx is not None:
         cnt = X[:, domain_idx].to(torch.int64).bincount()
@@ -130,7 +141,11 @@ def make_loader(X, y, batch_size, device, domain_idx=None, domain2group=None, do
         if int(group.min()) < 0:
             raise ValueError("a domain of the data has no tower in domain2group")   # pandas .map would give NaN -> cast error
         tensors.append(group.view(-1, 1).to(device))
-    return DeviceLoader(tensors, batch_size, shuffle=shuffle, rank=rank, world=world), weight
+    if row_weight is not None:
+        tensors.append(row_weight.to(device))
+    loader = DeviceLoader(tensors, batch_size, shuffle=shuffle, rank=rank, world=world)
+    loader.has_weight = row_weight is not None
+    return loader, weight
 
 
 def make_domain_loaders(X, y, batch_size, device, domain_idx, n_domain, domain_filter=None, shuffle=True):
@@ -189,7 +204,12 @@ def train_epoch(step, loader, log_interval=None, log=None):
             else:
                 ts = step.sibling(X.shape[0])
         ahead = nxt[0] if (nxt is not None and ts is step and nxt[0].shape[0] == step.B) else None
-        bce, reg = ts.step(*batch, next_X=ahead) if ahead is not None else ts.step(*batch)
+        kw = {}
+        if getattr(loader, "has_weight", False):                 # (X, y[, group], weight): the weight is the tuple's last tensor
+            batch, kw["weight"] = batch[:-1], batch[-1]
+        if ahead is not None:
+            kw["next_X"] = ahead
+        bce, reg = ts.step(*batch, **kw)
         batch = nxt
         acc += bce.double().sum() + reg
         done += 1

@@ -37,6 +37,49 @@ def _merge_pieces(seq):
     return merged
 
 
+class LossWeights:
+    """How a TrainStep weights the rows of its loss — torch's `F.binary_cross_entropy(p, y, weight=w, reduction='mean')` with
+           w[b] = (row[b] * domain_weight[X[b, domain_idx]]) * (pos_weight if y[b] > 0 else 1)
+    formed on the device once per step, in fp32 and in this order (csrc/rowops.hip cdc_stage_weights).
+      row            True: every step(...) call is given `weight=` (fp32 [B] or [B,1] on the device)
+      domain_weight  one weight per id of field `domain_idx` (a sequence or tensor of feature_dims[domain_idx] floats); an id outside
+                     the table weighs 0 (check_ids() reports such ids)
+      pos_weight     the weight of the positive rows (the hard-label case of BCEWithLogitsLoss(pos_weight=))
+    The mean stays over the batch's rows (1 / global batch), NOT over sum(w): normalise the weights for a weighted mean.  Weights
+    are finite and expected to be >= 0; they are not validated on the device."""
+
+    def __init__(self, row=False, domain_weight=None, domain_idx=None, pos_weight=1.0):
+        self.row = bool(row)
+        self.pos_weight = float(pos_weight)
+        if not (self.pos_weight == self.pos_weight and abs(self.pos_weight) != float("inf")):
+            raise ValueError("pos_weight must be finite")
+        if (domain_weight is None) != (domain_idx is None):
+            raise ValueError("domain_weight and domain_idx belong together")
+        self.domain_idx = None if domain_idx is None else int(domain_idx)
+        if domain_weight is not None:
+            dw = torch.as_tensor(domain_weight).detach().to(device="cpu", dtype=torch.float32).reshape(-1).clone()
+            if dw.numel() == 0 or not bool(torch.isfinite(dw).all()):
+                raise ValueError("domain_weight must hold at least one weight, all finite")
+            if self.domain_idx < 0:
+                raise ValueError("domain_idx must be a field index")
+            domain_weight = dw
+        self.domain_weight = domain_weight
+
+    @property
+    def active(self):
+        return self.row or self.domain_weight is not None or self.pos_weight != 1.0
+
+    def check(self, feature_dims):
+        """against the model the step is built for: one weight per id of the domain field"""
+        if self.domain_weight is None:
+            return
+        if self.domain_idx >= len(feature_dims):
+            raise ValueError(f"domain_idx {self.domain_idx} is not one of the model's {len(feature_dims)} fields")
+        if self.domain_weight.numel() != int(feature_dims[self.domain_idx]):
+            raise ValueError(f"domain_weight holds {self.domain_weight.numel()} weights, field {self.domain_idx} has "
+                             f"{int(feature_dims[self.domain_idx])} ids")
+
+
 class TrainStep:
     """mode:
          "multi"   multi-tower models (PLE / MMoE / CDC split): pred = model(X).gather(1, group)  (run.py:481-484)
@@ -51,7 +94,8 @@ class TrainStep:
 
     def __init__(self, model, optimizer: FusedAdam, batch_size, mode="multi", use_graph=False, dist=None, sync_bn=True,
                  table_dist=None, shard_slack=1.5, train_mode=True, overlap=True, overlap_waves=2, sort_ahead=True, fuse_gather=False,
-                 defer_dw_reduce=None, global_rows=None, cap_rows=None, tower_one_launch=True, rows_dense_one_launch=True):
+                 defer_dw_reduce=None, global_rows=None, cap_rows=None, tower_one_launch=True, rows_dense_one_launch=True,
+                 loss_weights=None):
         """sync_bn (data parallel only): BatchNorm statistics over the GLOBAL batch, as the reference's single process
         computes them — two small all-reduces per BatchNorm launch; False = per-rank statistics.
         table_dist (data parallel only): "sharded" (row r owned by rank r % world; default with the lazy table optimiser)
@@ -63,7 +107,9 @@ class TrainStep:
         overlap / overlap_waves / sort_ahead / fuse_gather (single GPU, lazy table; for tests and A/B runs — the defaults are what is
         measured and shipped): the replay slice in the background on a second chain (waves per SIMD of its capped grid), the next
         batch's row sort on that chain (step(..., next_X=); sort_ahead=False ignores next_X), the catch-up launch that also writes
-        the gathered embeddings (slower: profiles/round3/README.md section 3)."""
+        the gathered embeddings (slower: profiles/round3/README.md section 3).
+        loss_weights: a LossWeights — per-row, per-domain and positive-class weights of the loss, decided here so that a captured
+        graph has fixed pointers; None (or one that weights nothing) is the unweighted step."""
         self.model, self.opt, self.B, self.mode = model, optimizer, int(batch_size), mode
         self.lib = L.load()
         self.dist = dist
@@ -97,6 +143,19 @@ class TrainStep:
             self.order = self.holder.extra_outputs[0]             # row order after the partition (ascending group)
             self.y_perm = torch.zeros(self.B, dtype=torch.int16, device=dev)
         self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        # loss weights: the step's effective row weights in a static buffer the (replayed) weighted BCE launch reads; written by
+        # one eager launch beside the staging launch of every step()
+        if loss_weights is not None and not isinstance(loss_weights, LossWeights):
+            raise TypeError("loss_weights must be a LossWeights")
+        self.loss_weights = loss_weights if (loss_weights is not None and loss_weights.active) else None
+        self.w = None
+        if self.loss_weights is not None:
+            self.loss_weights.check(model.feature_dims)
+            self.w = torch.ones(self.B, dtype=torch.float32, device=dev)
+            dw = self.loss_weights.domain_weight
+            self._domain_w = None if dw is None else dw.to(dev)
+            if mode == "star":
+                self.w_perm = torch.ones(self.B, dtype=torch.float32, device=dev)
         # ids are checked against their FIELD's vocabulary while a batch is staged (an id past it that still lies inside the table
         # aliases another field's row: check_ids reports it)
         self.field_dims_dev = torch.tensor([int(d) for d in model.feature_dims], dtype=torch.int32, device=dev)
@@ -256,8 +315,27 @@ class TrainStep:
                 if hasattr(type(head), "bce_partial"):            # (the fused tower launch keeps its partial sums in its own workspace)
                     head.bce_partial = self._bce_partial.data_ptr()
                 head.bce_inv_count = 1.0 / self.global_B
+                # loss weights ride the same launch; cleared for an unweighted step that shares the plan with a weighted one
+                head.bce_weight = None if self.w is None else self.w.data_ptr()
                 return
-            head.bce_y_i16 = head.bce_y_f32 = None
+            head.bce_y_i16 = head.bce_y_f32 = head.bce_weight = None
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if self.w is not None:
+            if self.mode == "mean":
+                L.launch("cdc_bce_mean_weighted_fwd_bwd", self.lib.cdc_bce_mean_weighted_fwd_bwd,
+                         (self.out.ptr, self.out.ld, self.y.data_ptr(), None, self.w.data_ptr(), self.loss.data_ptr(), og.ptr, og.ld,
+                          self.B, self.out.cols, 1.0 / self.global_B), st)
+                return
+            y, group, w = self.y, self.group, self.w
+            if self.mode == "star":                               # targets[order] (star.py:181) and their weights, one column
+                order = self.order.long()
+                torch.index_select(self.y, 0, order, out=self.y_perm)
+                torch.index_select(self.w, 0, order, out=self.w_perm)
+                y, group, w = self.y_perm, None, self.w_perm
+            L.launch("cdc_bce_weighted_fwd_bwd", self.lib.cdc_bce_weighted_fwd_bwd,
+                     (self.out.ptr, self.out.ld, None if group is None else group.data_ptr(), y.data_ptr(), None, w.data_ptr(),
+                      self.loss.data_ptr(), og.ptr, og.ld, self.B, self.out.cols, 1.0 / self.global_B), st)
+            return
         if self.mode == "mean":
             L.launch("cdc_bce_mean_fwd_bwd", self.lib.cdc_bce_mean_fwd_bwd,
                      (self.out.ptr, self.out.ld, self.y.data_ptr(), None, self.loss.data_ptr(), og.ptr, og.ld, self.B, self.out.cols,
@@ -665,11 +743,42 @@ class TrainStep:
             g.replay()
         self._warm += 1
 
-    def step(self, X, y, group=None, next_X=None):
+    def _row_weight(self, weight):
+        """step()'s weight= against what the step was built with, before anything is staged -> the flat fp32 row weights or None"""
+        lw = self.loss_weights
+        if weight is None:
+            if lw is not None and lw.row:
+                raise ValueError("this TrainStep was built with LossWeights(row=True): step(...) needs weight=")
+            return None
+        if lw is None:
+            raise ValueError("weight= given to a TrainStep built without loss_weights")
+        if not lw.row:
+            raise ValueError("weight= given to a TrainStep whose LossWeights has row=False")
+        row = weight.reshape(-1)
+        if not (row.is_cuda and row.dtype == torch.float32 and row.numel() == self.B):
+            raise ValueError(f"weight must be fp32 [{self.B}] or [{self.B},1] on the device")
+        return row.contiguous()
+
+    def _stage_weights(self, row):
+        """the step's effective row weights into the static buffer: one eager launch, after the batch has been staged (it reads the
+        staged ids and labels), no host synchronisation"""
+        lw = self.loss_weights
+        if lw is None:
+            return
+        dw = self._domain_w
+        L.launch("cdc_stage_weights", self.lib.cdc_stage_weights,
+                 (None if row is None else row.data_ptr(), self.emb.ids.data_ptr(), self.emb.F, 0 if dw is None else lw.domain_idx,
+                  None if dw is None else dw.data_ptr(), 0 if dw is None else dw.numel(), self.y.data_ptr(), lw.pos_weight,
+                  self.w.data_ptr(), self.B), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+
+    def step(self, X, y, group=None, next_X=None, *, weight=None):
         """One training step. X int32 [B,F]; y int16/float [B] or [B,1]; group int64 [B] or [B,1] (multi mode).
         next_X (optional): the ids of the batch the NEXT call will be given (device int32 [B,F], not modified until then) — with the
         look-ahead sort (_ahead_ok; data parallel: _ahead_dp_ok) its rows are sorted beside this step's forward/backward; a next call
-        with another tensor simply sorts its own.  Returns (bce_loss, reg_loss) as device tensors (no host synchronisation)."""
+        with another tensor simply sorts its own.  weight (required iff the step was built with LossWeights(row=True)): fp32 [B] or
+        [B,1] on the device, this batch's per-row loss weights.  Returns (bce_loss, reg_loss) as device tensors (no host
+        synchronisation)."""
+        row_w = self._row_weight(weight)
         gdst = self.group if self.group is not None else (self.group_in if self.mode == "single_group" else None)
         yf = y.reshape(-1)
         gf = None if (group is None or gdst is None) else group.reshape(-1)
@@ -709,6 +818,7 @@ class TrainStep:
                 gdst.copy_(gf)
             if self._stage_begins:
                 self.opt.begin_step()
+        self._stage_weights(row_w)
         if self.dp_on:
             self._step_dp(X if fast else None, nx)
             return self.loss, self.reg
@@ -781,9 +891,10 @@ class TrainStep:
                                               "all-gathers are equal-sized)")
                 ts = TrainStep(self.model, self.opt, int(batch_size), mode=self.mode, use_graph=False, dist=self.dist, sync_bn=self.sync_bn,
                                table_dist=self.table_dist, shard_slack=self._shard_slack, train_mode=self.train_mode, sort_ahead=False,
-                               global_rows=int(global_rows), cap_rows=int(cap_rows))
+                               global_rows=int(global_rows), cap_rows=int(cap_rows), loss_weights=self.loss_weights)
             else:
-                ts = TrainStep(self.model, self.opt, int(batch_size), mode=self.mode, use_graph=False, train_mode=self.train_mode)
+                ts = TrainStep(self.model, self.opt, int(batch_size), mode=self.mode, use_graph=False, train_mode=self.train_mode,
+                               loss_weights=self.loss_weights)
             sib[key] = ts
         return ts
 

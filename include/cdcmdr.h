@@ -766,12 +766,16 @@ typedef struct {
      * groups are the columns of one prediction matrix (sigmoid must be 1, no row_offsets), g[].dout is NOT read: for row b
      * and group c, dout = (c == col(b)) ? bce_inv_count * (o - t) / max((1 - o) o, 1e-12) : 0 with col(b) = bce_group[b]
      * (clamped into the launch's columns; column 0 when bce_group is NULL), and *bce_loss = mean BCE of the own columns
-     * (ordered sum of per-block partials in bce_partial, >= n_groups * CDC_ROWDOT_PARTS doubles). */
+     * (ordered sum of per-block partials in bce_partial, >= n_groups * CDC_ROWDOT_PARTS doubles).
+     * bce_weight (optional, [M] fp32, finite, expected >= 0, not validated): the weighted loss of cdc_bce_weighted_fwd_bwd — row b's
+     * loss term is added as (double)l * (double)w[b] and its finished dout is multiplied by w[b] as the last fp32 factor.  NULL =
+     * unweighted, the bits of a launch without the field; set without bce_y_*: CDC_E_BADARG. */
     const int64_t* bce_group;
     const int16_t* bce_y_i16;
     const float* bce_y_f32;
     float* bce_loss;
     double* bce_partial;
+    const float* bce_weight;
     float bce_inv_count;
     int32_t pad_;
     cdc_rowdot_bgroup g[CDC_MAX_GROUPS];
@@ -821,6 +825,7 @@ typedef struct {
     const float* bce_y_f32;
     float* bce_loss;
     double* bce_partial;                  /* >= CDC_ROWDOT_PARTS doubles */
+    const float* bce_weight;              /* optional [M] row weights of the loss, as in cdc_rowdot_bwd_args (NULL: unweighted) */
     float bce_inv_count;
     int32_t pad2_;
     cdc_head_tower t[CDC_HEAD_MAX_TOWERS];
@@ -887,7 +892,7 @@ typedef struct {
     int64_t M;
     int32_t relu, sigmoid;
     float drop_p, eps, momentum;
-    int32_t pad_;
+    uint32_t bce_weight_lo;               /* low word of the bce_weight address (below) */
     uint64_t seed1, seed2;                /* dropout streams of the two BatchNorm launches this replaces */
     const int32_t* seed_offset_dev;
     float* out; int64_t ld_out;           /* [M, n_tower] */
@@ -903,13 +908,20 @@ typedef struct {
     const float* bce_y_f32;
     float* bce_loss;
     float bce_inv_count;
-    int32_t pad2_;
+    /* bce_weight: optional [M] row weights of the fused loss, as in cdc_rowdot_bwd_args (NULL: unweighted; without bce_y_*:
+     * CDC_E_BADARG from the backward entry points); under cdc_tower_dp the weights of THIS rank's rows.  The address travels as
+     * two 32-bit words, bce_weight_hi : bce_weight_lo, in what were this struct's two padding words, so that its size and every
+     * offset stay what callers were built against; zero-initialised blocks mean NULL.  CDC_TOWER_SET_BCE_WEIGHT(a, p) sets it. */
+    uint32_t bce_weight_hi;
     void* workspace;                      /* >= cdc_tower_workspace_bytes(), zeroed once */
     int32_t* err;                         /* device word that receives CDC_TOWER_ERR_TIMEOUT (may be NULL) */
     double* exchange[4];                  /* cdc_tower_dp only: per exchange [2 * n_tower * C column sums | n_tower row counts] doubles
                                              (C = H1, H2, H2, H1): written by the phase in front of it, summed over the ranks by the caller */
     cdc_tower_desc t[CDC_TOWER_MAX];
 } cdc_tower_args;
+#define CDC_TOWER_SET_BCE_WEIGHT(a, p) \
+    ((a)->bce_weight_lo = (uint32_t)((uint64_t)(uintptr_t)(p) & 0xffffffffu), (a)->bce_weight_hi = (uint32_t)((uint64_t)(uintptr_t)(p) >> 32))
+#define CDC_TOWER_BCE_WEIGHT(a) ((const float*)(uintptr_t)(((uint64_t)(a)->bce_weight_hi << 32) | (uint64_t)(a)->bce_weight_lo))
 int64_t cdc_tower_workspace_bytes(const cdc_tower_args* a);
 int cdc_tower_fwd(const cdc_tower_args* a, void* stream);
 int cdc_tower_bwd(const cdc_tower_args* a, void* stream);
@@ -942,6 +954,27 @@ int cdc_bce_fwd_bwd(const float* p, int64_t ldp, const int64_t* group, const int
  * dp[b, c] = bce'(mean_b) / n_col for every column. */
 int cdc_bce_mean_fwd_bwd(const float* p, int64_t ldp, const int16_t* y_i16, const float* y_f32, float* loss, float* dp,
                          int64_t lddp, int64_t B, int32_t n_col, float inv_count, void* stream);
+
+/* Weighted forms: torch's F.binary_cross_entropy(p, y, weight=w, reduction='mean').  weight [B] fp32 (non-NULL here), finite and
+ * expected >= 0; it is NOT validated on the device.
+ *   loss  = inv_count * sum_b w[b] * l[b]            (l: the unweighted row term, both clamps included; added as (double)l * (double)w)
+ *   dp[b] = (inv_count * (p - y) / max((1 - p) p, 1e-12)) * w[b]     (the weight is the LAST fp32 factor: w = 1 gives the unweighted
+ *           bits, w = 0 an exactly zero gradient; in the mean form it comes before the 1 / n_col)
+ * inv_count stays 1 / global_batch — NOT 1 / sum(w): a caller who wants a weighted mean normalises the weights.  Everything else
+ * (out-of-range group -> column 0, nullable dp, the other columns of dp zeroed) as in the unweighted siblings above. */
+int cdc_bce_weighted_fwd_bwd(const float* p, int64_t ldp, const int64_t* group, const int16_t* y_i16, const float* y_f32,
+                             const float* weight, float* loss, float* dp, int64_t lddp, int64_t B, int32_t n_col, float inv_count,
+                             void* stream);
+int cdc_bce_mean_weighted_fwd_bwd(const float* p, int64_t ldp, const int16_t* y_i16, const float* y_f32, const float* weight,
+                                  float* loss, float* dp, int64_t lddp, int64_t B, int32_t n_col, float inv_count, void* stream);
+/* The effective row weight of a step, formed once in fp32 and in this order:  w_out[b] = (row[b] * dom[b]) * pos[b]
+ *   row[b] = row_w[b]                              (1 when row_w is NULL)
+ *   dom[b] = domain_w[ids[b * ld_ids + domain_col]] (1 when domain_w is NULL; 0 for an id outside [0, n_domain_w))
+ *   pos[b] = y_i16[b] > 0 ? pos_weight : 1          (1 when y_i16 is NULL, which needs pos_weight == 1): the hard-label case of
+ *            BCEWithLogitsLoss(pos_weight=)
+ * Elements of w_out past B are not touched. */
+int cdc_stage_weights(const float* row_w, const int32_t* ids, int64_t ld_ids, int32_t domain_col, const float* domain_w,
+                      int32_t n_domain_w, const int16_t* y_i16, float pos_weight, float* w_out, int64_t B, void* stream);
 
 /* Second-order factorisation-machine term (reference: model/layer.py:160-175 FactorizationMachine(reduce_sum=True), used by
  * model/dfm.py:33): e [B, F*D] gathered embeddings; out[b] = 0.5 * sum_d((sum_f e)^2 - sum_f e^2);
