@@ -9,8 +9,12 @@
 // in the backward Q, dO, the probabilities and dS) are staged in LDS.  fp32 throughout.
 #include "common.h"
 
+// waves per workgroup: four where their LDS fits, else two, else one (ATTN_DISPATCH).  Every wave works on its own (sample, head)
+// pair in its own LDS region, and nothing a wave computes depends on its place in the workgroup: the kernels take the count from
+// the launch (blockDim.x / 64), and the choice moves no bit of the result.
 #define ATTN_WAVES 4
 #define ATTN_THREADS (ATTN_WAVES * 64)
+#define ATTN_LDS_MAX (160 * 1024)
 
 // dropout on the attention probabilities: the same counter-based stream as the linears (common.h), keyed by the flat index
 // of the probability; the backward regenerates the decisions instead of storing a mask
@@ -48,7 +52,7 @@ __global__ void __launch_bounds__(ATTN_THREADS) k_attn_fwd(const float* __restri
                                                            float drop_p, uint64_t seed, const int32_t* __restrict__ seed_offset_dev) {
     extern __shared__ __attribute__((aligned(16))) float attn_smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t pair = (int64_t)blockIdx.x * ATTN_WAVES + wave;          // (sample, head)
+    const int64_t pair = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;   // (sample, head)
     float* Ks = attn_smem + (int64_t)wave * (2 * F * DH + F * (F + 1));
     float* Vs = Ks + F * DH;
     float* Ps = Vs + F * DH;                                                // [F][F+1]
@@ -107,7 +111,7 @@ __global__ void __launch_bounds__(ATTN_THREADS) k_attn_bwd(const float* __restri
                                                            uint64_t seed, const int32_t* __restrict__ seed_offset_dev) {
     extern __shared__ __attribute__((aligned(16))) float attn_smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t pair = (int64_t)blockIdx.x * ATTN_WAVES + wave;
+    const int64_t pair = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
     // phase 1 (per query row) reads K and V, phase 2 (per key row) reads Q and dO: the two pairs share one LDS region, which
     // keeps a wave at 12 KB (F = 26, dh = 32) and thirteen waves resident per CU instead of eight
     float* Ks = attn_smem + (int64_t)wave * (2 * F * DH + 2 * F * (F + 1));
@@ -193,21 +197,24 @@ static bool attn_args_ok(int64_t B, int32_t F, int32_t A, int32_t H, float drop_
 #define ATTN_DISPATCH(KERNEL, LDS_FLOATS, ...)                                                                               \
     do {                                                                                                                      \
         const int dh__ = A / H;                                                                                               \
-        const size_t lds__ = (size_t)ATTN_WAVES * (LDS_FLOATS) * sizeof(float);                                               \
-        const dim3 grid__((unsigned)cdc_ceil_div(B * H, ATTN_WAVES));                                                         \
-        CDC_CHECK_ARG(lds__ <= 160 * 1024, CDC_E_TOOBIG, "attention: F=%d dh=%d needs %zu bytes of LDS", F, dh__, lds__);     \
+        const size_t wave_lds__ = (size_t)(LDS_FLOATS) * sizeof(float);                                                       \
+        int waves__ = ATTN_WAVES;                                                                                             \
+        while (waves__ > 1 && waves__ * wave_lds__ > ATTN_LDS_MAX) waves__ >>= 1;                                              \
+        const size_t lds__ = waves__ * wave_lds__;                                                                            \
+        const dim3 grid__((unsigned)cdc_ceil_div(B * H, waves__)), block__(waves__ * 64);                                     \
+        CDC_CHECK_ARG(lds__ <= ATTN_LDS_MAX, CDC_E_TOOBIG, "attention: F=%d dh=%d needs %zu bytes of LDS", F, dh__, lds__);   \
         if (lds__ > 64 * 1024) {                                                                                              \
             const void* fn__ = dh__ == 4 ? (const void*)KERNEL<4> : dh__ == 8 ? (const void*)KERNEL<8> :                      \
                                dh__ == 16 ? (const void*)KERNEL<16> : dh__ == 32 ? (const void*)KERNEL<32> : (const void*)KERNEL<64>; \
-            hipError_t e__ = hipFuncSetAttribute(fn__, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);               \
+            hipError_t e__ = hipFuncSetAttribute(fn__, hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_LDS_MAX);             \
             if (e__ != hipSuccess) { cdc_set_error("attention: cannot raise the LDS limit: %s", hipGetErrorString(e__)); return (int)e__; } \
         }                                                                                                                     \
         switch (dh__) {                                                                                                       \
-            case 4:  hipLaunchKernelGGL(KERNEL<4>,  grid__, dim3(ATTN_THREADS), lds__, (hipStream_t)stream, __VA_ARGS__); break; \
-            case 8:  hipLaunchKernelGGL(KERNEL<8>,  grid__, dim3(ATTN_THREADS), lds__, (hipStream_t)stream, __VA_ARGS__); break; \
-            case 16: hipLaunchKernelGGL(KERNEL<16>, grid__, dim3(ATTN_THREADS), lds__, (hipStream_t)stream, __VA_ARGS__); break; \
-            case 32: hipLaunchKernelGGL(KERNEL<32>, grid__, dim3(ATTN_THREADS), lds__, (hipStream_t)stream, __VA_ARGS__); break; \
-            default: hipLaunchKernelGGL(KERNEL<64>, grid__, dim3(ATTN_THREADS), lds__, (hipStream_t)stream, __VA_ARGS__); break; \
+            case 4:  hipLaunchKernelGGL(KERNEL<4>,  grid__, block__, lds__, (hipStream_t)stream, __VA_ARGS__); break;         \
+            case 8:  hipLaunchKernelGGL(KERNEL<8>,  grid__, block__, lds__, (hipStream_t)stream, __VA_ARGS__); break;         \
+            case 16: hipLaunchKernelGGL(KERNEL<16>, grid__, block__, lds__, (hipStream_t)stream, __VA_ARGS__); break;         \
+            case 32: hipLaunchKernelGGL(KERNEL<32>, grid__, block__, lds__, (hipStream_t)stream, __VA_ARGS__); break;         \
+            default: hipLaunchKernelGGL(KERNEL<64>, grid__, block__, lds__, (hipStream_t)stream, __VA_ARGS__); break;         \
         }                                                                                                                     \
     } while (0)
 

@@ -1154,7 +1154,9 @@ int cdc_rows_permute(const float* in, int64_t ld_in, const int32_t* order, float
  *   qkv [B*F, 3A] (row b*F+f; q | k | v, head h in columns h*dh..(h+1)*dh of each third), dh = A/H
  *   probs [B, H, F, F] = softmax_j(q_i*dh^-1/2 . k_j)          (saved for the backward)
  *   out   [B*F, A]: head h's columns = dropout(probs) @ v      (dropout on the probabilities, training only)
- * F <= 64, dh in {4, 8, 16, 32, 64}.  The backward writes every column of dqkv. */
+ * F <= 64, dh in {4, 8, 16, 32, 64}: every such shape is taken by both launches (one wave per (sample, head) pair; four, two or
+ * one of them share a workgroup, whichever fits the CU's 160 KB of LDS, with the same bits either way).  The backward writes every
+ * column of dqkv. */
 int cdc_attn_fwd(const float* qkv, int64_t ld, float* out, int64_t ldo, float* probs, int64_t B, int32_t F, int32_t A, int32_t H,
                  float drop_p, uint64_t seed, const int32_t* seed_offset_dev, void* stream);
 int cdc_attn_bwd(const float* qkv, int64_t ld, const float* probs, const float* dout, int64_t lddo, float* dqkv, int64_t lddq,

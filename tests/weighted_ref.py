@@ -56,9 +56,10 @@ HEAD_LOSS_ULPS_HOST = 2.4                       # tests/test_gpu_head.py ref_bac
 def head_backward(K, wide_K, n_add, D, out32, w, inv):
     """The fused-BCE backward of cdc_head_args / cdc_rowdot_bwd_args with row weights as name -> (want, bound): towers of widths K,
     an optional wide term, n_add addends, every gradient a plain store.  D: x, w (lists), wx, ww, wb, y, group as
-    tests/test_gpu_head.py's make_data gives them.  The names are that file's."""
+    tests/test_gpu_head.py's make_data gives them.  The names are that file's.  w = None: the unweighted launch (the NULL pointer),
+    without the weight's rounding."""
     M, nt = out32.shape[0], len(K)
-    o, wd, y = f64(out32), f64(w), f64(D["y"])
+    o, wd, y = f64(out32), (np.ones(M) if w is None else f64(w)), f64(D["y"])
     own = np.zeros(M, dtype=np.int64) if D["group"] is None else D["group"].copy()
     own[(own < 0) | (own >= nt)] = 0
     oo = o[np.arange(M), own]
@@ -70,7 +71,7 @@ def head_backward(K, wide_K, n_add, D, out32, w, inv):
     Rr = {"loss": (np.array([loss]), capped(np.array([b_loss]), loss, OUT_FIG))}
     dout = np.zeros((M, nt))
     dout[np.arange(M), own] = inv * (oo - y) / np.maximum((1.0 - oo) * oo, 1e-12) * wd
-    cd = 7 + 1 + 3                              # the unweighted dout, the weight, dout o (1 - o)
+    cd = 7 + (0 if w is None else 1) + 3        # the unweighted dout, the weight, dout o (1 - o)
     d = dout * o * (1.0 - o)
     ad = np.abs(d)
     dsum, a_dsum = d.sum(1), ad.sum(1)
