@@ -425,7 +425,8 @@ extern "C" int64_t cdc_eval_gauc_workspace_bytes(int64_t n, int32_t n_domain, in
 }
 
 // keys, sort, the two scans and the segment bounds of one score vector: leaves keys_out, sc and start describing its order and W, the
-// running sum of scan 2 (the caller says where: by default over the unsorted keys, dead once the sort has run)
+// running sum of scan 2 (the caller says where: by default over the unsorted keys, dead once the sort has run; nullptr: scan 2 is
+// skipped — cdc_eval_rank needs the order and scan 1 alone)
 static int gauc_order(const float* pred, const int16_t* label, const int32_t* user, int64_t ld_user, int64_t n_user, const int32_t* domain,
                       int64_t ld_domain, int32_t n_domain, int64_t n, int32_t* err_flag, char* base, const GaucLayout& L,
                       unsigned long long* W, const char* what, hipStream_t st) {
@@ -453,10 +454,12 @@ static int gauc_order(const float* pred, const int16_t* label, const int32_t* us
     e = rocprim::inclusive_scan(base + L.temp, temp_bytes, GaucScanIt(rocprim::counting_iterator<uint32_t>(0), GaucScanIn{keys_out, vals_out}),
                                 sc, (size_t)n2, GaucScanOp(), st, false);
     if (e != hipSuccess) { cdc_set_error("%s: group scan failed: %s", what, hipGetErrorString(e)); return (int)e; }
-    temp_bytes = (size_t)L.temp_bytes;
-    e = rocprim::inclusive_scan(base + L.temp, temp_bytes, GaucShareIt(rocprim::counting_iterator<uint32_t>(0), GaucShareIn{sc, vals_out}),
-                                W, (size_t)n2, rocprim::plus<unsigned long long>(), st, false);
-    if (e != hipSuccess) { cdc_set_error("%s: rank scan failed: %s", what, hipGetErrorString(e)); return (int)e; }
+    if (W) {
+        temp_bytes = (size_t)L.temp_bytes;
+        e = rocprim::inclusive_scan(base + L.temp, temp_bytes, GaucShareIt(rocprim::counting_iterator<uint32_t>(0), GaucShareIn{sc, vals_out}),
+                                    W, (size_t)n2, rocprim::plus<unsigned long long>(), st, false);
+        if (e != hipSuccess) { cdc_set_error("%s: rank scan failed: %s", what, hipGetErrorString(e)); return (int)e; }
+    }
     hipLaunchKernelGGL(k_gauc_starts, dim3((int)cdc_ceil_div(seg + 1, 64)), dim3(64), 0, st, keys_out, n2, seg, n_user, start);
     CDC_LAUNCH_CHECK("eval_gauc(starts)");
     return 0;
@@ -495,6 +498,269 @@ extern "C" int cdc_eval_gauc(const float* pred, const int16_t* label, const int3
     CDC_LAUNCH_CHECK("eval_gauc(sum)");
     hipLaunchKernelGGL(k_gauc_final, dim3(seg), dim3(GAUC_SLICES), 0, st, part, part_cnt, seg, out, counts);
     CDC_LAUNCH_CHECK("eval_gauc(final)");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Per-user top-K figures: NDCG@K, Recall@K, Precision@K, HitRate@K and MRR@K over GAUC's groups, every figure the EXPECTATION over
+// a uniformly random order of the rows that tie in score (McSherry & Najork 2008; sklearn's ndcg_score(ignore_ties=False)).
+// gauc_order() without its second scan leaves every group as one ascending score-ordered run with h, f and cn per position, so
+// the group's ranking is read from its LAST row downwards:
+//
+//   walk    the thread that finds a group's last row i (rank 0) steps from tie run to tie run: from position p the run is
+//           [sc[p].f, p], T = p - f + 1 rows at ranks [a, b) = [i - p, i - p + T), of which P_t = T - (cn(p) - cn(f - 1)) are
+//           positive; the next position is f - 1 (whose scan element is the one cn(f - 1) came from: one dependent load per run).
+//           It stops below the group's first row h or once a reaches the largest K: O(1) per run, at most ks[n_k-1] runs.
+//   H, dcg  a run inside the top K adds the integer P_t to H, the one run that straddles K adds P_t (K - a) / T; a run with
+//           positives adds (P_t / T) (D[min(b, K)] - D[a]) to the DCG.  ndcg = dcg / D[min(P, K)], recall = H / P, precision = H / K.
+//   hit, mrr depend on the FIRST run with a positive alone: a later run with a positive lies behind one that is wholly inside the
+//           top K or is not reached, so the product of q_t over the runs collapses to that run's q.  One loop over j < min(c, N_t + 1)
+//           (N_t = T - P_t, c = min(b, K) - a) carries q_j = prod_{i<j} (N_t - i) / (T - i), pr_j and the reciprocal-rank sum from
+//           one K to the next larger one; the factor at i = N_t is 0, which is the case c > N_t.
+//   sum     as k_gauc_sum: every (pseudo-)domain's stretch is cut into RANK_SLICES slices, a workgroup adds w m of the groups ENDING
+//           in its slice per thread, then over the threads in a fixed tree (a wave butterfly, then the waves in order); a last launch
+//           adds the slices in a tree and divides.  No atomics: the same rows in any order give the same bits.
+// K is clamped into [1, RANK_MAX_K] where it is read, so a launch reads at most discounts[RANK_MAX_K] whatever ks holds: the
+// caller validates ks (it lives on the device, and nothing here reads it back).
+#define RANK_MAX_NK 8
+#define RANK_MAX_K 1024
+#define RANK_FIGS 5                     // ndcg, recall, precision, hit, mrr
+#define RANK_SLICES 256                 // a walk is a chain of dependent loads and divisions: more, shorter slices than k_gauc_sum's
+
+template <int NK>
+__global__ void __launch_bounds__(GAUC_THREADS) k_rank_sum(const uint64_t* __restrict__ keys, const GaucScan* __restrict__ sc,
+                                                           const int64_t* __restrict__ start, const double* __restrict__ user_weight,
+                                                           const int32_t* __restrict__ ks, const double* __restrict__ D, int64_t n_user,
+                                                           int64_t n2, double* __restrict__ part, int64_t* __restrict__ part_cnt) {
+    constexpr int NV = RANK_FIGS * NK + 1;
+    __shared__ double s_w[GAUC_THREADS / 64][NV];
+    __shared__ int64_t s_c[GAUC_THREADS / 64][2];
+    const int d = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
+    const int64_t s0 = start[d], s1 = start[d + 1];
+    const int64_t per = (s1 - s0 + RANK_SLICES - 1) / RANK_SLICES;
+    const int64_t a0 = s0 + (int64_t)sl * per, b0 = a0 + per < s1 ? a0 + per : s1;
+    const uint64_t base = (uint64_t)d * (uint64_t)n_user;
+    int32_t K[NK];
+    double DK[NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        int32_t v = ks[k];
+        v = v < 1 ? 1 : (v > RANK_MAX_K ? RANK_MAX_K : v);
+        K[k] = v;
+        DK[k] = D[v];
+    }
+    const int64_t k_max = K[NK - 1];
+    double acc[RANK_FIGS][NK];
+#pragma unroll
+    for (int f = 0; f < RANK_FIGS; ++f)
+#pragma unroll
+        for (int k = 0; k < NK; ++k) acc[f][k] = 0.0;
+    double den = 0.0;
+    int64_t n_in = 0, n_out = 0;
+    for (int64_t i = a0 + tid; i < b0; i += GAUC_THREADS) {
+        const uint64_t g = keys[i] >> 32;
+        if (i + 1 < n2 && (keys[i + 1] >> 32) == g) continue;              // not the last row of its group
+        GaucScan e = sc[i];
+        const int64_t h = e.h;
+        const int64_t rows = i - h + 1;
+        const int64_t P = rows - (int64_t)(e.cn - (h ? sc[h - 1].cn : 0u));
+        if (P == 0) { ++n_out; continue; }
+        int64_t H[NK];
+        double Hf[NK], dcg[NK], hit[NK], mrr[NK];
+#pragma unroll
+        for (int k = 0; k < NK; ++k) { H[k] = 0; Hf[k] = 0.0; dcg[k] = 0.0; hit[k] = 0.0; mrr[k] = 0.0; }
+        bool first = true;
+        int64_t p = i;
+        while (p >= h && i - p < k_max) {
+            const int64_t f = e.f;                                         // >= h: a group change is a key change
+            GaucScan below;
+            below.h = below.f = below.cn = 0u;
+            if (f) below = sc[f - 1];
+            const int64_t T = p - f + 1, a = i - p, b = a + T;
+            const int64_t Nt = (int64_t)(e.cn - below.cn), Pt = T - Nt;
+            if (Pt > 0) {
+                const double share = (double)Pt / (double)T;
+                const double Da = D[a], Db = D[b < k_max ? b : k_max];
+#pragma unroll
+                for (int k = 0; k < NK; ++k) {
+                    if (a >= K[k]) continue;
+                    if (b <= K[k]) {
+                        H[k] += Pt;
+                        dcg[k] += share * (Db - Da);                       // b <= K[k] <= k_max: Db is D[b]
+                    } else {
+                        Hf[k] = (double)(Pt * (K[k] - a)) / (double)T;
+                        dcg[k] += share * (DK[k] - Da);
+                    }
+                }
+                if (first) {
+                    first = false;
+                    double q = 1.0, pr = share, rr = 0.0;
+                    int64_t j = 0;
+#pragma unroll
+                    for (int k = 0; k < NK; ++k) {
+                        if (a >= K[k]) continue;
+                        const int64_t c = (b < K[k] ? b : K[k]) - a;
+                        const int64_t lim = c < Nt + 1 ? c : Nt + 1;
+                        for (; j < lim; ++j) {
+                            rr += pr / (double)(a + 1 + j);
+                            q *= (double)(Nt - j) / (double)(T - j);
+                            if (j < Nt) pr *= (double)(Nt - j) / (double)(T - 1 - j);
+                        }
+                        hit[k] = 1.0 - q;
+                        mrr[k] = rr;
+                    }
+                }
+            }
+            e = below;
+            p = f - 1;
+        }
+        const double w = user_weight ? user_weight[g - base] : 1.0;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const double hh = (double)H[k] + Hf[k];
+            acc[0][k] += w * (dcg[k] / (P < K[k] ? D[P] : DK[k]));
+            acc[1][k] += w * (hh / (double)P);
+            acc[2][k] += w * (hh / (double)K[k]);
+            acc[3][k] += w * hit[k];
+            acc[4][k] += w * mrr[k];
+        }
+        den += w;
+        ++n_in;
+    }
+    const int wv = tid >> 6;
+#pragma unroll
+    for (int f = 0; f < RANK_FIGS; ++f)
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const double v = wave_sum_d(acc[f][k]);
+            if ((tid & 63) == 0) s_w[wv][f * NK + k] = v;
+        }
+    den = wave_sum_d(den);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        n_in += __shfl_xor(n_in, o, 64);
+        n_out += __shfl_xor(n_out, o, 64);
+    }
+    if ((tid & 63) == 0) { s_w[wv][NV - 1] = den; s_c[wv][0] = n_in; s_c[wv][1] = n_out; }
+    __syncthreads();
+    const int64_t o = (int64_t)d * RANK_SLICES + sl;
+    if (tid < NV) {
+        double v = s_w[0][tid];
+        for (int w = 1; w < GAUC_THREADS / 64; ++w) v += s_w[w][tid];
+        part[o * NV + tid] = v;
+    }
+    if (tid < 2) {
+        int64_t v = s_c[0][tid];
+        for (int w = 1; w < GAUC_THREADS / 64; ++w) v += s_c[w][tid];
+        part_cnt[o * 2 + tid] = v;
+    }
+}
+
+// workgroup d: the tree over the slices, one sum after the other, then figure = numerator / denominator; out [RANK_FIGS, n_k, n_seg]
+__global__ void __launch_bounds__(RANK_SLICES) k_rank_final(const double* __restrict__ part, const int64_t* __restrict__ part_cnt,
+                                                            int32_t n_k, int32_t n_seg, double* __restrict__ out,
+                                                            int64_t* __restrict__ counts) {
+    __shared__ double s_v[RANK_SLICES], s_sum[RANK_FIGS * RANK_MAX_NK + 1];
+    __shared__ int64_t s_in[RANK_SLICES], s_out[RANK_SLICES];
+    const int d = blockIdx.x, tid = threadIdx.x;
+    const int nv = RANK_FIGS * n_k + 1;
+    const int64_t o = (int64_t)d * RANK_SLICES + tid;
+    s_in[tid] = part_cnt[o * 2];
+    s_out[tid] = part_cnt[o * 2 + 1];
+    for (int v = 0; v < nv; ++v) {
+        s_v[tid] = part[o * nv + v];
+        __syncthreads();
+        for (int off = RANK_SLICES / 2; off > 0; off >>= 1) {
+            if (tid < off) {
+                s_v[tid] += s_v[tid + off];
+                if (v == 0) { s_in[tid] += s_in[tid + off]; s_out[tid] += s_out[tid + off]; }
+            }
+            __syncthreads();
+        }
+        if (tid == 0) s_sum[v] = s_v[0];
+        __syncthreads();
+    }
+    if (tid < nv - 1)                                                       // tid = figure * n_k + k
+        out[(int64_t)tid * n_seg + d] = s_in[0] > 0 ? s_sum[tid] / s_sum[nv - 1] : __longlong_as_double(0x7ff8000000000000ll);
+    if (tid == 0) {
+        counts[d] = s_in[0];
+        counts[n_seg + d] = s_out[0];
+    }
+}
+
+struct RankLayout {
+    GaucLayout g;
+    int64_t part, part_cnt, total;
+};
+// as gauc_fixed_layout: plain arithmetic; the slices' sums stand between GAUC's fixed part and rocPRIM's temporary storage
+static void rank_fixed_layout(int64_t n, int32_t n_domain, int32_t n_k, RankLayout* L) {
+    gauc_fixed_layout(n, n_domain, &L->g);
+    const int64_t seg = (int64_t)n_domain + 1;
+    int64_t off = L->g.temp;
+    L->part = off;     off += align_up(seg * RANK_SLICES * (RANK_FIGS * n_k + 1) * 8);
+    L->part_cnt = off; off += align_up(seg * RANK_SLICES * 2 * 8);
+    L->g.temp = off;
+    L->total = off;
+}
+static int rank_layout(int64_t n, int32_t n_domain, int32_t n_k, RankLayout* L) {
+    rank_fixed_layout(n, n_domain, n_k, L);
+    const int rc = gauc_temp_bytes(n, "eval_rank", &L->g.temp_bytes);
+    if (rc != 0) return rc;
+    L->total = L->g.temp + align_up(L->g.temp_bytes);
+    return 0;
+}
+
+extern "C" int64_t cdc_eval_rank_workspace_bytes(int64_t n, int32_t n_domain, int64_t n_user, int32_t n_k) {
+    if (!gauc_sizes_ok(n, n_domain, n_user) || n_k < 1 || n_k > RANK_MAX_NK) return 0;
+    RankLayout L;
+    if (rank_layout(n, n_domain, n_k, &L) != 0) return -1;
+    return L.total;
+}
+
+template <int NK>
+static void rank_sum_launch(int seg, hipStream_t st, const uint64_t* keys, const GaucScan* sc, const int64_t* start, const double* user_weight,
+                            const int32_t* ks, const double* D, int64_t n_user, int64_t n2, double* part, int64_t* part_cnt) {
+    hipLaunchKernelGGL(k_rank_sum<NK>, dim3(seg, RANK_SLICES), dim3(GAUC_THREADS), 0, st, keys, sc, start, user_weight, ks, D, n_user, n2,
+                       part, part_cnt);
+}
+
+extern "C" int cdc_eval_rank(const float* pred, const int16_t* label, const int32_t* user, int64_t ld_user, int64_t n_user,
+                             const int32_t* domain, int64_t ld_domain, int32_t n_domain, const double* user_weight, const int32_t* ks,
+                             int32_t n_k, const double* discounts, int64_t n, double* out, int64_t* counts, int32_t* err_flag,
+                             void* workspace, int64_t workspace_bytes, void* stream) {
+    CDC_CHECK_ARG(pred && label && user && ks && discounts && out && counts && workspace, CDC_E_BADARG, "eval_rank: null pointer");
+    CDC_CHECK_ARG(n > 0 && n < (1ll << 31) && n_domain > 0 && n_domain < (1 << 20) && n_user > 0 && ld_user >= 0 && ld_domain >= 0,
+                  CDC_E_BADARG, "eval_rank: bad sizes n=%ld n_domain=%d n_user=%ld", (long)n, n_domain, (long)n_user);
+    CDC_CHECK_ARG(n_k >= 1 && n_k <= RANK_MAX_NK, CDC_E_BADARG, "eval_rank: n_k=%d cut-offs, 1 to %d are served", n_k, RANK_MAX_NK);
+    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_rank: n_domain=%d needs the domain column", n_domain);
+    CDC_CHECK_ARG(gauc_sizes_ok(n, n_domain, n_user), CDC_E_BADARG,
+                  "eval_rank: (n_domain + 1) * n_user = %ld * %ld group ids exceed 2^32", (long)n_domain + 1, (long)n_user);
+    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_rank: workspace must be 256-byte aligned");
+    RankLayout L;
+    rank_fixed_layout(n, n_domain, n_k, &L);
+    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_rank: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
+    int rc = rank_layout(n, n_domain, n_k, &L);
+    if (rc != 0) return rc;
+    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_rank: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
+    char* base = (char*)workspace;
+    const uint64_t* keys_out = (const uint64_t*)(base + L.g.keys_out);
+    const GaucScan* sc = (const GaucScan*)(base + L.g.scan);
+    const int64_t* start = (const int64_t*)(base + L.g.start);
+    double* part = (double*)(base + L.part);
+    int64_t* part_cnt = (int64_t*)(base + L.part_cnt);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n2 = 2 * n;
+    const int seg = n_domain + 1;
+    rc = gauc_order(pred, label, user, ld_user, n_user, domain, ld_domain, n_domain, n, err_flag, base, L.g, nullptr, "eval_rank", st);
+    if (rc != 0) return rc;
+    switch (n_k) {
+#define RANK_CASE(NK) case NK: rank_sum_launch<NK>(seg, st, keys_out, sc, start, user_weight, ks, discounts, n_user, n2, part, part_cnt); break;
+        RANK_CASE(1) RANK_CASE(2) RANK_CASE(3) RANK_CASE(4) RANK_CASE(5) RANK_CASE(6) RANK_CASE(7) RANK_CASE(8)
+#undef RANK_CASE
+    }
+    CDC_LAUNCH_CHECK("eval_rank(sum)");
+    hipLaunchKernelGGL(k_rank_final, dim3(seg), dim3(RANK_SLICES), 0, st, part, part_cnt, n_k, seg, out, counts);
+    CDC_LAUNCH_CHECK("eval_rank(final)");
     return 0;
 }
 

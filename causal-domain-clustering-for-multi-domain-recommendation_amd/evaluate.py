@@ -11,6 +11,10 @@ With a user column configured the same pass also yields GAUC — the reference's
 user's rows, averaged over the users that have both classes, weighted by their row count or a given weight — from one more
 C-ABI call (`cdc_eval_gauc`) on the same device-resident predictions.
 
+`eval_rank` answers what stands at the top of each user's list: NDCG@K, Recall@K, Precision@K, HitRate@K and MRR@K per user, averaged
+per domain and over all rows, every figure the expectation over the order of tied scores (`cdc_eval_rank`, on GAUC's sort and first
+scan); `Evaluator(rank_at=(1, 10))` reports them and `Runner(select_by="mean_ndcg@10")` selects by one.
+
 `eval_auc_ci` adds what an AUC needs to be judged: its DeLong standard error on this evaluation set, and for two prediction
 vectors over the same rows the difference of their AUCs with the standard error of that difference (`cdc_eval_auc_delong`);
 `Evaluator(auc_ci=True)` and `Evaluator.compare` report them.
@@ -204,6 +208,101 @@ def eval_gauc(pred, label, user, n_user, domain=None, n_domain=1, user_weight=No
               err.data_ptr(), ws.data_ptr(), nbytes), C.c_void_p(torch.cuda.current_stream().cuda_stream))
     eval_gauc.last_err = err
     return out, counts[:seg], counts[seg:]
+
+
+Rank = collections.namedtuple("Rank", "ndcg recall precision hit mrr counted left_out")
+RANK_FIGURES = ("ndcg", "recall", "precision", "hit", "mrr")
+RANK_MAX_K, RANK_MAX_NK = 1024, 8
+_rank_tables = {}
+
+
+def _rank_ks(ks):
+    """an int or a sequence of ints -> the tuple of cut-offs, checked against cdc_eval_rank's limits"""
+    ks = (ks,) if isinstance(ks, int) and not isinstance(ks, bool) else tuple(ks)
+    if not 1 <= len(ks) <= RANK_MAX_NK:
+        raise ValueError(f"ks={ks!r} holds {len(ks)} cut-offs: 1 to {RANK_MAX_NK} are served")
+    for k in ks:
+        if isinstance(k, bool) or int(k) != k or not 1 <= k <= RANK_MAX_K:
+            raise ValueError(f"ks={ks!r}: the cut-off {k!r} is no integer in [1, {RANK_MAX_K}]")
+    ks = tuple(int(k) for k in ks)
+    for a, b in zip(ks, ks[1:]):
+        if b <= a:
+            raise ValueError(f"ks={ks!r} must be strictly increasing: {b} follows {a}")
+    return ks
+
+
+def rank_discounts(k_max, device=None):
+    """The cumulative discounts of NDCG, f64 [k_max + 1]: D[0] = 0, D[r + 1] = D[r] + 1 / log2(r + 2), added sequentially in float64 on
+    the host — D[min(P, K)] is the ideal DCG of P positives.  Cached per (device, k_max); device None: a host tensor."""
+    k_max = int(k_max)
+    if not 1 <= k_max <= RANK_MAX_K:
+        raise ValueError(f"k_max={k_max} must lie in [1, {RANK_MAX_K}]")
+    key = ("D", None if device is None else str(device), k_max)
+    if key not in _rank_tables:
+        table = [0.0]
+        for r in range(k_max):
+            table.append(table[-1] + 1.0 / math.log2(r + 2))
+        if device is None:
+            _rank_tables[key] = torch.tensor(table, dtype=torch.float64)
+        else:                                                  # from pinned memory: stream-ordered, the host does not wait for the device
+            _rank_tables[key] = torch.tensor(table, dtype=torch.float64, pin_memory=True).to(device, non_blocking=True)
+    return _rank_tables[key]
+
+
+def eval_rank(pred, label, user, n_user, domain=None, n_domain=1, ks=(10,), user_weight=None):
+    """Per-user top-K ranking figures per domain and over all rows: NDCG@K, Recall@K, Precision@K, HitRate@K and MRR@K for every K of
+    `ks` (1 to 8 strictly increasing integers in [1, 1024]).  Inputs and groups as `eval_gauc`: a group is a user's rows of a domain,
+    or all of a user's rows for the last entry.  A group is ranked by descending score and every figure is the expectation over a
+    uniformly random order of the rows that tie in score (-0.0 ties with +0.0), so no figure depends on how a sort left tied rows;
+    the definitions are in include/cdcmdr.h (`cdc_eval_rank`).  A segment's value is sum_g w_g m_g / sum_g w_g over its groups with at
+    least one positive; w_g = user_weight[user], or 1 when user_weight is None: the MACRO average over users, as these figures are
+    reported in the literature — unlike `eval_gauc`, whose default weight is the user's row count.
+    Returns Rank(ndcg, recall, precision, hit, mrr, counted, left_out): the figures f64 device tensors [len(ks), n_domain + 1], NaN
+    where no group is counted; counted / left_out i64 [n_domain + 1], the groups with / without a positive.  The same rows in any
+    order give the same bits.  No host synchronisation; the error word (as `eval_gauc`'s) is kept as `eval_rank.last_err`."""
+    lib = L.load()
+    n_user, n_domain = int(n_user), int(n_domain)
+    if n_user <= 0 or n_domain <= 0:
+        raise ValueError(f"n_user={n_user} and n_domain={n_domain} must be positive")
+    if (n_domain + 1) * n_user > 1 << 32:
+        raise ValueError(f"(n_domain + 1) * n_user = {(n_domain + 1) * n_user} group ids exceed 2^32, the upper half of a sort key")
+    ks = _rank_ks(ks)
+    if not pred.is_cuda:
+        raise L.HipExtensionError("eval_rank needs device tensors; there is no CPU fallback")
+    pred = pred.reshape(-1).to(torch.float32).contiguous()
+    label = label.reshape(-1).to(torch.int16).contiguous()
+    n = pred.numel()
+    if label.numel() != n:
+        raise ValueError(f"{n} predictions but {label.numel()} labels")
+    user, ld_user = _id_column(user, n, "user")
+    ld_domain = 0
+    if domain is not None:
+        domain, ld_domain = _id_column(domain, n, "domain")
+    elif n_domain != 1:
+        raise ValueError("n_domain > 1 needs the domain column")
+    dev = pred.device
+    if user_weight is not None:
+        user_weight = torch.as_tensor(user_weight, dtype=torch.float64).to(dev).reshape(-1).contiguous()
+        if user_weight.numel() != n_user:
+            raise ValueError(f"user_weight holds {user_weight.numel()} entries for {n_user} users")
+    key = ("ks", str(dev), ks)
+    if key not in _rank_tables:
+        _rank_tables[key] = torch.tensor(ks, dtype=torch.int32, pin_memory=True).to(dev, non_blocking=True)
+    ks_dev, disc = _rank_tables[key], rank_discounts(ks[-1], dev)
+    seg, n_k = n_domain + 1, len(ks)
+    out = torch.empty((len(RANK_FIGURES), n_k, seg), dtype=torch.float64, device=dev)
+    counts = torch.empty((2, seg), dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    nbytes = lib.cdc_eval_rank_workspace_bytes(n, n_domain, n_user, n_k)
+    if nbytes <= 0:
+        raise RuntimeError(f"cdc_eval_rank_workspace_bytes refused n={n}, n_domain={n_domain}, n_user={n_user}, n_k={n_k}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    L.launch("cdc_eval_rank", lib.cdc_eval_rank,
+             (pred.data_ptr(), label.data_ptr(), user.data_ptr(), ld_user, n_user, None if domain is None else domain.data_ptr(),
+              ld_domain, n_domain, None if user_weight is None else user_weight.data_ptr(), ks_dev.data_ptr(), n_k, disc.data_ptr(), n,
+              out.data_ptr(), counts.data_ptr(), err.data_ptr(), ws.data_ptr(), nbytes), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    eval_rank.last_err = err
+    return Rank(out[0], out[1], out[2], out[3], out[4], counts[0], counts[1])
 
 
 AucCI = collections.namedtuple("AucCI", "auc var rows positives")
@@ -1020,6 +1119,14 @@ class Evaluator:
             per-replicate differences under shared weights.  The bootstrap launches are queued with the others, before the one
             synchronisation.
             Not offered: significance-aware early stopping in `Runner`, BCa or studentised intervals.
+    rank_at: None (off: the result dictionaries and launches are exactly those without it), an int or a tuple of ints (needs user_idx):
+            the cut-offs K of the per-user top-K figures (`eval_rank`: up to 8 strictly increasing values in [1, 1024]).  test() adds,
+            for fig in ndcg, recall, precision, hit, mrr and every K, total_<fig>@<K>, and with per-domain evaluation domain_<fig>@<K>
+            {d: value} and mean_<fig>@<K>, weighted like mean_gauc (NaN when a present domain counts no user), and total_rank_users
+            (+ domain_rank_users): the users with at least one positive, over whom the figures are averaged — with user_weight when one
+            was given, uniformly otherwise (GAUC's default is the row count).  The launch is queued with the others, before the one
+            synchronisation.  Not offered: standard errors, bootstrap replicates or `compare` deltas of these figures, graded gains,
+            sampled-negative protocols, MAP.
     calibration: test() adds calibration figures (`eval_calibration`; True: 10 bins, an int: that many): total_pcoc (predicted over
             observed CTR), total_brier, total_ece, total_ece_quantile, and with per-domain evaluation domain_pcoc / domain_brier /
             domain_ece / domain_ece_quantile {d: value} and mean_pcoc / mean_brier / mean_ece / mean_ece_quantile, weighted like
@@ -1046,8 +1153,11 @@ class Evaluator:
     def __init__(self, model, mode="multi", domain_idx=None, n_domain=1, domain_cnt_weight=None, is_evaluate_multi_domain=True,
                  user_idx=None, n_user=None, user_weight=None, auc_ci=False, precision=None, calibration=False, recalibration=None,
                  recalibration_eps=0.0, loss_ci=False, gauc_ci=False, bootstrap=None, bootstrap_seed=0, bootstrap_level=0.95,
-                 calibration_ci=False):
+                 calibration_ci=False, rank_at=None):
         self.model, self.mode = model, mode
+        self.rank_at = None if rank_at is None else _rank_ks(rank_at)
+        if self.rank_at is not None and user_idx is None:
+            raise ValueError("rank_at needs user_idx, the column that holds a row's user: the top-K figures rank every user's own rows")
         self.bootstrap = 0 if bootstrap is None else int(bootstrap)         # 0: off
         if bootstrap is not None and (isinstance(bootstrap, bool) or not 1 <= self.bootstrap <= BOOT_MAX_REP):
             raise ValueError(f"bootstrap must be None or a number of replicates in [1, {BOOT_MAX_REP}], not {bootstrap!r}")
@@ -1166,12 +1276,17 @@ class Evaluator:
         total_pcoc, total_brier, total_ece, total_ece_quantile (+ domain_* and mean_* of the four); with loss_ci also total_loss_se
         (+ domain_loss_se, mean_loss_se); with gauc_ci also total_gauc_se (+ domain_gauc_se; no mean_gauc_se: the per-domain GAUCs
         share users and are not independent); with bootstrap also total_*_boot_se/lo/hi, domain_*_boot_*, mean_*_boot_* for auc, loss
-        and (with user_idx) gauc, and boot_valid; with calibration_ci the same *_boot_* keys for pcoc, brier, ece and ece_quantile."""
+        and (with user_idx) gauc, and boot_valid; with calibration_ci the same *_boot_* keys for pcoc, brier, ece and ece_quantile;
+        with rank_at also total_<fig>@<K> (+ domain_<fig>@<K>, mean_<fig>@<K>) for ndcg, recall, precision, hit, mrr and
+        total_rank_users (+ domain_rank_users)."""
         pred, label, domain, user = self._score(data_loader)
         multi = self.is_evaluate_multi_domain
         auc, loss, rows, pos = eval_metrics(pred, label, domain if multi else None, self.n_domain if multi else 1)
         if user is not None:                                   # queued behind the metrics: still nothing has been read back
             gauc = eval_gauc(pred, label, user, self.n_user, domain if multi else None, self.n_domain if multi else 1, self.user_weight)[0]
+        if self.rank_at is not None:                           # likewise queued
+            rank = eval_rank(pred, label, user, self.n_user, domain if multi else None, self.n_domain if multi else 1, self.rank_at,
+                             self.user_weight)
         if self.auc_ci:                                        # likewise queued
             ci_var = eval_auc_ci(pred, label, domain if multi else None, self.n_domain if multi else 1).var
         if self.calibration_bins:                              # likewise queued
@@ -1218,6 +1333,18 @@ class Evaluator:
                 domain_gauc = {d: gauc[d] for d in range(self.n_domain) if rows[d] > 0}
                 result["domain_gauc"] = domain_gauc
                 result["mean_gauc"] = sum(self._weight(d) * v for d, v in domain_gauc.items())     # as mean_auc; NaN when a domain has no countable user
+        if self.rank_at is not None:                           # a bad user id has been raised above: the two calls flag the same rows
+            figures, counted = torch.stack(rank[:len(RANK_FIGURES)]).cpu().tolist(), rank.counted.cpu().tolist()
+            present = [d for d in range(self.n_domain) if rows[d] > 0] if multi else []
+            for fig, per_k in zip(RANK_FIGURES, figures):
+                for K, v in zip(self.rank_at, per_k):
+                    result[f"total_{fig}@{K}"] = v[-1]
+                    if multi:
+                        result[f"domain_{fig}@{K}"] = {d: v[d] for d in present}
+                        result[f"mean_{fig}@{K}"] = sum(self._weight(d) * v[d] for d in present)   # as mean_gauc: NaN when a domain counts no user
+            result["total_rank_users"] = counted[-1]
+            if multi:
+                result["domain_rank_users"] = {d: counted[d] for d in present}
         if self.auc_ci:
             var = ci_var.cpu().tolist()
             result["total_auc_se"] = _se(var[-1])

@@ -5,20 +5,27 @@ checkpoint and evaluate on the test set.  wandb logging, dataset preprocessing a
 with the caller (they are the reference's control plane: SURVEY §2).
 
 `select_by="mean_gauc"` / `"total_gauc"` makes the per-user GAUC of an Evaluator with a user column (evaluate.py) the criterion
-of both the best checkpoint and the early stop instead."""
+of both the best checkpoint and the early stop instead; `"mean_<fig>@<K>"` / `"total_<fig>@<K>"` with fig one of ndcg, recall,
+precision, hit, mrr does the same with a per-user top-K figure of an Evaluator with `rank_at` (higher is better)."""
+import re
+
 import torch
 
 from .data import train_epoch
-from .evaluate import Evaluator
+from .evaluate import RANK_FIGURES, Evaluator
+
+_RANK_KEY = re.compile(r"(?:mean|total)_(?:%s)@[1-9][0-9]*" % "|".join(RANK_FIGURES))
 
 
 class Runner:
     def __init__(self, model, step, evaluator: Evaluator, save_model_path, num_trials=3, cdc_trainer=None, log=print, select_by=None):
         """step: the TrainStep (its optimiser is checkpointed); cdc_trainer: a CDCTrainer whose train_epoch replaces the
         plain epoch for CDC models (run.py:738-750).  select_by: None = the reference's rule (mean_auc, else total_auc);
-        "mean_gauc" or "total_gauc" = that key of the evaluator's result."""
-        if select_by not in (None, "mean_gauc", "total_gauc"):
-            raise ValueError(f"select_by={select_by!r}: None, 'mean_gauc' or 'total_gauc'")
+        "mean_gauc" or "total_gauc" = that key of the evaluator's result; likewise "mean_<fig>@<K>" or "total_<fig>@<K>", a top-K
+        figure (ndcg, recall, precision, hit, mrr) of an evaluator whose rank_at holds K."""
+        if select_by not in (None, "mean_gauc", "total_gauc") and not (isinstance(select_by, str) and _RANK_KEY.fullmatch(select_by)):
+            raise ValueError(f"select_by={select_by!r}: None, 'mean_gauc', 'total_gauc', or 'mean_<fig>@<K>' / 'total_<fig>@<K>' with fig "
+                             f"one of {', '.join(RANK_FIGURES)}")
         self.select_by, self.best_select = select_by, 0.0
         self.model, self.step, self.evaluator = model, step, evaluator
         self.save_model_path, self.num_trials = save_model_path, int(num_trials)
@@ -48,6 +55,10 @@ class Runner:
         if score is None:                       # is_evaluate_multi_domain off: the reference's commented-out total_auc criterion
             score, best = result_dict["total_auc"], self.best_auc
         if self.select_by is not None:
+            if self.select_by not in result_dict and "@" in self.select_by:
+                raise KeyError(f"select_by={self.select_by!r} but the evaluator's result has no such key: construct the Evaluator with "
+                               f"user_idx (and n_user) and rank_at={self.select_by.split('@')[1]}"
+                               + (", and per-domain evaluation for a mean_ figure" if self.select_by.startswith("mean_") else ""))
             if self.select_by not in result_dict:
                 raise KeyError(f"select_by={self.select_by!r} but the evaluator's result has no such key: construct the Evaluator with "
                                f"user_idx (and n_user)" + (", and per-domain evaluation for mean_gauc" if self.select_by == "mean_gauc" else ""))

@@ -1206,6 +1206,35 @@ int cdc_eval_gauc(const float* pred, const int16_t* label, const int32_t* user, 
                   const int32_t* domain, int64_t ld_domain, int32_t n_domain, const double* user_weight, int64_t n,
                   double* out, int64_t* counts, int32_t* err_flag, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Per-user top-K ranking figures over cdc_eval_gauc's groups: NDCG@K, Recall@K, Precision@K, HitRate@K and MRR@K for binary
+ * labels.  pred, label, user, ld_user, n_user, domain, ld_domain, n_domain, user_weight, err_flag as for cdc_eval_gauc.  A group
+ * (a user's rows of a domain, or all of a user's rows for the pseudo-domain n_domain) is ranked by DESCENDING score, -0.0 tying
+ * with +0.0, and every figure is the expectation over a uniformly random order of the rows that tie (McSherry & Najork 2008).  For a
+ * group with P >= 1 positives whose tie runs t occupy the 0-based ranks [a_t, b_t), T_t = b_t - a_t rows of which P_t are positive,
+ * and c_t = max(0, min(b_t, K) - a_t):
+ *     H         = sum_t P_t c_t / T_t                        recall = H / P        precision = H / K (also when the group is shorter)
+ *     ndcg      = sum_{a_t < K} (P_t / T_t) (D[min(b_t, K)] - D[a_t]) / D[min(P, K)],   D[0] = 0, D[r+1] = D[r] + 1 / log2(r + 2)
+ *     hit       = 1 - prod_{a_t < K, P_t > 0} q_t,   q_t = 0 if c_t > T_t - P_t, else prod_{i < c_t} (T_t - P_t - i) / (T_t - i)
+ *     mrr       = sum_{j=0}^{min(T - Pt, K - a - 1)} pr_j / (a + 1 + j) over the first run (a, T, Pt) with a positive, 0 if a >= K;
+ *                 pr_0 = Pt / T, pr_{j+1} = pr_j (T - Pt - j) / (T - 1 - j)
+ *   ks     DEVICE int32 [n_k], n_k in [1, 8]: the cut-offs, strictly increasing, in [1, 1024].  The values are read by the launches
+ *          alone, so the CALLER validates them (evaluate.eval_rank does); a launch clamps each into [1, 1024] where it reads it.
+ *   discounts  DEVICE f64 [ks[n_k-1] + 1]: D[0..ks[n_k-1]] of the recurrence above (evaluate.rank_discounts).
+ *   out    [5, n_k, n_domain+1] doubles, figures in the order ndcg, recall, precision, hit, mrr:
+ *          sum_g w_g m_g / sum_g w_g over the groups of the (pseudo-)domain with P_g >= 1; w_g = user_weight[user of g], or 1 when
+ *          user_weight == NULL (the macro average over users; cdc_eval_gauc's default is the row count).  NaN where no group counts.
+ *   counts [2, n_domain+1] int64: the groups counted, then the groups without a positive (left out: every figure is undefined).
+ * The weighted sums are added in an order fixed by the sorted keys (no atomics): the same rows in any order give the same bits.
+ * Limits and checks as cdc_eval_gauc, and n_k outside [1, 8] is CDC_E_BADARG — all before anything is launched.  Stream-ordered:
+ * no allocation, no synchronisation, nothing read back; the launch dimensions depend on (n, n_domain, n_k) alone, so the call can
+ * be captured in a graph.  workspace: cdc_eval_rank_workspace_bytes(n, n_domain, n_user, n_k) bytes, 256-byte aligned; 0 for
+ * sizes the call refuses. */
+int64_t cdc_eval_rank_workspace_bytes(int64_t n, int32_t n_domain, int64_t n_user, int32_t n_k);
+int cdc_eval_rank(const float* pred, const int16_t* label, const int32_t* user, int64_t ld_user, int64_t n_user,
+                  const int32_t* domain, int64_t ld_domain, int32_t n_domain, const double* user_weight, const int32_t* ks,
+                  int32_t n_k, const double* discounts, int64_t n, double* out, int64_t* counts, int32_t* err_flag,
+                  void* workspace, int64_t workspace_bytes, void* stream);
+
 /* DeLong standard errors (DeLong, DeLong & Clarke-Pearson 1988) of the AUCs cdc_eval_metrics reports, and the paired comparison of
  * two score vectors on the same rows.  pred_a, label, domain, ld_domain, n_domain as for cdc_eval_metrics; pred_b f32 [n] or NULL
  * (unpaired).  Per segment (domain 0..n_domain-1, then ALL rows) with positives x_1..x_P, negatives y_1..y_N, scores compared in
