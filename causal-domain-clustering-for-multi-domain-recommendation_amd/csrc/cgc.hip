@@ -568,13 +568,17 @@ __global__ void __launch_bounds__(MID_THREADS) __attribute__((amdgpu_waves_per_e
     const int64_t rowq = row0 + rq;
     const bool liveq = rowq < B;
     f32x4_t x2q[MID_XW], x1q[MID_XW][2];
-    const float* ex2p = a.ex2 + rowq * a.ld_ex2 + 4 * l16;
-    const float* ex1p = a.ex1 + rowq * a.ld_ex1 + 4 * l16;
+    // a lane's place in the block's rows as a 32-bit element offset from a wave-uniform base (row0's row, in scalar registers): a
+    // 64-bit pointer per lane and buffer, alive from the entry to phase 3, was part of what pushed the kernel into scratch under its
+    // cap of 96 registers (profiles/round9/README.md section 1); the launcher bounds the row strides so that the offsets fit
+    const float* ex2b = a.ex2 + row0 * a.ld_ex2;
+    const float* ex1b = a.ex1 + row0 * a.ld_ex1;
+    const uint32_t ex2o = (uint32_t)rq * (uint32_t)a.ld_ex2 + 4u * l16, ex1o = (uint32_t)rq * (uint32_t)a.ld_ex1 + 4u * l16;
     auto load_x2 = [&](int c) __attribute__((always_inline)) {
 #pragma unroll
         for (int u = 0; u < MID_XW; ++u) {
             const int e = eg + 4 * (MID_XW * c + u);
-            x2q[u] = (liveq && e < ne2) ? *reinterpret_cast<const f32x4_t*>(ex2p + (int64_t)e * H2) : f32x4_t{0.f, 0.f, 0.f, 0.f};
+            x2q[u] = (liveq && e < ne2) ? *reinterpret_cast<const f32x4_t*>(ex2b + e * H2 + ex2o) : f32x4_t{0.f, 0.f, 0.f, 0.f};
         }
     };
     auto load_x1 = [&](int c) __attribute__((always_inline)) {
@@ -583,7 +587,7 @@ __global__ void __launch_bounds__(MID_THREADS) __attribute__((amdgpu_waves_per_e
             const int e = eg + 4 * (MID_XW * c + u);
 #pragma unroll
             for (int h = 0; h < 2; ++h)
-                x1q[u][h] = (liveq && e < ne1) ? *reinterpret_cast<const f32x4_t*>(ex1p + (int64_t)e * H1 + 64 * h) : f32x4_t{0.f, 0.f, 0.f, 0.f};
+                x1q[u][h] = (liveq && e < ne1) ? *reinterpret_cast<const f32x4_t*>(ex1b + (e * H1 + 64 * h) + ex1o) : f32x4_t{0.f, 0.f, 0.f, 0.f};
         }
     };
     load_x2(0);
@@ -702,15 +706,22 @@ __global__ void __launch_bounds__(MID_THREADS) __attribute__((amdgpu_waves_per_e
             if (job >= n_jobs) return;
             const int s = job / Cfg::NT1, nt = job % Cfg::NT1;
             const int ns = n_steps[s];
-            bf16x8_t af[MID_MAXSTEP];
-#pragma unroll
-            for (int st = 0; st < MID_MAXSTEP; ++st) {                 // past the source's steps: w[st] is zero, any finite A fragment will do
-                const int sc = st < ns ? st : ns - 1;
-                af[st] = *reinterpret_cast<const bf16x8_t*>(dz2 + steps[s][sc].a_off + frow * steps[s][sc].a_ld + fk);
-            }
+            // the A fragments in two halves, the second read under the first half's MFMAs: all MID_MAXSTEP of them at once, beside
+            // both tiles' B fragments and the level-k rows held for phase 3, were more than the cap of 96 registers holds (the
+            // compiler spilled a B fragment around the first MFMA); the K order of the accumulation is unchanged
+            constexpr int HS = MID_MAXSTEP / 2;
             f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int st = 0; st < MID_MAXSTEP; ++st) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[st], w[st], acc, 0, 0, 0);
+            for (int h0 = 0; h0 < MID_MAXSTEP; h0 += HS) {
+                bf16x8_t af[HS];
+#pragma unroll
+                for (int q = 0; q < HS; ++q) {                         // past the source's steps: w[st] is zero, any finite A fragment will do
+                    const int sc = h0 + q < ns ? h0 + q : ns - 1;
+                    af[q] = *reinterpret_cast<const bf16x8_t*>(dz2 + steps[s][sc].a_off + frow * steps[s][sc].a_ld + fk);
+                }
+#pragma unroll
+                for (int q = 0; q < HS; ++q) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[q], w[h0 + q], acc, 0, 0, 0);
+            }
 #pragma unroll
             for (int r4 = 0; r4 < 4; ++r4)
                 dP1[((size_t)s * MID_BM + (lane >> 4) * 4 + r4) * Cfg::DP_LD + nt * 16 + (lane & 15)] = acc[r4];
@@ -799,6 +810,8 @@ extern "C" int cdc_cgc_mid_bwd(const cdc_cgc_mid_bwd_args* a, void* stream) {
                   "cgc_mid_bwd: misaligned expert buffers");
     CDC_CHECK_ARG(a->ld_ex1 >= (int64_t)a->n_exp1 * a->H1 && a->ld_ex2 >= (int64_t)a->n_exp2 * a->H2, CDC_E_ALIGN,
                   "cgc_mid_bwd: expert buffers must be wide enough (as cgc_mid_fwd asks)");
+    // (the kernel addresses a workgroup's 16 rows of the expert buffers with 32-bit element offsets from the first of them)
+    CDC_CHECK_ARG(a->ld_ex1 <= (1 << 27) && a->ld_ex2 <= (1 << 27), CDC_E_TOOBIG, "cgc_mid_bwd: expert buffers' row strides above 2^27 elements");
     for (int g = 0; g < a->n_gate1; ++g)
         CDC_CHECK_ARG(a->g1[g].probs && a->g1[g].d_logits && mid_check_sel(a->g1[g].sel, a->g1[g].n_sel, a->n_exp1), CDC_E_BADARG,
                       "cgc_mid_bwd: level-k gate %d malformed", g);
