@@ -381,6 +381,9 @@ _SIGNATURES = {
     "cdc_eval_gauc": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_i32, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p]),
     "cdc_eval_rank_workspace_bytes": (c_i64, [c_i64, c_i32, c_i64, c_i32]),
     "cdc_eval_rank": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_i32, c_p, c_p, c_i32, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p]),
+    "cdc_eval_topk_workspace_bytes": (c_i64, [c_i64, c_i32, c_i64, c_i32]),
+    "cdc_eval_topk": (c_i32, [c_p, c_p, c_i64, c_i64, c_p, c_i64, c_i32, c_p, c_i64, c_i32, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                              c_i64, c_p]),
     "cdc_eval_auc_delong_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
     "cdc_eval_auc_delong": (c_i32, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i32, c_p, c_p, c_p, c_p, c_i64, c_p]),
     "cdc_eval_loss_ci_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),

@@ -765,6 +765,270 @@ extern "C" int cdc_eval_rank(const float* pred, const int16_t* label, const int3
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Per-user top-K LISTS: for every (domain, user) group its K best-scored rows, best first, no item twice.  The order inside a group is
+// total — descending score (score_key: -0.0 is +0.0), then ascending item, then ascending row index — and every step below realises
+// it by a STABLE radix sort (rocPRIM) over keys that carry the row index as the value, so nothing depends on how a sort leaves ties:
+//
+//   keys    one key per row: group << 32 | ~score_key (no item) or group << 32 | item; a row that belongs to no list (NaN score, an
+//           id out of range, a negative item) gets TOPK_DEAD = all ones, which no live row can have (~score_key of a non-NaN score is
+//           below 0xff800001, an item is below 2^31) and which sorts behind every live key.  No id is clamped.
+//   no item one sort over all 64 bits: a group's rows stand in rank order, equal scores in row order (the rows enter in row order).
+//   item    sort 1 on (group, item) lays every (group, item) run out in row order; a segmented scan (rocPRIM, elements formed on the fly:
+//           run head, ~score_key and row in one word, the operator keeps the smaller (~score_key, row) inside a run) leaves the run's
+//           best row at the run's LAST position; k_topk_rekey keys that position (group << 32 | the best row's ~score_key, value = the
+//           best row) and every other position TOPK_DEAD; sort 2 over these keys is the score sort — its input stands in (group, item)
+//           order, so equal scores of a group come out in item order.
+//   scan 1  over the sorted keys: h(i) = first position of i's group (a running maximum), g(i) = groups that begin at or before i.
+//   scan 2  running count of the positions with rank i - h(i) < k: a kept row's place in the entry arrays.
+//   emit    a group's first row writes the group's id and start, its last row the survivor count, every kept row its entry; the thread
+//           of position n - 1 writes G, E and group_start[G].  Every output index is below n (group_start: n) by construction.
+// The only atomic is err_flag's atomicMax (a maximum: order-free).  All launches have dimensions that depend on (n, item != NULL)
+// alone — the sorts always cover all 64 bits, TOPK_DEAD needs them; nothing is allocated, synchronised or read back.
+#define TOPK_DEAD (~0ull)
+
+typedef unsigned long long TopkPick;    // ~score_key << 32 | row << 1 | run head: one word (a three-field struct spills in rocPRIM's scan)
+struct TopkPickOp {                     // the segmented minimum of (~score_key, row); row < 2^31
+    __host__ __device__ TopkPick operator()(const TopkPick& a, const TopkPick& b) const {
+        if (b & 1ull) return b;
+        const TopkPick m = (b >> 1) < (a >> 1) ? b : a;
+        return (m & ~1ull) | (a & 1ull);
+    }
+};
+struct TopkPickIn {                     // element i of the pick scan: position i of the (group, item) order
+    const uint64_t* keys;
+    const uint32_t* rows;
+    const float* pred;
+    __device__ TopkPick operator()(uint32_t i) const {
+        const uint32_t row = rows[i];
+        return ((TopkPick)~score_key(pred[row]) << 32) | ((TopkPick)row << 1) | ((i == 0 || keys[i] != keys[i - 1]) ? 1ull : 0ull);
+    }
+};
+struct TopkScan { uint32_t h, g; };
+struct TopkScanOp {
+    __host__ __device__ TopkScan operator()(const TopkScan& a, const TopkScan& b) const {
+        TopkScan r;
+        r.h = a.h > b.h ? a.h : b.h;
+        r.g = a.g + b.g;
+        return r;
+    }
+};
+struct TopkScanIn {                     // element i of scan 1
+    const uint64_t* keys;
+    __host__ __device__ TopkScan operator()(uint32_t i) const {
+        const uint64_t k = keys[i];
+        const bool head = k != TOPK_DEAD && (i == 0 || (k >> 32) != (keys[i - 1] >> 32));
+        TopkScan r;
+        r.h = head ? i : 0u;
+        r.g = head ? 1u : 0u;
+        return r;
+    }
+};
+struct TopkKeptIn {                     // element i of scan 2: 1 when position i is among its group's first k
+    const uint64_t* keys;
+    const TopkScan* sc;
+    uint32_t k;
+    __host__ __device__ uint32_t operator()(uint32_t i) const { return (keys[i] != TOPK_DEAD && i - sc[i].h < k) ? 1u : 0u; }
+};
+typedef rocprim::transform_iterator<rocprim::counting_iterator<uint32_t>, TopkPickIn, TopkPick> TopkPickIt;
+typedef rocprim::transform_iterator<rocprim::counting_iterator<uint32_t>, TopkScanIn, TopkScan> TopkScanIt;
+typedef rocprim::transform_iterator<rocprim::counting_iterator<uint32_t>, TopkKeptIn, uint32_t> TopkKeptIt;
+
+template <bool ITEM>
+__global__ void __launch_bounds__(MET_THREADS) k_topk_keys(const float* __restrict__ pred, const int32_t* __restrict__ user, int64_t ld_user,
+                                                           int64_t n_user, const int32_t* __restrict__ domain, int64_t ld_domain,
+                                                           int32_t n_domain, const int32_t* __restrict__ item, int64_t ld_item, int64_t n,
+                                                           uint64_t* __restrict__ keys, uint32_t* __restrict__ rows,
+                                                           int32_t* __restrict__ err) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float p = pred[i];
+        const int32_t d = domain ? domain[i * ld_domain] : 0;
+        const int64_t u = user[i * ld_user];
+        const int32_t it = ITEM ? item[i * ld_item] : 0;
+        uint64_t key = TOPK_DEAD;
+        if (p != p || d < 0 || d >= n_domain || u < 0 || u >= n_user || it < 0) {
+            if (err) atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
+        } else {
+            const uint64_t g = (uint64_t)d * (uint64_t)n_user + (uint64_t)u;
+            key = (g << 32) | (ITEM ? (uint32_t)it : ~score_key(p));
+        }
+        keys[i] = key;
+        rows[i] = (uint32_t)i;
+    }
+}
+
+// position i of the (group, item) order -> its key and row for the score sort: the run's last position stands for the run's best row
+__global__ void __launch_bounds__(MET_THREADS) k_topk_rekey(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ rows,
+                                                            const TopkPick* __restrict__ pick, int64_t n, uint64_t* __restrict__ keys2,
+                                                            uint32_t* __restrict__ rows2) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t k = keys[i];
+        uint64_t out = TOPK_DEAD;
+        uint32_t row = rows[i];
+        if (k != TOPK_DEAD && (i + 1 == n || keys[i + 1] != k)) {
+            const TopkPick best = pick[i];
+            out = (k & 0xffffffff00000000ull) | (best >> 32);
+            row = (uint32_t)(best >> 1) & 0x7fffffffu;
+        }
+        keys2[i] = out;
+        rows2[i] = row;
+    }
+}
+
+__global__ void __launch_bounds__(MET_THREADS) k_topk_emit(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ rows,
+                                                           const TopkScan* __restrict__ sc, const uint32_t* __restrict__ kept,
+                                                           const float* __restrict__ pred, int64_t n_user, uint32_t k, int64_t n,
+                                                           int64_t* __restrict__ n_out, int32_t* __restrict__ group_domain,
+                                                           int32_t* __restrict__ group_user, int32_t* __restrict__ group_start,
+                                                           int32_t* __restrict__ group_rows, int32_t* __restrict__ entry_row,
+                                                           float* __restrict__ entry_score) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t key = keys[i];
+        const TopkScan s = sc[i];
+        const uint32_t e = kept[i];                                        // kept positions up to and including i
+        if (i == n - 1) {                                                  // s.g <= n and e <= n: group_start holds n + 1 entries
+            n_out[0] = (int64_t)s.g;
+            n_out[1] = (int64_t)e;
+            group_start[s.g] = (int32_t)e;
+        }
+        if (key == TOPK_DEAD) continue;
+        const uint64_t g = key >> 32;
+        const uint32_t rank = (uint32_t)i - s.h, j = s.g - 1u;             // a live position lies in group j < G
+        if (rank == 0) {                                                   // k >= 1: the first row is kept, it is entry e - 1
+            const uint64_t d = g / (uint64_t)n_user;
+            group_domain[j] = (int32_t)d;
+            group_user[j] = (int32_t)(g - d * (uint64_t)n_user);
+            group_start[j] = (int32_t)(e - 1u);
+        }
+        if (i + 1 == n || keys[i + 1] == TOPK_DEAD || (keys[i + 1] >> 32) != g) group_rows[j] = (int32_t)(rank + 1u);
+        if (rank < k) {
+            const uint32_t row = rows[i];
+            entry_row[e - 1u] = (int32_t)row;
+            entry_score[e - 1u] = pred[row];
+        }
+    }
+}
+
+struct TopkLayout {
+    int64_t keys_a, keys_b, rows_a, rows_b, scan, kept, temp, temp_bytes, total;
+};
+// everything but rocPRIM's temporary storage: plain arithmetic (argument checks use it before any HIP or rocPRIM call)
+static void topk_fixed_layout(int64_t n, int32_t has_item, TopkLayout* L) {
+    int64_t off = 0;
+    L->keys_a = off; off += align_up(n * 8);
+    L->keys_b = off; off += align_up(n * 8);
+    L->rows_a = off; off += align_up(n * 4);
+    L->rows_b = off; off += align_up(n * 4);
+    L->scan = off;   off += align_up(n * (int64_t)(has_item ? sizeof(TopkPick) : sizeof(TopkScan)));   // the pick scan, then scan 1
+    L->kept = off;   off += align_up(n * 4);
+    L->temp = off;
+    L->temp_bytes = 0;
+    L->total = off;
+}
+// rocPRIM's temporary storage for the sorts and scans of n keys: they run one after the other
+static int topk_layout(int64_t n, int32_t has_item, TopkLayout* L) {
+    topk_fixed_layout(n, has_item, L);
+    const size_t sz = (size_t)n;
+    size_t t_sort = 0, t_pick = 0, t_scan = 0, t_kept = 0;
+    hipError_t e = rocprim::radix_sort_pairs(nullptr, t_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr,
+                                             (uint32_t*)nullptr, sz, 0, 64, (hipStream_t)0, false);
+    if (e == hipSuccess && has_item)
+        e = rocprim::inclusive_scan(nullptr, t_pick, TopkPickIt(rocprim::counting_iterator<uint32_t>(0), TopkPickIn{nullptr, nullptr, nullptr}),
+                                    (TopkPick*)nullptr, sz, TopkPickOp(), (hipStream_t)0, false);
+    if (e == hipSuccess)
+        e = rocprim::inclusive_scan(nullptr, t_scan, TopkScanIt(rocprim::counting_iterator<uint32_t>(0), TopkScanIn{nullptr}),
+                                    (TopkScan*)nullptr, sz, TopkScanOp(), (hipStream_t)0, false);
+    if (e == hipSuccess)
+        e = rocprim::inclusive_scan(nullptr, t_kept, TopkKeptIt(rocprim::counting_iterator<uint32_t>(0), TopkKeptIn{nullptr, nullptr, 1u}),
+                                    (uint32_t*)nullptr, sz, rocprim::plus<uint32_t>(), (hipStream_t)0, false);
+    if (e != hipSuccess) { cdc_set_error("eval_topk: rocprim size query failed: %s", hipGetErrorString(e)); return (int)e; }
+    L->temp_bytes = (int64_t)std::max(std::max(t_sort, t_pick), std::max(t_scan, t_kept));
+    L->total = L->temp + align_up(L->temp_bytes);
+    return 0;
+}
+// n_domain * n_user group ids must fit the upper half of a key
+static bool topk_sizes_ok(int64_t n, int32_t n_domain, int64_t n_user) {
+    return n > 0 && n < (1ll << 31) && n_domain > 0 && n_user > 0 && n_user <= (1ll << 32) && (int64_t)n_domain * n_user <= (1ll << 32);
+}
+
+extern "C" int64_t cdc_eval_topk_workspace_bytes(int64_t n, int32_t n_domain, int64_t n_user, int32_t has_item) {
+    if (!topk_sizes_ok(n, n_domain, n_user)) return 0;
+    TopkLayout L;
+    if (topk_layout(n, has_item != 0, &L) != 0) return -1;
+    return L.total;
+}
+
+extern "C" int cdc_eval_topk(const float* pred, const int32_t* user, int64_t ld_user, int64_t n_user, const int32_t* domain,
+                             int64_t ld_domain, int32_t n_domain, const int32_t* item, int64_t ld_item, int32_t k, int64_t n,
+                             int64_t* n_out, int32_t* group_domain, int32_t* group_user, int32_t* group_start, int32_t* group_rows,
+                             int32_t* entry_row, float* entry_score, int32_t* err_flag, void* workspace, int64_t workspace_bytes,
+                             void* stream) {
+    CDC_CHECK_ARG(pred && user && n_out && group_domain && group_user && group_start && group_rows && entry_row && entry_score && workspace,
+                  CDC_E_BADARG, "eval_topk: null pointer");
+    CDC_CHECK_ARG(n > 0 && n < (1ll << 31) && n_domain > 0 && n_user > 0 && ld_user >= 0 && ld_domain >= 0 && ld_item >= 0, CDC_E_BADARG,
+                  "eval_topk: bad sizes n=%ld n_domain=%d n_user=%ld", (long)n, n_domain, (long)n_user);
+    CDC_CHECK_ARG(k >= 1, CDC_E_BADARG, "eval_topk: k=%d, a list holds at least one row", k);
+    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_topk: n_domain=%d needs the domain column", n_domain);
+    CDC_CHECK_ARG(topk_sizes_ok(n, n_domain, n_user), CDC_E_BADARG, "eval_topk: n_domain * n_user = %ld * %ld group ids exceed 2^32",
+                  (long)n_domain, (long)n_user);
+    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_topk: workspace must be 256-byte aligned");
+    const int32_t has_item = item != nullptr;
+    TopkLayout L;
+    topk_fixed_layout(n, has_item, &L);
+    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_topk: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
+    int rc = topk_layout(n, has_item, &L);
+    if (rc != 0) return rc;
+    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_topk: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
+    char* base = (char*)workspace;
+    uint64_t* keys_a = (uint64_t*)(base + L.keys_a);
+    uint64_t* keys_b = (uint64_t*)(base + L.keys_b);
+    uint32_t* rows_a = (uint32_t*)(base + L.rows_a);
+    uint32_t* rows_b = (uint32_t*)(base + L.rows_b);
+    uint32_t* kept = (uint32_t*)(base + L.kept);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t sz = (size_t)n;
+    const int blocks = (int)std::min<int64_t>(cdc_ceil_div(n, MET_THREADS), 4096);
+    size_t temp_bytes;
+    hipError_t e;
+    if (has_item)
+        hipLaunchKernelGGL(k_topk_keys<true>, dim3(blocks), dim3(MET_THREADS), 0, st, pred, user, ld_user, n_user, domain, ld_domain, n_domain,
+                           item, ld_item, n, keys_a, rows_a, err_flag);
+    else
+        hipLaunchKernelGGL(k_topk_keys<false>, dim3(blocks), dim3(MET_THREADS), 0, st, pred, user, ld_user, n_user, domain, ld_domain, n_domain,
+                           item, ld_item, n, keys_a, rows_a, err_flag);
+    CDC_LAUNCH_CHECK("eval_topk(keys)");
+    temp_bytes = (size_t)L.temp_bytes;
+    e = rocprim::radix_sort_pairs(base + L.temp, temp_bytes, (const uint64_t*)keys_a, keys_b, (const uint32_t*)rows_a, rows_b, sz, 0, 64, st,
+                                  false);
+    if (e != hipSuccess) { cdc_set_error("eval_topk: radix sort failed: %s", hipGetErrorString(e)); return (int)e; }
+    if (has_item) {
+        TopkPick* pick = (TopkPick*)(base + L.scan);
+        temp_bytes = (size_t)L.temp_bytes;
+        e = rocprim::inclusive_scan(base + L.temp, temp_bytes, TopkPickIt(rocprim::counting_iterator<uint32_t>(0), TopkPickIn{keys_b, rows_b, pred}),
+                                    pick, sz, TopkPickOp(), st, false);
+        if (e != hipSuccess) { cdc_set_error("eval_topk: pick scan failed: %s", hipGetErrorString(e)); return (int)e; }
+        hipLaunchKernelGGL(k_topk_rekey, dim3(blocks), dim3(MET_THREADS), 0, st, keys_b, rows_b, pick, n, keys_a, rows_a);
+        CDC_LAUNCH_CHECK("eval_topk(rekey)");
+        temp_bytes = (size_t)L.temp_bytes;
+        e = rocprim::radix_sort_pairs(base + L.temp, temp_bytes, (const uint64_t*)keys_a, keys_b, (const uint32_t*)rows_a, rows_b, sz, 0, 64,
+                                      st, false);
+        if (e != hipSuccess) { cdc_set_error("eval_topk: score sort failed: %s", hipGetErrorString(e)); return (int)e; }
+    }
+    TopkScan* sc = (TopkScan*)(base + L.scan);
+    temp_bytes = (size_t)L.temp_bytes;
+    e = rocprim::inclusive_scan(base + L.temp, temp_bytes, TopkScanIt(rocprim::counting_iterator<uint32_t>(0), TopkScanIn{keys_b}), sc, sz,
+                                TopkScanOp(), st, false);
+    if (e != hipSuccess) { cdc_set_error("eval_topk: group scan failed: %s", hipGetErrorString(e)); return (int)e; }
+    temp_bytes = (size_t)L.temp_bytes;
+    e = rocprim::inclusive_scan(base + L.temp, temp_bytes, TopkKeptIt(rocprim::counting_iterator<uint32_t>(0), TopkKeptIn{keys_b, sc, (uint32_t)k}),
+                                kept, sz, rocprim::plus<uint32_t>(), st, false);
+    if (e != hipSuccess) { cdc_set_error("eval_topk: offset scan failed: %s", hipGetErrorString(e)); return (int)e; }
+    hipLaunchKernelGGL(k_topk_emit, dim3(blocks), dim3(MET_THREADS), 0, st, keys_b, rows_b, sc, kept, pred, n_user, (uint32_t)k, n, n_out,
+                       group_domain, group_user, group_start, group_rows, entry_row, entry_score);
+    CDC_LAUNCH_CHECK("eval_topk(emit)");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Per-segment BCE of CDC's probe evaluation (run.py:549-558): every domain's batch went through ONE eval forward, its rows
 // form a contiguous segment of the [rows, n_cols] tower probabilities, and segment s is scored by column seg_col[s].  One
 // workgroup per segment; the per-element loss is the expression of the step's BCE kernels (rowops.hip k_bce: ATen's, pinned

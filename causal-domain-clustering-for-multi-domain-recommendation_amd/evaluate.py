@@ -15,6 +15,10 @@ C-ABI call (`cdc_eval_gauc`) on the same device-resident predictions.
 per domain and over all rows, every figure the expectation over the order of tied scores (`cdc_eval_rank`, on GAUC's sort and first
 scan); `Evaluator(rank_at=(1, 10))` reports them and `Runner(select_by="mean_ndcg@10")` selects by one.
 
+`eval_topk` hands the ranking itself back: for every user, per domain or over all rows, the K best-scored rows, best first, no item
+twice, under a total order (score, item id, row index) that does not depend on how a sort leaves ties (`cdc_eval_topk`); `TopK`
+holds the lists, `TopK.merge` joins the lists of two passes, and `Evaluator.recommend` returns them for a loader.
+
 `eval_auc_ci` adds what an AUC needs to be judged: its DeLong standard error on this evaluation set, and for two prediction
 vectors over the same rows the difference of their AUCs with the standard error of that difference (`cdc_eval_auc_delong`);
 `Evaluator(auc_ci=True)` and `Evaluator.compare` report them.
@@ -303,6 +307,151 @@ def eval_rank(pred, label, user, n_user, domain=None, n_domain=1, ks=(10,), user
               out.data_ptr(), counts.data_ptr(), err.data_ptr(), ws.data_ptr(), nbytes), C.c_void_p(torch.cuda.current_stream().cuda_stream))
     eval_rank.last_err = err
     return Rank(out[0], out[1], out[2], out[3], out[4], counts[0], counts[1])
+
+
+TOPK_MAX_K = (1 << 31) - 1
+
+
+class TopK:
+    """The per-user top-K lists of `eval_topk` (the definitions are in include/cdcmdr.h, `cdc_eval_topk`).  G groups with at least one
+    surviving row, in ascending (domain, user) order, and E entries in all lists together:
+      domain, user  int32 [G]: the group's ids (domain is 0 throughout when the lists are over all rows by user)
+      start         int32 [G + 1]: group j's entries are start[j]:start[j + 1]; start[G] == E
+      rows          int32 [G]: the group's survivors BEFORE the cut — larger than the list's length where the list was truncated
+      row, score    int32 / f32 [E]: the input row index and its score (bit-copied), best first inside a group
+      item, label   [E] or None: the entries' item ids (when the call de-duplicated by item) and labels (`Evaluator.recommend`)
+      n_out         int64 [2] device tensor (G, E);  k: the cut;  n, n_user, n_domain: the call's sizes;  err: the device error word
+    synced: the counts were read and every tensor is sliced to G or E.  Otherwise (`eval_topk(sync=False)`) nothing was read back: the
+    tensors keep their capacity n (start: n + 1), what stands past n_out's counts is unspecified, and `dense`, `lists` and `merge`
+    are not served."""
+
+    def __init__(self, domain, user, start, rows, row, score, n_out, k, n, n_user, n_domain, item=None, label=None, err=None, synced=True):
+        self.domain, self.user, self.start, self.rows, self.row, self.score = domain, user, start, rows, row, score
+        self.n_out, self.k, self.n, self.n_user, self.n_domain = n_out, int(k), int(n), int(n_user), int(n_domain)
+        self.item, self.label, self.err, self.synced = item, label, err, bool(synced)
+
+    def _need_sync(self, what):
+        if not self.synced:
+            raise ValueError(f"TopK.{what} needs the counts: call eval_topk with sync=True")
+
+    def _group_of_entry(self):
+        """int64 [E]: the group index of every entry"""
+        start = self.start.to(torch.int64)
+        return torch.repeat_interleave(torch.arange(self.domain.numel(), device=start.device), start[1:] - start[:-1],
+                                       output_size=self.row.numel())
+
+    def dense(self, fill=-1):
+        """-> (row int32 [G, k], score f32 [G, k]): list j in line j, padded with `fill` and NaN.  k is the call's cut: ask for the
+        lists with the k the table should have."""
+        self._need_sync("dense")
+        G, dev = self.domain.numel(), self.row.device
+        row = torch.full((G, self.k), fill, dtype=torch.int32, device=dev)
+        score = torch.full((G, self.k), math.nan, dtype=torch.float32, device=dev)
+        if self.row.numel():
+            grp = self._group_of_entry()
+            pos = torch.arange(self.row.numel(), device=dev) - self.start.to(torch.int64)[grp]
+            row[grp, pos] = self.row
+            score[grp, pos] = self.score
+        return row, score
+
+    def lists(self):
+        """-> host dict {(domain, user): (rows, scores)}, two lists per group, for inspection"""
+        self._need_sync("lists")
+        dom, usr, start = self.domain.cpu().tolist(), self.user.cpu().tolist(), self.start.cpu().tolist()
+        row, score = self.row.cpu().tolist(), self.score.cpu().tolist()
+        return {(dom[j], usr[j]): (row[start[j]:start[j + 1]], score[start[j]:start[j + 1]]) for j in range(len(dom))}
+
+    @staticmethod
+    def merge(a, b, k=None, row_offset=None):
+        """The lists of two passes over disjoint row sets as one: both entry sets concatenated (a's first), b's row indices shifted by
+        `row_offset` (default a.n: b's rows follow a's), and ranked again under the same rules by one more `eval_topk` call over the
+        E_a + E_b entries.  k: the cut of the result (default min(a.k, b.k)).  For k <= min(a.k, b.k) the result's domain, user, start,
+        row, score, item and label equal those of `eval_topk` over the concatenated inputs: a row outside its pass's first k cannot
+        stand inside the first k of the union, de-duplication included (a better row of the same item is in the same list or has
+        displaced it), and an entry's place in the concatenation orders like its row index wherever the two can tie.  `rows` counts
+        the survivors among the MERGED ENTRIES — the rows a pass has cut are gone — so it equals the one-call value only for groups
+        no pass truncated.  Both need the same n_user, n_domain and either both or neither the item ids."""
+        a._need_sync("merge")
+        b._need_sync("merge")
+        if (a.n_user, a.n_domain) != (b.n_user, b.n_domain):
+            raise ValueError(f"merge: the lists are over (n_domain, n_user) = {(a.n_domain, a.n_user)} and {(b.n_domain, b.n_user)}")
+        if (a.item is None) != (b.item is None):
+            raise ValueError("merge: one side carries item ids and the other does not")
+        k = min(a.k, b.k) if k is None else int(k)
+        off = a.n if row_offset is None else int(row_offset)
+        if off < a.n or off + b.n >= 1 << 31:                   # b's rows behind a's: ties then break as over the concatenated rows
+            raise ValueError(f"merge: row_offset={off} must put b's {b.n} rows behind a's {a.n} and below 2^31")
+        n = off + b.n
+        ga, gb = a._group_of_entry(), b._group_of_entry()
+        orig = torch.cat([a.row, b.row + off])
+        if orig.numel() == 0:
+            return TopK(a.domain, a.user, a.start, a.rows, a.row, a.score, a.n_out, k, n, a.n_user, a.n_domain, a.item, a.label, a.err)
+        item = None if a.item is None else torch.cat([a.item, b.item])
+        m = eval_topk(torch.cat([a.score, b.score]), torch.cat([a.user[ga], b.user[gb]]), a.n_user,
+                      torch.cat([a.domain[ga], b.domain[gb]]), a.n_domain, item, k)
+        pos = m.row.to(torch.int64)
+        m.row, m.n = orig[pos], n
+        if a.label is not None and b.label is not None:
+            m.label = torch.cat([a.label, b.label])[pos]
+        return m
+
+
+def eval_topk(pred, user, n_user, domain=None, n_domain=1, item=None, k=10, sync=True):
+    """Per-user top-K recommendation lists: for every (domain, user) group — every user when `domain` is None — the k best-scored rows,
+    best first, no item twice.  pred f32 [n]; user, domain and item int32 [n] or strided column views (X[:, idx]) with user in
+    [0, n_user), domain in [0, n_domain) and item >= 0.  Inside a group: descending score (-0.0 ties with +0.0), equal scores by
+    ascending item id (when `item` is given), then by ascending row index; with `item`, of a group's rows with one item only the first
+    in that order survives; the first min(k, survivors) rows are the list (`cdc_eval_topk`; k in [1, 2^31 - 1], a k above every
+    group's size returns full rankings).  A row with a NaN score or an id out of range is in no list, and the error word (1 + the
+    largest such row index) is kept as `eval_topk.last_err` and as the result's `err`.
+    Returns a `TopK`.  sync=True reads the two counts once and slices every tensor to them; sync=False reads nothing back (the tensors
+    keep capacity n and `n_out` stays on the device): the call can be captured in a graph.  The same input gives the same bits."""
+    lib = L.load()
+    n_user, n_domain = int(n_user), int(n_domain)
+    if n_user <= 0 or n_domain <= 0:
+        raise ValueError(f"n_user={n_user} and n_domain={n_domain} must be positive")
+    if n_domain * n_user > 1 << 32:
+        raise ValueError(f"n_domain * n_user = {n_domain * n_user} group ids exceed 2^32, the upper half of a sort key")
+    if isinstance(k, bool) or int(k) != k or not 1 <= k <= TOPK_MAX_K:
+        raise ValueError(f"k={k!r} is no integer in [1, {TOPK_MAX_K}]")
+    k = int(k)
+    if not pred.is_cuda:
+        raise L.HipExtensionError("eval_topk needs device tensors; there is no CPU fallback")
+    pred = pred.reshape(-1).to(torch.float32).contiguous()
+    n = pred.numel()
+    user, ld_user = _id_column(user, n, "user")
+    ld_domain = ld_item = 0
+    if domain is not None:
+        domain, ld_domain = _id_column(domain, n, "domain")
+    elif n_domain != 1:
+        raise ValueError("n_domain > 1 needs the domain column")
+    if item is not None:
+        item, ld_item = _id_column(item, n, "item")
+    dev = pred.device
+    n_out = torch.empty(2, dtype=torch.int64, device=dev)
+    groups = torch.empty((3, n), dtype=torch.int32, device=dev)               # domain, user, rows
+    start = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    row = torch.empty(n, dtype=torch.int32, device=dev)
+    score = torch.empty(n, dtype=torch.float32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    nbytes = lib.cdc_eval_topk_workspace_bytes(n, n_domain, n_user, int(item is not None))
+    if nbytes <= 0:
+        raise RuntimeError(f"cdc_eval_topk_workspace_bytes refused n={n}, n_domain={n_domain}, n_user={n_user}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    L.launch("cdc_eval_topk", lib.cdc_eval_topk,
+             (pred.data_ptr(), user.data_ptr(), ld_user, n_user, None if domain is None else domain.data_ptr(), ld_domain, n_domain,
+              None if item is None else item.data_ptr(), ld_item, k, n, n_out.data_ptr(), groups[0].data_ptr(), groups[1].data_ptr(),
+              start.data_ptr(), groups[2].data_ptr(), row.data_ptr(), score.data_ptr(), err.data_ptr(), ws.data_ptr(), nbytes),
+             C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    eval_topk.last_err = err
+    if not sync:
+        # entries past E are unspecified: the gather stays inside the column whatever stands there
+        it = None if item is None else item[row.clamp(0, n - 1).to(torch.int64)]
+        return TopK(groups[0], groups[1], start, groups[2], row, score, n_out, k, n, n_user, n_domain, it, None, err, synced=False)
+    G, E = n_out.cpu().tolist()                                              # the one read
+    row = row[:E]
+    it = None if item is None else item[row.to(torch.int64)]
+    return TopK(groups[0, :G], groups[1, :G], start[:G + 1], groups[2, :G], row, score[:E], n_out, k, n, n_user, n_domain, it, None, err)
 
 
 AucCI = collections.namedtuple("AucCI", "auc var rows positives")
@@ -1127,6 +1276,11 @@ class Evaluator:
             was given, uniformly otherwise (GAUC's default is the row count).  The launch is queued with the others, before the one
             synchronisation.  Not offered: standard errors, bootstrap replicates or `compare` deltas of these figures, graded gains,
             sampled-negative protocols, MAP.
+    recommend(loader, k, item_idx, by): (a method, needs user_idx; no constructor argument, test() and compare() are untouched) the
+            per-user top-K lists themselves (`eval_topk`): one scoring pass, recalibrated like predict(), -> a `TopK` with every
+            (domain, user) group's — by="user": every user's — k best rows, best first, no item of column item_idx twice, and the
+            entries' labels.  Not offered: candidate generation (user x item pool) or a pool-scoring driver (`TopK.merge` is the hook),
+            graded relevance, diversity or business re-ranking, lists under data parallelism.
     calibration: test() adds calibration figures (`eval_calibration`; True: 10 bins, an int: that many): total_pcoc (predicted over
             observed CTR), total_brier, total_ece, total_ece_quantile, and with per-domain evaluation domain_pcoc / domain_brier /
             domain_ece / domain_ece_quantile {d: value} and mean_pcoc / mean_brier / mean_ece / mean_ece_quantile, weighted like
@@ -1214,9 +1368,32 @@ class Evaluator:
             return Recalibration.fit(pred, label, domain, n_domain, **kw)
         return PlattRecalibration.fit(pred, label, domain, n_domain, method=method, **kw)
 
-    def _score(self, data_loader, raw=False):
+    def recommend(self, data_loader, k=10, item_idx=None, by="domain"):
+        """The ranker's output: every user's k best-scored rows of `data_loader`, best first (`eval_topk`), from one scoring pass,
+        recalibrated like `predict()`.  by "domain": lists per (domain, user) (needs domain_idx); by "user": lists per user over all
+        rows.  item_idx: the column of X that holds the item id (>= 0) — a list then never repeats an item and equal scores order by
+        item id; None: every row is its own candidate.  Returns the `TopK` with `label`, the entries' labels, attached (and `item`
+        with item_idx); row indices count the rows in the order the loader yields them, as `predict()` returns them.  A NaN
+        prediction or an id out of range raises ValueError, as in `test()`."""
+        if self.user_idx is None:
+            raise ValueError("recommend needs user_idx, the column that holds a row's user: a list ranks a user's own rows")
+        if by not in ("domain", "user"):
+            raise ValueError(f"by must be 'domain' or 'user', not {by!r}")
+        if by == "domain" and self.domain_idx is None:
+            raise ValueError("by='domain' needs domain_idx, the column that holds a row's domain; by='user' ranks over all rows")
+        pred, label, domain, user, item = self._score(data_loader, with_item=True, item_idx=item_idx)
+        per_domain = by == "domain"
+        top = eval_topk(pred, user, self.n_user, domain if per_domain else None, self.n_domain if per_domain else 1, item, k)
+        bad = int(top.err.item())
+        if bad:
+            raise ValueError(f"evaluation row {bad - 1}: NaN prediction, user outside [0, {self.n_user}), domain outside "
+                             f"[0, {self.n_domain}) or negative item id")
+        top.label = label[top.row.to(torch.int64)]
+        return top
+
+    def _score(self, data_loader, raw=False, with_item=False, item_idx=None):
         """predict() and the user column: -> (pred, label, domain or None, user int32 [n] or None); with a recalibration map (and not
-        raw) pred has gone through it"""
+        raw) pred has gone through it.  with_item (recommend): a fifth entry follows, X[:, item_idx] int32 [n], None without item_idx"""
         model = self.model
         was_training = model.training
         model.eval()
@@ -1224,7 +1401,7 @@ class Evaluator:
         if self.precision is not None:
             was_precision = getattr(model, "base_model_instance", model).precision
             model.set_precision(self.precision)
-        preds, labels, domains, users = [], [], [], []
+        preds, labels, domains, users, items = [], [], [], [], []
         try:
             with torch.no_grad():
                 for batch in (self._domain_batches(*data_loader) if self.mode == "cdc" else data_loader):
@@ -1243,6 +1420,8 @@ class Evaluator:
                         domains.append(X[:, self.domain_idx].to(torch.int32))
                     if self.user_idx is not None:
                         users.append(X[:, self.user_idx].to(torch.int32))
+                    if item_idx is not None:
+                        items.append(X[:, item_idx].to(torch.int32))
         finally:
             model.train(was_training)
             if was_precision is not None and was_precision != self.precision:
@@ -1252,7 +1431,8 @@ class Evaluator:
         pred, domain = torch.cat(preds), (torch.cat(domains) if domains else None)
         if self.recalibration is not None and not raw:
             pred = self.recalibration.apply(pred, domain if self.recalibration.n_domain > 1 else None, self.recalibration_eps)
-        return pred, torch.cat(labels), domain, (torch.cat(users) if users else None)
+        out = pred, torch.cat(labels), domain, (torch.cat(users) if users else None)
+        return out + (torch.cat(items) if items else None,) if with_item else out
 
     @staticmethod
     def _domain_batches(loaders, domain_batch_seq):

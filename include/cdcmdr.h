@@ -1235,6 +1235,42 @@ int cdc_eval_rank(const float* pred, const int16_t* label, const int32_t* user, 
                   int32_t n_k, const double* discounts, int64_t n, double* out, int64_t* counts, int32_t* err_flag,
                   void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Per-user top-K LISTS: for every group the k best-scored rows, best first, no item twice — the ranking cdc_eval_rank averages over,
+ * handed back.  pred, user, ld_user, n_user, domain, ld_domain, n_domain as for cdc_eval_gauc (strided id columns; domain == NULL with
+ * n_domain == 1: all rows grouped by user).  item: NULL, or a strided int32 column (stride ld_item) of non-negative item ids.
+ *   group     a row's group is (domain, user).  One call serves one grouping: the lists over all rows by user are a second call
+ *             without the domain column.
+ *   excluded  a row is left out of every list when its score is NaN, its user lies outside [0, n_user), its domain outside
+ *             [0, n_domain), or (with item) its item id is negative.  err_flag (optional, zeroed by the caller) receives 1 + the largest
+ *             index of such a row.  No id is clamped into another user's list.
+ *   order     inside a group: DESCENDING score, -0.0 and +0.0 counting as one score; equal scores by ascending item id when item is
+ *             given; then by ascending row index.  A total order: nothing depends on how a sort leaves tied rows.
+ *   de-dup    (only with item) of a group's rows that carry the same item only the first in that order survives — the highest score,
+ *             then the lowest row index — so a list never repeats an item.
+ *   cut       the first min(k, survivors) rows of each group, 1 <= k <= 2^31 - 1; a k larger than every group returns every group's
+ *             full ranking.
+ *   outputs   device buffers of the caller with capacity n entries (group_start: n + 1); nothing is written past that capacity.
+ *             n_out[0] = G, the groups with at least one surviving row; n_out[1] = E, the entries in all lists together.
+ *             group_domain[j], group_user[j], j < G: the groups in ascending (domain, user) order.
+ *             group_start[j] .. group_start[j + 1]: group j's slice of the entry arrays; group_start[G] = E.
+ *             group_rows[j]: the group's survivors BEFORE the cut (larger than the slice: the list was truncated).
+ *             entry_row[e], e < E: the input row index, in rank order within the group; entry_score[e] = pred[entry_row[e]],
+ *             bit-copied.  What stands past G or E is unspecified.
+ * The same input gives the same bits, and with item the lists read as (domain, user, item, score) sequences do not change under a
+ * permutation of the input rows (without item, rows of equal score in a group are told apart by their index alone).  No atomic
+ * influences the order or contents of an output.  Limits: n in [1, 2^31), n_domain * n_user <= 2^32 (a group id is the upper half
+ * of a 64-bit sort key), k >= 1; CDC_E_BADARG otherwise — checked, like every argument, before anything is launched.
+ * Stream-ordered: no allocation, no synchronisation, nothing read back; the launch dimensions depend on (n, item != NULL) alone, so
+ * the call can be captured in a graph.  workspace: cdc_eval_topk_workspace_bytes(n, n_domain, n_user, item != NULL) bytes (O(n):
+ * nothing is sized by n_user), 256-byte aligned; 0 is returned for sizes the call refuses. */
+int64_t cdc_eval_topk_workspace_bytes(int64_t n, int32_t n_domain, int64_t n_user, int32_t has_item);
+int cdc_eval_topk(const float* pred, const int32_t* user, int64_t ld_user, int64_t n_user,
+                  const int32_t* domain, int64_t ld_domain, int32_t n_domain,
+                  const int32_t* item, int64_t ld_item, int32_t k, int64_t n,
+                  int64_t* n_out, int32_t* group_domain, int32_t* group_user, int32_t* group_start, int32_t* group_rows,
+                  int32_t* entry_row, float* entry_score, int32_t* err_flag,
+                  void* workspace, int64_t workspace_bytes, void* stream);
+
 /* DeLong standard errors (DeLong, DeLong & Clarke-Pearson 1988) of the AUCs cdc_eval_metrics reports, and the paired comparison of
  * two score vectors on the same rows.  pred_a, label, domain, ld_domain, n_domain as for cdc_eval_metrics; pred_b f32 [n] or NULL
  * (unpaired).  Per segment (domain 0..n_domain-1, then ALL rows) with positives x_1..x_P, negatives y_1..y_N, scores compared in
