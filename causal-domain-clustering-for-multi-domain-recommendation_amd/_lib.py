@@ -390,6 +390,9 @@ _SIGNATURES = {
     "cdc_eval_loss_ci": (c_i32, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i32, c_p, c_p, c_p, c_p, c_i64, c_p]),
     "cdc_eval_gauc_ci_workspace_bytes": (c_i64, [c_i64, c_i32, c_i64, c_i32]),
     "cdc_eval_gauc_ci": (c_i32, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_i32, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p]),
+    "cdc_eval_rank_ci_workspace_bytes": (c_i64, [c_i64, c_i32, c_i64, c_i32, c_i32, c_i32]),
+    "cdc_eval_rank_ci": (c_i32, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_i32, c_p, c_p, c_i32, c_p, c_i64, c_i32, C.c_uint64, c_p, c_p,
+                                 c_p, c_p, c_p, c_p, c_i64, c_p]),
     "cdc_eval_bootstrap_workspace_bytes": (c_i64, [c_i64, c_i32, c_i64, c_i32, c_i32]),
     "cdc_eval_bootstrap": (c_i32, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_i32, c_p, c_i64, c_i32, C.c_uint64, c_i32, c_p, c_p, c_p,
                                    c_p, c_i64, c_p]),

@@ -527,6 +527,72 @@ extern "C" int cdc_eval_gauc(const float* pred, const int16_t* label, const int3
 #define RANK_FIGS 5                     // ndcg, recall, precision, hit, mrr
 #define RANK_SLICES 256                 // a walk is a chain of dependent loads and divisions: more, shorter slices than k_gauc_sum's
 
+// one group's figures m[figure][k]: the walk above from the group's last row i (e = sc[i], first row h, P positives), shared by
+// k_rank_sum and k_rank_ci_pass so that both form a group's value with the same operations
+template <int NK>
+__device__ __forceinline__ void rank_group(const GaucScan* __restrict__ sc, const double* __restrict__ D, const int32_t (&K)[NK],
+                                           const double (&DK)[NK], int64_t k_max, int64_t i, GaucScan e, int64_t h, int64_t P,
+                                           double (&m)[RANK_FIGS][NK]) {
+    int64_t H[NK];
+    double Hf[NK], dcg[NK], hit[NK], mrr[NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) { H[k] = 0; Hf[k] = 0.0; dcg[k] = 0.0; hit[k] = 0.0; mrr[k] = 0.0; }
+    bool first = true;
+    int64_t p = i;
+    while (p >= h && i - p < k_max) {
+        const int64_t f = e.f;                                         // >= h: a group change is a key change
+        GaucScan below;
+        below.h = below.f = below.cn = 0u;
+        if (f) below = sc[f - 1];
+        const int64_t T = p - f + 1, a = i - p, b = a + T;
+        const int64_t Nt = (int64_t)(e.cn - below.cn), Pt = T - Nt;
+        if (Pt > 0) {
+            const double share = (double)Pt / (double)T;
+            const double Da = D[a], Db = D[b < k_max ? b : k_max];
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                if (a >= K[k]) continue;
+                if (b <= K[k]) {
+                    H[k] += Pt;
+                    dcg[k] += share * (Db - Da);                       // b <= K[k] <= k_max: Db is D[b]
+                } else {
+                    Hf[k] = (double)(Pt * (K[k] - a)) / (double)T;
+                    dcg[k] += share * (DK[k] - Da);
+                }
+            }
+            if (first) {
+                first = false;
+                double q = 1.0, pr = share, rr = 0.0;
+                int64_t j = 0;
+#pragma unroll
+                for (int k = 0; k < NK; ++k) {
+                    if (a >= K[k]) continue;
+                    const int64_t c = (b < K[k] ? b : K[k]) - a;
+                    const int64_t lim = c < Nt + 1 ? c : Nt + 1;
+                    for (; j < lim; ++j) {
+                        rr += pr / (double)(a + 1 + j);
+                        q *= (double)(Nt - j) / (double)(T - j);
+                        if (j < Nt) pr *= (double)(Nt - j) / (double)(T - 1 - j);
+                    }
+                    hit[k] = 1.0 - q;
+                    mrr[k] = rr;
+                }
+            }
+        }
+        e = below;
+        p = f - 1;
+    }
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        const double hh = (double)H[k] + Hf[k];
+        m[0][k] = dcg[k] / (P < K[k] ? D[P] : DK[k]);
+        m[1][k] = hh / (double)P;
+        m[2][k] = hh / (double)K[k];
+        m[3][k] = hit[k];
+        m[4][k] = mrr[k];
+    }
+}
+
 template <int NK>
 __global__ void __launch_bounds__(GAUC_THREADS) k_rank_sum(const uint64_t* __restrict__ keys, const GaucScan* __restrict__ sc,
                                                            const int64_t* __restrict__ start, const double* __restrict__ user_weight,
@@ -560,70 +626,18 @@ __global__ void __launch_bounds__(GAUC_THREADS) k_rank_sum(const uint64_t* __res
     for (int64_t i = a0 + tid; i < b0; i += GAUC_THREADS) {
         const uint64_t g = keys[i] >> 32;
         if (i + 1 < n2 && (keys[i + 1] >> 32) == g) continue;              // not the last row of its group
-        GaucScan e = sc[i];
+        const GaucScan e = sc[i];
         const int64_t h = e.h;
         const int64_t rows = i - h + 1;
         const int64_t P = rows - (int64_t)(e.cn - (h ? sc[h - 1].cn : 0u));
         if (P == 0) { ++n_out; continue; }
-        int64_t H[NK];
-        double Hf[NK], dcg[NK], hit[NK], mrr[NK];
-#pragma unroll
-        for (int k = 0; k < NK; ++k) { H[k] = 0; Hf[k] = 0.0; dcg[k] = 0.0; hit[k] = 0.0; mrr[k] = 0.0; }
-        bool first = true;
-        int64_t p = i;
-        while (p >= h && i - p < k_max) {
-            const int64_t f = e.f;                                         // >= h: a group change is a key change
-            GaucScan below;
-            below.h = below.f = below.cn = 0u;
-            if (f) below = sc[f - 1];
-            const int64_t T = p - f + 1, a = i - p, b = a + T;
-            const int64_t Nt = (int64_t)(e.cn - below.cn), Pt = T - Nt;
-            if (Pt > 0) {
-                const double share = (double)Pt / (double)T;
-                const double Da = D[a], Db = D[b < k_max ? b : k_max];
-#pragma unroll
-                for (int k = 0; k < NK; ++k) {
-                    if (a >= K[k]) continue;
-                    if (b <= K[k]) {
-                        H[k] += Pt;
-                        dcg[k] += share * (Db - Da);                       // b <= K[k] <= k_max: Db is D[b]
-                    } else {
-                        Hf[k] = (double)(Pt * (K[k] - a)) / (double)T;
-                        dcg[k] += share * (DK[k] - Da);
-                    }
-                }
-                if (first) {
-                    first = false;
-                    double q = 1.0, pr = share, rr = 0.0;
-                    int64_t j = 0;
-#pragma unroll
-                    for (int k = 0; k < NK; ++k) {
-                        if (a >= K[k]) continue;
-                        const int64_t c = (b < K[k] ? b : K[k]) - a;
-                        const int64_t lim = c < Nt + 1 ? c : Nt + 1;
-                        for (; j < lim; ++j) {
-                            rr += pr / (double)(a + 1 + j);
-                            q *= (double)(Nt - j) / (double)(T - j);
-                            if (j < Nt) pr *= (double)(Nt - j) / (double)(T - 1 - j);
-                        }
-                        hit[k] = 1.0 - q;
-                        mrr[k] = rr;
-                    }
-                }
-            }
-            e = below;
-            p = f - 1;
-        }
+        double m[RANK_FIGS][NK];
+        rank_group<NK>(sc, D, K, DK, k_max, i, e, h, P, m);
         const double w = user_weight ? user_weight[g - base] : 1.0;
 #pragma unroll
-        for (int k = 0; k < NK; ++k) {
-            const double hh = (double)H[k] + Hf[k];
-            acc[0][k] += w * (dcg[k] / (P < K[k] ? D[P] : DK[k]));
-            acc[1][k] += w * (hh / (double)P);
-            acc[2][k] += w * (hh / (double)K[k]);
-            acc[3][k] += w * hit[k];
-            acc[4][k] += w * mrr[k];
-        }
+        for (int f = 0; f < RANK_FIGS; ++f)
+#pragma unroll
+            for (int k = 0; k < NK; ++k) acc[f][k] += w * m[f][k];
         den += w;
         ++n_in;
     }
@@ -4175,6 +4189,383 @@ extern "C" int cdc_eval_calibration_bootstrap(const float* pred_a, const float* 
                            (const unsigned long long*)segoff, n_rep, seg, n_bins, out + (int64_t)v * 4 * n_rep * seg,
                            v ? (int64_t*)nullptr : counts);                 // the counts follow from the labels and weights alone
         CDC_LAUNCH_CHECK("eval_calibration_bootstrap(final)");
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// User-clustered standard errors, paired deltas and bootstrap replicates of the top-K figures.  Groups, walk and figures are
+// cdc_eval_rank's, the variance is cdc_eval_gauc_ci's linearised ratio form with clusters = users, the replicate weights are
+// cdc_eval_bootstrap's boot_weight(boot_rep_base(seed, r), user):
+//
+//   order   gauc_order() without its second scan, once per vector.  The upper key halves of the two vectors are the same multiset, so a
+//           group ends at the SAME sorted position in both orders, with the same h and cn there; of the second vector's order only its
+//           scan (the tie runs inside a group differ) is kept
+//   pass 1  k_rank_sum / k_rank_final exactly as cdc_eval_rank launches them, once per vector: M and M_b are its figures bit for bit
+//   pass 2  k_rank_ci_pass: a domain's stretch is cut into S = rank_ci_slices() slices and the "all rows" stretch — n of the 2 n
+//           positions, which the host knows — into min(n_domain S, 512), so that the slices are of one length on average; a workgroup
+//           walks its slice in chunks of
+//           CH = rank_ci_chunk() sorted positions, at most one group end per thread (paired: one half of the threads walks the first
+//           vector's order, the other half the second's, position for position).  The counted groups of a chunk are numbered in position
+//           order (ballot + wave counts) and parked in LDS: 5 n_k values per vector, the weight and the user id — at most 61 KB
+//           (n_k = 4, unpaired; CH halves above 4 cut-offs), so a CU of 160 KB holds two workgroups.  After a barrier the threads re-map:
+//             squares     (replicate tile 0 only) lane = value, wave = every fourth group: (w (m - M))^2 with M read from device memory,
+//                         paired also (w (m_b - M_b))^2 and (w ((m - m_b) - delta))^2, carried in registers across the slice's chunks
+//             replicates  lane = replicate of the workgroup's tile of RANK_CI_REP_TILE = 64: the chunk's weights are hashed once into LDS
+//                         (a byte each), then wave q adds w(seed, r, u_g) w_g m_g of the chunk's groups IN POSITION ORDER into the
+//                         columns q, q + 4, .. — (5 n_k values per vector, sum of weights) / 4 register accumulators per thread
+//           m_g does not depend on the replicate: a group is walked once per tile of 64 replicates (4 times for 200), not once per replicate
+//   final   k_rank_ci_final: the slices' squares in slice order, cdc_eval_rank's tree for sum w, the variances and the delta;
+//           k_rank_ci_rep_final: a thread per (segment, value, replicate) adds the slices' partials in slice order and divides
+// The replicate partials are [slice, column, replicate] doubles: with S = 512 / (n_domain + 1) clamped into [8, 64] that is
+// (50 * 10 + 500) * 21 * 200 * 8 = 34 MB at 50 domains, 200 replicates and 4 cut-offs (66 MB paired); RANK_SLICES = 256 slices per
+// segment would be 439 MB.
+// No per-group array, nothing indexed by a user id, no float atomics: every addition's order is a function of the sorted keys alone —
+// same rows, same bits.  The launch dimensions depend on (n, n_domain, n_k, paired, n_rep) alone.
+#define RANK_CI_REP_TILE 64
+#define RANK_CI_MAX_CELLS (1 << 20)     // n_rep * (n_domain + 1) * n_k
+#define RANK_CI_WAVES (GAUC_THREADS / 64)
+
+__host__ __device__ constexpr int rank_ci_chunk(int n_k, bool paired) { return (n_k <= 4 ? 256 : 128) / (paired ? 2 : 1); }
+static int rank_ci_slices(int32_t n_domain) {                              // per domain
+    const int s = 512 / (n_domain + 1);
+    return s < 8 ? 8 : (s > 64 ? 64 : s);
+}
+static int rank_ci_slices_all(int32_t n_domain) {                          // of the "all rows" stretch
+    const int64_t s = (int64_t)n_domain * rank_ci_slices(n_domain);
+    return (int)(s > 512 ? 512 : s);
+}
+// slice `cell` of the launch -> its (pseudo-)domain, its index there and the domain's slice count; a domain's first cell
+__device__ __forceinline__ void rank_ci_cell(int cell, int n_domain, int n_sl, int n_sl_all, int* d, int* sl, int* n) {
+    if (cell < n_domain * n_sl) { *d = cell / n_sl; *sl = cell - *d * n_sl; *n = n_sl; }
+    else { *d = n_domain; *sl = cell - n_domain * n_sl; *n = n_sl_all; }
+}
+
+template <int NK, bool PAIRED>
+__global__ void __launch_bounds__(GAUC_THREADS) k_rank_ci_pass(const uint64_t* __restrict__ keys, const GaucScan* __restrict__ sc,
+                                                               const GaucScan* __restrict__ sc_b, const int64_t* __restrict__ start,
+                                                               const double* __restrict__ user_weight, const int32_t* __restrict__ ks,
+                                                               const double* __restrict__ D, int64_t n_user, int64_t n2, int32_t n_seg,
+                                                               int32_t n_sl, int32_t n_sl_all, int32_t n_rep, uint64_t seed,
+                                                               const double* __restrict__ out,
+                                                               double* __restrict__ part_sq, double* __restrict__ part_rep,
+                                                               int64_t* __restrict__ part_rep_cnt) {
+    constexpr int NVAL = RANK_FIGS * NK, NVEC = PAIRED ? 2 : 1, NCV = NVEC * NVAL, NCOL = NCV + 1, NSQ = PAIRED ? 3 : 1;
+    constexpr int CH = rank_ci_chunk(NK, PAIRED), WPV = CH / 64, NQ = (NCOL + RANK_CI_WAVES - 1) / RANK_CI_WAVES;
+    static_assert(CH % 64 == 0 && NVEC * CH <= GAUC_THREADS && NVAL <= 64, "rank_ci chunk arithmetic");
+    __shared__ double s_v[NCV][CH + 1];                                    // the odd row length spreads a column over the banks
+    __shared__ double s_w[CH];
+    __shared__ uint32_t s_u[CH];
+    __shared__ uint8_t s_wt[CH][RANK_CI_REP_TILE];
+    __shared__ double s_sq[RANK_CI_WAVES][NSQ][NVAL];
+    __shared__ int s_wc[RANK_CI_WAVES];
+    const int tile = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int d, sl, n_sl_d;
+    rank_ci_cell(blockIdx.x, n_seg - 1, n_sl, n_sl_all, &d, &sl, &n_sl_d);
+    const int vec = tid / CH, sidx = tid % CH, wv0 = vec * WPV;
+    const bool walker = vec < NVEC;
+    const GaucScan* __restrict__ scv = PAIRED && vec == 1 ? sc_b : sc;
+    const int64_t s0 = start[d], s1 = start[d + 1];
+    const int64_t per = (s1 - s0 + n_sl_d - 1) / n_sl_d;
+    const int64_t a0 = s0 + (int64_t)sl * per, b0 = a0 + per < s1 ? a0 + per : s1;
+    const uint64_t base = (uint64_t)d * (uint64_t)n_user;
+    int32_t K[NK];
+    double DK[NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        int32_t v = ks[k];
+        v = v < 1 ? 1 : (v > RANK_MAX_K ? RANK_MAX_K : v);
+        K[k] = v;
+        DK[k] = D[v];
+    }
+    const int64_t k_max = K[NK - 1];
+    const bool squares = tile == 0 && lane < NVAL;
+    double M = 0.0, M_b = 0.0;                                             // NaN when no group is counted: then none is added
+    if (squares) {
+        M = out[(int64_t)lane * n_seg + d];
+        if constexpr (PAIRED) M_b = out[((int64_t)2 * NVAL + lane) * n_seg + d];
+    }
+    const double delta = M - M_b;
+    double qa = 0.0, qb = 0.0, qd = 0.0;
+    const uint64_t rbase = boot_rep_base(seed, (uint32_t)(tile * RANK_CI_REP_TILE + lane));
+    double acc[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) acc[q] = 0.0;
+    int64_t cnt = 0;
+    for (int64_t cb = a0; cb < b0; cb += CH) {
+        const int64_t i = cb + sidx;
+        bool counted = false;
+        GaucScan e;
+        e.h = e.f = e.cn = 0u;
+        int64_t h = 0, P = 0;
+        uint64_t g = 0;
+        if (walker && i < b0) {
+            g = keys[i] >> 32;
+            if (!(i + 1 < n2 && (keys[i + 1] >> 32) == g)) {               // the last row of its group
+                e = scv[i];
+                h = e.h;
+                P = (i - h + 1) - (int64_t)(e.cn - (h ? scv[h - 1].cn : 0u));
+                counted = P > 0;
+            }
+        }
+        const unsigned long long bal = __ballot(counted);
+        if (lane == 0) s_wc[wv] = __popcll(bal);
+        __syncthreads();
+        int ng = 0;                                                        // the chunk's counted groups: the first vector's waves
+#pragma unroll
+        for (int j = 0; j < WPV; ++j) ng += s_wc[j];
+        if (counted) {
+            int slot = __popcll(bal & ((1ull << lane) - 1ull));
+            for (int j = wv0; j < wv; ++j) slot += s_wc[j];
+            double m[RANK_FIGS][NK];
+            rank_group<NK>(scv, D, K, DK, k_max, i, e, h, P, m);
+#pragma unroll
+            for (int f = 0; f < RANK_FIGS; ++f)
+#pragma unroll
+                for (int k = 0; k < NK; ++k) s_v[vec * NVAL + f * NK + k][slot] = m[f][k];
+            if (vec == 0) {
+                s_w[slot] = user_weight ? user_weight[g - base] : 1.0;
+                s_u[slot] = (uint32_t)(g - base);
+            }
+        }
+        __syncthreads();
+        if (squares) {
+            for (int gi = wv; gi < ng; gi += RANK_CI_WAVES) {
+                const double w = s_w[gi], ma = s_v[lane][gi];
+                const double ta = w * (ma - M);
+                qa += ta * ta;
+                if constexpr (PAIRED) {
+                    const double mb = s_v[NVAL + lane][gi];
+                    const double tb = w * (mb - M_b), td = w * ((ma - mb) - delta);
+                    qb += tb * tb;
+                    qd += td * td;
+                }
+            }
+        }
+        if (n_rep > 0) {
+            for (int gi = wv; gi < ng; gi += RANK_CI_WAVES) s_wt[gi][lane] = (uint8_t)boot_weight(rbase, s_u[gi]);
+            __syncthreads();
+            for (int gi = 0; gi < ng; ++gi) {
+                const uint32_t wt = s_wt[gi][lane];
+                const double ww = (double)wt * s_w[gi];                    // a weight of 0 adds +0.0: the sums keep their bits
+                cnt += wt != 0u;
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) {
+                    const int c = wv + RANK_CI_WAVES * q;
+                    if (c < NCOL) acc[q] += ww * (c < NCV ? s_v[c < NCV ? c : 0][gi] : 1.0);
+                }
+            }
+        }
+        // no barrier here: nothing above is overwritten before the next chunk's first barrier, which every wave has to reach
+    }
+    const int64_t o = blockIdx.x;
+    if (tile == 0) {
+        if (lane < NVAL) {
+            s_sq[wv][0][lane] = qa;
+            if constexpr (PAIRED) { s_sq[wv][1][lane] = qb; s_sq[wv][2][lane] = qd; }
+        }
+        __syncthreads();
+        if (tid < NSQ * NVAL) {
+            const int s = tid / NVAL, v = tid - s * NVAL;
+            double t = s_sq[0][s][v];
+            for (int w = 1; w < RANK_CI_WAVES; ++w) t += s_sq[w][s][v];
+            part_sq[(o * NSQ + s) * NVAL + v] = t;
+        }
+    }
+    const int r = tile * RANK_CI_REP_TILE + lane;
+    if (r < n_rep) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int c = wv + RANK_CI_WAVES * q;
+            if (c < NCOL) part_rep[(o * NCOL + c) * n_rep + r] = acc[q];
+        }
+        if (wv == 0) part_rep_cnt[o * n_rep + r] = cnt;
+    }
+}
+
+// workgroup d: sum w by k_rank_final's tree over k_rank_sum's slices, the squares in slice order; out [n_stat, 5, n_k, n_seg] with the
+// figures (stat 0, paired also 2) in place: var (1), paired also var_b (3), delta (4), var_delta (5)
+__global__ void __launch_bounds__(RANK_SLICES) k_rank_ci_final(const double* __restrict__ part, const int64_t* __restrict__ counts,
+                                                               const double* __restrict__ part_sq, int32_t n_k, int32_t n_seg,
+                                                               int32_t n_sl, int32_t n_sl_all, int32_t paired, double* __restrict__ out) {
+    __shared__ double s_v[RANK_SLICES];
+    const int d = blockIdx.x, tid = threadIdx.x;
+    const int nval = RANK_FIGS * n_k, nsq = paired ? 3 : 1;
+    s_v[tid] = part[((int64_t)d * RANK_SLICES + tid) * (nval + 1) + nval];
+    __syncthreads();
+    for (int off = RANK_SLICES / 2; off > 0; off >>= 1) {
+        if (tid < off) s_v[tid] += s_v[tid + off];
+        __syncthreads();
+    }
+    if (tid >= nsq * nval) return;
+    const int s = tid / nval, v = tid - s * nval;
+    const int64_t G = counts[d];
+    const double den = s_v[0];
+    const int64_t c0 = (int64_t)d * n_sl, c1 = c0 + (d < n_seg - 1 ? n_sl : n_sl_all);       // the segment's cells
+    double sq = 0.0;
+    for (int64_t c = c0; c < c1; ++c) sq += part_sq[(c * nsq + s) * nval + v];
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const double scale = G >= 2 ? (double)G / (double)(G - 1) / (den * den) : nan;
+    out[((int64_t)(2 * s + 1) * nval + v) * n_seg + d] = G >= 2 ? scale * sq : nan;
+    if (s == 2)                                                             // NaN - NaN when no group is counted
+        out[((int64_t)4 * nval + v) * n_seg + d] = out[(int64_t)v * n_seg + d] - out[((int64_t)2 * nval + v) * n_seg + d];
+}
+
+// a thread per (segment, vector and value, replicate): reps [n_vec, n_rep, 5 n_k, n_seg], rep_counts [n_rep, n_seg]
+__global__ void __launch_bounds__(GAUC_THREADS) k_rank_ci_rep_final(const double* __restrict__ part_rep,
+                                                                    const int64_t* __restrict__ part_rep_cnt, int32_t n_k, int32_t n_vec,
+                                                                    int32_t n_seg, int32_t n_sl, int32_t n_sl_all, int32_t n_rep,
+                                                                    double* __restrict__ reps,
+                                                                    int64_t* __restrict__ rep_counts) {
+    const int nval = RANK_FIGS * n_k, ncv = n_vec * nval, ncol = ncv + 1;
+    const int64_t id = (int64_t)blockIdx.x * GAUC_THREADS + threadIdx.x;
+    const int64_t r = id % n_rep, c = (id / n_rep) % ncv, d = id / ((int64_t)n_rep * ncv);
+    if (d >= n_seg) return;
+    double num = 0.0, den = 0.0;
+    int64_t cnt = 0;
+    const int64_t c0 = d * n_sl, c1 = c0 + (d < n_seg - 1 ? n_sl : n_sl_all);                  // the segment's cells
+    for (int64_t o = c0; o < c1; ++o) {
+        num += part_rep[(o * ncol + c) * n_rep + r];
+        den += part_rep[(o * ncol + ncv) * n_rep + r];
+        cnt += part_rep_cnt[o * n_rep + r];
+    }
+    const int64_t vec = c / nval, v = c - vec * nval;
+    reps[((vec * n_rep + r) * nval + v) * n_seg + d] = cnt > 0 ? num / den : __longlong_as_double(0x7ff8000000000000ll);
+    if (c == 0 && rep_counts) rep_counts[r * n_seg + d] = cnt;
+}
+
+struct RankCiLayout {
+    RankLayout r;                       // cdc_eval_rank's arrays; r.g.temp / r.total lie behind the ones below
+    int64_t scan_b, part_b, part_cnt_b, counts_b, part_sq, part_rep, part_rep_cnt;
+};
+static void rank_ci_fixed_layout(int64_t n, int32_t n_domain, int32_t n_k, int32_t paired, int32_t n_rep, RankCiLayout* L) {
+    const int64_t n2 = 2 * n, seg = (int64_t)n_domain + 1, nval = RANK_FIGS * n_k, ncol = (paired ? 2 : 1) * nval + 1;
+    const int64_t cells = (int64_t)n_domain * rank_ci_slices(n_domain) + rank_ci_slices_all(n_domain);
+    rank_fixed_layout(n, n_domain, n_k, &L->r);
+    int64_t off = L->r.g.temp;
+    L->scan_b = off;       off += paired ? align_up(n2 * (int64_t)sizeof(GaucScan)) : 0;
+    L->part_b = off;       off += paired ? align_up(seg * RANK_SLICES * (nval + 1) * 8) : 0;
+    L->part_cnt_b = off;   off += paired ? align_up(seg * RANK_SLICES * 2 * 8) : 0;
+    L->counts_b = off;     off += paired ? align_up(seg * 2 * 8) : 0;
+    L->part_sq = off;      off += align_up(cells * (paired ? 3 : 1) * nval * 8);
+    L->part_rep = off;     off += align_up(cells * ncol * n_rep * 8);
+    L->part_rep_cnt = off; off += align_up(cells * n_rep * 8);
+    L->r.g.temp = off;
+    L->r.total = off;
+}
+static int rank_ci_layout(int64_t n, int32_t n_domain, int32_t n_k, int32_t paired, int32_t n_rep, RankCiLayout* L) {
+    rank_ci_fixed_layout(n, n_domain, n_k, paired, n_rep, L);
+    const int rc = gauc_temp_bytes(n, "eval_rank_ci", &L->r.g.temp_bytes);
+    if (rc != 0) return rc;
+    L->r.total = L->r.g.temp + align_up(L->r.g.temp_bytes);
+    return 0;
+}
+static bool rank_ci_sizes_ok(int64_t n, int32_t n_domain, int64_t n_user, int32_t n_k, int32_t n_rep) {
+    return gauc_sizes_ok(n, n_domain, n_user) && n_k >= 1 && n_k <= RANK_MAX_NK && n_rep >= 0 && n_rep <= BOOT_MAX_REP &&
+           (int64_t)n_rep * ((int64_t)n_domain + 1) * n_k <= RANK_CI_MAX_CELLS;
+}
+
+extern "C" int64_t cdc_eval_rank_ci_workspace_bytes(int64_t n, int32_t n_domain, int64_t n_user, int32_t n_k, int32_t paired,
+                                                    int32_t n_rep) {
+    if (!rank_ci_sizes_ok(n, n_domain, n_user, n_k, n_rep)) return 0;
+    RankCiLayout L;
+    if (rank_ci_layout(n, n_domain, n_k, paired != 0, n_rep, &L) != 0) return -1;
+    return L.r.total;
+}
+
+template <int NK>
+static void rank_ci_pass_launch(bool paired, dim3 grid, hipStream_t st, const uint64_t* keys, const GaucScan* sc, const GaucScan* sc_b,
+                                const int64_t* start, const double* user_weight, const int32_t* ks, const double* D, int64_t n_user,
+                                int64_t n2, int32_t n_seg, int32_t n_sl, int32_t n_sl_all, int32_t n_rep, uint64_t seed, const double* out,
+                                double* part_sq, double* part_rep, int64_t* part_rep_cnt) {
+    if (paired)
+        hipLaunchKernelGGL((k_rank_ci_pass<NK, true>), grid, dim3(GAUC_THREADS), 0, st, keys, sc, sc_b, start, user_weight, ks, D, n_user,
+                           n2, n_seg, n_sl, n_sl_all, n_rep, seed, out, part_sq, part_rep, part_rep_cnt);
+    else
+        hipLaunchKernelGGL((k_rank_ci_pass<NK, false>), grid, dim3(GAUC_THREADS), 0, st, keys, sc, sc_b, start, user_weight, ks, D, n_user,
+                           n2, n_seg, n_sl, n_sl_all, n_rep, seed, out, part_sq, part_rep, part_rep_cnt);
+}
+
+extern "C" int cdc_eval_rank_ci(const float* pred_a, const float* pred_b, const int16_t* label, const int32_t* user, int64_t ld_user,
+                                int64_t n_user, const int32_t* domain, int64_t ld_domain, int32_t n_domain, const double* user_weight,
+                                const int32_t* ks, int32_t n_k, const double* discounts, int64_t n, int32_t n_rep, uint64_t seed,
+                                double* out, double* reps, int64_t* counts, int64_t* rep_counts, int32_t* err_flag, void* workspace,
+                                int64_t workspace_bytes, void* stream) {
+    CDC_CHECK_ARG(pred_a && label && user && ks && discounts && out && counts && workspace, CDC_E_BADARG, "eval_rank_ci: null pointer");
+    CDC_CHECK_ARG(n > 0 && n_domain > 0 && n_domain < (1 << 20) && n_user > 0 && ld_user >= 0 && ld_domain >= 0, CDC_E_BADARG,
+                  "eval_rank_ci: bad sizes n=%ld n_domain=%d n_user=%ld", (long)n, n_domain, (long)n_user);
+    CDC_CHECK_ARG(n_k >= 1 && n_k <= RANK_MAX_NK, CDC_E_BADARG, "eval_rank_ci: n_k=%d cut-offs, 1 to %d are served", n_k, RANK_MAX_NK);
+    CDC_CHECK_ARG(n_rep >= 0 && n_rep <= BOOT_MAX_REP, CDC_E_BADARG, "eval_rank_ci: n_rep=%d outside [0, %d]", n_rep, BOOT_MAX_REP);
+    CDC_CHECK_ARG(n_rep == 0 || reps, CDC_E_BADARG, "eval_rank_ci: n_rep=%d needs the replicate array", n_rep);
+    CDC_CHECK_ARG(n_rep > 0 || !reps, CDC_E_BADARG, "eval_rank_ci: a replicate array without replicates");
+    CDC_CHECK_ARG((int64_t)n_rep * ((int64_t)n_domain + 1) * n_k <= RANK_CI_MAX_CELLS, CDC_E_BADARG,
+                  "eval_rank_ci: n_rep * (n_domain + 1) * n_k = %ld cells exceed %d", (long)((int64_t)n_rep * ((int64_t)n_domain + 1) * n_k),
+                  RANK_CI_MAX_CELLS);
+    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_rank_ci: n_domain=%d needs the domain column", n_domain);
+    CDC_CHECK_ARG(n < (1ll << 31), CDC_E_TOOBIG, "eval_rank_ci: n=%ld exceeds the 2^31 rows a sorted position counts in 32 bits", (long)n);
+    CDC_CHECK_ARG(gauc_sizes_ok(n, n_domain, n_user), CDC_E_BADARG,
+                  "eval_rank_ci: (n_domain + 1) * n_user = %ld * %ld group ids exceed 2^32", (long)n_domain + 1, (long)n_user);
+    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_rank_ci: workspace must be 256-byte aligned");
+    const int32_t paired = pred_b != nullptr;
+    RankCiLayout L;
+    rank_ci_fixed_layout(n, n_domain, n_k, paired, n_rep, &L);
+    CDC_CHECK_ARG(workspace_bytes >= L.r.total, CDC_E_BADARG, "eval_rank_ci: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.r.total);
+    int rc = rank_ci_layout(n, n_domain, n_k, paired, n_rep, &L);
+    if (rc != 0) return rc;
+    CDC_CHECK_ARG(workspace_bytes >= L.r.total, CDC_E_BADARG, "eval_rank_ci: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.r.total);
+    char* base = (char*)workspace;
+    const uint64_t* keys = (const uint64_t*)(base + L.r.g.keys_out);
+    const GaucScan* sc = (const GaucScan*)(base + L.r.g.scan);
+    const GaucScan* sc_b = (const GaucScan*)(base + L.scan_b);
+    const int64_t* start = (const int64_t*)(base + L.r.g.start);
+    double* part = (double*)(base + L.r.part);
+    int64_t* part_cnt = (int64_t*)(base + L.r.part_cnt);
+    double* part_b = (double*)(base + L.part_b);
+    int64_t* part_cnt_b = (int64_t*)(base + L.part_cnt_b);
+    int64_t* counts_b = (int64_t*)(base + L.counts_b);
+    double* part_sq = (double*)(base + L.part_sq);
+    double* part_rep = (double*)(base + L.part_rep);
+    int64_t* part_rep_cnt = (int64_t*)(base + L.part_rep_cnt);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n2 = 2 * n;
+    const int seg = n_domain + 1, nval = RANK_FIGS * n_k, n_sl = rank_ci_slices(n_domain), n_sl_all = rank_ci_slices_all(n_domain);
+    const int ntiles = n_rep > 0 ? (n_rep + RANK_CI_REP_TILE - 1) / RANK_CI_REP_TILE : 1;
+    if (paired) {                                                   // the second vector first: of its order only the scan stays
+        GaucLayout Lb = L.r.g;
+        Lb.scan = L.scan_b;
+        rc = gauc_order(pred_b, label, user, ld_user, n_user, domain, ld_domain, n_domain, n, err_flag, base, Lb, nullptr, "eval_rank_ci", st);
+        if (rc != 0) return rc;
+    }
+    rc = gauc_order(pred_a, label, user, ld_user, n_user, domain, ld_domain, n_domain, n, err_flag, base, L.r.g, nullptr, "eval_rank_ci", st);
+    if (rc != 0) return rc;
+    for (int v = 0; v <= paired; ++v) {                             // the counts follow from the labels alone: the second set is dropped
+        switch (n_k) {
+#define RANK_CASE(NK) case NK: rank_sum_launch<NK>(seg, st, keys, v ? sc_b : sc, start, user_weight, ks, discounts, n_user, n2, \
+                                                   v ? part_b : part, v ? part_cnt_b : part_cnt); break;
+            RANK_CASE(1) RANK_CASE(2) RANK_CASE(3) RANK_CASE(4) RANK_CASE(5) RANK_CASE(6) RANK_CASE(7) RANK_CASE(8)
+#undef RANK_CASE
+        }
+        CDC_LAUNCH_CHECK("eval_rank_ci(sum)");
+        hipLaunchKernelGGL(k_rank_final, dim3(seg), dim3(RANK_SLICES), 0, st, (const double*)(v ? part_b : part),
+                           (const int64_t*)(v ? part_cnt_b : part_cnt), n_k, seg, out + (int64_t)v * 2 * nval * seg, v ? counts_b : counts);
+        CDC_LAUNCH_CHECK("eval_rank_ci(final)");
+    }
+    const dim3 grid(n_domain * n_sl + n_sl_all, ntiles);
+    switch (n_k) {
+#define RANK_CASE(NK) case NK: rank_ci_pass_launch<NK>(paired, grid, st, keys, sc, sc_b, start, user_weight, ks, discounts, n_user, n2, seg, \
+                                                       n_sl, n_sl_all, n_rep, seed, (const double*)out, part_sq, part_rep, part_rep_cnt); break;
+        RANK_CASE(1) RANK_CASE(2) RANK_CASE(3) RANK_CASE(4) RANK_CASE(5) RANK_CASE(6) RANK_CASE(7) RANK_CASE(8)
+#undef RANK_CASE
+    }
+    CDC_LAUNCH_CHECK("eval_rank_ci(pass)");
+    hipLaunchKernelGGL(k_rank_ci_final, dim3(seg), dim3(RANK_SLICES), 0, st, (const double*)part, (const int64_t*)counts,
+                       (const double*)part_sq, n_k, seg, n_sl, n_sl_all, paired, out);
+    CDC_LAUNCH_CHECK("eval_rank_ci(variances)");
+    if (n_rep > 0) {
+        const int64_t items = (int64_t)seg * (paired ? 2 : 1) * nval * n_rep;
+        hipLaunchKernelGGL(k_rank_ci_rep_final, dim3((unsigned)cdc_ceil_div(items, GAUC_THREADS)), dim3(GAUC_THREADS), 0, st,
+                           (const double*)part_rep, (const int64_t*)part_rep_cnt, n_k, paired ? 2 : 1, seg, n_sl, n_sl_all, n_rep, reps, rep_counts);
+        CDC_LAUNCH_CHECK("eval_rank_ci(replicates)");
     }
     return 0;
 }

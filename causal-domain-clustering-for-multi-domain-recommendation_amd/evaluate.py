@@ -14,6 +14,8 @@ C-ABI call (`cdc_eval_gauc`) on the same device-resident predictions.
 `eval_rank` answers what stands at the top of each user's list: NDCG@K, Recall@K, Precision@K, HitRate@K and MRR@K per user, averaged
 per domain and over all rows, every figure the expectation over the order of tied scores (`cdc_eval_rank`, on GAUC's sort and first
 scan); `Evaluator(rank_at=(1, 10))` reports them and `Runner(select_by="mean_ndcg@10")` selects by one.
+`eval_rank_ci` adds their user-clustered standard errors, the paired delta of two prediction vectors and bootstrap replicates under
+`eval_bootstrap`'s user weights (`cdc_eval_rank_ci`); `Evaluator(rank_ci=True)` and `Evaluator.compare` report them.
 
 `eval_topk` hands the ranking itself back: for every user, per domain or over all rows, the K best-scored rows, best first, no item
 twice, under a total order (score, item id, row index) that does not depend on how a sort leaves ties (`cdc_eval_topk`); `TopK`
@@ -721,6 +723,91 @@ def eval_bootstrap(pred, label, cluster=None, n_cluster=None, domain=None, n_dom
                      out[k + 1] if paired else None, out[k + 2] if paired and gauc else None)
 
 
+RankCI = collections.namedtuple("RankCI", "ndcg recall precision hit mrr var counted left_out reps reps_b rep_counted")
+RankCIPaired = collections.namedtuple("RankCIPaired", "ndcg recall precision hit mrr var counted left_out fig_b var_b delta var_delta "
+                                                      "reps reps_b rep_counted")
+RANK_CI_MAX_CELLS = 1 << 20     # csrc/metrics.hip RANK_CI_MAX_CELLS: n_rep * (n_domain + 1) * len(ks)
+
+
+def eval_rank_ci(pred, label, user, n_user, domain=None, n_domain=1, ks=(10,), user_weight=None, pred_b=None, n_rep=0, seed=0):
+    """`eval_rank`'s figures with their user-clustered variances, the paired comparison of two prediction vectors and bootstrap
+    replicates (`cdc_eval_rank_ci`).  Inputs, groups, ties and figures as `eval_rank`; `pred_b`, `n_rep` and `seed` as `eval_gauc_ci` and
+    `eval_bootstrap`.  The sampling unit is the user: over a segment's G counted groups with weight w_g and value m_g,
+    `var` = G / (G - 1) * sum (w_g (m_g - M))^2 / (sum w_g)^2, the linearised variance of the ratio M = sum w m / sum w.
+    Returns a namedtuple of device tensors: `ndcg`, `recall`, `precision`, `hit`, `mrr` f64 [len(ks), n_domain + 1] — `eval_rank`'s
+    figures bit for bit — `var` f64 [5, len(ks), n_domain + 1] in that order of figures, `counted`, `left_out` i64 [n_domain + 1].
+    With `pred_b` also `fig_b`, `var_b`, `delta` = figure - fig_b and `var_delta`, the variance of the PAIRED difference (the same
+    formula on the users' differences), each [5, len(ks), n_domain + 1]; identical vectors give delta = 0 and var_delta = 0 exactly.
+    With `n_rep` >= 1: `reps` (and `reps_b`) f64 [n_rep, 5, len(ks), n_domain + 1], replicate r under the user weights of replicate r
+    of `eval_bootstrap(seed=seed)`, NaN where no counted user has a positive weight, and `rep_counted` i64 [n_rep, n_domain + 1], the
+    counted users with one; a delta's replicates are `reps - reps_b`.  Otherwise these three are None.  A figure or delta is NaN where
+    no group is counted, a variance where fewer than two are.  The same rows in any order give the same bits.  n_rep in [0, 4096] and
+    n_rep * (n_domain + 1) * len(ks) <= 2^20.  No host synchronisation; the error word (as `eval_rank`'s, over both vectors) is kept
+    as `eval_rank_ci.last_err`."""
+    lib = L.load()
+    n_user, n_domain, n_rep, seed = int(n_user), int(n_domain), int(n_rep), int(seed)
+    if n_user <= 0 or n_domain <= 0:
+        raise ValueError(f"n_user={n_user} and n_domain={n_domain} must be positive")
+    if (n_domain + 1) * n_user > 1 << 32:
+        raise ValueError(f"(n_domain + 1) * n_user = {(n_domain + 1) * n_user} group ids exceed 2^32, the upper half of a sort key")
+    ks = _rank_ks(ks)
+    if not 0 <= n_rep <= BOOT_MAX_REP:
+        raise ValueError(f"n_rep={n_rep} must lie in [0, {BOOT_MAX_REP}]")
+    if n_rep * (n_domain + 1) * len(ks) > RANK_CI_MAX_CELLS:
+        raise ValueError(f"n_rep * (n_domain + 1) * len(ks) = {n_rep * (n_domain + 1) * len(ks)} cells exceed {RANK_CI_MAX_CELLS}")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed={seed} must fit 64 unsigned bits")
+    if not pred.is_cuda:
+        raise L.HipExtensionError("eval_rank_ci needs device tensors; there is no CPU fallback")
+    pred = pred.reshape(-1).to(torch.float32).contiguous()
+    label = label.reshape(-1).to(torch.int16).contiguous()
+    n = pred.numel()
+    if label.numel() != n:
+        raise ValueError(f"{n} predictions but {label.numel()} labels")
+    if pred_b is not None:
+        pred_b = pred_b.reshape(-1).to(device=pred.device, dtype=torch.float32).contiguous()
+        if pred_b.numel() != n:
+            raise ValueError(f"{n} predictions but {pred_b.numel()} in pred_b")
+    user, ld_user = _id_column(user, n, "user")
+    ld_domain = 0
+    if domain is not None:
+        domain, ld_domain = _id_column(domain, n, "domain")
+    elif n_domain != 1:
+        raise ValueError("n_domain > 1 needs the domain column")
+    dev = pred.device
+    if user_weight is not None:
+        user_weight = torch.as_tensor(user_weight, dtype=torch.float64).to(dev).reshape(-1).contiguous()
+        if user_weight.numel() != n_user:
+            raise ValueError(f"user_weight holds {user_weight.numel()} entries for {n_user} users")
+    key = ("ks", str(dev), ks)
+    if key not in _rank_tables:
+        _rank_tables[key] = torch.tensor(ks, dtype=torch.int32, pin_memory=True).to(dev, non_blocking=True)
+    ks_dev, disc = _rank_tables[key], rank_discounts(ks[-1], dev)
+    seg, n_k, n_fig = n_domain + 1, len(ks), len(RANK_FIGURES)
+    paired = pred_b is not None
+    out = torch.empty((6 if paired else 2, n_fig, n_k, seg), dtype=torch.float64, device=dev)
+    counts = torch.empty((2, seg), dtype=torch.int64, device=dev)
+    reps = torch.empty((2 if paired else 1, n_rep, n_fig, n_k, seg), dtype=torch.float64, device=dev) if n_rep else None
+    rep_counts = torch.empty((n_rep, seg), dtype=torch.int64, device=dev) if n_rep else None
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    nbytes = lib.cdc_eval_rank_ci_workspace_bytes(n, n_domain, n_user, n_k, int(paired), n_rep)
+    if nbytes <= 0:
+        raise RuntimeError(f"cdc_eval_rank_ci_workspace_bytes refused n={n}, n_domain={n_domain}, n_user={n_user}, n_k={n_k}, n_rep={n_rep}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    L.launch("cdc_eval_rank_ci", lib.cdc_eval_rank_ci,
+             (pred.data_ptr(), pred_b.data_ptr() if paired else None, label.data_ptr(), user.data_ptr(), ld_user, n_user,
+              None if domain is None else domain.data_ptr(), ld_domain, n_domain, None if user_weight is None else user_weight.data_ptr(),
+              ks_dev.data_ptr(), n_k, disc.data_ptr(), n, n_rep, seed, out.data_ptr(), reps.data_ptr() if n_rep else None,
+              counts.data_ptr(), rep_counts.data_ptr() if n_rep else None, err.data_ptr(), ws.data_ptr(), nbytes),
+             C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    eval_rank_ci.last_err = err
+    fig = out[0]
+    tail = (reps[0] if n_rep else None, reps[1] if n_rep and paired else None, rep_counts)
+    if paired:
+        return RankCIPaired(fig[0], fig[1], fig[2], fig[3], fig[4], out[1], counts[0], counts[1], out[2], out[3], out[4], out[5], *tail)
+    return RankCI(fig[0], fig[1], fig[2], fig[3], fig[4], out[1], counts[0], counts[1], *tail)
+
+
 def summarize_bootstrap(reps, level=0.95):
     """reps: a tensor [n_rep, ...] of bootstrap replicates (any device) -> (se, lo, hi, valid), each of reps' shape without its first
     axis, on the same device: `se` the standard deviation (ddof 1) over the non-NaN replicates, `lo` / `hi` the percentile interval
@@ -1274,8 +1361,17 @@ class Evaluator:
             {d: value} and mean_<fig>@<K>, weighted like mean_gauc (NaN when a present domain counts no user), and total_rank_users
             (+ domain_rank_users): the users with at least one positive, over whom the figures are averaged — with user_weight when one
             was given, uniformly otherwise (GAUC's default is the row count).  The launch is queued with the others, before the one
-            synchronisation.  Not offered: standard errors, bootstrap replicates or `compare` deltas of these figures, graded gains,
+            synchronisation.  Standard errors, bootstrap intervals and `compare` deltas come with `rank_ci`.  Not offered: graded gains,
             sampled-negative protocols, MAP.
+    rank_ci: (needs rank_at, and hence user_idx; ValueError otherwise) the user-clustered standard errors of the top-K figures
+            (`eval_rank_ci`, one call in place of `eval_rank`'s: the total_/domain_/mean_<fig>@<K> keys keep their bits).  test() adds
+            total_<fig>@<K>_se and with per-domain evaluation domain_<fig>@<K>_se {d: value}; no mean_<fig>@<K>_se, for mean_gauc_se's
+            reason: a user's rows span domains.  With bootstrap also total_/domain_/mean_<fig>@<K>_boot_se/lo/hi from the same call's
+            replicates (the evaluator's replicate count, seed and level; the mean formed per replicate under mean_<fig>@<K>'s weights);
+            boot_valid covers them.  compare() adds total_<fig>@<K>_delta, _delta_se and _z and the domain_ forms, and with bootstrap
+            the *_delta_boot_se/lo/hi forms, mean_<fig>@<K>_delta, mean_<fig>@<K>_delta_boot_* and mean_<fig>@<K>_z = delta / boot_se —
+            then both passes must see the same user column.  Without it every result dictionary and every launch is exactly as
+            before.  Not offered: BCa or studentised intervals, significance-aware early stopping in `Runner`.
     recommend(loader, k, item_idx, by): (a method, needs user_idx; no constructor argument, test() and compare() are untouched) the
             per-user top-K lists themselves (`eval_topk`): one scoring pass, recalibrated like predict(), -> a `TopK` with every
             (domain, user) group's — by="user": every user's — k best rows, best first, no item of column item_idx twice, and the
@@ -1307,11 +1403,14 @@ class Evaluator:
     def __init__(self, model, mode="multi", domain_idx=None, n_domain=1, domain_cnt_weight=None, is_evaluate_multi_domain=True,
                  user_idx=None, n_user=None, user_weight=None, auc_ci=False, precision=None, calibration=False, recalibration=None,
                  recalibration_eps=0.0, loss_ci=False, gauc_ci=False, bootstrap=None, bootstrap_seed=0, bootstrap_level=0.95,
-                 calibration_ci=False, rank_at=None):
+                 calibration_ci=False, rank_at=None, rank_ci=False):
         self.model, self.mode = model, mode
         self.rank_at = None if rank_at is None else _rank_ks(rank_at)
         if self.rank_at is not None and user_idx is None:
             raise ValueError("rank_at needs user_idx, the column that holds a row's user: the top-K figures rank every user's own rows")
+        self.rank_ci = bool(rank_ci)
+        if self.rank_ci and self.rank_at is None:
+            raise ValueError("rank_ci needs rank_at, the cut-offs of the top-K figures (and user_idx): it reports their standard errors")
         self.bootstrap = 0 if bootstrap is None else int(bootstrap)         # 0: off
         if bootstrap is not None and (isinstance(bootstrap, bool) or not 1 <= self.bootstrap <= BOOT_MAX_REP):
             raise ValueError(f"bootstrap must be None or a number of replicates in [1, {BOOT_MAX_REP}], not {bootstrap!r}")
@@ -1458,13 +1557,17 @@ class Evaluator:
         share users and are not independent); with bootstrap also total_*_boot_se/lo/hi, domain_*_boot_*, mean_*_boot_* for auc, loss
         and (with user_idx) gauc, and boot_valid; with calibration_ci the same *_boot_* keys for pcoc, brier, ece and ece_quantile;
         with rank_at also total_<fig>@<K> (+ domain_<fig>@<K>, mean_<fig>@<K>) for ndcg, recall, precision, hit, mrr and
-        total_rank_users (+ domain_rank_users)."""
+        total_rank_users (+ domain_rank_users); with rank_ci also total_<fig>@<K>_se (+ domain_<fig>@<K>_se) and, with bootstrap,
+        the total_/domain_/mean_<fig>@<K>_boot_* keys."""
         pred, label, domain, user = self._score(data_loader)
         multi = self.is_evaluate_multi_domain
         auc, loss, rows, pos = eval_metrics(pred, label, domain if multi else None, self.n_domain if multi else 1)
         if user is not None:                                   # queued behind the metrics: still nothing has been read back
             gauc = eval_gauc(pred, label, user, self.n_user, domain if multi else None, self.n_domain if multi else 1, self.user_weight)[0]
-        if self.rank_at is not None:                           # likewise queued
+        if self.rank_ci:                                       # likewise queued: eval_rank's figures bit for bit, variances, replicates
+            rank = eval_rank_ci(pred, label, user, self.n_user, domain if multi else None, self.n_domain if multi else 1, self.rank_at,
+                                self.user_weight, n_rep=self.bootstrap, seed=self.bootstrap_seed)
+        elif self.rank_at is not None:                         # likewise queued
             rank = eval_rank(pred, label, user, self.n_user, domain if multi else None, self.n_domain if multi else 1, self.rank_at,
                              self.user_weight)
         if self.auc_ci:                                        # likewise queued
@@ -1484,6 +1587,8 @@ class Evaluator:
             if self.calibration_ci:                            # likewise queued: the same weights over the calibration figures
                 cb = self._calibration_bootstrap(pred, label, domain, user, multi)
                 stats.update({"pcoc": cb.pcoc, "brier": cb.brier, "ece": cb.ece, "ece_quantile": cb.ece_q})
+            if self.rank_ci:
+                stats.update(self._rank_stats(rank.reps))
             boot_sum = self._boot_summary(stats, rows, multi)
         auc, loss, rows, pos = auc.cpu().tolist(), loss.cpu().tolist(), rows.cpu().tolist(), pos.cpu().tolist()   # the one sync
         bad = int(eval_metrics.last_err.item())
@@ -1525,6 +1630,12 @@ class Evaluator:
             result["total_rank_users"] = counted[-1]
             if multi:
                 result["domain_rank_users"] = {d: counted[d] for d in present}
+        if self.rank_ci:
+            for fig, per_k in zip(RANK_FIGURES, rank.var.cpu().tolist()):
+                for K, v in zip(self.rank_at, per_k):
+                    result[f"total_{fig}@{K}_se"] = _se(v[-1])
+                    if multi:
+                        result[f"domain_{fig}@{K}_se"] = {d: _se(v[d]) for d in present}
         if self.auc_ci:
             var = ci_var.cpu().tolist()
             result["total_auc_se"] = _se(var[-1])
@@ -1567,6 +1678,10 @@ class Evaluator:
         return eval_bootstrap(pred, label, user, self.n_user if user is not None else None, domain if multi else None,
                               self.n_domain if multi else 1, self.bootstrap, self.bootstrap_seed,
                               self.user_weight if user is not None else None, gauc=gauc, pred_b=pred_b)
+
+    def _rank_stats(self, reps, suffix=""):
+        """replicates [n_rep, 5, len(rank_at), seg] -> {"<fig>@<K><suffix>": [n_rep, seg]} in `_boot_summary`'s form"""
+        return {f"{fig}@{K}{suffix}": reps[:, f, k] for f, fig in enumerate(RANK_FIGURES) for k, K in enumerate(self.rank_at)}
 
     def _calibration_bootstrap(self, pred, label, domain, user, multi, pred_b=None):
         """the calibration figures' replicates under `_bootstrap`'s clusters, replicate count and seed, over the evaluator's bins"""
@@ -1650,15 +1765,18 @@ class Evaluator:
         (mean_gauc_delta_boot_* included), and boot_valid: the replicates weight both models' rows alike; with user_idx the users are
         resampled and both passes must see the same user column.  With calibration_ci, for fig in pcoc, brier, ece, ece_quantile:
         total_<fig>_delta (figure(self) - figure(other), from two `eval_calibration` calls), total_<fig>_delta_boot_se/lo/hi,
-        total_<fig>_z = delta / boot_se by the rules above, and the domain_ and mean_ forms."""
+        total_<fig>_z = delta / boot_se by the rules above, and the domain_ and mean_ forms.  With rank_ci, for fig in ndcg, recall,
+        precision, hit, mrr and every K of rank_at: total_<fig>@<K>_delta, _delta_se and _z (+ the domain_ forms) from one paired
+        `eval_rank_ci` call, and with bootstrap the *_delta_boot_* forms, mean_<fig>@<K>_delta and mean_<fig>@<K>_z = delta / boot_se;
+        both passes must then see the same user column."""
         pred_a, label, domain, user = self._score(data_loader)
         pred_b, label_b, domain_b, user_b = other._score(data_loader)
         if label.shape != label_b.shape or not torch.equal(label, label_b):
             raise ValueError("the two scoring passes saw different labels: compare() needs a loader that yields the same rows in the same order")
         if (domain is None) != (domain_b is None) or (domain is not None and not torch.equal(domain, domain_b)):
             raise ValueError("the two scoring passes saw different domain columns: compare() needs a loader that yields the same rows in the same order")
-        if self.gauc_ci and (user_b is None or not torch.equal(user, user_b)):
-            raise ValueError("the two scoring passes saw different user columns: compare() with gauc_ci needs the same user_idx in both "
+        if (self.gauc_ci or self.rank_ci) and (user_b is None or not torch.equal(user, user_b)):
+            raise ValueError("the two scoring passes saw different user columns: compare() with gauc_ci or rank_ci needs the same user_idx in both "
                              "evaluators and a loader that yields the same rows in the same order")
         if self.bootstrap and user is not None and (user_b is None or not torch.equal(user, user_b)):
             raise ValueError("the two scoring passes saw different user columns: compare() with bootstrap resamples users and needs the "
@@ -1670,6 +1788,9 @@ class Evaluator:
         if self.gauc_ci:                                       # likewise queued
             gci = eval_gauc_ci(pred_a, label, user, self.n_user, domain if multi else None, self.n_domain if multi else 1,
                                self.user_weight, pred_b=pred_b)
+        if self.rank_ci:                                       # likewise queued: the replicates of both vectors come with it
+            rci = eval_rank_ci(pred_a, label, user, self.n_user, domain if multi else None, self.n_domain if multi else 1, self.rank_at,
+                               self.user_weight, pred_b=pred_b, n_rep=self.bootstrap, seed=self.bootstrap_seed)
         if self.bootstrap:                                     # likewise queued: per-replicate differences under shared weights
             boot = self._bootstrap(pred_a, label, domain, user, multi, pred_b=pred_b, gauc=self.gauc_ci)
             stats = {"delta": boot.auc - boot.auc_b}
@@ -1686,6 +1807,8 @@ class Evaluator:
                              "ece_quantile": cal_a.ece_q - cal_b.ece_q}
                 stats.update({"pcoc_delta": cb.pcoc - cb.pcoc_b, "brier_delta": cb.brier - cb.brier_b, "ece_delta": cb.ece - cb.ece_b,
                               "ece_quantile_delta": cb.ece_q - cb.ece_q_b})
+            if self.rank_ci:
+                stats.update(self._rank_stats(rci.reps - rci.reps_b, "_delta"))
             boot_sum = self._boot_summary(stats, ci.rows, multi)
         delta, var, rows = ci.delta.cpu().tolist(), ci.var_delta.cpu().tolist(), ci.rows.cpu().tolist()
         bad = int(eval_auc_ci.last_err.item())
@@ -1742,6 +1865,24 @@ class Evaluator:
                     result.update({f"domain_{k}_delta": {d: delta[d] for d in present},
                                    f"domain_{k}_z": {d: _z(delta[d], se[d]) for d in present},
                                    f"mean_{k}_delta": mean_delta, f"mean_{k}_z": _z(mean_delta, se[n_all + 1])})
+        if self.rank_ci:
+            deltas, variances = rci.delta.cpu().tolist(), rci.var_delta.cpu().tolist()
+            bad = int(eval_rank_ci.last_err.item())
+            if bad:
+                raise ValueError(f"evaluation row {bad - 1}: user outside [0, {self.n_user})")
+            n_all = self.n_domain if multi else 1              # the "all rows" column; the mean's follows it
+            for fig, d_k, v_k in zip(RANK_FIGURES, deltas, variances):
+                for K, delta, var in zip(self.rank_at, d_k, v_k):
+                    k, se = f"{fig}@{K}", _se(var[-1])
+                    result.update({f"total_{k}_delta": delta[-1], f"total_{k}_delta_se": se, f"total_{k}_z": _z(delta[-1], se)})
+                    if multi:
+                        d_se = {d: _se(var[d]) for d in present}
+                        result.update({f"domain_{k}_delta": {d: delta[d] for d in present}, f"domain_{k}_delta_se": d_se,
+                                       f"domain_{k}_z": {d: _z(delta[d], d_se[d]) for d in present}})
+                        if self.bootstrap:                     # the mean's error exists only over the replicates
+                            mean_delta = sum(self._weight(d) * delta[d] for d in present)
+                            result.update({f"mean_{k}_delta": mean_delta,
+                                           f"mean_{k}_z": _z(mean_delta, summ[k + "_delta"][0][n_all + 1])})
         return result
 
     def _weight(self, d):

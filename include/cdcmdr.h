@@ -1455,6 +1455,42 @@ int cdc_eval_calibration_bootstrap(const float* pred_a, const float* pred_b, con
                                    int32_t n_bins, int64_t n, int32_t n_rep, uint64_t seed, double* out, int64_t* counts,
                                    int32_t* err_flag, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* User-clustered standard errors, paired deltas and bootstrap replicates of cdc_eval_rank's figures.  label, user, ld_user, n_user,
+ * domain, ld_domain, n_domain, user_weight, ks, n_k, discounts and err_flag as for cdc_eval_rank; pred_b f32 [n] or NULL.  Groups, the
+ * order inside a group, tie handling and the five figures are cdc_eval_rank's; a group counts iff it has a positive, which the labels
+ * alone decide: the counted groups are the same under pred_a and pred_b.  Per segment, figure and cut-off, over the G counted groups
+ * with weight w_g (1, or user_weight) and group value m_g (m_g^b under pred_b), the sampling unit being the user:
+ *     M = sum w m / sum w                              cdc_eval_rank's figure bit for bit (its own launches form it)
+ *     var = G / (G - 1) * sum_g (w_g (m_g - M))^2 / (sum_g w_g)^2                      cdc_eval_gauc_ci's linearised ratio form
+ *     delta = M_a - M_b     var_delta = G / (G - 1) * sum_g (w_g ((m_g^a - m_g^b) - delta))^2 / (sum_g w_g)^2
+ * — var_delta from the per-group differences, never as var + var_b - 2 cov: identical vectors give delta = 0 and var_delta = 0 exactly.
+ * Replicate r (n_rep >= 1) gives user c the integer weight w(seed, r, c) of cdc_eval_bootstrap — the same hash and thresholds, so
+ * replicate r here resamples the users replicate r of cdc_eval_bootstrap resamples under the same seed:
+ *     M_r = sum_g w(seed, r, u_g) w_g m_g / sum_g w(seed, r, u_g) w_g      over the counted groups; NaN iff none has a positive weight
+ * under pred_b with the same weights: a delta's replicates are the caller's differences.
+ *   out    [n_stat, 5, n_k, n_domain+1] doubles, figures in cdc_eval_rank's order: n_stat = 2 (figure, var), or 6 with pred_b (figure,
+ *          var, figure_b, var_b, delta, var_delta).  A figure or delta is NaN when G == 0, every variance when G < 2.
+ *   reps   [pred_b ? 2 : 1, n_rep, 5, n_k, n_domain+1] doubles; NULL iff n_rep == 0.
+ *   counts [2, n_domain+1] int64 as cdc_eval_rank.
+ *   rep_counts (optional) [n_rep, n_domain+1] int64: the counted groups with a positive replicate weight.
+ * m_g does not depend on the replicate: a group is walked once per tile of 64 replicates and once for the squares, its values parked in
+ * LDS; the squares are a second pass that reads M from device memory.  No per-group array, nothing indexed by a user id, no float
+ * atomics; every addition's order is a function of the sorted keys alone: the same rows in any order give the same bits in every
+ * output.  Limits: null pointers, bad sizes, n_k outside [1, 8], n_rep outside [0, 4096], reps == NULL with n_rep > 0 (or the
+ * reverse), (n_domain + 1) * n_user > 2^32, n_rep * (n_domain + 1) * n_k > 2^20 cells, a workspace too small or not 256-byte aligned:
+ * CDC_E_BADARG; n >= 2^31: CDC_E_TOOBIG — all before anything is launched.  Stream-ordered: no allocation, no synchronisation,
+ * nothing read back; the launch count and dimensions depend on (n, n_domain, n_k, pred_b != NULL, n_rep) alone, so the call can be
+ * captured in a graph.  workspace: cdc_eval_rank_ci_workspace_bytes(n, n_domain, n_user, n_k, paired, n_rep) bytes, 256-byte aligned:
+ * O(n) per vector plus the slices' partial sums — 8 C (5 n_k (1 + paired) + 2) n_rep bytes for the replicates over C = n_domain S +
+ * min(n_domain S, 512) slices, S = 512 / (n_domain+1) clamped into [8, 64]: 35 MB at 50 domains, 200 replicates and 4 cut-offs; 0 for
+ * sizes the call refuses. */
+int64_t cdc_eval_rank_ci_workspace_bytes(int64_t n, int32_t n_domain, int64_t n_user, int32_t n_k, int32_t paired, int32_t n_rep);
+int cdc_eval_rank_ci(const float* pred_a, const float* pred_b, const int16_t* label, const int32_t* user, int64_t ld_user,
+                     int64_t n_user, const int32_t* domain, int64_t ld_domain, int32_t n_domain, const double* user_weight,
+                     const int32_t* ks, int32_t n_k, const double* discounts, int64_t n, int32_t n_rep, uint64_t seed, double* out,
+                     double* reps, int64_t* counts, int64_t* rep_counts, int32_t* err_flag, void* workspace, int64_t workspace_bytes,
+                     void* stream);
+
 /* Isotonic recalibration: per segment (domain 0..n_domain-1, then ALL rows) the non-decreasing least-squares fit of the 0/1 labels
  * on the score (pool-adjacent-violators), and the map it defines.  pred, label, domain, ld_domain, n_domain as for cdc_eval_metrics;
  * pred is any finite float (-0.0 and +0.0 are one score, reported as +0.0).  Rows of one score are one point; the fit is delivered
