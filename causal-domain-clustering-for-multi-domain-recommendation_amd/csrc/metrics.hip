@@ -31,25 +31,6 @@ __device__ __forceinline__ float key_score(uint32_t k) {
     return __uint_as_float(u);
 }
 
-__global__ void __launch_bounds__(MET_THREADS) k_metric_keys(const float* __restrict__ pred, const int16_t* __restrict__ label,
-                                                             const int32_t* __restrict__ domain, int64_t ld_domain, int64_t n,
-                                                             int32_t n_domain, uint64_t* __restrict__ keys,
-                                                             uint8_t* __restrict__ vals, int32_t* __restrict__ err) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float p = pred[i];
-        int32_t d = domain ? domain[i * ld_domain] : 0;
-        const int16_t y = label[i];
-        if (err && (p != p || d < 0 || d >= n_domain || (y != 0 && y != 1))) {
-            atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
-            d = d < 0 ? 0 : (d >= n_domain ? n_domain - 1 : d);
-        }
-        const uint32_t sk = score_key(p);
-        keys[i] = ((uint64_t)(uint32_t)d << 32) | sk;
-        keys[n + i] = ((uint64_t)(uint32_t)n_domain << 32) | sk;
-        vals[i] = vals[n + i] = (uint8_t)(y != 0);
-    }
-}
-
 __device__ __forceinline__ int64_t lower_bound_u64(const uint64_t* a, int64_t lo, int64_t hi, uint64_t key) {
     while (lo < hi) {
         const int64_t mid = (lo + hi) >> 1;
@@ -65,11 +46,166 @@ __device__ __forceinline__ int64_t upper_bound_u64(const uint64_t* a, int64_t lo
     return lo;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// What every evaluation call below shares.  On the device: a family's key kernel keeps its own "bad row" predicate and what it
+// puts in place of a bad score, and uses these for the rest.
+// the error word (the caller has checked that one was passed): the largest bad row + 1, saturated; a maximum, so order-free
+__device__ __forceinline__ void met_flag_row(int32_t* err, int64_t i) { atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff)); }
+// an id out of range is clamped whether or not the flag is wanted: the id becomes the upper half of a key, and that indexes start[]
+// (a user: user_weight)
+template <class T>
+__device__ __forceinline__ T met_clamp_id(T v, T n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
+// row i twice: under its own segment (or group) `up` and under the one of the pseudo-domain "all rows", up_all
+__device__ __forceinline__ void met_write_pair(uint64_t* keys, int64_t n, int64_t i, uint64_t up, uint64_t up_all, int shift,
+                                               uint64_t low) {
+    keys[i] = (up << shift) | low;
+    keys[n + i] = (up_all << shift) | low;
+}
+// the same with the sort's payload: the label byte, or the copy index j in [0, 2n)
+template <class V>
+__device__ __forceinline__ void met_write_pair(uint64_t* keys, V* pay, int64_t n, int64_t i, uint64_t up, uint64_t up_all, int shift, uint64_t low,
+                                               V pay_own, V pay_all) {
+    keys[i] = (up << shift) | low;         // written out, not the call above: through two levels of inlining the compiler keeps
+    keys[n + i] = (up_all << shift) | low; // keys + n in registers of its own
+    pay[i] = pay_own;
+    pay[n + i] = pay_all;
+}
+// first sorted position of segment t, whose keys begin at first_key (not looked at for t = n_seg: the end of the array)
+template <class T>
+__device__ __forceinline__ int64_t met_seg_start(const uint64_t* keys, int64_t n2, T t, int32_t n_seg, uint64_t first_key) {
+    return t == n_seg ? n2 : lower_bound_u64(keys, 0, n2, first_key);
+}
+
+// On the host: the workspace of every call is a chain of 256-byte aligned regions — the unsorted and the sorted keys, their payloads,
+// start[], the family's own arrays, then rocPRIM's temporary storage.  Everything in front of the temporary storage is plain
+// arithmetic, and the argument checks use it before any HIP or rocPRIM call.
+static int64_t align_up(int64_t v) { return (v + 255) & ~(int64_t)255; }
+
+struct MetCursor {
+    int64_t off = 0;
+    int64_t take(int64_t bytes) { const int64_t at = off; off += align_up(bytes); return at; }
+};
+struct MetWs {
+    char* base;
+    template <class T> T* ptr(int64_t off) const { return (T*)(base + off); }
+};
+struct MetLayout {                      // the part every family's layout embeds
+    int64_t keys_in, keys_out, pay_in, pay_out, start, temp, temp_bytes, total;
+    void keys(MetCursor& c, int64_t n_keys, int pay_width) {               // pay_width 0: the sort carries no payload
+        keys_in = c.take(n_keys * 8);
+        keys_out = c.take(n_keys * 8);
+        pay_in = c.take(n_keys * pay_width);
+        pay_out = c.take(n_keys * pay_width);
+    }
+    void starts(MetCursor& c, int64_t n_seg) { start = c.take((n_seg + 1) * 8); }
+    void end_fixed(const MetCursor& c) { temp = total = c.off; temp_bytes = 0; }
+    void set_temp(int64_t bytes) { temp_bytes = bytes; total = temp + align_up(bytes); }
+};
+
+// rocPRIM over 64-bit keys, with a payload or without; temp = nullptr asks for the size of the temporary storage
+template <class V>
+static hipError_t met_radix(void* temp, size_t& bytes, const uint64_t* kin, uint64_t* kout, const V* vin, V* vout, size_t n, int end_bit,
+                            hipStream_t st) {
+    return rocprim::radix_sort_pairs(temp, bytes, kin, kout, vin, vout, n, 0, end_bit, st, false);
+}
+static hipError_t met_radix(void* temp, size_t& bytes, const uint64_t* kin, uint64_t* kout, size_t n, int end_bit, hipStream_t st) {
+    return rocprim::radix_sort_keys(temp, bytes, kin, kout, n, 0, end_bit, st, false);
+}
+// the temporary storage of a call's sorts and scans: they run one after the other, so the largest need serves all
+struct MetTemp {
+    size_t bytes = 0;
+    hipError_t e = hipSuccess;
+    void seen(size_t t) { bytes = std::max(bytes, t); }
+    template <class V> void sort_pairs(size_t n) {
+        size_t t = 0;
+        if (e == hipSuccess) e = met_radix<V>(nullptr, t, nullptr, nullptr, nullptr, nullptr, n, 64, (hipStream_t)0);
+        seen(t);
+    }
+    void sort_keys(size_t n) {
+        size_t t = 0;
+        if (e == hipSuccess) e = met_radix(nullptr, t, nullptr, nullptr, n, 64, (hipStream_t)0);
+        seen(t);
+    }
+    template <class Out, class In, class Op> void scan(In in, size_t n, Op op) {
+        size_t t = 0;
+        if (e == hipSuccess) e = rocprim::inclusive_scan(nullptr, t, in, (Out*)nullptr, n, op, (hipStream_t)0, false);
+        seen(t);
+    }
+    int done(const char* what, MetLayout* m) {                             // completes a fixed layout
+        if (e != hipSuccess) { cdc_set_error("%s: rocprim size query failed: %s", what, hipGetErrorString(e)); return (int)e; }
+        m->set_temp((int64_t)bytes);
+        return 0;
+    }
+};
+// the sort only has to look at the bits a key can have: low_bits below the upper part + the bits of the largest upper part
+static int met_end_bit(uint64_t max_upper, int low_bits) {
+    int end_bit = low_bits + 1;
+    while (end_bit < 64 && (max_upper >> (end_bit - low_bits)) != 0) ++end_bit;
+    return end_bit;
+}
+// the call's main sort, keys_in -> keys_out (and, given two payload pointers, pay_in -> pay_out)
+template <class... A>
+static int met_sort(const char* what, char* base, const MetLayout& m, A... a) {
+    size_t bytes = (size_t)m.temp_bytes;
+    const hipError_t e = met_radix(base + m.temp, bytes, (const uint64_t*)(base + m.keys_in), (uint64_t*)(base + m.keys_out), a...);
+    if (e != hipSuccess) { cdc_set_error("%s: radix sort failed: %s", what, hipGetErrorString(e)); return (int)e; }
+    return 0;
+}
+
+#define MET_TRY(call)                   \
+    do {                                \
+        const int rc__ = (call);        \
+        if (rc__ != 0) return rc__;     \
+    } while (0)
+
+static int met_need_domain(const char* what, const int32_t* domain, int32_t n_domain) {
+    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "%s: n_domain=%d needs the domain column", what, n_domain);
+    return 0;
+}
+static int met_ws_aligned(const char* what, const void* workspace) {
+    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "%s: workspace must be 256-byte aligned", what);
+    return 0;
+}
+// the workspace against m->total as the fixed layout left it (no HIP or rocPRIM call has been made, so a workspace that is too
+// small is refused where no device is present), then `complete` adds rocPRIM's part TO THE SAME LAYOUT, then against the new m->total
+template <class F>
+static int met_ws_fits(const char* what, int64_t workspace_bytes, const MetLayout* m, F complete) {
+    const auto fits = [&]() -> int {
+        CDC_CHECK_ARG(workspace_bytes >= m->total, CDC_E_BADARG, "%s: workspace %ld < %ld bytes", what, (long)workspace_bytes, (long)m->total);
+        return 0;
+    };
+    MET_TRY(fits());
+    MET_TRY(complete());
+    return fits();
+}
+template <class F>
+static int met_gate(const char* what, const void* workspace, int64_t workspace_bytes, const MetLayout* m, F complete) {
+    MET_TRY(met_ws_aligned(what, workspace));
+    return met_ws_fits(what, workspace_bytes, m, complete);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(MET_THREADS) k_metric_keys(const float* __restrict__ pred, const int16_t* __restrict__ label,
+                                                             const int32_t* __restrict__ domain, int64_t ld_domain, int64_t n,
+                                                             int32_t n_domain, uint64_t* __restrict__ keys,
+                                                             uint8_t* __restrict__ vals, int32_t* __restrict__ err) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float p = pred[i];
+        int32_t d = domain ? domain[i * ld_domain] : 0;
+        const int16_t y = label[i];
+        if (p != p || d < 0 || d >= n_domain || (y != 0 && y != 1)) {
+            if (err) met_flag_row(err, i);
+            d = met_clamp_id(d, n_domain);
+        }
+        met_write_pair(keys, vals, n, i, (uint32_t)d, (uint32_t)n_domain, 32, score_key(p), (uint8_t)(y != 0), (uint8_t)(y != 0));
+    }
+}
+
 // start[d] = first sorted position of (pseudo-)domain d, d in [0, n_domain + 1]; start[n_domain + 1] = 2n
 __global__ void k_metric_starts(const uint64_t* __restrict__ keys, int64_t n2, int32_t n_seg, int64_t* __restrict__ start,
                                 unsigned long long* __restrict__ s2, unsigned long long* __restrict__ npos) {
     const int d = blockIdx.x * blockDim.x + threadIdx.x;
-    if (d <= n_seg) start[d] = d == n_seg ? n2 : lower_bound_u64(keys, 0, n2, (uint64_t)(uint32_t)d << 32);
+    if (d <= n_seg) start[d] = met_seg_start(keys, n2, d, n_seg, (uint64_t)(uint32_t)d << 32);
     if (d < n_seg) { s2[d] = 0ull; npos[d] = 0ull; }
 }
 
@@ -133,37 +269,32 @@ __global__ void k_metric_final(const int64_t* __restrict__ start, const unsigned
     out[n_seg + d] = loss;
 }
 
-static int64_t align_up(int64_t v) { return (v + 255) & ~(int64_t)255; }
-
 struct MetricLayout {
-    int64_t keys_in, keys_out, vals_in, vals_out, start, s2, npos, loss, temp, temp_bytes, total;
+    MetLayout m;
+    int64_t s2, npos, loss;
 };
+static void metric_fixed_layout(int64_t n, int32_t n_domain, MetricLayout* L) {
+    const int64_t seg = (int64_t)n_domain + 1;
+    MetCursor c;
+    L->m.keys(c, 2 * n, 1);
+    L->m.starts(c, seg);
+    L->s2 = c.take(seg * 8);
+    L->npos = c.take(seg * 8);
+    L->loss = c.take(seg * 8);
+    L->m.end_fixed(c);
+}
 static int metric_layout(int64_t n, int32_t n_domain, MetricLayout* L) {
-    const int64_t n2 = 2 * n, seg = n_domain + 1;
-    size_t temp_bytes = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, temp_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint8_t*)nullptr,
-                                             (uint8_t*)nullptr, (size_t)n2, 0, 64, (hipStream_t)0, false);
-    if (e != hipSuccess) { cdc_set_error("eval_metrics: rocprim size query failed: %s", hipGetErrorString(e)); return (int)e; }
-    int64_t off = 0;
-    L->keys_in = off;  off += align_up(n2 * 8);
-    L->keys_out = off; off += align_up(n2 * 8);
-    L->vals_in = off;  off += align_up(n2);
-    L->vals_out = off; off += align_up(n2);
-    L->start = off;    off += align_up((seg + 1) * 8);
-    L->s2 = off;       off += align_up(seg * 8);
-    L->npos = off;     off += align_up(seg * 8);
-    L->loss = off;     off += align_up(seg * 8);
-    L->temp = off;     off += align_up((int64_t)temp_bytes);
-    L->temp_bytes = (int64_t)temp_bytes;
-    L->total = off;
-    return 0;
+    metric_fixed_layout(n, n_domain, L);
+    MetTemp t;
+    t.sort_pairs<uint8_t>((size_t)(2 * n));
+    return t.done("eval_metrics", &L->m);
 }
 
 extern "C" int64_t cdc_eval_workspace_bytes(int64_t n, int32_t n_domain) {
     if (n <= 0 || n_domain <= 0) return 0;
     MetricLayout L;
     if (metric_layout(n, n_domain, &L) != 0) return -1;
-    return L.total;
+    return L.m.total;
 }
 
 extern "C" int cdc_eval_metrics(const float* pred, const int16_t* label, const int32_t* domain, int64_t ld_domain, int64_t n,
@@ -173,33 +304,24 @@ extern "C" int cdc_eval_metrics(const float* pred, const int16_t* label, const i
     CDC_CHECK_ARG(n > 0 && n < (1ll << 31) && n_domain > 0 && n_domain < (1 << 20) && (domain || n_domain == 1) && ld_domain >= 0,
                   CDC_E_BADARG, "eval_metrics: bad sizes n=%ld n_domain=%d", (long)n, n_domain);
     MetricLayout L;
-    int rc = metric_layout(n, n_domain, &L);
-    if (rc != 0) return rc;
-    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_metrics: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
-    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_metrics: workspace must be 256-byte aligned");
-    char* base = (char*)workspace;
-    uint64_t* keys_in = (uint64_t*)(base + L.keys_in);
-    uint64_t* keys_out = (uint64_t*)(base + L.keys_out);
-    uint8_t* vals_in = (uint8_t*)(base + L.vals_in);
-    uint8_t* vals_out = (uint8_t*)(base + L.vals_out);
-    int64_t* start = (int64_t*)(base + L.start);
-    unsigned long long* s2 = (unsigned long long*)(base + L.s2);
-    unsigned long long* npos = (unsigned long long*)(base + L.npos);
-    double* loss = (double*)(base + L.loss);
+    metric_fixed_layout(n, n_domain, &L);
+    MET_TRY(met_ws_fits("eval_metrics", workspace_bytes, &L.m, [&] { return metric_layout(n, n_domain, &L); }));
+    MET_TRY(met_ws_aligned("eval_metrics", workspace));                    // this call has always looked at the size first
+    const MetWs ws{(char*)workspace};
+    uint64_t* keys_out = ws.ptr<uint64_t>(L.m.keys_out);
+    uint8_t* vals_out = ws.ptr<uint8_t>(L.m.pay_out);
+    int64_t* start = ws.ptr<int64_t>(L.m.start);
+    unsigned long long* s2 = ws.ptr<unsigned long long>(L.s2);
+    unsigned long long* npos = ws.ptr<unsigned long long>(L.npos);
+    double* loss = ws.ptr<double>(L.loss);
     hipStream_t st = (hipStream_t)stream;
     const int64_t n2 = 2 * n;
     const int seg = n_domain + 1;
     int blocks = (int)std::min<int64_t>(cdc_ceil_div(n, MET_THREADS), 4096);
-    hipLaunchKernelGGL(k_metric_keys, dim3(blocks), dim3(MET_THREADS), 0, st, pred, label, domain, ld_domain, n, n_domain, keys_in,
-                       vals_in, err_flag);
+    hipLaunchKernelGGL(k_metric_keys, dim3(blocks), dim3(MET_THREADS), 0, st, pred, label, domain, ld_domain, n, n_domain,
+                       ws.ptr<uint64_t>(L.m.keys_in), ws.ptr<uint8_t>(L.m.pay_in), err_flag);
     CDC_LAUNCH_CHECK("eval_metrics(keys)");
-    size_t temp_bytes = (size_t)L.temp_bytes;
-    // the sort only has to look at the bits a key can have: 32 score bits + the bits of n_domain
-    int end_bit = 33;
-    while (end_bit < 64 && ((uint64_t)n_domain >> (end_bit - 32)) != 0) ++end_bit;
-    hipError_t e = rocprim::radix_sort_pairs(base + L.temp, temp_bytes, (const uint64_t*)keys_in, keys_out, (const uint8_t*)vals_in,
-                                             vals_out, (size_t)n2, 0, end_bit, st, false);
-    if (e != hipSuccess) { cdc_set_error("eval_metrics: radix sort failed: %s", hipGetErrorString(e)); return (int)e; }
+    MET_TRY(met_sort("eval_metrics", ws.base, L.m, ws.ptr<const uint8_t>(L.m.pay_in), vals_out, (size_t)n2, met_end_bit((uint64_t)n_domain, 32), st));
     hipLaunchKernelGGL(k_metric_starts, dim3((int)cdc_ceil_div(seg + 1, 64)), dim3(64), 0, st, keys_out, n2, seg, start, s2, npos);
     CDC_LAUNCH_CHECK("eval_metrics(starts)");
     blocks = (int)std::min<int64_t>(cdc_ceil_div(n2, MET_THREADS), 8192);
@@ -284,21 +406,19 @@ __global__ void __launch_bounds__(MET_THREADS) k_gauc_keys(const float* __restri
         int64_t u = user[i * ld_user];
         const int16_t y = label[i];
         if (p != p || d < 0 || d >= n_domain || u < 0 || u >= n_user || (y != 0 && y != 1)) {
-            if (err) atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
-            d = d < 0 ? 0 : (d >= n_domain ? n_domain - 1 : d);           // the ids are clamped whether or not the flag is wanted:
-            u = u < 0 ? 0 : (u >= n_user ? n_user - 1 : u);               // u indexes user_weight
+            if (err) met_flag_row(err, i);
+            d = met_clamp_id(d, n_domain);
+            u = met_clamp_id(u, n_user);
         }
-        const uint32_t sk = score_key(p);
-        keys[i] = (((uint64_t)d * (uint64_t)n_user + (uint64_t)u) << 32) | sk;
-        keys[n + i] = (((uint64_t)n_domain * (uint64_t)n_user + (uint64_t)u) << 32) | sk;
-        vals[i] = vals[n + i] = (uint8_t)(y != 0);
+        met_write_pair(keys, vals, n, i, (uint64_t)d * (uint64_t)n_user + (uint64_t)u, (uint64_t)n_domain * (uint64_t)n_user + (uint64_t)u, 32,
+                       score_key(p), (uint8_t)(y != 0), (uint8_t)(y != 0));
     }
 }
 
 // start[d] = first sorted position of (pseudo-)domain d's groups, d in [0, n_seg]; start[n_seg] = 2n
 __global__ void k_gauc_starts(const uint64_t* __restrict__ keys, int64_t n2, int32_t n_seg, int64_t n_user, int64_t* __restrict__ start) {
     const int d = blockIdx.x * blockDim.x + threadIdx.x;
-    if (d <= n_seg) start[d] = d == n_seg ? n2 : lower_bound_u64(keys, 0, n2, ((uint64_t)d * (uint64_t)n_user) << 32);
+    if (d <= n_seg) start[d] = met_seg_start(keys, n2, d, n_seg, ((uint64_t)d * (uint64_t)n_user) << 32);
 }
 
 // workgroup (d, slice): the groups of (pseudo-)domain d whose LAST row lies in the slice
@@ -370,46 +490,31 @@ __global__ void __launch_bounds__(GAUC_SLICES) k_gauc_final(const double* __rest
 }
 
 struct GaucLayout {
-    int64_t keys_in, keys_out, vals_in, vals_out, scan, start, part, part_cnt, temp, temp_bytes, total;
+    MetLayout m;                        // keys_in is W, the running sum of scan 2, once the sort has run
+    int64_t scan, part, part_cnt;
 };
-// everything but rocPRIM's temporary storage: plain arithmetic (argument checks use it before any HIP or rocPRIM call)
 static void gauc_fixed_layout(int64_t n, int32_t n_domain, GaucLayout* L) {
     const int64_t n2 = 2 * n, seg = (int64_t)n_domain + 1;
-    int64_t off = 0;
-    L->keys_in = off;  off += align_up(n2 * 8);               // after the sort: W, the running sum of scan 2
-    L->keys_out = off; off += align_up(n2 * 8);
-    L->vals_in = off;  off += align_up(n2);
-    L->vals_out = off; off += align_up(n2);
-    L->scan = off;     off += align_up(n2 * (int64_t)sizeof(GaucScan));
-    L->start = off;    off += align_up((seg + 1) * 8);
-    L->part = off;     off += align_up(seg * GAUC_SLICES * 2 * 8);
-    L->part_cnt = off; off += align_up(seg * GAUC_SLICES * 2 * 8);
-    L->temp = off;
-    L->temp_bytes = 0;
-    L->total = off;
+    MetCursor c;
+    L->m.keys(c, n2, 1);
+    L->scan = c.take(n2 * (int64_t)sizeof(GaucScan));
+    L->m.starts(c, seg);
+    L->part = c.take(seg * GAUC_SLICES * 2 * 8);
+    L->part_cnt = c.take(seg * GAUC_SLICES * 2 * 8);
+    L->m.end_fixed(c);
 }
-// rocPRIM's temporary storage for the sort and the two scans of 2n keys: the three run one after the other
-static int gauc_temp_bytes(int64_t n, const char* what, int64_t* bytes) {
+// rocPRIM's temporary storage for gauc_order's sort and two scans of 2n keys; completes a layout whose m.temp the caller has placed
+static int gauc_temp(int64_t n, const char* what, MetLayout* m, MetTemp t = MetTemp()) {
     const size_t n2 = (size_t)(2 * n);
-    size_t t_sort = 0, t_scan = 0, t_share = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, t_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint8_t*)nullptr,
-                                             (uint8_t*)nullptr, n2, 0, 64, (hipStream_t)0, false);
-    if (e == hipSuccess)
-        e = rocprim::inclusive_scan(nullptr, t_scan, GaucScanIt(rocprim::counting_iterator<uint32_t>(0), GaucScanIn{nullptr, nullptr}),
-                                    (GaucScan*)nullptr, n2, GaucScanOp(), (hipStream_t)0, false);
-    if (e == hipSuccess)
-        e = rocprim::inclusive_scan(nullptr, t_share, GaucShareIt(rocprim::counting_iterator<uint32_t>(0), GaucShareIn{nullptr, nullptr}),
-                                    (unsigned long long*)nullptr, n2, rocprim::plus<unsigned long long>(), (hipStream_t)0, false);
-    if (e != hipSuccess) { cdc_set_error("%s: rocprim size query failed: %s", what, hipGetErrorString(e)); return (int)e; }
-    *bytes = (int64_t)std::max(t_sort, std::max(t_scan, t_share));
-    return 0;
+    t.sort_pairs<uint8_t>(n2);
+    t.scan<GaucScan>(GaucScanIt(rocprim::counting_iterator<uint32_t>(0), GaucScanIn{nullptr, nullptr}), n2, GaucScanOp());
+    t.scan<unsigned long long>(GaucShareIt(rocprim::counting_iterator<uint32_t>(0), GaucShareIn{nullptr, nullptr}), n2,
+                               rocprim::plus<unsigned long long>());
+    return t.done(what, m);
 }
 static int gauc_layout(int64_t n, int32_t n_domain, GaucLayout* L) {
     gauc_fixed_layout(n, n_domain, L);
-    const int rc = gauc_temp_bytes(n, "eval_gauc", &L->temp_bytes);
-    if (rc != 0) return rc;
-    L->total = L->temp + align_up(L->temp_bytes);
-    return 0;
+    return gauc_temp(n, "eval_gauc", &L->m);
 }
 // (n_domain + 1) * n_user group ids must fit the upper half of a key
 static bool gauc_sizes_ok(int64_t n, int32_t n_domain, int64_t n_user) {
@@ -421,7 +526,7 @@ extern "C" int64_t cdc_eval_gauc_workspace_bytes(int64_t n, int32_t n_domain, in
     if (!gauc_sizes_ok(n, n_domain, n_user)) return 0;
     GaucLayout L;
     if (gauc_layout(n, n_domain, &L) != 0) return -1;
-    return L.total;
+    return L.m.total;
 }
 
 // keys, sort, the two scans and the segment bounds of one score vector: leaves keys_out, sc and start describing its order and W, the
@@ -430,37 +535,32 @@ extern "C" int64_t cdc_eval_gauc_workspace_bytes(int64_t n, int32_t n_domain, in
 static int gauc_order(const float* pred, const int16_t* label, const int32_t* user, int64_t ld_user, int64_t n_user, const int32_t* domain,
                       int64_t ld_domain, int32_t n_domain, int64_t n, int32_t* err_flag, char* base, const GaucLayout& L,
                       unsigned long long* W, const char* what, hipStream_t st) {
-    uint64_t* keys_in = (uint64_t*)(base + L.keys_in);
-    uint64_t* keys_out = (uint64_t*)(base + L.keys_out);
-    uint8_t* vals_in = (uint8_t*)(base + L.vals_in);
-    uint8_t* vals_out = (uint8_t*)(base + L.vals_out);
-    GaucScan* sc = (GaucScan*)(base + L.scan);
-    int64_t* start = (int64_t*)(base + L.start);
+    const MetWs ws{base};
+    uint64_t* keys_out = ws.ptr<uint64_t>(L.m.keys_out);
+    uint8_t* vals_in = ws.ptr<uint8_t>(L.m.pay_in);
+    uint8_t* vals_out = ws.ptr<uint8_t>(L.m.pay_out);
+    GaucScan* sc = ws.ptr<GaucScan>(L.scan);
     const int64_t n2 = 2 * n;
     const int seg = n_domain + 1;
     const int blocks = (int)std::min<int64_t>(cdc_ceil_div(n, MET_THREADS), 4096);
     hipLaunchKernelGGL(k_gauc_keys, dim3(blocks), dim3(MET_THREADS), 0, st, pred, label, user, ld_user, n_user, domain, ld_domain,
-                       n_domain, n, keys_in, vals_in, err_flag);
+                       n_domain, n, ws.ptr<uint64_t>(L.m.keys_in), vals_in, err_flag);
     CDC_LAUNCH_CHECK("eval_gauc(keys)");
-    // the sort only has to look at the bits a key can have: 32 score bits + the bits of the largest group id
-    const uint64_t g_max = (uint64_t)seg * (uint64_t)n_user - 1;
-    int end_bit = 33;
-    while (end_bit < 64 && (g_max >> (end_bit - 32)) != 0) ++end_bit;
-    size_t temp_bytes = (size_t)L.temp_bytes;
-    hipError_t e = rocprim::radix_sort_pairs(base + L.temp, temp_bytes, (const uint64_t*)keys_in, keys_out, (const uint8_t*)vals_in,
-                                             vals_out, (size_t)n2, 0, end_bit, st, false);
-    if (e != hipSuccess) { cdc_set_error("%s: radix sort failed: %s", what, hipGetErrorString(e)); return (int)e; }
-    temp_bytes = (size_t)L.temp_bytes;
-    e = rocprim::inclusive_scan(base + L.temp, temp_bytes, GaucScanIt(rocprim::counting_iterator<uint32_t>(0), GaucScanIn{keys_out, vals_out}),
-                                sc, (size_t)n2, GaucScanOp(), st, false);
+    MET_TRY(met_sort(what, base, L.m, (const uint8_t*)vals_in, vals_out, (size_t)n2,
+                     met_end_bit((uint64_t)seg * (uint64_t)n_user - 1, 32), st));             // the upper half holds a group id below seg * n_user
+    size_t temp_bytes = (size_t)L.m.temp_bytes;
+    hipError_t e = rocprim::inclusive_scan(base + L.m.temp, temp_bytes,
+                                           GaucScanIt(rocprim::counting_iterator<uint32_t>(0), GaucScanIn{keys_out, vals_out}), sc, (size_t)n2,
+                                           GaucScanOp(), st, false);
     if (e != hipSuccess) { cdc_set_error("%s: group scan failed: %s", what, hipGetErrorString(e)); return (int)e; }
     if (W) {
-        temp_bytes = (size_t)L.temp_bytes;
-        e = rocprim::inclusive_scan(base + L.temp, temp_bytes, GaucShareIt(rocprim::counting_iterator<uint32_t>(0), GaucShareIn{sc, vals_out}),
+        temp_bytes = (size_t)L.m.temp_bytes;
+        e = rocprim::inclusive_scan(base + L.m.temp, temp_bytes, GaucShareIt(rocprim::counting_iterator<uint32_t>(0), GaucShareIn{sc, vals_out}),
                                     W, (size_t)n2, rocprim::plus<unsigned long long>(), st, false);
         if (e != hipSuccess) { cdc_set_error("%s: rank scan failed: %s", what, hipGetErrorString(e)); return (int)e; }
     }
-    hipLaunchKernelGGL(k_gauc_starts, dim3((int)cdc_ceil_div(seg + 1, 64)), dim3(64), 0, st, keys_out, n2, seg, n_user, start);
+    hipLaunchKernelGGL(k_gauc_starts, dim3((int)cdc_ceil_div(seg + 1, 64)), dim3(64), 0, st, (const uint64_t*)keys_out, n2, seg, n_user,
+                       ws.ptr<int64_t>(L.m.start));
     CDC_LAUNCH_CHECK("eval_gauc(starts)");
     return 0;
 }
@@ -471,28 +571,23 @@ extern "C" int cdc_eval_gauc(const float* pred, const int16_t* label, const int3
     CDC_CHECK_ARG(pred && label && user && out && counts && workspace, CDC_E_BADARG, "eval_gauc: null pointer");
     CDC_CHECK_ARG(n > 0 && n < (1ll << 31) && n_domain > 0 && n_domain < (1 << 20) && n_user > 0 && ld_user >= 0 && ld_domain >= 0,
                   CDC_E_BADARG, "eval_gauc: bad sizes n=%ld n_domain=%d n_user=%ld", (long)n, n_domain, (long)n_user);
-    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_gauc: n_domain=%d needs the domain column", n_domain);
+    MET_TRY(met_need_domain("eval_gauc", domain, n_domain));
     CDC_CHECK_ARG(gauc_sizes_ok(n, n_domain, n_user), CDC_E_BADARG,
                   "eval_gauc: (n_domain + 1) * n_user = %ld * %ld group ids exceed 2^32", (long)n_domain + 1, (long)n_user);
-    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_gauc: workspace must be 256-byte aligned");
     GaucLayout L;
     gauc_fixed_layout(n, n_domain, &L);
-    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_gauc: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
-    int rc = gauc_layout(n, n_domain, &L);
-    if (rc != 0) return rc;
-    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_gauc: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
-    char* base = (char*)workspace;
-    const uint64_t* keys_out = (const uint64_t*)(base + L.keys_out);
-    const GaucScan* sc = (const GaucScan*)(base + L.scan);
-    unsigned long long* W = (unsigned long long*)(base + L.keys_in);
-    const int64_t* start = (const int64_t*)(base + L.start);
-    double* part = (double*)(base + L.part);
-    int64_t* part_cnt = (int64_t*)(base + L.part_cnt);
+    MET_TRY(met_gate("eval_gauc", workspace, workspace_bytes, &L.m, [&] { return gauc_temp(n, "eval_gauc", &L.m); }));
+    const MetWs ws{(char*)workspace};
+    const uint64_t* keys_out = ws.ptr<const uint64_t>(L.m.keys_out);
+    const GaucScan* sc = ws.ptr<const GaucScan>(L.scan);
+    unsigned long long* W = ws.ptr<unsigned long long>(L.m.keys_in);
+    const int64_t* start = ws.ptr<const int64_t>(L.m.start);
+    double* part = ws.ptr<double>(L.part);
+    int64_t* part_cnt = ws.ptr<int64_t>(L.part_cnt);
     hipStream_t st = (hipStream_t)stream;
     const int64_t n2 = 2 * n;
     const int seg = n_domain + 1;
-    rc = gauc_order(pred, label, user, ld_user, n_user, domain, ld_domain, n_domain, n, err_flag, base, L, W, "eval_gauc", st);
-    if (rc != 0) return rc;
+    MET_TRY(gauc_order(pred, label, user, ld_user, n_user, domain, ld_domain, n_domain, n, err_flag, ws.base, L, W, "eval_gauc", st));
     hipLaunchKernelGGL(k_gauc_sum, dim3(seg, GAUC_SLICES), dim3(GAUC_THREADS), 0, st, keys_out, sc, W, start, user_weight, n_user, n2,
                        part, part_cnt);
     CDC_LAUNCH_CHECK("eval_gauc(sum)");
@@ -703,32 +798,25 @@ __global__ void __launch_bounds__(RANK_SLICES) k_rank_final(const double* __rest
 }
 
 struct RankLayout {
-    GaucLayout g;
-    int64_t part, part_cnt, total;
+    GaucLayout g;                       // g.m.temp / g.m.total lie behind the ones below
+    int64_t part, part_cnt;
 };
-// as gauc_fixed_layout: plain arithmetic; the slices' sums stand between GAUC's fixed part and rocPRIM's temporary storage
+// the slices' sums stand between GAUC's fixed part and rocPRIM's temporary storage
 static void rank_fixed_layout(int64_t n, int32_t n_domain, int32_t n_k, RankLayout* L) {
     gauc_fixed_layout(n, n_domain, &L->g);
     const int64_t seg = (int64_t)n_domain + 1;
-    int64_t off = L->g.temp;
-    L->part = off;     off += align_up(seg * RANK_SLICES * (RANK_FIGS * n_k + 1) * 8);
-    L->part_cnt = off; off += align_up(seg * RANK_SLICES * 2 * 8);
-    L->g.temp = off;
-    L->total = off;
-}
-static int rank_layout(int64_t n, int32_t n_domain, int32_t n_k, RankLayout* L) {
-    rank_fixed_layout(n, n_domain, n_k, L);
-    const int rc = gauc_temp_bytes(n, "eval_rank", &L->g.temp_bytes);
-    if (rc != 0) return rc;
-    L->total = L->g.temp + align_up(L->g.temp_bytes);
-    return 0;
+    MetCursor c{L->g.m.temp};
+    L->part = c.take(seg * RANK_SLICES * (RANK_FIGS * n_k + 1) * 8);
+    L->part_cnt = c.take(seg * RANK_SLICES * 2 * 8);
+    L->g.m.end_fixed(c);
 }
 
 extern "C" int64_t cdc_eval_rank_workspace_bytes(int64_t n, int32_t n_domain, int64_t n_user, int32_t n_k) {
     if (!gauc_sizes_ok(n, n_domain, n_user) || n_k < 1 || n_k > RANK_MAX_NK) return 0;
     RankLayout L;
-    if (rank_layout(n, n_domain, n_k, &L) != 0) return -1;
-    return L.total;
+    rank_fixed_layout(n, n_domain, n_k, &L);
+    if (gauc_temp(n, "eval_rank", &L.g.m) != 0) return -1;
+    return L.g.m.total;
 }
 
 template <int NK>
@@ -746,27 +834,22 @@ extern "C" int cdc_eval_rank(const float* pred, const int16_t* label, const int3
     CDC_CHECK_ARG(n > 0 && n < (1ll << 31) && n_domain > 0 && n_domain < (1 << 20) && n_user > 0 && ld_user >= 0 && ld_domain >= 0,
                   CDC_E_BADARG, "eval_rank: bad sizes n=%ld n_domain=%d n_user=%ld", (long)n, n_domain, (long)n_user);
     CDC_CHECK_ARG(n_k >= 1 && n_k <= RANK_MAX_NK, CDC_E_BADARG, "eval_rank: n_k=%d cut-offs, 1 to %d are served", n_k, RANK_MAX_NK);
-    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_rank: n_domain=%d needs the domain column", n_domain);
+    MET_TRY(met_need_domain("eval_rank", domain, n_domain));
     CDC_CHECK_ARG(gauc_sizes_ok(n, n_domain, n_user), CDC_E_BADARG,
                   "eval_rank: (n_domain + 1) * n_user = %ld * %ld group ids exceed 2^32", (long)n_domain + 1, (long)n_user);
-    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_rank: workspace must be 256-byte aligned");
     RankLayout L;
     rank_fixed_layout(n, n_domain, n_k, &L);
-    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_rank: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
-    int rc = rank_layout(n, n_domain, n_k, &L);
-    if (rc != 0) return rc;
-    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_rank: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
-    char* base = (char*)workspace;
-    const uint64_t* keys_out = (const uint64_t*)(base + L.g.keys_out);
-    const GaucScan* sc = (const GaucScan*)(base + L.g.scan);
-    const int64_t* start = (const int64_t*)(base + L.g.start);
-    double* part = (double*)(base + L.part);
-    int64_t* part_cnt = (int64_t*)(base + L.part_cnt);
+    MET_TRY(met_gate("eval_rank", workspace, workspace_bytes, &L.g.m, [&] { return gauc_temp(n, "eval_rank", &L.g.m); }));
+    const MetWs ws{(char*)workspace};
+    const uint64_t* keys_out = ws.ptr<const uint64_t>(L.g.m.keys_out);
+    const GaucScan* sc = ws.ptr<const GaucScan>(L.g.scan);
+    const int64_t* start = ws.ptr<const int64_t>(L.g.m.start);
+    double* part = ws.ptr<double>(L.part);
+    int64_t* part_cnt = ws.ptr<int64_t>(L.part_cnt);
     hipStream_t st = (hipStream_t)stream;
     const int64_t n2 = 2 * n;
     const int seg = n_domain + 1;
-    rc = gauc_order(pred, label, user, ld_user, n_user, domain, ld_domain, n_domain, n, err_flag, base, L.g, nullptr, "eval_rank", st);
-    if (rc != 0) return rc;
+    MET_TRY(gauc_order(pred, label, user, ld_user, n_user, domain, ld_domain, n_domain, n, err_flag, ws.base, L.g, nullptr, "eval_rank", st));
     switch (n_k) {
 #define RANK_CASE(NK) case NK: rank_sum_launch<NK>(seg, st, keys_out, sc, start, user_weight, ks, discounts, n_user, n2, part, part_cnt); break;
         RANK_CASE(1) RANK_CASE(2) RANK_CASE(3) RANK_CASE(4) RANK_CASE(5) RANK_CASE(6) RANK_CASE(7) RANK_CASE(8)
@@ -860,7 +943,7 @@ __global__ void __launch_bounds__(MET_THREADS) k_topk_keys(const float* __restri
         const int32_t it = ITEM ? item[i * ld_item] : 0;
         uint64_t key = TOPK_DEAD;
         if (p != p || d < 0 || d >= n_domain || u < 0 || u >= n_user || it < 0) {
-            if (err) atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
+            if (err) met_flag_row(err, i);
         } else {
             const uint64_t g = (uint64_t)d * (uint64_t)n_user + (uint64_t)u;
             key = (g << 32) | (ITEM ? (uint32_t)it : ~score_key(p));
@@ -923,41 +1006,25 @@ __global__ void __launch_bounds__(MET_THREADS) k_topk_emit(const uint64_t* __res
 }
 
 struct TopkLayout {
-    int64_t keys_a, keys_b, rows_a, rows_b, scan, kept, temp, temp_bytes, total;
+    MetLayout m;                        // n keys with their rows, sorted to and fro; no start[]
+    int64_t scan, kept;
 };
-// everything but rocPRIM's temporary storage: plain arithmetic (argument checks use it before any HIP or rocPRIM call)
 static void topk_fixed_layout(int64_t n, int32_t has_item, TopkLayout* L) {
-    int64_t off = 0;
-    L->keys_a = off; off += align_up(n * 8);
-    L->keys_b = off; off += align_up(n * 8);
-    L->rows_a = off; off += align_up(n * 4);
-    L->rows_b = off; off += align_up(n * 4);
-    L->scan = off;   off += align_up(n * (int64_t)(has_item ? sizeof(TopkPick) : sizeof(TopkScan)));   // the pick scan, then scan 1
-    L->kept = off;   off += align_up(n * 4);
-    L->temp = off;
-    L->temp_bytes = 0;
-    L->total = off;
+    MetCursor c;
+    L->m.keys(c, n, 4);
+    L->scan = c.take(n * (int64_t)(has_item ? sizeof(TopkPick) : sizeof(TopkScan)));                  // the pick scan, then scan 1
+    L->kept = c.take(n * 4);
+    L->m.end_fixed(c);
 }
-// rocPRIM's temporary storage for the sorts and scans of n keys: they run one after the other
-static int topk_layout(int64_t n, int32_t has_item, TopkLayout* L) {
-    topk_fixed_layout(n, has_item, L);
+// rocPRIM's temporary storage for the sorts and scans of n keys
+static int topk_temp(int64_t n, int32_t has_item, TopkLayout* L) {
     const size_t sz = (size_t)n;
-    size_t t_sort = 0, t_pick = 0, t_scan = 0, t_kept = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, t_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr,
-                                             (uint32_t*)nullptr, sz, 0, 64, (hipStream_t)0, false);
-    if (e == hipSuccess && has_item)
-        e = rocprim::inclusive_scan(nullptr, t_pick, TopkPickIt(rocprim::counting_iterator<uint32_t>(0), TopkPickIn{nullptr, nullptr, nullptr}),
-                                    (TopkPick*)nullptr, sz, TopkPickOp(), (hipStream_t)0, false);
-    if (e == hipSuccess)
-        e = rocprim::inclusive_scan(nullptr, t_scan, TopkScanIt(rocprim::counting_iterator<uint32_t>(0), TopkScanIn{nullptr}),
-                                    (TopkScan*)nullptr, sz, TopkScanOp(), (hipStream_t)0, false);
-    if (e == hipSuccess)
-        e = rocprim::inclusive_scan(nullptr, t_kept, TopkKeptIt(rocprim::counting_iterator<uint32_t>(0), TopkKeptIn{nullptr, nullptr, 1u}),
-                                    (uint32_t*)nullptr, sz, rocprim::plus<uint32_t>(), (hipStream_t)0, false);
-    if (e != hipSuccess) { cdc_set_error("eval_topk: rocprim size query failed: %s", hipGetErrorString(e)); return (int)e; }
-    L->temp_bytes = (int64_t)std::max(std::max(t_sort, t_pick), std::max(t_scan, t_kept));
-    L->total = L->temp + align_up(L->temp_bytes);
-    return 0;
+    MetTemp t;
+    t.sort_pairs<uint32_t>(sz);
+    if (has_item) t.scan<TopkPick>(TopkPickIt(rocprim::counting_iterator<uint32_t>(0), TopkPickIn{nullptr, nullptr, nullptr}), sz, TopkPickOp());
+    t.scan<TopkScan>(TopkScanIt(rocprim::counting_iterator<uint32_t>(0), TopkScanIn{nullptr}), sz, TopkScanOp());
+    t.scan<uint32_t>(TopkKeptIt(rocprim::counting_iterator<uint32_t>(0), TopkKeptIn{nullptr, nullptr, 1u}), sz, rocprim::plus<uint32_t>());
+    return t.done("eval_topk", &L->m);
 }
 // n_domain * n_user group ids must fit the upper half of a key
 static bool topk_sizes_ok(int64_t n, int32_t n_domain, int64_t n_user) {
@@ -967,8 +1034,9 @@ static bool topk_sizes_ok(int64_t n, int32_t n_domain, int64_t n_user) {
 extern "C" int64_t cdc_eval_topk_workspace_bytes(int64_t n, int32_t n_domain, int64_t n_user, int32_t has_item) {
     if (!topk_sizes_ok(n, n_domain, n_user)) return 0;
     TopkLayout L;
-    if (topk_layout(n, has_item != 0, &L) != 0) return -1;
-    return L.total;
+    topk_fixed_layout(n, has_item != 0, &L);
+    if (topk_temp(n, has_item != 0, &L) != 0) return -1;
+    return L.m.total;
 }
 
 extern "C" int cdc_eval_topk(const float* pred, const int32_t* user, int64_t ld_user, int64_t n_user, const int32_t* domain,
@@ -981,23 +1049,20 @@ extern "C" int cdc_eval_topk(const float* pred, const int32_t* user, int64_t ld_
     CDC_CHECK_ARG(n > 0 && n < (1ll << 31) && n_domain > 0 && n_user > 0 && ld_user >= 0 && ld_domain >= 0 && ld_item >= 0, CDC_E_BADARG,
                   "eval_topk: bad sizes n=%ld n_domain=%d n_user=%ld", (long)n, n_domain, (long)n_user);
     CDC_CHECK_ARG(k >= 1, CDC_E_BADARG, "eval_topk: k=%d, a list holds at least one row", k);
-    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_topk: n_domain=%d needs the domain column", n_domain);
+    MET_TRY(met_need_domain("eval_topk", domain, n_domain));
     CDC_CHECK_ARG(topk_sizes_ok(n, n_domain, n_user), CDC_E_BADARG, "eval_topk: n_domain * n_user = %ld * %ld group ids exceed 2^32",
                   (long)n_domain, (long)n_user);
-    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_topk: workspace must be 256-byte aligned");
     const int32_t has_item = item != nullptr;
     TopkLayout L;
     topk_fixed_layout(n, has_item, &L);
-    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_topk: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
-    int rc = topk_layout(n, has_item, &L);
-    if (rc != 0) return rc;
-    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_topk: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
-    char* base = (char*)workspace;
-    uint64_t* keys_a = (uint64_t*)(base + L.keys_a);
-    uint64_t* keys_b = (uint64_t*)(base + L.keys_b);
-    uint32_t* rows_a = (uint32_t*)(base + L.rows_a);
-    uint32_t* rows_b = (uint32_t*)(base + L.rows_b);
-    uint32_t* kept = (uint32_t*)(base + L.kept);
+    MET_TRY(met_gate("eval_topk", workspace, workspace_bytes, &L.m, [&] { return topk_temp(n, has_item, &L); }));
+    const MetWs ws{(char*)workspace};
+    char* base = ws.base;
+    uint64_t* keys_a = ws.ptr<uint64_t>(L.m.keys_in);
+    uint64_t* keys_b = ws.ptr<uint64_t>(L.m.keys_out);
+    uint32_t* rows_a = ws.ptr<uint32_t>(L.m.pay_in);
+    uint32_t* rows_b = ws.ptr<uint32_t>(L.m.pay_out);
+    uint32_t* kept = ws.ptr<uint32_t>(L.kept);
     hipStream_t st = (hipStream_t)stream;
     const size_t sz = (size_t)n;
     const int blocks = (int)std::min<int64_t>(cdc_ceil_div(n, MET_THREADS), 4096);
@@ -1010,30 +1075,26 @@ extern "C" int cdc_eval_topk(const float* pred, const int32_t* user, int64_t ld_
         hipLaunchKernelGGL(k_topk_keys<false>, dim3(blocks), dim3(MET_THREADS), 0, st, pred, user, ld_user, n_user, domain, ld_domain, n_domain,
                            item, ld_item, n, keys_a, rows_a, err_flag);
     CDC_LAUNCH_CHECK("eval_topk(keys)");
-    temp_bytes = (size_t)L.temp_bytes;
-    e = rocprim::radix_sort_pairs(base + L.temp, temp_bytes, (const uint64_t*)keys_a, keys_b, (const uint32_t*)rows_a, rows_b, sz, 0, 64, st,
-                                  false);
-    if (e != hipSuccess) { cdc_set_error("eval_topk: radix sort failed: %s", hipGetErrorString(e)); return (int)e; }
+    MET_TRY(met_sort("eval_topk", base, L.m, (const uint32_t*)rows_a, rows_b, sz, 64, st));
     if (has_item) {
-        TopkPick* pick = (TopkPick*)(base + L.scan);
-        temp_bytes = (size_t)L.temp_bytes;
-        e = rocprim::inclusive_scan(base + L.temp, temp_bytes, TopkPickIt(rocprim::counting_iterator<uint32_t>(0), TopkPickIn{keys_b, rows_b, pred}),
+        TopkPick* pick = ws.ptr<TopkPick>(L.scan);
+        temp_bytes = (size_t)L.m.temp_bytes;
+        e = rocprim::inclusive_scan(base + L.m.temp, temp_bytes, TopkPickIt(rocprim::counting_iterator<uint32_t>(0), TopkPickIn{keys_b, rows_b, pred}),
                                     pick, sz, TopkPickOp(), st, false);
         if (e != hipSuccess) { cdc_set_error("eval_topk: pick scan failed: %s", hipGetErrorString(e)); return (int)e; }
         hipLaunchKernelGGL(k_topk_rekey, dim3(blocks), dim3(MET_THREADS), 0, st, keys_b, rows_b, pick, n, keys_a, rows_a);
         CDC_LAUNCH_CHECK("eval_topk(rekey)");
-        temp_bytes = (size_t)L.temp_bytes;
-        e = rocprim::radix_sort_pairs(base + L.temp, temp_bytes, (const uint64_t*)keys_a, keys_b, (const uint32_t*)rows_a, rows_b, sz, 0, 64,
-                                      st, false);
+        temp_bytes = (size_t)L.m.temp_bytes;
+        e = met_radix(base + L.m.temp, temp_bytes, (const uint64_t*)keys_a, keys_b, (const uint32_t*)rows_a, rows_b, sz, 64, st);
         if (e != hipSuccess) { cdc_set_error("eval_topk: score sort failed: %s", hipGetErrorString(e)); return (int)e; }
     }
-    TopkScan* sc = (TopkScan*)(base + L.scan);
-    temp_bytes = (size_t)L.temp_bytes;
-    e = rocprim::inclusive_scan(base + L.temp, temp_bytes, TopkScanIt(rocprim::counting_iterator<uint32_t>(0), TopkScanIn{keys_b}), sc, sz,
+    TopkScan* sc = ws.ptr<TopkScan>(L.scan);
+    temp_bytes = (size_t)L.m.temp_bytes;
+    e = rocprim::inclusive_scan(base + L.m.temp, temp_bytes, TopkScanIt(rocprim::counting_iterator<uint32_t>(0), TopkScanIn{keys_b}), sc, sz,
                                 TopkScanOp(), st, false);
     if (e != hipSuccess) { cdc_set_error("eval_topk: group scan failed: %s", hipGetErrorString(e)); return (int)e; }
-    temp_bytes = (size_t)L.temp_bytes;
-    e = rocprim::inclusive_scan(base + L.temp, temp_bytes, TopkKeptIt(rocprim::counting_iterator<uint32_t>(0), TopkKeptIn{keys_b, sc, (uint32_t)k}),
+    temp_bytes = (size_t)L.m.temp_bytes;
+    e = rocprim::inclusive_scan(base + L.m.temp, temp_bytes, TopkKeptIt(rocprim::counting_iterator<uint32_t>(0), TopkKeptIn{keys_b, sc, (uint32_t)k}),
                                 kept, sz, rocprim::plus<uint32_t>(), st, false);
     if (e != hipSuccess) { cdc_set_error("eval_topk: offset scan failed: %s", hipGetErrorString(e)); return (int)e; }
     hipLaunchKernelGGL(k_topk_emit, dim3(blocks), dim3(MET_THREADS), 0, st, keys_b, rows_b, sc, kept, pred, n_user, (uint32_t)k, n, n_out,
@@ -1081,7 +1142,7 @@ __global__ void __launch_bounds__(SEGS_THREADS) k_eval_segments(const float* __r
             if (i >= s1) continue;
             const float t = (float)y[q];
             acc += (double)((t - 1.f) * fmaxf(log1pf(-x[q]), -100.f) - t * fmaxf(logf(x[q]), -100.f));
-            if (err && (x[q] != x[q] || (y[q] != 0 && y[q] != 1))) atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
+            if (err && (x[q] != x[q] || (y[q] != 0 && y[q] != 1))) met_flag_row(err, i);
             if (sel_pred) sel_pred[i] = x[q];
             if (seg_of_row) seg_of_row[i] = s;
         }
@@ -1168,14 +1229,10 @@ __global__ void __launch_bounds__(MET_THREADS) k_delong_keys(const float* __rest
         int32_t d = domain ? domain[i * ld_domain] : 0;
         const int16_t y = label[i];
         if (p != p || d < 0 || d >= n_domain || (y != 0 && y != 1)) {
-            if (err) atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
-            d = d < 0 ? 0 : (d >= n_domain ? n_domain - 1 : d);
+            if (err) met_flag_row(err, i);
+            d = met_clamp_id(d, n_domain);
         }
-        const uint32_t sk = score_key(p);
-        keys[i] = ((uint64_t)(uint32_t)d << 32) | sk;
-        keys[n + i] = ((uint64_t)(uint32_t)n_domain << 32) | sk;
-        idx[i] = (uint32_t)i;
-        idx[n + i] = (uint32_t)(n + i);
+        met_write_pair(keys, idx, n, i, (uint32_t)d, (uint32_t)n_domain, 32, score_key(p), (uint32_t)i, (uint32_t)(n + i));
     }
 }
 
@@ -1183,7 +1240,7 @@ __global__ void __launch_bounds__(MET_THREADS) k_delong_keys(const float* __rest
 __global__ void k_delong_starts(const uint64_t* __restrict__ keys, int64_t n2, int32_t n_seg, int64_t* __restrict__ start,
                                 unsigned long long* __restrict__ acc) {
     const int d = blockIdx.x * blockDim.x + threadIdx.x;
-    if (d <= n_seg) start[d] = d == n_seg ? n2 : lower_bound_u64(keys, 0, n2, (uint64_t)(uint32_t)d << 32);
+    if (d <= n_seg) start[d] = met_seg_start(keys, n2, d, n_seg, (uint64_t)(uint32_t)d << 32);
     if (d < n_seg && acc)
         for (int k = 0; k < 2 * DL_NSUM; ++k) acc[(int64_t)d * 2 * DL_NSUM + k] = 0ull;
 }
@@ -1327,72 +1384,57 @@ __global__ void k_delong_final(const int64_t* __restrict__ start, const DlScan* 
 }
 
 struct DelongLayout {
-    int64_t keys_in, keys_out, idx_in, idx_out, pl_b, start, acc, temp, temp_bytes, total;
+    MetLayout m;                        // once the sort has run, keys_in holds the scan's (f, cp) and pay_in runend
+    int64_t pl_b, acc;
 };
-// everything but rocPRIM's temporary storage: plain arithmetic (argument checks use it before any HIP or rocPRIM call)
 static void delong_fixed_layout(int64_t n, int32_t n_domain, int32_t paired, DelongLayout* L) {
     const int64_t n2 = 2 * n, seg = (int64_t)n_domain + 1;
-    int64_t off = 0;
-    L->keys_in = off;  off += align_up(n2 * 8);               // after the sort: the scan's (f, cp)
-    L->keys_out = off; off += align_up(n2 * 8);
-    L->idx_in = off;   off += align_up(n2 * 4);               // after the sort: runend
-    L->idx_out = off;  off += align_up(n2 * 4);
-    L->pl_b = off;     off += paired ? align_up(n2 * 4) : 0;
-    L->start = off;    off += align_up((seg + 1) * 8);
-    L->acc = off;      off += align_up(seg * 2 * DL_NSUM * 8);
-    L->temp = off;
-    L->temp_bytes = 0;
-    L->total = off;
+    MetCursor c;
+    L->m.keys(c, n2, 4);
+    L->pl_b = c.take(paired ? n2 * 4 : 0);
+    L->m.starts(c, seg);
+    L->acc = c.take(seg * 2 * DL_NSUM * 8);
+    L->m.end_fixed(c);
 }
-static int delong_layout(int64_t n, int32_t n_domain, int32_t paired, DelongLayout* L) {
-    delong_fixed_layout(n, n_domain, paired, L);
+static int delong_temp(int64_t n, DelongLayout* L) {
     const size_t n2 = (size_t)(2 * n);
-    size_t t_sort = 0, t_scan = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, t_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr,
-                                             (uint32_t*)nullptr, n2, 0, 64, (hipStream_t)0, false);
-    if (e == hipSuccess)
-        e = rocprim::inclusive_scan(nullptr, t_scan, DlScanIt(rocprim::counting_iterator<uint32_t>(0), DlScanIn{nullptr, nullptr, nullptr, 0u}),
-                                    (DlScan*)nullptr, n2, DlScanOp(), (hipStream_t)0, false);
-    if (e != hipSuccess) { cdc_set_error("eval_auc_delong: rocprim size query failed: %s", hipGetErrorString(e)); return (int)e; }
-    L->temp_bytes = (int64_t)std::max(t_sort, t_scan);        // the two run one after the other
-    L->total = L->temp + align_up(L->temp_bytes);
-    return 0;
+    MetTemp t;
+    t.sort_pairs<uint32_t>(n2);
+    t.scan<DlScan>(DlScanIt(rocprim::counting_iterator<uint32_t>(0), DlScanIn{nullptr, nullptr, nullptr, 0u}), n2, DlScanOp());
+    return t.done("eval_auc_delong", &L->m);
 }
 static bool delong_sizes_ok(int64_t n, int32_t n_domain) { return n > 0 && n < (1ll << 31) && n_domain > 0 && n_domain < (1 << 20); }
 
 extern "C" int64_t cdc_eval_auc_delong_workspace_bytes(int64_t n, int32_t n_domain, int32_t paired) {
     if (!delong_sizes_ok(n, n_domain)) return 0;
     DelongLayout L;
-    if (delong_layout(n, n_domain, paired != 0, &L) != 0) return -1;
-    return L.total;
+    delong_fixed_layout(n, n_domain, paired != 0, &L);
+    if (delong_temp(n, &L) != 0) return -1;
+    return L.m.total;
 }
 
 // sort one score vector's 2n keys, scan them, mark the tie runs' ends: leaves keys_out, idx_out, sc, runend and start describing it
 static int delong_order(const float* pred, const int16_t* label, const int32_t* domain, int64_t ld_domain, int64_t n, int32_t n_domain,
-                        int32_t* err_flag, char* base, const DelongLayout& L, unsigned long long* acc, hipStream_t st) {
-    uint64_t* keys_in = (uint64_t*)(base + L.keys_in);
-    uint64_t* keys_out = (uint64_t*)(base + L.keys_out);
-    uint32_t* idx_in = (uint32_t*)(base + L.idx_in);
-    uint32_t* idx_out = (uint32_t*)(base + L.idx_out);
+                        int32_t* err_flag, const MetWs& ws, const DelongLayout& L, unsigned long long* acc, hipStream_t st) {
+    char* base = ws.base;
+    uint64_t* keys_in = ws.ptr<uint64_t>(L.m.keys_in);
+    uint64_t* keys_out = ws.ptr<uint64_t>(L.m.keys_out);
+    uint32_t* idx_in = ws.ptr<uint32_t>(L.m.pay_in);
+    uint32_t* idx_out = ws.ptr<uint32_t>(L.m.pay_out);
     DlScan* sc = (DlScan*)keys_in;                                  // the unsorted keys and payloads are dead once the sort has run
     uint32_t* runend = idx_in;
-    int64_t* start = (int64_t*)(base + L.start);
+    int64_t* start = ws.ptr<int64_t>(L.m.start);
     const int64_t n2 = 2 * n;
     const int seg = n_domain + 1;
     int blocks = (int)std::min<int64_t>(cdc_ceil_div(n, MET_THREADS), 4096);
     hipLaunchKernelGGL(k_delong_keys, dim3(blocks), dim3(MET_THREADS), 0, st, pred, label, domain, ld_domain, n, n_domain, keys_in, idx_in,
                        err_flag);
     CDC_LAUNCH_CHECK("eval_auc_delong(keys)");
-    int end_bit = 33;
-    while (end_bit < 64 && ((uint64_t)n_domain >> (end_bit - 32)) != 0) ++end_bit;
-    size_t temp_bytes = (size_t)L.temp_bytes;
-    hipError_t e = rocprim::radix_sort_pairs(base + L.temp, temp_bytes, (const uint64_t*)keys_in, keys_out, (const uint32_t*)idx_in, idx_out,
-                                             (size_t)n2, 0, end_bit, st, false);
-    if (e != hipSuccess) { cdc_set_error("eval_auc_delong: radix sort failed: %s", hipGetErrorString(e)); return (int)e; }
+    MET_TRY(met_sort("eval_auc_delong", base, L.m, (const uint32_t*)idx_in, idx_out, (size_t)n2, met_end_bit((uint64_t)n_domain, 32), st));
     hipLaunchKernelGGL(k_delong_starts, dim3((int)cdc_ceil_div(seg + 1, 64)), dim3(64), 0, st, keys_out, n2, seg, start, acc);
     CDC_LAUNCH_CHECK("eval_auc_delong(starts)");
-    temp_bytes = (size_t)L.temp_bytes;
-    e = rocprim::inclusive_scan(base + L.temp, temp_bytes,
+    size_t temp_bytes = (size_t)L.m.temp_bytes;
+    hipError_t e = rocprim::inclusive_scan(base + L.m.temp, temp_bytes,
                                 DlScanIt(rocprim::counting_iterator<uint32_t>(0), DlScanIn{keys_out, idx_out, label, (uint32_t)n}), sc,
                                 (size_t)n2, DlScanOp(), st, false);
     if (e != hipSuccess) { cdc_set_error("eval_auc_delong: scan failed: %s", hipGetErrorString(e)); return (int)e; }
@@ -1408,36 +1450,30 @@ extern "C" int cdc_eval_auc_delong(const float* pred_a, const float* pred_b, con
     CDC_CHECK_ARG(pred_a && label && out && counts && workspace, CDC_E_BADARG, "eval_auc_delong: null pointer");
     CDC_CHECK_ARG(n > 0 && n_domain > 0 && n_domain < (1 << 20) && ld_domain >= 0, CDC_E_BADARG,
                   "eval_auc_delong: bad sizes n=%ld n_domain=%d ld_domain=%ld", (long)n, n_domain, (long)ld_domain);
-    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_auc_delong: n_domain=%d needs the domain column", n_domain);
+    MET_TRY(met_need_domain("eval_auc_delong", domain, n_domain));
     CDC_CHECK_ARG(n < (1ll << 31), CDC_E_TOOBIG, "eval_auc_delong: n=%ld exceeds the 2^31 rows a placement counts in 32 bits", (long)n);
-    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_auc_delong: workspace must be 256-byte aligned");
     const int32_t paired = pred_b != nullptr;
     DelongLayout L;
     delong_fixed_layout(n, n_domain, paired, &L);
-    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_auc_delong: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
-    int rc = delong_layout(n, n_domain, paired, &L);
-    if (rc != 0) return rc;
-    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_auc_delong: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
-    char* base = (char*)workspace;
-    const uint64_t* keys = (const uint64_t*)(base + L.keys_out);
-    const uint32_t* idx = (const uint32_t*)(base + L.idx_out);
-    const DlScan* sc = (const DlScan*)(base + L.keys_in);
-    const uint32_t* runend = (const uint32_t*)(base + L.idx_in);
-    uint32_t* pl_b = (uint32_t*)(base + L.pl_b);
-    const int64_t* start = (const int64_t*)(base + L.start);
-    unsigned long long* acc = (unsigned long long*)(base + L.acc);
+    MET_TRY(met_gate("eval_auc_delong", workspace, workspace_bytes, &L.m, [&] { return delong_temp(n, &L); }));
+    const MetWs ws{(char*)workspace};
+    const uint64_t* keys = ws.ptr<const uint64_t>(L.m.keys_out);
+    const uint32_t* idx = ws.ptr<const uint32_t>(L.m.pay_out);
+    const DlScan* sc = ws.ptr<const DlScan>(L.m.keys_in);
+    const uint32_t* runend = ws.ptr<const uint32_t>(L.m.pay_in);
+    uint32_t* pl_b = ws.ptr<uint32_t>(L.pl_b);
+    const int64_t* start = ws.ptr<const int64_t>(L.m.start);
+    unsigned long long* acc = ws.ptr<unsigned long long>(L.acc);
     hipStream_t st = (hipStream_t)stream;
     const int64_t n2 = 2 * n;
     const int seg = n_domain + 1;
     if (paired) {                                                   // the second vector first: its placements wait in pl_b
-        rc = delong_order(pred_b, label, domain, ld_domain, n, n_domain, err_flag, base, L, nullptr, st);
-        if (rc != 0) return rc;
+        MET_TRY(delong_order(pred_b, label, domain, ld_domain, n, n_domain, err_flag, ws, L, nullptr, st));
         const int blocks = (int)std::min<int64_t>(cdc_ceil_div(n2, MET_THREADS), 8192);
         hipLaunchKernelGGL(k_delong_place, dim3(blocks), dim3(MET_THREADS), 0, st, keys, idx, sc, runend, start, n2, pl_b);
         CDC_LAUNCH_CHECK("eval_auc_delong(place)");
     }
-    rc = delong_order(pred_a, label, domain, ld_domain, n, n_domain, err_flag, base, L, acc, st);
-    if (rc != 0) return rc;
+    MET_TRY(delong_order(pred_a, label, domain, ld_domain, n, n_domain, err_flag, ws, L, acc, st));
     const int blocks = (int)cdc_ceil_div(n2, DL_THREADS * DL_ITEMS);
     if (paired)
         hipLaunchKernelGGL(k_delong_reduce<true>, dim3(blocks), dim3(DL_THREADS), 0, st, keys, idx, sc, runend, (const uint32_t*)pl_b, start, n2, acc);
@@ -1476,14 +1512,10 @@ __global__ void __launch_bounds__(MET_THREADS) k_lossci_keys(const float* __rest
         bool bad = !(p >= 0.f && p <= 1.f) || (y != 0 && y != 1);           // a NaN too
         if (pred_b) { const float q = pred_b[i]; bad = bad || !(q >= 0.f && q <= 1.f); }
         if (bad || d < 0 || d >= n_domain) {
-            if (err) atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
-            d = d < 0 ? 0 : (d >= n_domain ? n_domain - 1 : d);
+            if (err) met_flag_row(err, i);
+            d = met_clamp_id(d, n_domain);
         }
-        const uint32_t sk = score_key(p);
-        keys[i] = ((uint64_t)(uint32_t)d << 32) | sk;
-        keys[n + i] = ((uint64_t)(uint32_t)n_domain << 32) | sk;
-        idx[i] = (uint32_t)i;
-        idx[n + i] = (uint32_t)(n + i);
+        met_write_pair(keys, idx, n, i, (uint32_t)d, (uint32_t)n_domain, 32, score_key(p), (uint32_t)i, (uint32_t)(n + i));
     }
 }
 
@@ -1572,38 +1604,30 @@ __global__ void __launch_bounds__(MET_LOSS_THREADS) k_lossci(const uint64_t* __r
 }
 
 struct LossCiLayout {
-    int64_t keys_in, keys_out, idx_in, idx_out, term_b, start, temp, temp_bytes, total;
+    MetLayout m;                        // once the sort has run, keys_in holds the first vector's terms
+    int64_t term_b;
 };
-// everything but rocPRIM's temporary storage: plain arithmetic (argument checks use it before any HIP or rocPRIM call)
 static void lossci_fixed_layout(int64_t n, int32_t n_domain, int32_t paired, LossCiLayout* L) {
-    const int64_t n2 = 2 * n, seg = (int64_t)n_domain + 1;
-    int64_t off = 0;
-    L->keys_in = off;  off += align_up(n2 * 8);               // after the sort: the first vector's terms
-    L->keys_out = off; off += align_up(n2 * 8);
-    L->idx_in = off;   off += align_up(n2 * 4);
-    L->idx_out = off;  off += align_up(n2 * 4);
-    L->term_b = off;   off += paired ? align_up(n2 * 8) : 0;
-    L->start = off;    off += align_up((seg + 1) * 8);
-    L->temp = off;
-    L->temp_bytes = 0;
-    L->total = off;
+    const int64_t n2 = 2 * n;
+    MetCursor c;
+    L->m.keys(c, n2, 4);
+    L->term_b = c.take(paired ? n2 * 8 : 0);
+    L->m.starts(c, (int64_t)n_domain + 1);
+    L->m.end_fixed(c);
 }
-static int lossci_layout(int64_t n, int32_t n_domain, int32_t paired, LossCiLayout* L) {
-    lossci_fixed_layout(n, n_domain, paired, L);
-    size_t t_sort = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, t_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr,
-                                             (uint32_t*)nullptr, (size_t)(2 * n), 0, 64, (hipStream_t)0, false);
-    if (e != hipSuccess) { cdc_set_error("eval_loss_ci: rocprim size query failed: %s", hipGetErrorString(e)); return (int)e; }
-    L->temp_bytes = (int64_t)t_sort;
-    L->total = L->temp + align_up(L->temp_bytes);
-    return 0;
+// rocPRIM's temporary storage of a call whose only rocPRIM work is one sort of 2n keys with 32-bit payloads
+static int met_pairs32_temp(int64_t n, const char* what, MetLayout* m) {
+    MetTemp t;
+    t.sort_pairs<uint32_t>((size_t)(2 * n));
+    return t.done(what, m);
 }
 
 extern "C" int64_t cdc_eval_loss_ci_workspace_bytes(int64_t n, int32_t n_domain, int32_t paired) {
     if (!delong_sizes_ok(n, n_domain)) return 0;
     LossCiLayout L;
-    if (lossci_layout(n, n_domain, paired != 0, &L) != 0) return -1;
-    return L.total;
+    lossci_fixed_layout(n, n_domain, paired != 0, &L);
+    if (met_pairs32_temp(n, "eval_loss_ci", &L.m) != 0) return -1;
+    return L.m.total;
 }
 
 extern "C" int cdc_eval_loss_ci(const float* pred_a, const float* pred_b, const int16_t* label, const int32_t* domain, int64_t ld_domain,
@@ -1612,24 +1636,20 @@ extern "C" int cdc_eval_loss_ci(const float* pred_a, const float* pred_b, const 
     CDC_CHECK_ARG(pred_a && label && out && counts && workspace, CDC_E_BADARG, "eval_loss_ci: null pointer");
     CDC_CHECK_ARG(n > 0 && n_domain > 0 && n_domain < (1 << 20) && ld_domain >= 0, CDC_E_BADARG,
                   "eval_loss_ci: bad sizes n=%ld n_domain=%d ld_domain=%ld", (long)n, n_domain, (long)ld_domain);
-    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_loss_ci: n_domain=%d needs the domain column", n_domain);
+    MET_TRY(met_need_domain("eval_loss_ci", domain, n_domain));
     CDC_CHECK_ARG(n < (1ll << 31), CDC_E_TOOBIG, "eval_loss_ci: n=%ld exceeds the 2^31 rows a sorted position counts in 32 bits", (long)n);
-    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_loss_ci: workspace must be 256-byte aligned");
     const int32_t paired = pred_b != nullptr;
     LossCiLayout L;
     lossci_fixed_layout(n, n_domain, paired, &L);
-    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_loss_ci: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
-    int rc = lossci_layout(n, n_domain, paired, &L);
-    if (rc != 0) return rc;
-    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_loss_ci: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
-    char* base = (char*)workspace;
-    uint64_t* keys_in = (uint64_t*)(base + L.keys_in);
-    uint64_t* keys_out = (uint64_t*)(base + L.keys_out);
-    uint32_t* idx_in = (uint32_t*)(base + L.idx_in);
-    uint32_t* idx_out = (uint32_t*)(base + L.idx_out);
+    MET_TRY(met_gate("eval_loss_ci", workspace, workspace_bytes, &L.m, [&] { return met_pairs32_temp(n, "eval_loss_ci", &L.m); }));
+    const MetWs ws{(char*)workspace};
+    uint64_t* keys_in = ws.ptr<uint64_t>(L.m.keys_in);
+    uint64_t* keys_out = ws.ptr<uint64_t>(L.m.keys_out);
+    uint32_t* idx_in = ws.ptr<uint32_t>(L.m.pay_in);
+    uint32_t* idx_out = ws.ptr<uint32_t>(L.m.pay_out);
     double* term_a = (double*)keys_in;                              // the unsorted keys are dead once the sort has run
-    double* term_b = (double*)(base + L.term_b);
-    int64_t* start = (int64_t*)(base + L.start);
+    double* term_b = ws.ptr<double>(L.term_b);
+    int64_t* start = ws.ptr<int64_t>(L.m.start);
     hipStream_t st = (hipStream_t)stream;
     const int64_t n2 = 2 * n;
     const int seg = n_domain + 1;
@@ -1637,12 +1657,7 @@ extern "C" int cdc_eval_loss_ci(const float* pred_a, const float* pred_b, const 
     hipLaunchKernelGGL(k_lossci_keys, dim3(blocks), dim3(MET_THREADS), 0, st, pred_a, pred_b, label, domain, ld_domain, n, n_domain, keys_in,
                        idx_in, err_flag);
     CDC_LAUNCH_CHECK("eval_loss_ci(keys)");
-    int end_bit = 33;
-    while (end_bit < 64 && ((uint64_t)n_domain >> (end_bit - 32)) != 0) ++end_bit;
-    size_t temp_bytes = (size_t)L.temp_bytes;
-    hipError_t e = rocprim::radix_sort_pairs(base + L.temp, temp_bytes, (const uint64_t*)keys_in, keys_out, (const uint32_t*)idx_in, idx_out,
-                                             (size_t)n2, 0, end_bit, st, false);
-    if (e != hipSuccess) { cdc_set_error("eval_loss_ci: radix sort failed: %s", hipGetErrorString(e)); return (int)e; }
+    MET_TRY(met_sort("eval_loss_ci", ws.base, L.m, (const uint32_t*)idx_in, idx_out, (size_t)n2, met_end_bit((uint64_t)n_domain, 32), st));
     hipLaunchKernelGGL(k_delong_starts, dim3((int)cdc_ceil_div(seg + 1, 64)), dim3(64), 0, st, (const uint64_t*)keys_out, n2, seg, start,
                        (unsigned long long*)nullptr);
     CDC_LAUNCH_CHECK("eval_loss_ci(starts)");
@@ -1754,34 +1769,27 @@ __global__ void __launch_bounds__(GAUC_SLICES) k_gauc_ci_final(const double* __r
 }
 
 struct GaucCiLayout {
-    GaucLayout g;                       // cdc_eval_gauc's arrays; g.temp / g.total lie behind the ones below
+    GaucLayout g;                       // cdc_eval_gauc's arrays; g.m.temp / g.m.total lie behind the ones below
     int64_t w_b, part_b, part_cnt_b, counts_b, part_sq;
 };
 static void gauc_ci_fixed_layout(int64_t n, int32_t n_domain, int32_t paired, GaucCiLayout* L) {
     const int64_t n2 = 2 * n, seg = (int64_t)n_domain + 1;
     gauc_fixed_layout(n, n_domain, &L->g);
-    int64_t off = L->g.temp;
-    L->w_b = off;        off += paired ? align_up(n2 * 8) : 0;
-    L->part_b = off;     off += paired ? align_up(seg * GAUC_SLICES * 2 * 8) : 0;
-    L->part_cnt_b = off; off += paired ? align_up(seg * GAUC_SLICES * 2 * 8) : 0;
-    L->counts_b = off;   off += paired ? align_up(seg * 2 * 8) : 0;
-    L->part_sq = off;    off += align_up(seg * GAUC_SLICES * 3 * 8);
-    L->g.temp = off;
-    L->g.total = off;
-}
-static int gauc_ci_layout(int64_t n, int32_t n_domain, int32_t paired, GaucCiLayout* L) {
-    gauc_ci_fixed_layout(n, n_domain, paired, L);
-    const int rc = gauc_temp_bytes(n, "eval_gauc_ci", &L->g.temp_bytes);
-    if (rc != 0) return rc;
-    L->g.total = L->g.temp + align_up(L->g.temp_bytes);
-    return 0;
+    MetCursor c{L->g.m.temp};
+    L->w_b = c.take(paired ? n2 * 8 : 0);
+    L->part_b = c.take(paired ? seg * GAUC_SLICES * 2 * 8 : 0);
+    L->part_cnt_b = c.take(paired ? seg * GAUC_SLICES * 2 * 8 : 0);
+    L->counts_b = c.take(paired ? seg * 2 * 8 : 0);
+    L->part_sq = c.take(seg * GAUC_SLICES * 3 * 8);
+    L->g.m.end_fixed(c);
 }
 
 extern "C" int64_t cdc_eval_gauc_ci_workspace_bytes(int64_t n, int32_t n_domain, int64_t n_user, int32_t paired) {
     if (!gauc_sizes_ok(n, n_domain, n_user)) return 0;
     GaucCiLayout L;
-    if (gauc_ci_layout(n, n_domain, paired != 0, &L) != 0) return -1;
-    return L.g.total;
+    gauc_ci_fixed_layout(n, n_domain, paired != 0, &L);
+    if (gauc_temp(n, "eval_gauc_ci", &L.g.m) != 0) return -1;
+    return L.g.m.total;
 }
 
 extern "C" int cdc_eval_gauc_ci(const float* pred_a, const float* pred_b, const int16_t* label, const int32_t* user, int64_t ld_user,
@@ -1791,39 +1799,34 @@ extern "C" int cdc_eval_gauc_ci(const float* pred_a, const float* pred_b, const 
     CDC_CHECK_ARG(pred_a && label && user && out && counts && workspace, CDC_E_BADARG, "eval_gauc_ci: null pointer");
     CDC_CHECK_ARG(n > 0 && n_domain > 0 && n_domain < (1 << 20) && n_user > 0 && ld_user >= 0 && ld_domain >= 0, CDC_E_BADARG,
                   "eval_gauc_ci: bad sizes n=%ld n_domain=%d n_user=%ld", (long)n, n_domain, (long)n_user);
-    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_gauc_ci: n_domain=%d needs the domain column", n_domain);
+    MET_TRY(met_need_domain("eval_gauc_ci", domain, n_domain));
     CDC_CHECK_ARG(n < (1ll << 31), CDC_E_TOOBIG, "eval_gauc_ci: n=%ld exceeds the 2^31 rows a sorted position counts in 32 bits", (long)n);
     CDC_CHECK_ARG(gauc_sizes_ok(n, n_domain, n_user), CDC_E_BADARG,
                   "eval_gauc_ci: (n_domain + 1) * n_user = %ld * %ld group ids exceed 2^32", (long)n_domain + 1, (long)n_user);
-    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_gauc_ci: workspace must be 256-byte aligned");
     const int32_t paired = pred_b != nullptr;
     GaucCiLayout L;
     gauc_ci_fixed_layout(n, n_domain, paired, &L);
-    CDC_CHECK_ARG(workspace_bytes >= L.g.total, CDC_E_BADARG, "eval_gauc_ci: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.g.total);
-    int rc = gauc_ci_layout(n, n_domain, paired, &L);
-    if (rc != 0) return rc;
-    CDC_CHECK_ARG(workspace_bytes >= L.g.total, CDC_E_BADARG, "eval_gauc_ci: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.g.total);
-    char* base = (char*)workspace;
-    const uint64_t* keys = (const uint64_t*)(base + L.g.keys_out);
-    const GaucScan* sc = (const GaucScan*)(base + L.g.scan);
-    unsigned long long* W = (unsigned long long*)(base + L.g.keys_in);
-    unsigned long long* W_b = (unsigned long long*)(base + L.w_b);
-    const int64_t* start = (const int64_t*)(base + L.g.start);
-    double* part = (double*)(base + L.g.part);
-    int64_t* part_cnt = (int64_t*)(base + L.g.part_cnt);
-    double* part_b = (double*)(base + L.part_b);
-    int64_t* part_cnt_b = (int64_t*)(base + L.part_cnt_b);
-    int64_t* counts_b = (int64_t*)(base + L.counts_b);
-    double* part_sq = (double*)(base + L.part_sq);
+    MET_TRY(met_gate("eval_gauc_ci", workspace, workspace_bytes, &L.g.m, [&] { return gauc_temp(n, "eval_gauc_ci", &L.g.m); }));
+    const MetWs ws{(char*)workspace};
+    char* base = ws.base;
+    const uint64_t* keys = ws.ptr<const uint64_t>(L.g.m.keys_out);
+    const GaucScan* sc = ws.ptr<const GaucScan>(L.g.scan);
+    unsigned long long* W = ws.ptr<unsigned long long>(L.g.m.keys_in);
+    unsigned long long* W_b = ws.ptr<unsigned long long>(L.w_b);
+    const int64_t* start = ws.ptr<const int64_t>(L.g.m.start);
+    double* part = ws.ptr<double>(L.g.part);
+    int64_t* part_cnt = ws.ptr<int64_t>(L.g.part_cnt);
+    double* part_b = ws.ptr<double>(L.part_b);
+    int64_t* part_cnt_b = ws.ptr<int64_t>(L.part_cnt_b);
+    int64_t* counts_b = ws.ptr<int64_t>(L.counts_b);
+    double* part_sq = ws.ptr<double>(L.part_sq);
     hipStream_t st = (hipStream_t)stream;
     const int64_t n2 = 2 * n;
     const int seg = n_domain + 1;
     if (paired) {                                                   // the second vector first: of its order only W_b stays
-        rc = gauc_order(pred_b, label, user, ld_user, n_user, domain, ld_domain, n_domain, n, err_flag, base, L.g, W_b, "eval_gauc_ci", st);
-        if (rc != 0) return rc;
+        MET_TRY(gauc_order(pred_b, label, user, ld_user, n_user, domain, ld_domain, n_domain, n, err_flag, base, L.g, W_b, "eval_gauc_ci", st));
     }
-    rc = gauc_order(pred_a, label, user, ld_user, n_user, domain, ld_domain, n_domain, n, err_flag, base, L.g, W, "eval_gauc_ci", st);
-    if (rc != 0) return rc;
+    MET_TRY(gauc_order(pred_a, label, user, ld_user, n_user, domain, ld_domain, n_domain, n, err_flag, base, L.g, W, "eval_gauc_ci", st));
     hipLaunchKernelGGL(k_gauc_sum, dim3(seg, GAUC_SLICES), dim3(GAUC_THREADS), 0, st, keys, sc, (const unsigned long long*)W, start,
                        user_weight, n_user, n2, part, part_cnt);
     CDC_LAUNCH_CHECK("eval_gauc_ci(sum)");
@@ -1891,13 +1894,11 @@ __global__ void __launch_bounds__(MET_THREADS) k_calib_keys(const float* __restr
         const int16_t y = label[i];
         const bool bad_p = !(p >= 0.f && p <= 1.f);                       // a NaN too
         if (bad_p || d < 0 || d >= n_domain || (y != 0 && y != 1)) {
-            if (err) atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
-            d = d < 0 ? 0 : (d >= n_domain ? n_domain - 1 : d);
+            if (err) met_flag_row(err, i);
+            d = met_clamp_id(d, n_domain);
             if (bad_p) p = p > 1.f ? 1.f : 0.f;                           // the bins and q are only defined on [0, 1]
         }
-        const uint64_t low = ((uint64_t)score_key(p) << 1) | (uint64_t)(y != 0);
-        keys[i] = ((uint64_t)(uint32_t)d << 33) | low;
-        keys[n + i] = ((uint64_t)(uint32_t)n_domain << 33) | low;
+        met_write_pair(keys, n, i, (uint32_t)d, (uint32_t)n_domain, 33, ((uint64_t)score_key(p) << 1) | (uint64_t)(y != 0));
     }
 }
 
@@ -1906,7 +1907,7 @@ __global__ void __launch_bounds__(MET_THREADS) k_calib_starts(const uint64_t* __
                                                               int64_t* __restrict__ start, unsigned long long* __restrict__ acc_w,
                                                               unsigned long long* __restrict__ acc_q, unsigned long long* __restrict__ acc_seg) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t <= n_seg) start[t] = t == n_seg ? n2 : lower_bound_u64(keys, 0, n2, (uint64_t)t << 33);
+    if (t <= n_seg) start[t] = met_seg_start(keys, n2, t, n_seg, (uint64_t)t << 33);
     if (t < n_seg) acc_seg[2 * t] = acc_seg[2 * t + 1] = 0ull;
     if (t < n_cells) acc_w[2 * t] = acc_w[2 * t + 1] = acc_q[2 * t] = acc_q[2 * t + 1] = 0ull;
 }
@@ -2130,31 +2131,24 @@ __global__ void __launch_bounds__(CAL_THREADS) k_calib_final(const uint64_t* __r
 }
 
 struct CalibLayout {
-    int64_t keys_in, keys_out, start, acc_w, acc_q, acc_seg, temp, temp_bytes, total;
+    MetLayout m;
+    int64_t acc_w, acc_q, acc_seg;
 };
-// everything but rocPRIM's temporary storage: plain arithmetic (argument checks use it before any HIP or rocPRIM call)
 static void calib_fixed_layout(int64_t n, int32_t n_domain, int32_t n_bins, CalibLayout* L) {
-    const int64_t n2 = 2 * n, seg = (int64_t)n_domain + 1;
-    int64_t off = 0;
-    L->keys_in = off;  off += align_up(n2 * 8);
-    L->keys_out = off; off += align_up(n2 * 8);
-    L->start = off;    off += align_up((seg + 1) * 8);
-    L->acc_w = off;    off += align_up(seg * n_bins * 16);
-    L->acc_q = off;    off += align_up(seg * n_bins * 16);
-    L->acc_seg = off;  off += align_up(seg * 16);
-    L->temp = off;
-    L->temp_bytes = 0;
-    L->total = off;
+    const int64_t seg = (int64_t)n_domain + 1;
+    MetCursor c;
+    L->m.keys(c, 2 * n, 0);
+    L->m.starts(c, seg);
+    L->acc_w = c.take(seg * n_bins * 16);
+    L->acc_q = c.take(seg * n_bins * 16);
+    L->acc_seg = c.take(seg * 16);
+    L->m.end_fixed(c);
 }
-static int calib_layout(int64_t n, int32_t n_domain, int32_t n_bins, CalibLayout* L) {
-    calib_fixed_layout(n, n_domain, n_bins, L);
-    size_t t_sort = 0;
-    hipError_t e = rocprim::radix_sort_keys(nullptr, t_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr, (size_t)(2 * n), 0, 64,
-                                            (hipStream_t)0, false);
-    if (e != hipSuccess) { cdc_set_error("eval_calibration: rocprim size query failed: %s", hipGetErrorString(e)); return (int)e; }
-    L->temp_bytes = (int64_t)t_sort;
-    L->total = L->temp + align_up(L->temp_bytes);
-    return 0;
+// rocPRIM's temporary storage of a call whose only rocPRIM work is one sort of 2n keys without a payload
+static int met_keys_temp(int64_t n, const char* what, MetLayout* m) {
+    MetTemp t;
+    t.sort_keys((size_t)(2 * n));
+    return t.done(what, m);
 }
 static bool calib_sizes_ok(int64_t n, int32_t n_domain, int32_t n_bins) {
     return n > 0 && n < (1ll << 31) && n_domain > 0 && n_domain < (1 << 20) && n_bins >= 1 && n_bins <= CAL_MAX_BINS;
@@ -2163,8 +2157,9 @@ static bool calib_sizes_ok(int64_t n, int32_t n_domain, int32_t n_bins) {
 extern "C" int64_t cdc_eval_calibration_workspace_bytes(int64_t n, int32_t n_domain, int32_t n_bins) {
     if (!calib_sizes_ok(n, n_domain, n_bins)) return 0;
     CalibLayout L;
-    if (calib_layout(n, n_domain, n_bins, &L) != 0) return -1;
-    return L.total;
+    calib_fixed_layout(n, n_domain, n_bins, &L);
+    if (met_keys_temp(n, "eval_calibration", &L.m) != 0) return -1;
+    return L.m.total;
 }
 
 extern "C" int cdc_eval_calibration(const float* pred, const int16_t* label, const int32_t* domain, int64_t ld_domain, int64_t n,
@@ -2176,34 +2171,25 @@ extern "C" int cdc_eval_calibration(const float* pred, const int16_t* label, con
     CDC_CHECK_ARG(n > 0 && n_domain > 0 && n_domain < (1 << 20) && ld_domain >= 0, CDC_E_BADARG,
                   "eval_calibration: bad sizes n=%ld n_domain=%d ld_domain=%ld", (long)n, n_domain, (long)ld_domain);
     CDC_CHECK_ARG(n_bins >= 1 && n_bins <= CAL_MAX_BINS, CDC_E_BADARG, "eval_calibration: n_bins=%d outside [1, %d]", n_bins, CAL_MAX_BINS);
-    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_calibration: n_domain=%d needs the domain column", n_domain);
+    MET_TRY(met_need_domain("eval_calibration", domain, n_domain));
     CDC_CHECK_ARG(n < (1ll << 31), CDC_E_TOOBIG, "eval_calibration: n=%ld exceeds the 2^31 rows whose sums fit 64 bits", (long)n);
-    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_calibration: workspace must be 256-byte aligned");
     CalibLayout L;
     calib_fixed_layout(n, n_domain, n_bins, &L);
-    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_calibration: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
-    int rc = calib_layout(n, n_domain, n_bins, &L);
-    if (rc != 0) return rc;
-    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_calibration: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
-    char* base = (char*)workspace;
-    uint64_t* keys_in = (uint64_t*)(base + L.keys_in);
-    uint64_t* keys_out = (uint64_t*)(base + L.keys_out);
-    int64_t* start = (int64_t*)(base + L.start);
-    unsigned long long* acc_w = (unsigned long long*)(base + L.acc_w);
-    unsigned long long* acc_q = (unsigned long long*)(base + L.acc_q);
-    unsigned long long* acc_seg = (unsigned long long*)(base + L.acc_seg);
+    MET_TRY(met_gate("eval_calibration", workspace, workspace_bytes, &L.m, [&] { return met_keys_temp(n, "eval_calibration", &L.m); }));
+    const MetWs ws{(char*)workspace};
+    uint64_t* keys_out = ws.ptr<uint64_t>(L.m.keys_out);
+    int64_t* start = ws.ptr<int64_t>(L.m.start);
+    unsigned long long* acc_w = ws.ptr<unsigned long long>(L.acc_w);
+    unsigned long long* acc_q = ws.ptr<unsigned long long>(L.acc_q);
+    unsigned long long* acc_seg = ws.ptr<unsigned long long>(L.acc_seg);
     hipStream_t st = (hipStream_t)stream;
     const int64_t n2 = 2 * n, cells = ((int64_t)n_domain + 1) * n_bins;
     const int seg = n_domain + 1;
     int blocks = (int)std::min<int64_t>(cdc_ceil_div(n, MET_THREADS), 4096);
-    hipLaunchKernelGGL(k_calib_keys, dim3(blocks), dim3(MET_THREADS), 0, st, pred, label, domain, ld_domain, n, n_domain, keys_in, err_flag);
+    hipLaunchKernelGGL(k_calib_keys, dim3(blocks), dim3(MET_THREADS), 0, st, pred, label, domain, ld_domain, n, n_domain,
+                       ws.ptr<uint64_t>(L.m.keys_in), err_flag);
     CDC_LAUNCH_CHECK("eval_calibration(keys)");
-    // the sort only has to look at the bits a key can have: label + 32 score bits + the bits of n_domain
-    int end_bit = 34;
-    while (end_bit < 64 && ((uint64_t)n_domain >> (end_bit - 33)) != 0) ++end_bit;
-    size_t temp_bytes = (size_t)L.temp_bytes;
-    hipError_t e = rocprim::radix_sort_keys(base + L.temp, temp_bytes, (const uint64_t*)keys_in, keys_out, (size_t)n2, 0, end_bit, st, false);
-    if (e != hipSuccess) { cdc_set_error("eval_calibration: radix sort failed: %s", hipGetErrorString(e)); return (int)e; }
+    MET_TRY(met_sort("eval_calibration", ws.base, L.m, (size_t)n2, met_end_bit((uint64_t)n_domain, 33), st));     // low part: label + 32 score bits
     hipLaunchKernelGGL(k_calib_starts, dim3((int)cdc_ceil_div(std::max<int64_t>(seg + 1, cells), MET_THREADS)), dim3(MET_THREADS), 0, st,
                        keys_out, n2, seg, cells, start, acc_w, acc_q, acc_seg);
     CDC_LAUNCH_CHECK("eval_calibration(starts)");
@@ -2266,13 +2252,11 @@ __global__ void __launch_bounds__(MET_THREADS) k_iso_keys(const float* __restric
         const int16_t y = label[i];
         const bool bad_p = !(fabsf(p) <= 3.4028234663852886e38f);         // NaN, +inf, -inf
         if (bad_p || d < 0 || d >= n_domain || (y != 0 && y != 1)) {
-            if (err) atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
-            d = d < 0 ? 0 : (d >= n_domain ? n_domain - 1 : d);
+            if (err) met_flag_row(err, i);
+            d = met_clamp_id(d, n_domain);
             if (bad_p) p = 0.f;
         }
-        const uint64_t low = ((uint64_t)score_key(p) << 1) | (uint64_t)(y != 0);
-        keys[i] = ((uint64_t)(uint32_t)d << 33) | low;
-        keys[n + i] = ((uint64_t)(uint32_t)n_domain << 33) | low;
+        met_write_pair(keys, n, i, (uint32_t)d, (uint32_t)n_domain, 33, ((uint64_t)score_key(p) << 1) | (uint64_t)(y != 0));
     }
 }
 
@@ -2280,7 +2264,7 @@ __global__ void __launch_bounds__(MET_THREADS) k_iso_keys(const float* __restric
 __global__ void __launch_bounds__(MET_THREADS) k_iso_starts(const uint64_t* __restrict__ keys, int64_t n2, int32_t n_seg,
                                                             int64_t* __restrict__ pos) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t <= n_seg) pos[t] = t == n_seg ? n2 : lower_bound_u64(keys, 0, n2, (uint64_t)t << 33);
+    if (t <= n_seg) pos[t] = met_seg_start(keys, n2, t, n_seg, (uint64_t)t << 33);
 }
 
 // a < b < c by position: is the corner at b strictly convex (b stays a vertex between a and c)?
@@ -2481,37 +2465,28 @@ __global__ void __launch_bounds__(MET_THREADS) k_iso_segments(const IsoPt* __res
 }
 
 struct IsoLayout {
-    int64_t keys_in, keys_out, cp, pos, verts_a, verts_b, cnt_a, cnt_b, temp, temp_bytes, total, chunks;
+    MetLayout m;                        // m.start is pos
+    int64_t cp, verts_a, verts_b, cnt_a, cnt_b, chunks;
 };
-// everything but rocPRIM's temporary storage: plain arithmetic (argument checks use it before any HIP or rocPRIM call)
 static void iso_fixed_layout(int64_t n, int32_t n_domain, IsoLayout* L) {
-    const int64_t n2 = 2 * n, seg = (int64_t)n_domain + 1;
+    const int64_t n2 = 2 * n;
     L->chunks = (n2 + 1 + ISO_CHUNK - 1) / ISO_CHUNK;                      // the points 0 .. 2n
-    int64_t off = 0;
-    L->keys_in = off;  off += align_up(n2 * 8);
-    L->keys_out = off; off += align_up(n2 * 8);
-    L->cp = off;       off += align_up(n2 * 4);
-    L->pos = off;      off += align_up((seg + 1) * 8);
-    L->verts_a = off;  off += align_up(L->chunks * ISO_CHUNK * (int64_t)sizeof(IsoPt));
-    L->verts_b = off;  off += align_up(L->chunks * ISO_CHUNK * (int64_t)sizeof(IsoPt));
-    L->cnt_a = off;    off += align_up(L->chunks * 4);
-    L->cnt_b = off;    off += align_up(L->chunks * 4);
-    L->temp = off;
-    L->temp_bytes = 0;
-    L->total = off;
+    MetCursor c;
+    L->m.keys(c, n2, 0);
+    L->cp = c.take(n2 * 4);
+    L->m.starts(c, (int64_t)n_domain + 1);
+    L->verts_a = c.take(L->chunks * ISO_CHUNK * (int64_t)sizeof(IsoPt));
+    L->verts_b = c.take(L->chunks * ISO_CHUNK * (int64_t)sizeof(IsoPt));
+    L->cnt_a = c.take(L->chunks * 4);
+    L->cnt_b = c.take(L->chunks * 4);
+    L->m.end_fixed(c);
 }
-static int iso_layout(int64_t n, int32_t n_domain, IsoLayout* L) {
-    iso_fixed_layout(n, n_domain, L);
+static int iso_temp(int64_t n, IsoLayout* L) {
     const size_t n2 = (size_t)(2 * n);
-    size_t t_sort = 0, t_scan = 0;
-    hipError_t e = rocprim::radix_sort_keys(nullptr, t_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr, n2, 0, 64, (hipStream_t)0, false);
-    if (e == hipSuccess)
-        e = rocprim::inclusive_scan(nullptr, t_scan, IsoLabelIt(rocprim::counting_iterator<uint32_t>(0), IsoLabelIn{nullptr}),
-                                    (uint32_t*)nullptr, n2, rocprim::plus<uint32_t>(), (hipStream_t)0, false);
-    if (e != hipSuccess) { cdc_set_error("eval_isotonic_fit: rocprim size query failed: %s", hipGetErrorString(e)); return (int)e; }
-    L->temp_bytes = (int64_t)std::max(t_sort, t_scan);                     // the two run one after the other
-    L->total = L->temp + align_up(L->temp_bytes);
-    return 0;
+    MetTemp t;
+    t.sort_keys(n2);
+    t.scan<uint32_t>(IsoLabelIt(rocprim::counting_iterator<uint32_t>(0), IsoLabelIn{nullptr}), n2, rocprim::plus<uint32_t>());
+    return t.done("eval_isotonic_fit", &L->m);
 }
 static bool iso_sizes_ok(int64_t n, int32_t n_domain) { return n > 0 && n < (1ll << 31) && n_domain > 0 && n_domain < (1 << 20); }
 
@@ -2522,8 +2497,9 @@ extern "C" int64_t cdc_eval_isotonic_max_blocks(int64_t n, int32_t n_domain) {
 extern "C" int64_t cdc_eval_isotonic_fit_workspace_bytes(int64_t n, int32_t n_domain) {
     if (!iso_sizes_ok(n, n_domain)) return 0;
     IsoLayout L;
-    if (iso_layout(n, n_domain, &L) != 0) return -1;
-    return L.total;
+    iso_fixed_layout(n, n_domain, &L);
+    if (iso_temp(n, &L) != 0) return -1;
+    return L.m.total;
 }
 
 extern "C" int cdc_eval_isotonic_fit(const float* pred, const int16_t* label, const int32_t* domain, int64_t ld_domain, int64_t n,
@@ -2534,40 +2510,31 @@ extern "C" int cdc_eval_isotonic_fit(const float* pred, const int16_t* label, co
                   CDC_E_BADARG, "eval_isotonic_fit: null pointer");
     CDC_CHECK_ARG(n > 0 && n_domain > 0 && n_domain < (1 << 20) && ld_domain >= 0, CDC_E_BADARG,
                   "eval_isotonic_fit: bad sizes n=%ld n_domain=%d ld_domain=%ld", (long)n, n_domain, (long)ld_domain);
-    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_isotonic_fit: n_domain=%d needs the domain column", n_domain);
+    MET_TRY(met_need_domain("eval_isotonic_fit", domain, n_domain));
     CDC_CHECK_ARG(n < (1ll << 31), CDC_E_TOOBIG, "eval_isotonic_fit: n=%ld exceeds the 2^31 rows whose products fit 64 bits", (long)n);
     CDC_CHECK_ARG(cap >= 2 * n, CDC_E_BADARG, "eval_isotonic_fit: cap=%ld < 2n = %ld blocks", (long)cap, (long)(2 * n));
-    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_isotonic_fit: workspace must be 256-byte aligned");
     IsoLayout L;
     iso_fixed_layout(n, n_domain, &L);
-    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_isotonic_fit: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
-    int rc = iso_layout(n, n_domain, &L);
-    if (rc != 0) return rc;
-    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_isotonic_fit: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
-    char* base = (char*)workspace;
-    uint64_t* keys_in = (uint64_t*)(base + L.keys_in);
-    uint64_t* keys_out = (uint64_t*)(base + L.keys_out);
-    uint32_t* cp = (uint32_t*)(base + L.cp);
-    int64_t* pos = (int64_t*)(base + L.pos);
-    IsoPt* va = (IsoPt*)(base + L.verts_a);
-    IsoPt* vb = (IsoPt*)(base + L.verts_b);
-    uint32_t* na = (uint32_t*)(base + L.cnt_a);
-    uint32_t* nb = (uint32_t*)(base + L.cnt_b);
+    MET_TRY(met_gate("eval_isotonic_fit", workspace, workspace_bytes, &L.m, [&] { return iso_temp(n, &L); }));
+    const MetWs ws{(char*)workspace};
+    uint64_t* keys_out = ws.ptr<uint64_t>(L.m.keys_out);
+    uint32_t* cp = ws.ptr<uint32_t>(L.cp);
+    int64_t* pos = ws.ptr<int64_t>(L.m.start);
+    IsoPt* va = ws.ptr<IsoPt>(L.verts_a);
+    IsoPt* vb = ws.ptr<IsoPt>(L.verts_b);
+    uint32_t* na = ws.ptr<uint32_t>(L.cnt_a);
+    uint32_t* nb = ws.ptr<uint32_t>(L.cnt_b);
     hipStream_t st = (hipStream_t)stream;
     const int64_t n2 = 2 * n;
     const int seg = n_domain + 1;
     int blocks = (int)std::min<int64_t>(cdc_ceil_div(n, MET_THREADS), 4096);
-    hipLaunchKernelGGL(k_iso_keys, dim3(blocks), dim3(MET_THREADS), 0, st, pred, label, domain, ld_domain, n, n_domain, keys_in, err_flag);
+    hipLaunchKernelGGL(k_iso_keys, dim3(blocks), dim3(MET_THREADS), 0, st, pred, label, domain, ld_domain, n, n_domain,
+                       ws.ptr<uint64_t>(L.m.keys_in), err_flag);
     CDC_LAUNCH_CHECK("eval_isotonic_fit(keys)");
-    // the sort only has to look at the bits a key can have: label + 32 score bits + the bits of n_domain
-    int end_bit = 34;
-    while (end_bit < 64 && ((uint64_t)n_domain >> (end_bit - 33)) != 0) ++end_bit;
-    size_t temp_bytes = (size_t)L.temp_bytes;
-    hipError_t e = rocprim::radix_sort_keys(base + L.temp, temp_bytes, (const uint64_t*)keys_in, keys_out, (size_t)n2, 0, end_bit, st, false);
-    if (e != hipSuccess) { cdc_set_error("eval_isotonic_fit: radix sort failed: %s", hipGetErrorString(e)); return (int)e; }
-    temp_bytes = (size_t)L.temp_bytes;
-    e = rocprim::inclusive_scan(base + L.temp, temp_bytes, IsoLabelIt(rocprim::counting_iterator<uint32_t>(0), IsoLabelIn{keys_out}), cp,
-                                (size_t)n2, rocprim::plus<uint32_t>(), st, false);
+    MET_TRY(met_sort("eval_isotonic_fit", ws.base, L.m, (size_t)n2, met_end_bit((uint64_t)n_domain, 33), st));
+    size_t temp_bytes = (size_t)L.m.temp_bytes;
+    hipError_t e = rocprim::inclusive_scan(ws.base + L.m.temp, temp_bytes, IsoLabelIt(rocprim::counting_iterator<uint32_t>(0), IsoLabelIn{keys_out}),
+                                           cp, (size_t)n2, rocprim::plus<uint32_t>(), st, false);
     if (e != hipSuccess) { cdc_set_error("eval_isotonic_fit: label scan failed: %s", hipGetErrorString(e)); return (int)e; }
     hipLaunchKernelGGL(k_iso_starts, dim3((int)cdc_ceil_div(seg + 1, MET_THREADS)), dim3(MET_THREADS), 0, st, (const uint64_t*)keys_out, n2, seg, pos);
     CDC_LAUNCH_CHECK("eval_isotonic_fit(starts)");
@@ -2609,7 +2576,7 @@ __global__ void __launch_bounds__(MET_THREADS) k_iso_apply(const float* __restri
         if (s >= 0 && s <= n_domain) { b0 = start[s]; b1 = start[s + 1]; }
     }
     if (b1 <= b0) {                                                       // a NaN score, a domain outside range, a segment without blocks
-        if (err) atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
+        if (err) met_flag_row(err, i);
         out[i] = __uint_as_float(0x7fc00000u);
         return;
     }
@@ -2644,7 +2611,7 @@ extern "C" int cdc_eval_isotonic_apply(const float* pred, const int32_t* domain,
     CDC_CHECK_ARG(pred && seg_of_domain && start && x_lo && x_hi && value && out, CDC_E_BADARG, "eval_isotonic_apply: null pointer");
     CDC_CHECK_ARG(n > 0 && n_domain > 0 && n_domain < (1 << 20) && ld_domain >= 0 && eps >= 0.f && eps <= 0.5f, CDC_E_BADARG,
                   "eval_isotonic_apply: bad sizes n=%ld n_domain=%d ld_domain=%ld eps=%g", (long)n, n_domain, (long)ld_domain, (double)eps);
-    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_isotonic_apply: n_domain=%d needs the domain column", n_domain);
+    MET_TRY(met_need_domain("eval_isotonic_apply", domain, n_domain));
     CDC_CHECK_ARG(n < (1ll << 31), CDC_E_TOOBIG, "eval_isotonic_apply: n=%ld exceeds 2^31 rows", (long)n);
     hipLaunchKernelGGL(k_iso_apply, dim3((unsigned)cdc_ceil_div(n, MET_THREADS)), dim3(MET_THREADS), 0, (hipStream_t)stream, pred, domain,
                        ld_domain, n, n_domain, seg_of_domain, start, x_lo, x_hi, value, eps, out, err_flag);
@@ -2714,14 +2681,12 @@ __global__ void __launch_bounds__(MET_THREADS) k_platt_keys(const float* __restr
         bool positive = y == 1;
         const bool bad_p = input == 0 ? !(p >= 0.f && p <= 1.f) : p != p;
         if (bad_p || d < 0 || d >= n_domain || (y != 0 && y != 1)) {      // counted with z = 0, label 0, the domain clamped
-            if (err) atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
-            d = d < 0 ? 0 : (d >= n_domain ? n_domain - 1 : d);
+            if (err) met_flag_row(err, i);
+            d = met_clamp_id(d, n_domain);
             p = input == 0 ? 0.5f : 0.f;
             positive = false;
         }
-        const uint64_t low = ((uint64_t)score_key(p) << 1) | (uint64_t)positive;
-        keys[i] = ((uint64_t)(uint32_t)d << 33) | low;
-        keys[n + i] = ((uint64_t)(uint32_t)n_domain << 33) | low;
+        met_write_pair(keys, n, i, (uint32_t)d, (uint32_t)n_domain, 33, ((uint64_t)score_key(p) << 1) | (uint64_t)positive);
     }
 }
 
@@ -2731,7 +2696,7 @@ __global__ void __launch_bounds__(MET_THREADS) k_platt_starts(const uint64_t* __
                                                               uint32_t* __restrict__ cnt) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t > n_seg) return;
-    const int64_t p0 = t == n_seg ? n2 : lower_bound_u64(keys, 0, n2, (uint64_t)t << 33);
+    const int64_t p0 = met_seg_start(keys, n2, t, n_seg, (uint64_t)t << 33);
     pos[t] = p0;
     if (t == n_seg) return;
     const int64_t p1 = t + 1 == n_seg ? n2 : lower_bound_u64(keys, p0, n2, (uint64_t)(t + 1) << 33);
@@ -2773,12 +2738,6 @@ __global__ void __launch_bounds__(PL_THREADS) k_platt_prep(const uint64_t* __res
         const uint32_t all = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
         if (all) atomicAdd(&st[seg_lo].P, (unsigned long long)all);
     }
-}
-
-__device__ __forceinline__ double pl_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // one thread, holding the sums of a whole segment at the four trial points: the line search and the next Newton direction
@@ -2905,7 +2864,7 @@ __global__ void __launch_bounds__(PL_THREADS) k_platt_pass(const double* __restr
         for (int k = 0; k < PL_NT; ++k)
 #pragma unroll
             for (int j = 0; j < PL_NQ; ++j) {
-                const double v = pl_wave_sum(acc[k][j]);
+                const double v = wave_sum_d(acc[k][j]);
                 if (lane == 0) sh[wave][k * PL_NQ + j] = v;
             }
         __syncthreads();
@@ -2979,39 +2938,29 @@ __global__ void __launch_bounds__(MET_THREADS) k_platt_final(const PlattSeg* __r
 }
 
 struct PlattLayout {
-    int64_t keys_in, keys_out, lab, pos, st, cnt, part, temp, temp_bytes, total, chunks;
+    MetLayout m;                        // once the sort has run, keys_in holds z per sorted position; m.start is pos
+    int64_t lab, st, cnt, part, chunks;
 };
 static void platt_fixed_layout(int64_t n, int32_t n_domain, PlattLayout* L) {
     const int64_t n2 = 2 * n, seg = (int64_t)n_domain + 1;
     L->chunks = cdc_ceil_div(n2, PL_CHUNK);
-    int64_t off = 0;
-    L->keys_in = off;  off += align_up(n2 * 8);                // after the sort: z per sorted position
-    L->keys_out = off; off += align_up(n2 * 8);
-    L->lab = off;      off += align_up(n2);
-    L->pos = off;      off += align_up((seg + 1) * 8);
-    L->st = off;       off += align_up(seg * (int64_t)sizeof(PlattSeg));
-    L->cnt = off;      off += align_up(seg * 4);
-    L->part = off;     off += align_up((L->chunks + seg) * PL_NV * 8);    // slot = chunk + segment < chunks + seg
-    L->temp = off;
-    L->temp_bytes = 0;
-    L->total = off;
-}
-static int platt_layout(int64_t n, int32_t n_domain, PlattLayout* L) {
-    platt_fixed_layout(n, n_domain, L);
-    size_t t_sort = 0;
-    hipError_t e = rocprim::radix_sort_keys(nullptr, t_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr, (size_t)(2 * n), 0, 64, (hipStream_t)0, false);
-    if (e != hipSuccess) { cdc_set_error("eval_platt_fit: rocprim size query failed: %s", hipGetErrorString(e)); return (int)e; }
-    L->temp_bytes = (int64_t)t_sort;
-    L->total = L->temp + align_up(L->temp_bytes);
-    return 0;
+    MetCursor c;
+    L->m.keys(c, n2, 0);
+    L->lab = c.take(n2);
+    L->m.starts(c, seg);
+    L->st = c.take(seg * (int64_t)sizeof(PlattSeg));
+    L->cnt = c.take(seg * 4);
+    L->part = c.take((L->chunks + seg) * PL_NV * 8);           // slot = chunk + segment < chunks + seg
+    L->m.end_fixed(c);
 }
 static bool platt_clip_ok(double clip) { return clip >= 1e-12 && clip <= 0.25; }
 
 extern "C" int64_t cdc_eval_platt_fit_workspace_bytes(int64_t n, int32_t n_domain) {
     if (!iso_sizes_ok(n, n_domain)) return 0;
     PlattLayout L;
-    if (platt_layout(n, n_domain, &L) != 0) return -1;
-    return L.total;
+    platt_fixed_layout(n, n_domain, &L);
+    if (met_keys_temp(n, "eval_platt_fit", &L.m) != 0) return -1;
+    return L.m.total;
 }
 
 extern "C" int cdc_eval_platt_fit(const float* score, const int16_t* label, const int32_t* domain, int64_t ld_domain, int64_t n,
@@ -3023,29 +2972,25 @@ extern "C" int cdc_eval_platt_fit(const float* score, const int16_t* label, cons
                   CDC_E_BADARG, "eval_platt_fit: null pointer");
     CDC_CHECK_ARG(n > 0 && n_domain > 0 && n_domain < (1 << 20) && ld_domain >= 0, CDC_E_BADARG,
                   "eval_platt_fit: bad sizes n=%ld n_domain=%d ld_domain=%ld", (long)n, n_domain, (long)ld_domain);
-    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_platt_fit: n_domain=%d needs the domain column", n_domain);
+    MET_TRY(met_need_domain("eval_platt_fit", domain, n_domain));
     CDC_CHECK_ARG(method >= PL_METHOD_PLATT && method <= PL_METHOD_BIAS, CDC_E_BADARG, "eval_platt_fit: unknown method %d", method);
     CDC_CHECK_ARG(input == 0 || input == 1, CDC_E_BADARG, "eval_platt_fit: unknown input %d (0: probabilities, 1: logits)", input);
     CDC_CHECK_ARG(platt_clip_ok(clip), CDC_E_BADARG, "eval_platt_fit: clip=%g outside [1e-12, 0.25]", clip);
     CDC_CHECK_ARG(gtol > 0.0, CDC_E_BADARG, "eval_platt_fit: gtol=%g must be positive", gtol);
     CDC_CHECK_ARG(max_iter >= 1 && max_iter <= 1024, CDC_E_BADARG, "eval_platt_fit: max_iter=%d outside [1, 1024]", max_iter);
     CDC_CHECK_ARG(n < (1ll << 31), CDC_E_TOOBIG, "eval_platt_fit: n=%ld exceeds 2^31 rows", (long)n);
-    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_platt_fit: workspace must be 256-byte aligned");
     PlattLayout L;
     platt_fixed_layout(n, n_domain, &L);
-    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_platt_fit: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
-    int rc = platt_layout(n, n_domain, &L);
-    if (rc != 0) return rc;
-    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_platt_fit: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
-    char* base = (char*)workspace;
-    uint64_t* keys_in = (uint64_t*)(base + L.keys_in);
-    uint64_t* keys_out = (uint64_t*)(base + L.keys_out);
-    double* zs = (double*)(base + L.keys_in);                             // the unsorted keys are done with after the sort
-    uint8_t* lab = (uint8_t*)(base + L.lab);
-    int64_t* pos = (int64_t*)(base + L.pos);
-    PlattSeg* st = (PlattSeg*)(base + L.st);
-    double* part = (double*)(base + L.part);
-    uint32_t* cnt = (uint32_t*)(base + L.cnt);
+    MET_TRY(met_gate("eval_platt_fit", workspace, workspace_bytes, &L.m, [&] { return met_keys_temp(n, "eval_platt_fit", &L.m); }));
+    const MetWs ws{(char*)workspace};
+    uint64_t* keys_in = ws.ptr<uint64_t>(L.m.keys_in);
+    uint64_t* keys_out = ws.ptr<uint64_t>(L.m.keys_out);
+    double* zs = (double*)keys_in;                                        // the unsorted keys are done with after the sort
+    uint8_t* lab = ws.ptr<uint8_t>(L.lab);
+    int64_t* pos = ws.ptr<int64_t>(L.m.start);
+    PlattSeg* st = ws.ptr<PlattSeg>(L.st);
+    double* part = ws.ptr<double>(L.part);
+    uint32_t* cnt = ws.ptr<uint32_t>(L.cnt);
     hipStream_t sm = (hipStream_t)stream;
     const int64_t n2 = 2 * n;
     const int seg = n_domain + 1;
@@ -3053,11 +2998,7 @@ extern "C" int cdc_eval_platt_fit(const float* score, const int16_t* label, cons
     const int blocks = (int)std::min<int64_t>(cdc_ceil_div(n, MET_THREADS), 4096);
     hipLaunchKernelGGL(k_platt_keys, dim3(blocks), dim3(MET_THREADS), 0, sm, score, label, domain, ld_domain, n, n_domain, input, keys_in, err_flag);
     CDC_LAUNCH_CHECK("eval_platt_fit(keys)");
-    int end_bit = 34;
-    while (end_bit < 64 && ((uint64_t)n_domain >> (end_bit - 33)) != 0) ++end_bit;
-    size_t temp_bytes = (size_t)L.temp_bytes;
-    hipError_t e = rocprim::radix_sort_keys(base + L.temp, temp_bytes, (const uint64_t*)keys_in, keys_out, (size_t)n2, 0, end_bit, sm, false);
-    if (e != hipSuccess) { cdc_set_error("eval_platt_fit: radix sort failed: %s", hipGetErrorString(e)); return (int)e; }
+    MET_TRY(met_sort("eval_platt_fit", ws.base, L.m, (size_t)n2, met_end_bit((uint64_t)n_domain, 33), sm));
     hipLaunchKernelGGL(k_platt_starts, dim3((int)cdc_ceil_div(seg + 1, MET_THREADS)), dim3(MET_THREADS), 0, sm, (const uint64_t*)keys_out, n2, seg, pos, st, cnt);
     CDC_LAUNCH_CHECK("eval_platt_fit(starts)");
     hipLaunchKernelGGL(k_platt_prep, dim3((unsigned)L.chunks), dim3(PL_THREADS), 0, sm, (const uint64_t*)keys_out, n2, input, Z, zs, lab, st);
@@ -3086,7 +3027,7 @@ __global__ void __launch_bounds__(MET_THREADS) k_platt_apply(const float* __rest
     int32_t s = -1;
     if ((input == 0 ? (x >= 0.f && x <= 1.f) : x == x) && d >= 0 && d < n_domain) s = seg_of_domain[d];
     if (s < 0 || s > n_domain) {                                          // a NaN score, a probability outside [0, 1], a domain or a segment outside range
-        if (err) atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
+        if (err) met_flag_row(err, i);
         out[i] = __uint_as_float(0x7fc00000u);
         return;
     }
@@ -3105,7 +3046,7 @@ extern "C" int cdc_eval_platt_apply(const float* score, const int32_t* domain, i
     CDC_CHECK_ARG(score && seg_of_domain && a && b && out, CDC_E_BADARG, "eval_platt_apply: null pointer");
     CDC_CHECK_ARG(n > 0 && n_domain > 0 && n_domain < (1 << 20) && ld_domain >= 0, CDC_E_BADARG,
                   "eval_platt_apply: bad sizes n=%ld n_domain=%d ld_domain=%ld", (long)n, n_domain, (long)ld_domain);
-    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_platt_apply: n_domain=%d needs the domain column", n_domain);
+    MET_TRY(met_need_domain("eval_platt_apply", domain, n_domain));
     CDC_CHECK_ARG(input == 0 || input == 1, CDC_E_BADARG, "eval_platt_apply: unknown input %d (0: probabilities, 1: logits)", input);
     CDC_CHECK_ARG(platt_clip_ok(clip), CDC_E_BADARG, "eval_platt_apply: clip=%g outside [1e-12, 0.25]", clip);
     CDC_CHECK_ARG(eps >= 0.f && eps <= 0.5f, CDC_E_BADARG, "eval_platt_apply: eps=%g outside [0, 0.5]", (double)eps);
@@ -3170,11 +3111,6 @@ __device__ __forceinline__ uint32_t boot_weight(uint64_t base, uint32_t c) {
              (u >= 0xffffffd4u) + (u >= 0xfffffffcu);
     return w;
 }
-__device__ __forceinline__ double boot_wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __global__ void __launch_bounds__(MET_THREADS) k_boot_keys(const float* __restrict__ pred, const int16_t* __restrict__ label,
                                                            const int32_t* __restrict__ cluster, int64_t ld_cluster, int64_t n_cluster,
@@ -3187,20 +3123,17 @@ __global__ void __launch_bounds__(MET_THREADS) k_boot_keys(const float* __restri
         const int64_t u = cluster ? (int64_t)cluster[i * ld_cluster] : 0;
         const int16_t y = label[i];
         if (p != p || d < 0 || d >= n_domain || u < 0 || (cluster && u >= n_cluster) || (y != 0 && y != 1)) {
-            if (err) atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
-            d = d < 0 ? 0 : (d >= n_domain ? n_domain - 1 : d);
+            if (err) met_flag_row(err, i);
+            d = met_clamp_id(d, n_domain);
         }
-        const uint64_t low = ((uint64_t)score_key(p) << 1) | (uint64_t)(y != 0);
-        keys[i] = ((uint64_t)(uint32_t)d << 33) | low;
-        keys[n + i] = ((uint64_t)(uint32_t)n_domain << 33) | low;
-        idx[i] = (uint32_t)i;
-        idx[n + i] = (uint32_t)(n + i);
+        met_write_pair(keys, idx, n, i, (uint32_t)d, (uint32_t)n_domain, 33, ((uint64_t)score_key(p) << 1) | (uint64_t)(y != 0), (uint32_t)i,
+                       (uint32_t)(n + i));
     }
 }
 
 __global__ void k_boot_starts(const uint64_t* __restrict__ keys, int64_t n2, int32_t n_seg, int64_t* __restrict__ start) {
     const int d = blockIdx.x * blockDim.x + threadIdx.x;
-    if (d <= n_seg) start[d] = d == n_seg ? n2 : lower_bound_u64(keys, 0, n2, (uint64_t)(uint32_t)d << 33);
+    if (d <= n_seg) start[d] = met_seg_start(keys, n2, d, n_seg, (uint64_t)(uint32_t)d << 33);
 }
 
 // what a sorted position carries into every replicate: cluster (clamped as k_gauc_keys clamps a user), loss term, tie-run start
@@ -3419,7 +3352,7 @@ __global__ void __launch_bounds__(BOOT_THREADS) k_boot_pass(const uint64_t* __re
                 }
                 aw = dl_wave_sum(aw);
                 au = dl_wave_sum(au);
-                al = boot_wave_sum_f64(al);
+                al = wave_sum_d(al);
                 if (lane == 0) {
                     s_red[wave][r * 3] = aw;
                     s_red[wave][r * 3 + 1] = au;
@@ -3550,7 +3483,7 @@ __global__ void __launch_bounds__(GAUC_THREADS) k_boot_gauc(const uint64_t* __re
         }
 #pragma unroll
         for (int r = 0; r < BOOT_REP_TILE; ++r) {
-            const double x = boot_wave_sum_f64(num[r]), y = boot_wave_sum_f64(den[r]), z = boot_wave_sum_f64(cnt[r]);
+            const double x = wave_sum_d(num[r]), y = wave_sum_d(den[r]), z = wave_sum_d(cnt[r]);
             if (lane == 0) { s_red[wave][r * 3] = x; s_red[wave][r * 3 + 1] = y; s_red[wave][r * 3 + 2] = z; }
         }
         __syncthreads();
@@ -3582,57 +3515,42 @@ __global__ void __launch_bounds__(BOOT_THREADS) k_boot_gauc_final(const double* 
 }
 
 struct BootLayout {
-    int64_t keys_in, keys_out, idx_in, idx_out, f, start, ntot, ntail, off, parts, direct, tot, gauc, gpart, gcnt, temp, temp_bytes, total;
+    MetLayout m;                        // once the sort has run, keys_in holds the loss terms and pay_in the clusters
+    int64_t f, ntot, ntail, off, parts, direct, tot, gauc, gpart, gcnt;
     int64_t nchunks;
     GaucLayout g;                       // cdc_eval_gauc's arrays, offsets from `gauc`
 };
-// everything but rocPRIM's temporary storage: plain arithmetic (argument checks use it before any HIP or rocPRIM call)
 static void boot_fixed_layout(int64_t n, int32_t n_domain, int32_t n_rep, int32_t gauc, BootLayout* L) {
     const int64_t n2 = 2 * n, seg = (int64_t)n_domain + 1, nc = cdc_ceil_div(n2, BOOT_CHUNK), R = n_rep;
-    int64_t off = 0;
+    MetCursor c;
     L->nchunks = nc;
-    L->keys_in = off;  off += align_up(n2 * 8);               // after the sort: the loss terms
-    L->keys_out = off; off += align_up(n2 * 8);
-    L->idx_in = off;   off += align_up(n2 * 4);               // after the sort: the clusters
-    L->idx_out = off;  off += align_up(n2 * 4);
-    L->f = off;        off += align_up(n2 * 4);
-    L->start = off;    off += align_up((seg + 1) * 8);
-    L->ntot = off;     off += align_up(R * nc * 4);
-    L->ntail = off;    off += align_up(R * nc * 4);
-    L->off = off;      off += align_up(R * (nc + 1) * 8);
-    L->parts = off;    off += align_up(nc * 2 * 3 * R * 8);
-    L->direct = off;   off += align_up(seg * 3 * R * 8);
-    L->tot = off;      off += align_up(seg * 4 * R * 8);
-    L->gauc = off;
-    L->gpart = off; L->gcnt = off;
+    L->m.keys(c, n2, 4);
+    L->f = c.take(n2 * 4);
+    L->m.starts(c, seg);
+    L->ntot = c.take(R * nc * 4);
+    L->ntail = c.take(R * nc * 4);
+    L->off = c.take(R * (nc + 1) * 8);
+    L->parts = c.take(nc * 2 * 3 * R * 8);
+    L->direct = c.take(seg * 3 * R * 8);
+    L->tot = c.take(seg * 4 * R * 8);
+    L->gauc = L->gpart = L->gcnt = c.off;
     if (gauc) {
         gauc_fixed_layout(n, n_domain, &L->g);
-        off += L->g.total;
-        L->gpart = off; off += align_up(seg * GAUC_SLICES * R * 2 * 8);
-        L->gcnt = off;  off += align_up(seg * GAUC_SLICES * R * 8);
+        c.off += L->g.m.total;
+        L->gpart = c.take(seg * GAUC_SLICES * R * 2 * 8);
+        L->gcnt = c.take(seg * GAUC_SLICES * R * 8);
     }
-    L->temp = off;
-    L->temp_bytes = 0;
-    L->total = off;
+    L->m.end_fixed(c);
 }
-static int boot_layout(int64_t n, int32_t n_domain, int32_t n_rep, int32_t gauc, BootLayout* L) {
-    boot_fixed_layout(n, n_domain, n_rep, gauc, L);
-    size_t t_sort = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, t_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr,
-                                             (uint32_t*)nullptr, (size_t)(2 * n), 0, 64, (hipStream_t)0, false);
-    if (e != hipSuccess) { cdc_set_error("eval_bootstrap: rocprim size query failed: %s", hipGetErrorString(e)); return (int)e; }
-    int64_t t_gauc = 0;
-    if (gauc) {
-        const int rc = gauc_temp_bytes(n, "eval_bootstrap", &t_gauc);
-        if (rc != 0) return rc;
+static int boot_temp(int64_t n, int32_t gauc, BootLayout* L) {
+    MetTemp t;
+    t.sort_pairs<uint32_t>((size_t)(2 * n));
+    const int rc = gauc ? gauc_temp(n, "eval_bootstrap", &L->m, t) : t.done("eval_bootstrap", &L->m);
+    if (rc == 0 && gauc) {                                                  // as gauc_order reads them: from the sub-block's base
+        L->g.m.temp = L->m.temp - L->gauc;
+        L->g.m.temp_bytes = L->m.temp_bytes;
     }
-    L->temp_bytes = std::max<int64_t>((int64_t)t_sort, t_gauc);             // the sorts and scans run one after the other
-    L->total = L->temp + align_up(L->temp_bytes);
-    if (gauc) {                                                             // as gauc_order reads them: from the sub-block's base
-        L->g.temp = L->temp - L->gauc;
-        L->g.temp_bytes = L->temp_bytes;
-    }
-    return 0;
+    return rc;
 }
 // 72 n^2 bounds U2 and 2 Wp Wn (weights <= 12): it must fit 64 bits
 static bool boot_sizes_ok(int64_t n, int32_t n_domain, int32_t n_rep) {
@@ -3643,8 +3561,9 @@ extern "C" int64_t cdc_eval_bootstrap_workspace_bytes(int64_t n, int32_t n_domai
     if (!boot_sizes_ok(n, n_domain, n_rep)) return 0;
     if (gauc && !gauc_sizes_ok(n, n_domain, n_cluster)) return 0;
     BootLayout L;
-    if (boot_layout(n, n_domain, n_rep, gauc != 0, &L) != 0) return -1;
-    return L.total;
+    boot_fixed_layout(n, n_domain, n_rep, gauc != 0, &L);
+    if (boot_temp(n, gauc != 0, &L) != 0) return -1;
+    return L.m.total;
 }
 
 extern "C" int cdc_eval_bootstrap(const float* pred_a, const float* pred_b, const int16_t* label, const int32_t* cluster, int64_t ld_cluster,
@@ -3654,39 +3573,35 @@ extern "C" int cdc_eval_bootstrap(const float* pred_a, const float* pred_b, cons
     CDC_CHECK_ARG(pred_a && label && out && counts && workspace, CDC_E_BADARG, "eval_bootstrap: null pointer");
     CDC_CHECK_ARG(n > 0 && n_domain > 0 && n_domain < (1 << 20) && ld_cluster >= 0 && ld_domain >= 0 && (!cluster || n_cluster > 0),
                   CDC_E_BADARG, "eval_bootstrap: bad sizes n=%ld n_domain=%d n_cluster=%ld", (long)n, n_domain, (long)n_cluster);
-    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_bootstrap: n_domain=%d needs the domain column", n_domain);
+    MET_TRY(met_need_domain("eval_bootstrap", domain, n_domain));
     CDC_CHECK_ARG(n_rep >= 1 && n_rep <= BOOT_MAX_REP, CDC_E_BADARG, "eval_bootstrap: n_rep=%d outside [1, %d]", n_rep, BOOT_MAX_REP);
     CDC_CHECK_ARG(!gauc || cluster, CDC_E_BADARG, "eval_bootstrap: GAUC needs the cluster column (a row's user)");
     CDC_CHECK_ARG(n < (1ll << 28), CDC_E_TOOBIG, "eval_bootstrap: n=%ld exceeds the 2^28 rows whose weighted pair count fits 64 bits", (long)n);
     CDC_CHECK_ARG(!gauc || gauc_sizes_ok(n, n_domain, n_cluster), CDC_E_BADARG,
                   "eval_bootstrap: (n_domain + 1) * n_cluster = %ld * %ld group ids exceed 2^32", (long)n_domain + 1, (long)n_cluster);
-    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_bootstrap: workspace must be 256-byte aligned");
     gauc = gauc != 0;
     const int32_t paired = pred_b != nullptr;
     BootLayout L;
     boot_fixed_layout(n, n_domain, n_rep, gauc, &L);
-    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_bootstrap: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
-    int rc = boot_layout(n, n_domain, n_rep, gauc, &L);
-    if (rc != 0) return rc;
-    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_bootstrap: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.total);
-    char* base = (char*)workspace;
-    uint64_t* keys_in = (uint64_t*)(base + L.keys_in);
-    uint64_t* keys = (uint64_t*)(base + L.keys_out);
-    uint32_t* idx_in = (uint32_t*)(base + L.idx_in);
-    uint32_t* idx = (uint32_t*)(base + L.idx_out);
+    MET_TRY(met_gate("eval_bootstrap", workspace, workspace_bytes, &L.m, [&] { return boot_temp(n, gauc, &L); }));
+    const MetWs ws{(char*)workspace};
+    uint64_t* keys_in = ws.ptr<uint64_t>(L.m.keys_in);
+    uint64_t* keys = ws.ptr<uint64_t>(L.m.keys_out);
+    uint32_t* idx_in = ws.ptr<uint32_t>(L.m.pay_in);
+    uint32_t* idx = ws.ptr<uint32_t>(L.m.pay_out);
     double* term = (double*)keys_in;                                // the unsorted keys and payloads are dead once the sort has run
     uint32_t* cl = idx_in;
-    uint32_t* f = (uint32_t*)(base + L.f);
-    int64_t* start = (int64_t*)(base + L.start);
-    uint32_t* ntot = (uint32_t*)(base + L.ntot);
-    uint32_t* ntail = (uint32_t*)(base + L.ntail);
-    unsigned long long* off = (unsigned long long*)(base + L.off);
-    unsigned long long* parts = (unsigned long long*)(base + L.parts);
-    unsigned long long* direct = (unsigned long long*)(base + L.direct);
-    unsigned long long* tot = (unsigned long long*)(base + L.tot);
-    char* gbase = base + L.gauc;
-    double* gpart = (double*)(base + L.gpart);
-    int64_t* gcnt = (int64_t*)(base + L.gcnt);
+    uint32_t* f = ws.ptr<uint32_t>(L.f);
+    int64_t* start = ws.ptr<int64_t>(L.m.start);
+    uint32_t* ntot = ws.ptr<uint32_t>(L.ntot);
+    uint32_t* ntail = ws.ptr<uint32_t>(L.ntail);
+    unsigned long long* off = ws.ptr<unsigned long long>(L.off);
+    unsigned long long* parts = ws.ptr<unsigned long long>(L.parts);
+    unsigned long long* direct = ws.ptr<unsigned long long>(L.direct);
+    unsigned long long* tot = ws.ptr<unsigned long long>(L.tot);
+    char* gbase = ws.ptr<char>(L.gauc);
+    double* gpart = ws.ptr<double>(L.gpart);
+    int64_t* gcnt = ws.ptr<int64_t>(L.gcnt);
     hipStream_t st = (hipStream_t)stream;
     const int64_t n2 = 2 * n, nc = L.nchunks;
     const int seg = n_domain + 1, n_stat = 2 + gauc;
@@ -3695,8 +3610,7 @@ extern "C" int cdc_eval_bootstrap(const float* pred_a, const float* pred_b, cons
     // GAUC's slices are uneven ("all rows" holds half the positions in 64 of them), so there the tiles go side by side much longer
     const int gy = (int)std::min<int64_t>(ntiles, std::max<int64_t>(1, 2048 / nc));
     const int gz = (int)std::min<int64_t>(ntiles, std::max<int64_t>(1, 131072 / ((int64_t)seg * GAUC_SLICES)));
-    int end_bit = 34;
-    while (end_bit < 64 && ((uint64_t)n_domain >> (end_bit - 33)) != 0) ++end_bit;
+    const int end_bit = met_end_bit((uint64_t)n_domain, 33);
     for (int v = 0; v <= paired; ++v) {
         const float* pred = v ? pred_b : pred_a;
         double* o = out + (int64_t)v * n_stat * n_rep * seg;
@@ -3704,10 +3618,7 @@ extern "C" int cdc_eval_bootstrap(const float* pred_a, const float* pred_b, cons
         hipLaunchKernelGGL(k_boot_keys, dim3(blocks), dim3(MET_THREADS), 0, st, pred, label, cluster, ld_cluster, n_cluster, domain,
                            ld_domain, n, n_domain, keys_in, idx_in, err_flag);
         CDC_LAUNCH_CHECK("eval_bootstrap(keys)");
-        size_t temp_bytes = (size_t)L.temp_bytes;
-        hipError_t e = rocprim::radix_sort_pairs(base + L.temp, temp_bytes, (const uint64_t*)keys_in, keys, (const uint32_t*)idx_in, idx,
-                                                 (size_t)n2, 0, end_bit, st, false);
-        if (e != hipSuccess) { cdc_set_error("eval_bootstrap: radix sort failed: %s", hipGetErrorString(e)); return (int)e; }
+        MET_TRY(met_sort("eval_bootstrap", ws.base, L.m, (const uint32_t*)idx_in, idx, (size_t)n2, end_bit, st));
         hipLaunchKernelGGL(k_boot_starts, dim3((int)cdc_ceil_div(seg + 1, 64)), dim3(64), 0, st, (const uint64_t*)keys, n2, seg, start);
         CDC_LAUNCH_CHECK("eval_bootstrap(starts)");
         blocks = (int)std::min<int64_t>(cdc_ceil_div(n2, MET_THREADS), 8192);
@@ -3731,12 +3642,12 @@ extern "C" int cdc_eval_bootstrap(const float* pred_a, const float* pred_b, cons
                            (const unsigned long long*)tot, n_rep, seg, o, v ? (int64_t*)nullptr : counts);   // the counts follow from the
         CDC_LAUNCH_CHECK("eval_bootstrap(final)");                                                         // labels and weights alone
         if (!gauc) continue;
-        unsigned long long* Wg = (unsigned long long*)(gbase + L.g.keys_in);
-        rc = gauc_order(pred, label, cluster, ld_cluster, n_cluster, domain, ld_domain, n_domain, n, err_flag, gbase, L.g, Wg,
-                        "eval_bootstrap", st);
-        if (rc != 0) return rc;
-        hipLaunchKernelGGL(k_boot_gauc, dim3(seg, GAUC_SLICES, gz), dim3(GAUC_THREADS), 0, st, (const uint64_t*)(gbase + L.g.keys_out),
-                           (const GaucScan*)(gbase + L.g.scan), (const unsigned long long*)Wg, (const int64_t*)(gbase + L.g.start),
+        const MetWs gws{gbase};
+        unsigned long long* Wg = gws.ptr<unsigned long long>(L.g.m.keys_in);
+        MET_TRY(gauc_order(pred, label, cluster, ld_cluster, n_cluster, domain, ld_domain, n_domain, n, err_flag, gbase, L.g, Wg,
+                        "eval_bootstrap", st));
+        hipLaunchKernelGGL(k_boot_gauc, dim3(seg, GAUC_SLICES, gz), dim3(GAUC_THREADS), 0, st, gws.ptr<const uint64_t>(L.g.m.keys_out),
+                           gws.ptr<const GaucScan>(L.g.scan), (const unsigned long long*)Wg, gws.ptr<const int64_t>(L.g.m.start),
                            user_weight, n_cluster, n2, n_rep, seed, gpart, gcnt);
         CDC_LAUNCH_CHECK("eval_bootstrap(gauc)");
         hipLaunchKernelGGL(k_boot_gauc_final, dim3((unsigned)cdc_ceil_div((int64_t)seg * n_rep, BOOT_THREADS)), dim3(BOOT_THREADS), 0, st,
@@ -3787,15 +3698,12 @@ __global__ void __launch_bounds__(MET_THREADS) k_cboot_keys(const float* __restr
         const int16_t y = label[i];
         const bool bad_p = !(p >= 0.f && p <= 1.f);                       // a NaN too
         if (bad_p || d < 0 || d >= n_domain || u < 0 || (cluster && u >= n_cluster) || (y != 0 && y != 1)) {
-            if (err) atomicMax(err, (int32_t)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
-            d = d < 0 ? 0 : (d >= n_domain ? n_domain - 1 : d);
+            if (err) met_flag_row(err, i);
+            d = met_clamp_id(d, n_domain);
             if (bad_p) p = p > 1.f ? 1.f : 0.f;                           // as k_calib_keys clamps
         }
-        const uint64_t low = ((uint64_t)score_key(p) << 1) | (uint64_t)(y != 0);
-        keys[i] = ((uint64_t)(uint32_t)d << 33) | low;
-        keys[n + i] = ((uint64_t)(uint32_t)n_domain << 33) | low;
-        idx[i] = (uint32_t)i;
-        idx[n + i] = (uint32_t)(n + i);
+        met_write_pair(keys, idx, n, i, (uint32_t)d, (uint32_t)n_domain, 33, ((uint64_t)score_key(p) << 1) | (uint64_t)(y != 0), (uint32_t)i,
+                       (uint32_t)(n + i));
     }
 }
 
@@ -4065,7 +3973,8 @@ __global__ void __launch_bounds__(CALBOOT_THREADS) k_cboot_final(const unsigned 
 }
 
 struct CalBootLayout {
-    int64_t keys_in, keys_out, idx_in, idx_out, start, ntot, off, segoff, acc, acc_words, temp, temp_bytes, total;
+    MetLayout m;                        // once the sort has run, pay_in holds the clusters
+    int64_t ntot, off, segoff, acc, acc_words;
     int64_t nchunks, cells;
 };
 // plain arithmetic, rocPRIM's temporary storage included: the size query must answer where no device is present.  The sort gets
@@ -4073,22 +3982,18 @@ struct CalBootLayout {
 // its tiles; the call asks rocPRIM what it needs and refuses to run if that is ever more
 static void calboot_layout(int64_t n, int32_t n_domain, int32_t n_bins, int32_t n_rep, CalBootLayout* L) {
     const int64_t n2 = 2 * n, seg = (int64_t)n_domain + 1, nc = cdc_ceil_div(n2, CALBOOT_CHUNK), R = n_rep;
-    int64_t off = 0;
+    MetCursor c;
     L->nchunks = nc;
     L->cells = R * seg * n_bins;
     L->acc_words = 2 * (2 * L->cells + R * seg);               // acc_w, acc_q, acc_seg: one block, cleared together
-    L->keys_in = off;  off += align_up(n2 * 8);
-    L->keys_out = off; off += align_up(n2 * 8);
-    L->idx_in = off;   off += align_up(n2 * 4);                // after the sort: the clusters
-    L->idx_out = off;  off += align_up(n2 * 4);
-    L->start = off;    off += align_up((seg + 1) * 8);
-    L->ntot = off;     off += align_up(R * nc * 4);
-    L->off = off;      off += align_up(R * (nc + 1) * 8);
-    L->segoff = off;   off += align_up(R * (seg + 1) * 8);
-    L->acc = off;      off += align_up(L->acc_words * 8);
-    L->temp = off;
-    L->temp_bytes = n2 * 16 + (1 << 20);
-    L->total = L->temp + align_up(L->temp_bytes);
+    L->m.keys(c, n2, 4);
+    L->m.starts(c, seg);
+    L->ntot = c.take(R * nc * 4);
+    L->off = c.take(R * (nc + 1) * 8);
+    L->segoff = c.take(R * (seg + 1) * 8);
+    L->acc = c.take(L->acc_words * 8);
+    L->m.end_fixed(c);
+    L->m.set_temp(n2 * 16 + (1 << 20));
 }
 static bool calboot_sizes_ok(int64_t n, int32_t n_domain, int32_t n_bins, int32_t n_rep) {
     return n > 0 && n < (1ll << 28) && n_domain > 0 && n_domain < (1 << 20) && n_bins >= 1 && n_bins <= CAL_MAX_BINS && n_rep >= 1 &&
@@ -4101,7 +4006,7 @@ extern "C" int64_t cdc_eval_calibration_bootstrap_workspace_bytes(int64_t n, int
     if (!calboot_sizes_ok(n, n_domain, n_bins, n_rep)) return 0;
     CalBootLayout L;
     calboot_layout(n, n_domain, n_bins, n_rep, &L);
-    return L.total;
+    return L.m.total;
 }
 
 extern "C" int cdc_eval_calibration_bootstrap(const float* pred_a, const float* pred_b, const int16_t* label, const int32_t* cluster,
@@ -4116,35 +4021,34 @@ extern "C" int cdc_eval_calibration_bootstrap(const float* pred_a, const float* 
                   CAL_MAX_BINS);
     CDC_CHECK_ARG(n_rep >= 1 && n_rep <= BOOT_MAX_REP, CDC_E_BADARG, "eval_calibration_bootstrap: n_rep=%d outside [1, %d]", n_rep,
                   BOOT_MAX_REP);
-    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_calibration_bootstrap: n_domain=%d needs the domain column", n_domain);
+    MET_TRY(met_need_domain("eval_calibration_bootstrap", domain, n_domain));
     CDC_CHECK_ARG(n < (1ll << 28), CDC_E_TOOBIG, "eval_calibration_bootstrap: n=%ld exceeds the 2^28 rows whose weighted sums fit 64 bits",
                   (long)n);
     CDC_CHECK_ARG((int64_t)n_rep * ((int64_t)n_domain + 1) * n_bins <= CALBOOT_MAX_CELLS, CDC_E_TOOBIG,
                   "eval_calibration_bootstrap: n_rep * (n_domain + 1) * n_bins = %ld cells exceed 2^22",
                   (long)((int64_t)n_rep * ((int64_t)n_domain + 1) * n_bins));
-    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_calibration_bootstrap: workspace must be 256-byte aligned");
     const int32_t paired = pred_b != nullptr;
     CalBootLayout L;
     calboot_layout(n, n_domain, n_bins, n_rep, &L);
-    CDC_CHECK_ARG(workspace_bytes >= L.total, CDC_E_BADARG, "eval_calibration_bootstrap: workspace %ld < %ld bytes", (long)workspace_bytes,
-                  (long)L.total);
-    size_t t_sort = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, t_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr,
-                                             (uint32_t*)nullptr, (size_t)(2 * n), 0, 64, (hipStream_t)0, false);
-    if (e != hipSuccess) { cdc_set_error("eval_calibration_bootstrap: rocprim size query failed: %s", hipGetErrorString(e)); return (int)e; }
-    CDC_CHECK_ARG((int64_t)t_sort <= L.temp_bytes, CDC_E_BADARG, "eval_calibration_bootstrap: the sort needs %ld temporary bytes, %ld reserved",
-                  (long)t_sort, (long)L.temp_bytes);
-    char* base = (char*)workspace;
-    uint64_t* keys_in = (uint64_t*)(base + L.keys_in);
-    uint64_t* keys = (uint64_t*)(base + L.keys_out);
-    uint32_t* idx_in = (uint32_t*)(base + L.idx_in);
-    uint32_t* idx = (uint32_t*)(base + L.idx_out);
+    const auto ask_rocprim = [&]() -> int {                                // the layout is complete: rocPRIM is only asked
+        MetLayout asked = L.m;
+        MET_TRY(met_pairs32_temp(n, "eval_calibration_bootstrap", &asked));
+        CDC_CHECK_ARG(asked.temp_bytes <= L.m.temp_bytes, CDC_E_BADARG,
+                      "eval_calibration_bootstrap: the sort needs %ld temporary bytes, %ld reserved", (long)asked.temp_bytes, (long)L.m.temp_bytes);
+        return 0;
+    };
+    MET_TRY(met_gate("eval_calibration_bootstrap", workspace, workspace_bytes, &L.m, ask_rocprim));
+    const MetWs ws{(char*)workspace};
+    uint64_t* keys_in = ws.ptr<uint64_t>(L.m.keys_in);
+    uint64_t* keys = ws.ptr<uint64_t>(L.m.keys_out);
+    uint32_t* idx_in = ws.ptr<uint32_t>(L.m.pay_in);
+    uint32_t* idx = ws.ptr<uint32_t>(L.m.pay_out);
     uint32_t* cl = idx_in;                                          // the unsorted payloads are dead once the sort has run
-    int64_t* start = (int64_t*)(base + L.start);
-    uint32_t* ntot = (uint32_t*)(base + L.ntot);
-    unsigned long long* off = (unsigned long long*)(base + L.off);
-    unsigned long long* segoff = (unsigned long long*)(base + L.segoff);
-    unsigned long long* acc_w = (unsigned long long*)(base + L.acc);
+    int64_t* start = ws.ptr<int64_t>(L.m.start);
+    uint32_t* ntot = ws.ptr<uint32_t>(L.ntot);
+    unsigned long long* off = ws.ptr<unsigned long long>(L.off);
+    unsigned long long* segoff = ws.ptr<unsigned long long>(L.segoff);
+    unsigned long long* acc_w = ws.ptr<unsigned long long>(L.acc);
     unsigned long long* acc_q = acc_w + 2 * L.cells;
     unsigned long long* acc_seg = acc_q + 2 * L.cells;
     hipStream_t st = (hipStream_t)stream;
@@ -4154,18 +4058,14 @@ extern "C" int cdc_eval_calibration_bootstrap(const float* pred_a, const float* 
     // replicate tiles go side by side only while the grid is small, as in cdc_eval_bootstrap
     const int gy = (int)std::min<int64_t>(ntiles, std::max<int64_t>(1, 2048 / nc));
     const int gy_seg = (int)std::min<int64_t>(ntiles, std::max<int64_t>(1, 2048 / (seg + 1)));
-    int end_bit = 34;
-    while (end_bit < 64 && ((uint64_t)n_domain >> (end_bit - 33)) != 0) ++end_bit;
+    const int end_bit = met_end_bit((uint64_t)n_domain, 33);
     for (int v = 0; v <= paired; ++v) {
         const float* pred = v ? pred_b : pred_a;
         int blocks = (int)std::min<int64_t>(cdc_ceil_div(n, MET_THREADS), 4096);
         hipLaunchKernelGGL(k_cboot_keys, dim3(blocks), dim3(MET_THREADS), 0, st, pred, label, cluster, ld_cluster, n_cluster, domain,
                            ld_domain, n, n_domain, keys_in, idx_in, err_flag);
         CDC_LAUNCH_CHECK("eval_calibration_bootstrap(keys)");
-        size_t temp_bytes = (size_t)L.temp_bytes;
-        e = rocprim::radix_sort_pairs(base + L.temp, temp_bytes, (const uint64_t*)keys_in, keys, (const uint32_t*)idx_in, idx, (size_t)n2,
-                                      0, end_bit, st, false);
-        if (e != hipSuccess) { cdc_set_error("eval_calibration_bootstrap: radix sort failed: %s", hipGetErrorString(e)); return (int)e; }
+        MET_TRY(met_sort("eval_calibration_bootstrap", ws.base, L.m, (const uint32_t*)idx_in, idx, (size_t)n2, end_bit, st));
         hipLaunchKernelGGL(k_boot_starts, dim3((int)cdc_ceil_div(seg + 1, 64)), dim3(64), 0, st, (const uint64_t*)keys, n2, seg, start);
         CDC_LAUNCH_CHECK("eval_calibration_bootstrap(starts)");
         blocks = (int)std::min<int64_t>(cdc_ceil_div(std::max<int64_t>(n2, L.acc_words), MET_THREADS), 8192);
@@ -4435,30 +4335,22 @@ __global__ void __launch_bounds__(GAUC_THREADS) k_rank_ci_rep_final(const double
 }
 
 struct RankCiLayout {
-    RankLayout r;                       // cdc_eval_rank's arrays; r.g.temp / r.total lie behind the ones below
+    RankLayout r;                       // cdc_eval_rank's arrays; r.g.m.temp / r.g.m.total lie behind the ones below
     int64_t scan_b, part_b, part_cnt_b, counts_b, part_sq, part_rep, part_rep_cnt;
 };
 static void rank_ci_fixed_layout(int64_t n, int32_t n_domain, int32_t n_k, int32_t paired, int32_t n_rep, RankCiLayout* L) {
     const int64_t n2 = 2 * n, seg = (int64_t)n_domain + 1, nval = RANK_FIGS * n_k, ncol = (paired ? 2 : 1) * nval + 1;
     const int64_t cells = (int64_t)n_domain * rank_ci_slices(n_domain) + rank_ci_slices_all(n_domain);
     rank_fixed_layout(n, n_domain, n_k, &L->r);
-    int64_t off = L->r.g.temp;
-    L->scan_b = off;       off += paired ? align_up(n2 * (int64_t)sizeof(GaucScan)) : 0;
-    L->part_b = off;       off += paired ? align_up(seg * RANK_SLICES * (nval + 1) * 8) : 0;
-    L->part_cnt_b = off;   off += paired ? align_up(seg * RANK_SLICES * 2 * 8) : 0;
-    L->counts_b = off;     off += paired ? align_up(seg * 2 * 8) : 0;
-    L->part_sq = off;      off += align_up(cells * (paired ? 3 : 1) * nval * 8);
-    L->part_rep = off;     off += align_up(cells * ncol * n_rep * 8);
-    L->part_rep_cnt = off; off += align_up(cells * n_rep * 8);
-    L->r.g.temp = off;
-    L->r.total = off;
-}
-static int rank_ci_layout(int64_t n, int32_t n_domain, int32_t n_k, int32_t paired, int32_t n_rep, RankCiLayout* L) {
-    rank_ci_fixed_layout(n, n_domain, n_k, paired, n_rep, L);
-    const int rc = gauc_temp_bytes(n, "eval_rank_ci", &L->r.g.temp_bytes);
-    if (rc != 0) return rc;
-    L->r.total = L->r.g.temp + align_up(L->r.g.temp_bytes);
-    return 0;
+    MetCursor c{L->r.g.m.temp};
+    L->scan_b = c.take(paired ? n2 * (int64_t)sizeof(GaucScan) : 0);
+    L->part_b = c.take(paired ? seg * RANK_SLICES * (nval + 1) * 8 : 0);
+    L->part_cnt_b = c.take(paired ? seg * RANK_SLICES * 2 * 8 : 0);
+    L->counts_b = c.take(paired ? seg * 2 * 8 : 0);
+    L->part_sq = c.take(cells * (paired ? 3 : 1) * nval * 8);
+    L->part_rep = c.take(cells * ncol * n_rep * 8);
+    L->part_rep_cnt = c.take(cells * n_rep * 8);
+    L->r.g.m.end_fixed(c);
 }
 static bool rank_ci_sizes_ok(int64_t n, int32_t n_domain, int64_t n_user, int32_t n_k, int32_t n_rep) {
     return gauc_sizes_ok(n, n_domain, n_user) && n_k >= 1 && n_k <= RANK_MAX_NK && n_rep >= 0 && n_rep <= BOOT_MAX_REP &&
@@ -4469,8 +4361,9 @@ extern "C" int64_t cdc_eval_rank_ci_workspace_bytes(int64_t n, int32_t n_domain,
                                                     int32_t n_rep) {
     if (!rank_ci_sizes_ok(n, n_domain, n_user, n_k, n_rep)) return 0;
     RankCiLayout L;
-    if (rank_ci_layout(n, n_domain, n_k, paired != 0, n_rep, &L) != 0) return -1;
-    return L.r.total;
+    rank_ci_fixed_layout(n, n_domain, n_k, paired != 0, n_rep, &L);
+    if (gauc_temp(n, "eval_rank_ci", &L.r.g.m) != 0) return -1;
+    return L.r.g.m.total;
 }
 
 template <int NK>
@@ -4501,31 +4394,28 @@ extern "C" int cdc_eval_rank_ci(const float* pred_a, const float* pred_b, const 
     CDC_CHECK_ARG((int64_t)n_rep * ((int64_t)n_domain + 1) * n_k <= RANK_CI_MAX_CELLS, CDC_E_BADARG,
                   "eval_rank_ci: n_rep * (n_domain + 1) * n_k = %ld cells exceed %d", (long)((int64_t)n_rep * ((int64_t)n_domain + 1) * n_k),
                   RANK_CI_MAX_CELLS);
-    CDC_CHECK_ARG(domain || n_domain == 1, CDC_E_BADARG, "eval_rank_ci: n_domain=%d needs the domain column", n_domain);
+    MET_TRY(met_need_domain("eval_rank_ci", domain, n_domain));
     CDC_CHECK_ARG(n < (1ll << 31), CDC_E_TOOBIG, "eval_rank_ci: n=%ld exceeds the 2^31 rows a sorted position counts in 32 bits", (long)n);
     CDC_CHECK_ARG(gauc_sizes_ok(n, n_domain, n_user), CDC_E_BADARG,
                   "eval_rank_ci: (n_domain + 1) * n_user = %ld * %ld group ids exceed 2^32", (long)n_domain + 1, (long)n_user);
-    CDC_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, CDC_E_BADARG, "eval_rank_ci: workspace must be 256-byte aligned");
     const int32_t paired = pred_b != nullptr;
     RankCiLayout L;
     rank_ci_fixed_layout(n, n_domain, n_k, paired, n_rep, &L);
-    CDC_CHECK_ARG(workspace_bytes >= L.r.total, CDC_E_BADARG, "eval_rank_ci: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.r.total);
-    int rc = rank_ci_layout(n, n_domain, n_k, paired, n_rep, &L);
-    if (rc != 0) return rc;
-    CDC_CHECK_ARG(workspace_bytes >= L.r.total, CDC_E_BADARG, "eval_rank_ci: workspace %ld < %ld bytes", (long)workspace_bytes, (long)L.r.total);
-    char* base = (char*)workspace;
-    const uint64_t* keys = (const uint64_t*)(base + L.r.g.keys_out);
-    const GaucScan* sc = (const GaucScan*)(base + L.r.g.scan);
-    const GaucScan* sc_b = (const GaucScan*)(base + L.scan_b);
-    const int64_t* start = (const int64_t*)(base + L.r.g.start);
-    double* part = (double*)(base + L.r.part);
-    int64_t* part_cnt = (int64_t*)(base + L.r.part_cnt);
-    double* part_b = (double*)(base + L.part_b);
-    int64_t* part_cnt_b = (int64_t*)(base + L.part_cnt_b);
-    int64_t* counts_b = (int64_t*)(base + L.counts_b);
-    double* part_sq = (double*)(base + L.part_sq);
-    double* part_rep = (double*)(base + L.part_rep);
-    int64_t* part_rep_cnt = (int64_t*)(base + L.part_rep_cnt);
+    MET_TRY(met_gate("eval_rank_ci", workspace, workspace_bytes, &L.r.g.m, [&] { return gauc_temp(n, "eval_rank_ci", &L.r.g.m); }));
+    const MetWs ws{(char*)workspace};
+    char* base = ws.base;
+    const uint64_t* keys = ws.ptr<const uint64_t>(L.r.g.m.keys_out);
+    const GaucScan* sc = ws.ptr<const GaucScan>(L.r.g.scan);
+    const GaucScan* sc_b = ws.ptr<const GaucScan>(L.scan_b);
+    const int64_t* start = ws.ptr<const int64_t>(L.r.g.m.start);
+    double* part = ws.ptr<double>(L.r.part);
+    int64_t* part_cnt = ws.ptr<int64_t>(L.r.part_cnt);
+    double* part_b = ws.ptr<double>(L.part_b);
+    int64_t* part_cnt_b = ws.ptr<int64_t>(L.part_cnt_b);
+    int64_t* counts_b = ws.ptr<int64_t>(L.counts_b);
+    double* part_sq = ws.ptr<double>(L.part_sq);
+    double* part_rep = ws.ptr<double>(L.part_rep);
+    int64_t* part_rep_cnt = ws.ptr<int64_t>(L.part_rep_cnt);
     hipStream_t st = (hipStream_t)stream;
     const int64_t n2 = 2 * n;
     const int seg = n_domain + 1, nval = RANK_FIGS * n_k, n_sl = rank_ci_slices(n_domain), n_sl_all = rank_ci_slices_all(n_domain);
@@ -4533,11 +4423,9 @@ extern "C" int cdc_eval_rank_ci(const float* pred_a, const float* pred_b, const 
     if (paired) {                                                   // the second vector first: of its order only the scan stays
         GaucLayout Lb = L.r.g;
         Lb.scan = L.scan_b;
-        rc = gauc_order(pred_b, label, user, ld_user, n_user, domain, ld_domain, n_domain, n, err_flag, base, Lb, nullptr, "eval_rank_ci", st);
-        if (rc != 0) return rc;
+        MET_TRY(gauc_order(pred_b, label, user, ld_user, n_user, domain, ld_domain, n_domain, n, err_flag, base, Lb, nullptr, "eval_rank_ci", st));
     }
-    rc = gauc_order(pred_a, label, user, ld_user, n_user, domain, ld_domain, n_domain, n, err_flag, base, L.r.g, nullptr, "eval_rank_ci", st);
-    if (rc != 0) return rc;
+    MET_TRY(gauc_order(pred_a, label, user, ld_user, n_user, domain, ld_domain, n_domain, n, err_flag, base, L.r.g, nullptr, "eval_rank_ci", st));
     for (int v = 0; v <= paired; ++v) {                             // the counts follow from the labels alone: the second set is dropped
         switch (n_k) {
 #define RANK_CASE(NK) case NK: rank_sum_launch<NK>(seg, st, keys, v ? sc_b : sc, start, user_weight, ks, discounts, n_user, n2, \

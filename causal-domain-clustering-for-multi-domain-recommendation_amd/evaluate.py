@@ -63,41 +63,112 @@ import torch
 from . import _lib as L
 
 
+def _need_device(name, t):
+    if not t.is_cuda:
+        raise L.HipExtensionError(f"{name} needs device tensors; there is no CPU fallback")
+
+
+def _flat(t, dtype, dev=None):
+    """t as a contiguous 1-D tensor of dtype (on dev); a tensor that already is one passes through without a torch call"""
+    if t.dtype is dtype and t.dim() == 1 and t.is_contiguous() and (dev is None or t.device == dev):
+        return t
+    return t.reshape(-1).to(device=dev, dtype=dtype).contiguous()
+
+
+def _rows(name, pred, label=None, pred_b=None, max_rows=None):
+    """The row vectors of a call: device refusal, flattening, length checks -> (pred f32, label int16 or None, pred_b f32 or None, n).
+    max_rows: (limit, what the limit protects), checked between the labels and pred_b."""
+    _need_device(name, pred)
+    pred = _flat(pred, torch.float32)
+    n = pred.numel()
+    if label is not None:
+        label = _flat(label, torch.int16)
+        if label.numel() != n:
+            raise ValueError(f"{n} predictions but {label.numel()} labels")
+    if max_rows is not None and n > max_rows[0]:
+        raise ValueError(f"{n} rows exceed the {max_rows[0]} {max_rows[1]}")
+    if pred_b is not None:
+        pred_b = _flat(pred_b, torch.float32, pred.device)
+        if pred_b.numel() != n:
+            raise ValueError(f"{n} predictions but {pred_b.numel()} in pred_b")
+    return pred, label, pred_b, n
+
+
+def _id_column(col, n, what):
+    """int32 [n] or a strided column view (X[:, idx]) -> (tensor, element stride)"""
+    if col.dtype != torch.int32:
+        col = col.to(torch.int32)
+    col = col.reshape(-1) if col.dim() > 1 and col.is_contiguous() else col
+    if col.dim() != 1 or col.numel() != n:
+        raise ValueError(f"{what} must hold one entry per prediction")
+    return col, col.stride(0)
+
+
+def _id_arg(col, n, what):
+    """an optional id column -> (tensor or None, element stride, address or None)"""
+    if col is None:
+        return None, 0, None
+    col, ld = _id_column(col, n, what)
+    return col, ld, col.data_ptr()
+
+
+def _domain_arg(domain, n, n_domain):
+    if domain is None and n_domain != 1:
+        raise ValueError("n_domain > 1 needs the domain column")
+    return _id_arg(domain, n, "domain")
+
+
+def _user_weight_arg(w, n_user, dev, what="users"):
+    """-> (f64 [n_user] on the device or None, address or None)"""
+    if w is None:
+        return None, None
+    w = torch.as_tensor(w, dtype=torch.float64).to(dev).reshape(-1).contiguous()
+    if w.numel() != n_user:
+        raise ValueError(f"user_weight holds {w.numel()} entries for {n_user} {what}")
+    return w, w.data_ptr()
+
+
+def _group_ids_ok(n_user, n_domain, n_seg, n_seg_text):
+    """n_seg * n_user (domain, user) groups must fit the upper half of a sort key; n_seg_text: how the message spells n_seg"""
+    if n_user <= 0 or n_domain <= 0:
+        raise ValueError(f"n_user={n_user} and n_domain={n_domain} must be positive")
+    if n_seg * n_user > 1 << 32:
+        raise ValueError(f"{n_seg_text} * n_user = {n_seg * n_user} group ids exceed 2^32, the upper half of a sort key")
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _call(owner, entry, args, dev, size=None, refused=None, tail=()):
+    """One C-ABI launch on the current stream: entry(*args, error word, *tail[, workspace, bytes]).  size: the name of the entry's
+    workspace query and its arguments (None: the entry takes no workspace); `refused` is the RuntimeError's text when the query
+    answers <= 0.  The error word is kept as owner.last_err."""
+    lib = L.load()
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    args = args + (err.data_ptr(),) + tail
+    if size is not None:
+        nbytes = getattr(lib, size[0])(*size[1:])
+        if nbytes <= 0:
+            raise RuntimeError(refused or f"{size[0]} failed")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        args += (ws.data_ptr(), nbytes)
+    L.launch(entry, getattr(lib, entry), args, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    owner.last_err = err
+
+
 def eval_metrics(pred, label, domain=None, n_domain=1):
     """pred f32 [n], label int16 [n] (0/1), domain int32 [n] or a strided column view (e.g. X[:, domain_idx]).
     Returns (auc, loss, rows, positives): device tensors with n_domain + 1 entries each — domains 0..n_domain-1, then ALL
     rows.  NaN where a segment is empty or holds a single class.  No host synchronisation."""
-    lib = L.load()
-    if not pred.is_cuda:
-        raise L.HipExtensionError("eval_metrics needs device tensors; there is no CPU fallback")
-    pred = pred.reshape(-1).to(torch.float32).contiguous()
-    label = label.reshape(-1).to(torch.int16).contiguous()
-    n = pred.numel()
-    if label.numel() != n:
-        raise ValueError(f"{n} predictions but {label.numel()} labels")
-    ld = 0
-    if domain is not None:
-        if domain.dtype != torch.int32:
-            domain = domain.to(torch.int32)
-        domain = domain.reshape(-1) if domain.dim() > 1 and domain.is_contiguous() else domain
-        if domain.dim() != 1 or domain.numel() != n:
-            raise ValueError("domain must hold one entry per prediction")
-        ld = domain.stride(0)
-    elif n_domain != 1:
-        raise ValueError("n_domain > 1 needs the domain column")
+    pred, label, _, n = _rows("eval_metrics", pred, label)
+    domain, ld, domain_p = _domain_arg(domain, n, n_domain)
     dev = pred.device
     seg = n_domain + 1
     out = torch.empty(2 * seg, dtype=torch.float64, device=dev)
     counts = torch.empty(2 * seg, dtype=torch.int64, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    nbytes = lib.cdc_eval_workspace_bytes(n, n_domain)
-    if nbytes <= 0:
-        raise RuntimeError("cdc_eval_workspace_bytes failed")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    L.launch("cdc_eval_metrics", lib.cdc_eval_metrics,
-             (pred.data_ptr(), label.data_ptr(), None if domain is None else domain.data_ptr(), ld, n, n_domain, out.data_ptr(),
-              counts.data_ptr(), err.data_ptr(), ws.data_ptr(), nbytes), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    eval_metrics.last_err = err
+    _call(eval_metrics, "cdc_eval_metrics", (pred.data_ptr(), label.data_ptr(), domain_p, ld, n, n_domain, out.data_ptr(), counts.data_ptr()),
+          dev, ("cdc_eval_workspace_bytes", n, n_domain))
     return out[:seg], out[seg:], counts[:seg], counts[seg:]
 
 
@@ -112,9 +183,7 @@ def eval_segments(probs, label, seg_sizes, seg_col=None, metric="loss"):
     `eval_segments.last_err`."""
     if metric not in ("loss", "auc"):
         raise ValueError(f"metric must be 'loss' or 'auc', not {metric!r}")
-    lib = L.load()
-    if not probs.is_cuda:
-        raise L.HipExtensionError("eval_segments needs device tensors; there is no CPU fallback")
+    _need_device("eval_segments", probs)
     if probs.dim() == 1:
         probs = probs.reshape(-1, 1)
     if probs.dim() != 2:
@@ -143,30 +212,16 @@ def eval_segments(probs, label, seg_sizes, seg_col=None, metric="loss"):
     # bounds and columns travel in one copy from pinned memory: stream-ordered, the host does not wait for the device
     meta = torch.tensor(starts + cols, dtype=torch.int32, pin_memory=True).to(dev, non_blocking=True)
     loss = torch.empty(n_seg, dtype=torch.float64, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
     want_auc = metric == "auc" and n > 0
     sel = torch.empty(n, dtype=torch.float32, device=dev) if want_auc else None
     seg = torch.empty(n, dtype=torch.int32, device=dev) if want_auc else None
-    L.launch("cdc_eval_segments", lib.cdc_eval_segments,
-             (probs.data_ptr(), ld, label.data_ptr(), meta.data_ptr(), n_seg, meta[n_seg + 1:].data_ptr(), loss.data_ptr(),
-              None if sel is None else sel.data_ptr(), None if seg is None else seg.data_ptr(), err.data_ptr(), rows, n_cols),
-             C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    eval_segments.last_err = err
+    _call(eval_segments, "cdc_eval_segments", (probs.data_ptr(), ld, label.data_ptr(), meta.data_ptr(), n_seg, meta[n_seg + 1:].data_ptr(),
+                                               loss.data_ptr(), _ptr(sel), _ptr(seg)), dev, tail=(rows, n_cols))
     if metric == "loss":
         return loss.to(torch.float32)
     if not want_auc:
         return torch.full((n_seg,), math.nan, dtype=torch.float32, device=dev)
     return eval_metrics(sel, label[:n], seg, n_seg)[0][:n_seg].to(torch.float32)
-
-
-def _id_column(col, n, what):
-    """int32 [n] or a strided column view (X[:, idx]) -> (tensor, element stride)"""
-    if col.dtype != torch.int32:
-        col = col.to(torch.int32)
-    col = col.reshape(-1) if col.dim() > 1 and col.is_contiguous() else col
-    if col.dim() != 1 or col.numel() != n:
-        raise ValueError(f"{what} must hold one entry per prediction")
-    return col, col.stride(0)
 
 
 def eval_gauc(pred, label, user, n_user, domain=None, n_domain=1, user_weight=None):
@@ -176,43 +231,18 @@ def eval_gauc(pred, label, user, n_user, domain=None, n_domain=1, user_weight=No
     Returns (gauc f64, counted i64, left_out i64): device tensors with n_domain + 1 entries each — domains 0..n_domain-1 (their rows
     grouped by user), then ALL rows grouped by user across domains; counted / left_out are the users with both classes / with a
     single class.  NaN where no user is counted (the reference divides by zero there).  No host synchronisation."""
-    lib = L.load()
     n_user, n_domain = int(n_user), int(n_domain)
-    if n_user <= 0 or n_domain <= 0:
-        raise ValueError(f"n_user={n_user} and n_domain={n_domain} must be positive")
-    if (n_domain + 1) * n_user > 1 << 32:
-        raise ValueError(f"(n_domain + 1) * n_user = {(n_domain + 1) * n_user} group ids exceed 2^32, the upper half of a sort key")
-    if not pred.is_cuda:
-        raise L.HipExtensionError("eval_gauc needs device tensors; there is no CPU fallback")
-    pred = pred.reshape(-1).to(torch.float32).contiguous()
-    label = label.reshape(-1).to(torch.int16).contiguous()
-    n = pred.numel()
-    if label.numel() != n:
-        raise ValueError(f"{n} predictions but {label.numel()} labels")
+    _group_ids_ok(n_user, n_domain, n_domain + 1, "(n_domain + 1)")
+    pred, label, _, n = _rows("eval_gauc", pred, label)
     user, ld_user = _id_column(user, n, "user")
-    ld_domain = 0
-    if domain is not None:
-        domain, ld_domain = _id_column(domain, n, "domain")
-    elif n_domain != 1:
-        raise ValueError("n_domain > 1 needs the domain column")
+    domain, ld_domain, domain_p = _domain_arg(domain, n, n_domain)
     dev = pred.device
-    if user_weight is not None:
-        user_weight = torch.as_tensor(user_weight, dtype=torch.float64).to(dev).reshape(-1).contiguous()
-        if user_weight.numel() != n_user:
-            raise ValueError(f"user_weight holds {user_weight.numel()} entries for {n_user} users")
+    user_weight, weight_p = _user_weight_arg(user_weight, n_user, dev)
     seg = n_domain + 1
     out = torch.empty(seg, dtype=torch.float64, device=dev)
     counts = torch.empty(2 * seg, dtype=torch.int64, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    nbytes = lib.cdc_eval_gauc_workspace_bytes(n, n_domain, n_user)
-    if nbytes <= 0:
-        raise RuntimeError("cdc_eval_gauc_workspace_bytes failed")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    L.launch("cdc_eval_gauc", lib.cdc_eval_gauc,
-             (pred.data_ptr(), label.data_ptr(), user.data_ptr(), ld_user, n_user, None if domain is None else domain.data_ptr(),
-              ld_domain, n_domain, None if user_weight is None else user_weight.data_ptr(), n, out.data_ptr(), counts.data_ptr(),
-              err.data_ptr(), ws.data_ptr(), nbytes), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    eval_gauc.last_err = err
+    _call(eval_gauc, "cdc_eval_gauc", (pred.data_ptr(), label.data_ptr(), user.data_ptr(), ld_user, n_user, domain_p, ld_domain, n_domain,
+                                       weight_p, n, out.data_ptr(), counts.data_ptr()), dev, ("cdc_eval_gauc_workspace_bytes", n, n_domain, n_user))
     return out, counts[:seg], counts[seg:]
 
 
@@ -235,6 +265,14 @@ def _rank_ks(ks):
         if b <= a:
             raise ValueError(f"ks={ks!r} must be strictly increasing: {b} follows {a}")
     return ks
+
+
+def _rank_ks_dev(ks, dev):
+    """the cut-offs as an int32 device tensor, cached per (device, ks); from pinned memory, as rank_discounts' table"""
+    key = ("ks", str(dev), ks)
+    if key not in _rank_tables:
+        _rank_tables[key] = torch.tensor(ks, dtype=torch.int32, pin_memory=True).to(dev, non_blocking=True)
+    return _rank_tables[key]
 
 
 def rank_discounts(k_max, device=None):
@@ -266,48 +304,22 @@ def eval_rank(pred, label, user, n_user, domain=None, n_domain=1, ks=(10,), user
     Returns Rank(ndcg, recall, precision, hit, mrr, counted, left_out): the figures f64 device tensors [len(ks), n_domain + 1], NaN
     where no group is counted; counted / left_out i64 [n_domain + 1], the groups with / without a positive.  The same rows in any
     order give the same bits.  No host synchronisation; the error word (as `eval_gauc`'s) is kept as `eval_rank.last_err`."""
-    lib = L.load()
     n_user, n_domain = int(n_user), int(n_domain)
-    if n_user <= 0 or n_domain <= 0:
-        raise ValueError(f"n_user={n_user} and n_domain={n_domain} must be positive")
-    if (n_domain + 1) * n_user > 1 << 32:
-        raise ValueError(f"(n_domain + 1) * n_user = {(n_domain + 1) * n_user} group ids exceed 2^32, the upper half of a sort key")
+    _group_ids_ok(n_user, n_domain, n_domain + 1, "(n_domain + 1)")
     ks = _rank_ks(ks)
-    if not pred.is_cuda:
-        raise L.HipExtensionError("eval_rank needs device tensors; there is no CPU fallback")
-    pred = pred.reshape(-1).to(torch.float32).contiguous()
-    label = label.reshape(-1).to(torch.int16).contiguous()
-    n = pred.numel()
-    if label.numel() != n:
-        raise ValueError(f"{n} predictions but {label.numel()} labels")
+    pred, label, _, n = _rows("eval_rank", pred, label)
     user, ld_user = _id_column(user, n, "user")
-    ld_domain = 0
-    if domain is not None:
-        domain, ld_domain = _id_column(domain, n, "domain")
-    elif n_domain != 1:
-        raise ValueError("n_domain > 1 needs the domain column")
+    domain, ld_domain, domain_p = _domain_arg(domain, n, n_domain)
     dev = pred.device
-    if user_weight is not None:
-        user_weight = torch.as_tensor(user_weight, dtype=torch.float64).to(dev).reshape(-1).contiguous()
-        if user_weight.numel() != n_user:
-            raise ValueError(f"user_weight holds {user_weight.numel()} entries for {n_user} users")
-    key = ("ks", str(dev), ks)
-    if key not in _rank_tables:
-        _rank_tables[key] = torch.tensor(ks, dtype=torch.int32, pin_memory=True).to(dev, non_blocking=True)
-    ks_dev, disc = _rank_tables[key], rank_discounts(ks[-1], dev)
+    user_weight, weight_p = _user_weight_arg(user_weight, n_user, dev)
+    ks_dev, disc = _rank_ks_dev(ks, dev), rank_discounts(ks[-1], dev)
     seg, n_k = n_domain + 1, len(ks)
     out = torch.empty((len(RANK_FIGURES), n_k, seg), dtype=torch.float64, device=dev)
     counts = torch.empty((2, seg), dtype=torch.int64, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    nbytes = lib.cdc_eval_rank_workspace_bytes(n, n_domain, n_user, n_k)
-    if nbytes <= 0:
-        raise RuntimeError(f"cdc_eval_rank_workspace_bytes refused n={n}, n_domain={n_domain}, n_user={n_user}, n_k={n_k}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    L.launch("cdc_eval_rank", lib.cdc_eval_rank,
-             (pred.data_ptr(), label.data_ptr(), user.data_ptr(), ld_user, n_user, None if domain is None else domain.data_ptr(),
-              ld_domain, n_domain, None if user_weight is None else user_weight.data_ptr(), ks_dev.data_ptr(), n_k, disc.data_ptr(), n,
-              out.data_ptr(), counts.data_ptr(), err.data_ptr(), ws.data_ptr(), nbytes), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    eval_rank.last_err = err
+    _call(eval_rank, "cdc_eval_rank", (pred.data_ptr(), label.data_ptr(), user.data_ptr(), ld_user, n_user, domain_p, ld_domain, n_domain,
+                                       weight_p, ks_dev.data_ptr(), n_k, disc.data_ptr(), n, out.data_ptr(), counts.data_ptr()), dev,
+          ("cdc_eval_rank_workspace_bytes", n, n_domain, n_user, n_k),
+          f"cdc_eval_rank_workspace_bytes refused n={n}, n_domain={n_domain}, n_user={n_user}, n_k={n_k}")
     return Rank(out[0], out[1], out[2], out[3], out[4], counts[0], counts[1])
 
 
@@ -408,44 +420,26 @@ def eval_topk(pred, user, n_user, domain=None, n_domain=1, item=None, k=10, sync
     largest such row index) is kept as `eval_topk.last_err` and as the result's `err`.
     Returns a `TopK`.  sync=True reads the two counts once and slices every tensor to them; sync=False reads nothing back (the tensors
     keep capacity n and `n_out` stays on the device): the call can be captured in a graph.  The same input gives the same bits."""
-    lib = L.load()
     n_user, n_domain = int(n_user), int(n_domain)
-    if n_user <= 0 or n_domain <= 0:
-        raise ValueError(f"n_user={n_user} and n_domain={n_domain} must be positive")
-    if n_domain * n_user > 1 << 32:
-        raise ValueError(f"n_domain * n_user = {n_domain * n_user} group ids exceed 2^32, the upper half of a sort key")
+    _group_ids_ok(n_user, n_domain, n_domain, "n_domain")
     if isinstance(k, bool) or int(k) != k or not 1 <= k <= TOPK_MAX_K:
         raise ValueError(f"k={k!r} is no integer in [1, {TOPK_MAX_K}]")
     k = int(k)
-    if not pred.is_cuda:
-        raise L.HipExtensionError("eval_topk needs device tensors; there is no CPU fallback")
-    pred = pred.reshape(-1).to(torch.float32).contiguous()
-    n = pred.numel()
+    pred, _, _, n = _rows("eval_topk", pred)
     user, ld_user = _id_column(user, n, "user")
-    ld_domain = ld_item = 0
-    if domain is not None:
-        domain, ld_domain = _id_column(domain, n, "domain")
-    elif n_domain != 1:
-        raise ValueError("n_domain > 1 needs the domain column")
-    if item is not None:
-        item, ld_item = _id_column(item, n, "item")
+    domain, ld_domain, domain_p = _domain_arg(domain, n, n_domain)
+    item, ld_item, item_p = _id_arg(item, n, "item")
     dev = pred.device
     n_out = torch.empty(2, dtype=torch.int64, device=dev)
     groups = torch.empty((3, n), dtype=torch.int32, device=dev)               # domain, user, rows
     start = torch.empty(n + 1, dtype=torch.int32, device=dev)
     row = torch.empty(n, dtype=torch.int32, device=dev)
     score = torch.empty(n, dtype=torch.float32, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    nbytes = lib.cdc_eval_topk_workspace_bytes(n, n_domain, n_user, int(item is not None))
-    if nbytes <= 0:
-        raise RuntimeError(f"cdc_eval_topk_workspace_bytes refused n={n}, n_domain={n_domain}, n_user={n_user}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    L.launch("cdc_eval_topk", lib.cdc_eval_topk,
-             (pred.data_ptr(), user.data_ptr(), ld_user, n_user, None if domain is None else domain.data_ptr(), ld_domain, n_domain,
-              None if item is None else item.data_ptr(), ld_item, k, n, n_out.data_ptr(), groups[0].data_ptr(), groups[1].data_ptr(),
-              start.data_ptr(), groups[2].data_ptr(), row.data_ptr(), score.data_ptr(), err.data_ptr(), ws.data_ptr(), nbytes),
-             C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    eval_topk.last_err = err
+    _call(eval_topk, "cdc_eval_topk", (pred.data_ptr(), user.data_ptr(), ld_user, n_user, domain_p, ld_domain, n_domain, item_p, ld_item, k, n,
+                                       n_out.data_ptr(), groups[0].data_ptr(), groups[1].data_ptr(), start.data_ptr(), groups[2].data_ptr(),
+                                       row.data_ptr(), score.data_ptr()), dev, ("cdc_eval_topk_workspace_bytes", n, n_domain, n_user, int(item is not None)),
+          f"cdc_eval_topk_workspace_bytes refused n={n}, n_domain={n_domain}, n_user={n_user}")
+    err = eval_topk.last_err
     if not sync:
         # entries past E are unspecified: the gather stays inside the column whatever stands there
         it = None if item is None else item[row.clamp(0, n - 1).to(torch.int64)]
@@ -454,6 +448,21 @@ def eval_topk(pred, user, n_user, domain=None, n_domain=1, item=None, k=10, sync
     row = row[:E]
     it = None if item is None else item[row.to(torch.int64)]
     return TopK(groups[0, :G], groups[1, :G], start[:G + 1], groups[2, :G], row, score[:E], n_out, k, n, n_user, n_domain, it, None, err)
+
+
+def _segment_ci(owner, name, entry, pred, label, domain, n_domain, pred_b):
+    """eval_auc_ci and eval_loss_ci: the same arguments and outputs -> (out [2 or 6, seg], counts [2 seg], seg, paired)"""
+    pred, label, pred_b, n = _rows(name, pred, label, pred_b)
+    n_domain = int(n_domain)
+    domain, ld, domain_p = _domain_arg(domain, n, n_domain)
+    dev = pred.device
+    seg = n_domain + 1
+    paired = pred_b is not None
+    out = torch.empty((6 if paired else 2) * seg, dtype=torch.float64, device=dev)
+    counts = torch.empty(2 * seg, dtype=torch.int64, device=dev)
+    _call(owner, entry, (pred.data_ptr(), _ptr(pred_b), label.data_ptr(), domain_p, ld, n, n_domain, out.data_ptr(), counts.data_ptr()), dev,
+          (f"{entry}_workspace_bytes", n, n_domain, int(paired)), f"{entry}_workspace_bytes refused n={n}, n_domain={n_domain}")
+    return out.reshape(-1, seg), counts, seg, paired
 
 
 AucCI = collections.namedtuple("AucCI", "auc var rows positives")
@@ -469,40 +478,7 @@ def eval_auc_ci(pred, label, domain=None, n_domain=1, pred_b=None):
     the two vectors are close).  A standard error is `var.sqrt()`.  `auc` / `delta` are NaN for an empty or single-class segment,
     a variance is NaN when a class has fewer than two rows.  No host synchronisation; the error word (1 + a row with a NaN
     prediction in either vector, a label outside {0, 1} or a domain outside range) is kept as `eval_auc_ci.last_err`."""
-    lib = L.load()
-    if not pred.is_cuda:
-        raise L.HipExtensionError("eval_auc_ci needs device tensors; there is no CPU fallback")
-    pred = pred.reshape(-1).to(torch.float32).contiguous()
-    label = label.reshape(-1).to(torch.int16).contiguous()
-    n = pred.numel()
-    if label.numel() != n:
-        raise ValueError(f"{n} predictions but {label.numel()} labels")
-    if pred_b is not None:
-        pred_b = pred_b.reshape(-1).to(device=pred.device, dtype=torch.float32).contiguous()
-        if pred_b.numel() != n:
-            raise ValueError(f"{n} predictions but {pred_b.numel()} in pred_b")
-    n_domain = int(n_domain)
-    ld = 0
-    if domain is not None:
-        domain, ld = _id_column(domain, n, "domain")
-    elif n_domain != 1:
-        raise ValueError("n_domain > 1 needs the domain column")
-    dev = pred.device
-    seg = n_domain + 1
-    paired = pred_b is not None
-    out = torch.empty((6 if paired else 2) * seg, dtype=torch.float64, device=dev)
-    counts = torch.empty(2 * seg, dtype=torch.int64, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    nbytes = lib.cdc_eval_auc_delong_workspace_bytes(n, n_domain, int(paired))
-    if nbytes <= 0:
-        raise RuntimeError(f"cdc_eval_auc_delong_workspace_bytes refused n={n}, n_domain={n_domain}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    L.launch("cdc_eval_auc_delong", lib.cdc_eval_auc_delong,
-             (pred.data_ptr(), pred_b.data_ptr() if paired else None, label.data_ptr(), None if domain is None else domain.data_ptr(), ld,
-              n, n_domain, out.data_ptr(), counts.data_ptr(), err.data_ptr(), ws.data_ptr(), nbytes),
-             C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    eval_auc_ci.last_err = err
-    o = out.reshape(-1, seg)
+    o, counts, seg, paired = _segment_ci(eval_auc_ci, "eval_auc_ci", "cdc_eval_auc_delong", pred, label, domain, n_domain, pred_b)
     if paired:
         return AucCIPaired(o[0], o[1], counts[:seg], counts[seg:], o[2], o[3], o[4], o[5])
     return AucCI(o[0], o[1], counts[:seg], counts[seg:])
@@ -523,40 +499,7 @@ def eval_loss_ci(pred, label, domain=None, n_domain=1, pred_b=None):
     `eval_metrics`' loss is.  No host synchronisation; the error word (1 + a row with a NaN prediction or one outside [0, 1] in
     either vector, a label outside {0, 1} or a domain outside range) is kept as `eval_loss_ci.last_err`.
     A user-clustered error of the log-loss comes from `eval_bootstrap` with the user column as its clusters, not from here."""
-    lib = L.load()
-    if not pred.is_cuda:
-        raise L.HipExtensionError("eval_loss_ci needs device tensors; there is no CPU fallback")
-    pred = pred.reshape(-1).to(torch.float32).contiguous()
-    label = label.reshape(-1).to(torch.int16).contiguous()
-    n = pred.numel()
-    if label.numel() != n:
-        raise ValueError(f"{n} predictions but {label.numel()} labels")
-    if pred_b is not None:
-        pred_b = pred_b.reshape(-1).to(device=pred.device, dtype=torch.float32).contiguous()
-        if pred_b.numel() != n:
-            raise ValueError(f"{n} predictions but {pred_b.numel()} in pred_b")
-    n_domain = int(n_domain)
-    ld = 0
-    if domain is not None:
-        domain, ld = _id_column(domain, n, "domain")
-    elif n_domain != 1:
-        raise ValueError("n_domain > 1 needs the domain column")
-    dev = pred.device
-    seg = n_domain + 1
-    paired = pred_b is not None
-    out = torch.empty((6 if paired else 2) * seg, dtype=torch.float64, device=dev)
-    counts = torch.empty(2 * seg, dtype=torch.int64, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    nbytes = lib.cdc_eval_loss_ci_workspace_bytes(n, n_domain, int(paired))
-    if nbytes <= 0:
-        raise RuntimeError(f"cdc_eval_loss_ci_workspace_bytes refused n={n}, n_domain={n_domain}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    L.launch("cdc_eval_loss_ci", lib.cdc_eval_loss_ci,
-             (pred.data_ptr(), pred_b.data_ptr() if paired else None, label.data_ptr(), None if domain is None else domain.data_ptr(), ld,
-              n, n_domain, out.data_ptr(), counts.data_ptr(), err.data_ptr(), ws.data_ptr(), nbytes),
-             C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    eval_loss_ci.last_err = err
-    o = out.reshape(-1, seg)
+    o, counts, seg, paired = _segment_ci(eval_loss_ci, "eval_loss_ci", "cdc_eval_loss_ci", pred, label, domain, n_domain, pred_b)
     if paired:
         return LossCIPaired(o[0], o[1], counts[:seg], counts[seg:], o[2], o[3], o[4], o[5])
     return LossCI(o[0], o[1], counts[:seg], counts[seg:])
@@ -576,49 +519,21 @@ def eval_gauc_ci(pred, label, user, n_user, domain=None, n_domain=1, user_weight
     standard error is `var.sqrt()`.  `gauc` / `delta` are NaN where no user is counted, a variance where fewer than two are.  The
     same rows in any order give the same bits.  No host synchronisation; the error word (as `eval_gauc`'s, over both vectors) is
     kept as `eval_gauc_ci.last_err`."""
-    lib = L.load()
     n_user, n_domain = int(n_user), int(n_domain)
-    if n_user <= 0 or n_domain <= 0:
-        raise ValueError(f"n_user={n_user} and n_domain={n_domain} must be positive")
-    if (n_domain + 1) * n_user > 1 << 32:
-        raise ValueError(f"(n_domain + 1) * n_user = {(n_domain + 1) * n_user} group ids exceed 2^32, the upper half of a sort key")
-    if not pred.is_cuda:
-        raise L.HipExtensionError("eval_gauc_ci needs device tensors; there is no CPU fallback")
-    pred = pred.reshape(-1).to(torch.float32).contiguous()
-    label = label.reshape(-1).to(torch.int16).contiguous()
-    n = pred.numel()
-    if label.numel() != n:
-        raise ValueError(f"{n} predictions but {label.numel()} labels")
-    if pred_b is not None:
-        pred_b = pred_b.reshape(-1).to(device=pred.device, dtype=torch.float32).contiguous()
-        if pred_b.numel() != n:
-            raise ValueError(f"{n} predictions but {pred_b.numel()} in pred_b")
+    _group_ids_ok(n_user, n_domain, n_domain + 1, "(n_domain + 1)")
+    pred, label, pred_b, n = _rows("eval_gauc_ci", pred, label, pred_b)
     user, ld_user = _id_column(user, n, "user")
-    ld_domain = 0
-    if domain is not None:
-        domain, ld_domain = _id_column(domain, n, "domain")
-    elif n_domain != 1:
-        raise ValueError("n_domain > 1 needs the domain column")
+    domain, ld_domain, domain_p = _domain_arg(domain, n, n_domain)
     dev = pred.device
-    if user_weight is not None:
-        user_weight = torch.as_tensor(user_weight, dtype=torch.float64).to(dev).reshape(-1).contiguous()
-        if user_weight.numel() != n_user:
-            raise ValueError(f"user_weight holds {user_weight.numel()} entries for {n_user} users")
+    user_weight, weight_p = _user_weight_arg(user_weight, n_user, dev)
     seg = n_domain + 1
     paired = pred_b is not None
     out = torch.empty((6 if paired else 2) * seg, dtype=torch.float64, device=dev)
     counts = torch.empty(2 * seg, dtype=torch.int64, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    nbytes = lib.cdc_eval_gauc_ci_workspace_bytes(n, n_domain, n_user, int(paired))
-    if nbytes <= 0:
-        raise RuntimeError(f"cdc_eval_gauc_ci_workspace_bytes refused n={n}, n_domain={n_domain}, n_user={n_user}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    L.launch("cdc_eval_gauc_ci", lib.cdc_eval_gauc_ci,
-             (pred.data_ptr(), pred_b.data_ptr() if paired else None, label.data_ptr(), user.data_ptr(), ld_user, n_user,
-              None if domain is None else domain.data_ptr(), ld_domain, n_domain, None if user_weight is None else user_weight.data_ptr(),
-              n, out.data_ptr(), counts.data_ptr(), err.data_ptr(), ws.data_ptr(), nbytes),
-             C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    eval_gauc_ci.last_err = err
+    _call(eval_gauc_ci, "cdc_eval_gauc_ci", (pred.data_ptr(), _ptr(pred_b), label.data_ptr(), user.data_ptr(), ld_user, n_user, domain_p,
+                                             ld_domain, n_domain, weight_p, n, out.data_ptr(), counts.data_ptr()), dev,
+          ("cdc_eval_gauc_ci_workspace_bytes", n, n_domain, n_user, int(paired)),
+          f"cdc_eval_gauc_ci_workspace_bytes refused n={n}, n_domain={n_domain}, n_user={n_user}")
     o = out.reshape(-1, seg)
     if paired:
         return GaucCIPaired(o[0], o[1], counts[:seg], counts[seg:], o[2], o[3], o[4], o[5])
@@ -651,7 +566,6 @@ def eval_bootstrap(pred, label, cluster=None, n_cluster=None, domain=None, n_dom
     `eval_bootstrap.last_err`.  `summarize_bootstrap` turns a replicate matrix into a standard error and a percentile interval.
     The calibration figures' replicates under the same weights come from `eval_calibration_bootstrap`.  Not offered: BCa or studentised
     intervals."""
-    lib = L.load()
     n_domain, n_rep, seed = int(n_domain), int(n_rep), int(seed)
     if n_domain <= 0:
         raise ValueError(f"n_domain={n_domain} must be positive")
@@ -674,50 +588,20 @@ def eval_bootstrap(pred, label, cluster=None, n_cluster=None, domain=None, n_dom
             raise ValueError(f"(n_domain + 1) * n_cluster = {(n_domain + 1) * n_cluster} group ids exceed 2^32, the upper half of a sort key")
     else:
         n_cluster = 0
-    if not pred.is_cuda:
-        raise L.HipExtensionError("eval_bootstrap needs device tensors; there is no CPU fallback")
-    pred = pred.reshape(-1).to(torch.float32).contiguous()
-    label = label.reshape(-1).to(torch.int16).contiguous()
-    n = pred.numel()
-    if label.numel() != n:
-        raise ValueError(f"{n} predictions but {label.numel()} labels")
-    if n > BOOT_MAX_ROWS:
-        raise ValueError(f"{n} rows exceed the {BOOT_MAX_ROWS} whose weighted pair count fits 64 bits")
-    if pred_b is not None:
-        pred_b = pred_b.reshape(-1).to(device=pred.device, dtype=torch.float32).contiguous()
-        if pred_b.numel() != n:
-            raise ValueError(f"{n} predictions but {pred_b.numel()} in pred_b")
-    ld_cluster = 0
-    if cluster is not None:
-        cluster, ld_cluster = _id_column(cluster, n, "cluster")
-    ld_domain = 0
-    if domain is not None:
-        domain, ld_domain = _id_column(domain, n, "domain")
-    elif n_domain != 1:
-        raise ValueError("n_domain > 1 needs the domain column")
+    pred, label, pred_b, n = _rows("eval_bootstrap", pred, label, pred_b, (BOOT_MAX_ROWS, "whose weighted pair count fits 64 bits"))
+    cluster, ld_cluster, cluster_p = _id_arg(cluster, n, "cluster")
+    domain, ld_domain, domain_p = _domain_arg(domain, n, n_domain)
     dev = pred.device
-    if user_weight is not None and gauc:
-        user_weight = torch.as_tensor(user_weight, dtype=torch.float64).to(dev).reshape(-1).contiguous()
-        if user_weight.numel() != n_cluster:
-            raise ValueError(f"user_weight holds {user_weight.numel()} entries for {n_cluster} clusters")
-    else:
-        user_weight = None
+    user_weight, weight_p = _user_weight_arg(user_weight if gauc else None, n_cluster, dev, "clusters")
     seg = n_domain + 1
     paired = pred_b is not None
     n_stat = (3 if gauc else 2) * (2 if paired else 1)
     out = torch.empty((n_stat, n_rep, seg), dtype=torch.float64, device=dev)
     counts = torch.empty((2, n_rep, seg), dtype=torch.int64, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    nbytes = lib.cdc_eval_bootstrap_workspace_bytes(n, n_domain, n_cluster, n_rep, int(gauc))
-    if nbytes <= 0:
-        raise RuntimeError(f"cdc_eval_bootstrap_workspace_bytes refused n={n}, n_domain={n_domain}, n_cluster={n_cluster}, n_rep={n_rep}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    L.launch("cdc_eval_bootstrap", lib.cdc_eval_bootstrap,
-             (pred.data_ptr(), pred_b.data_ptr() if paired else None, label.data_ptr(), None if cluster is None else cluster.data_ptr(),
-              ld_cluster, n_cluster, None if domain is None else domain.data_ptr(), ld_domain, n_domain,
-              None if user_weight is None else user_weight.data_ptr(), n, n_rep, seed, int(gauc), out.data_ptr(), counts.data_ptr(),
-              err.data_ptr(), ws.data_ptr(), nbytes), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    eval_bootstrap.last_err = err
+    _call(eval_bootstrap, "cdc_eval_bootstrap", (pred.data_ptr(), _ptr(pred_b), label.data_ptr(), cluster_p, ld_cluster, n_cluster, domain_p,
+                                                 ld_domain, n_domain, weight_p, n, n_rep, seed, int(gauc), out.data_ptr(), counts.data_ptr()),
+          dev, ("cdc_eval_bootstrap_workspace_bytes", n, n_domain, n_cluster, n_rep, int(gauc)),
+          f"cdc_eval_bootstrap_workspace_bytes refused n={n}, n_domain={n_domain}, n_cluster={n_cluster}, n_rep={n_rep}")
     k = 3 if gauc else 2
     return Bootstrap(out[0], out[1], out[2] if gauc else None, counts[0], counts[1], out[k] if paired else None,
                      out[k + 1] if paired else None, out[k + 2] if paired and gauc else None)
@@ -744,12 +628,8 @@ def eval_rank_ci(pred, label, user, n_user, domain=None, n_domain=1, ks=(10,), u
     no group is counted, a variance where fewer than two are.  The same rows in any order give the same bits.  n_rep in [0, 4096] and
     n_rep * (n_domain + 1) * len(ks) <= 2^20.  No host synchronisation; the error word (as `eval_rank`'s, over both vectors) is kept
     as `eval_rank_ci.last_err`."""
-    lib = L.load()
     n_user, n_domain, n_rep, seed = int(n_user), int(n_domain), int(n_rep), int(seed)
-    if n_user <= 0 or n_domain <= 0:
-        raise ValueError(f"n_user={n_user} and n_domain={n_domain} must be positive")
-    if (n_domain + 1) * n_user > 1 << 32:
-        raise ValueError(f"(n_domain + 1) * n_user = {(n_domain + 1) * n_user} group ids exceed 2^32, the upper half of a sort key")
+    _group_ids_ok(n_user, n_domain, n_domain + 1, "(n_domain + 1)")
     ks = _rank_ks(ks)
     if not 0 <= n_rep <= BOOT_MAX_REP:
         raise ValueError(f"n_rep={n_rep} must lie in [0, {BOOT_MAX_REP}]")
@@ -757,50 +637,23 @@ def eval_rank_ci(pred, label, user, n_user, domain=None, n_domain=1, ks=(10,), u
         raise ValueError(f"n_rep * (n_domain + 1) * len(ks) = {n_rep * (n_domain + 1) * len(ks)} cells exceed {RANK_CI_MAX_CELLS}")
     if not 0 <= seed < 1 << 64:
         raise ValueError(f"seed={seed} must fit 64 unsigned bits")
-    if not pred.is_cuda:
-        raise L.HipExtensionError("eval_rank_ci needs device tensors; there is no CPU fallback")
-    pred = pred.reshape(-1).to(torch.float32).contiguous()
-    label = label.reshape(-1).to(torch.int16).contiguous()
-    n = pred.numel()
-    if label.numel() != n:
-        raise ValueError(f"{n} predictions but {label.numel()} labels")
-    if pred_b is not None:
-        pred_b = pred_b.reshape(-1).to(device=pred.device, dtype=torch.float32).contiguous()
-        if pred_b.numel() != n:
-            raise ValueError(f"{n} predictions but {pred_b.numel()} in pred_b")
+    pred, label, pred_b, n = _rows("eval_rank_ci", pred, label, pred_b)
     user, ld_user = _id_column(user, n, "user")
-    ld_domain = 0
-    if domain is not None:
-        domain, ld_domain = _id_column(domain, n, "domain")
-    elif n_domain != 1:
-        raise ValueError("n_domain > 1 needs the domain column")
+    domain, ld_domain, domain_p = _domain_arg(domain, n, n_domain)
     dev = pred.device
-    if user_weight is not None:
-        user_weight = torch.as_tensor(user_weight, dtype=torch.float64).to(dev).reshape(-1).contiguous()
-        if user_weight.numel() != n_user:
-            raise ValueError(f"user_weight holds {user_weight.numel()} entries for {n_user} users")
-    key = ("ks", str(dev), ks)
-    if key not in _rank_tables:
-        _rank_tables[key] = torch.tensor(ks, dtype=torch.int32, pin_memory=True).to(dev, non_blocking=True)
-    ks_dev, disc = _rank_tables[key], rank_discounts(ks[-1], dev)
+    user_weight, weight_p = _user_weight_arg(user_weight, n_user, dev)
+    ks_dev, disc = _rank_ks_dev(ks, dev), rank_discounts(ks[-1], dev)
     seg, n_k, n_fig = n_domain + 1, len(ks), len(RANK_FIGURES)
     paired = pred_b is not None
     out = torch.empty((6 if paired else 2, n_fig, n_k, seg), dtype=torch.float64, device=dev)
     counts = torch.empty((2, seg), dtype=torch.int64, device=dev)
     reps = torch.empty((2 if paired else 1, n_rep, n_fig, n_k, seg), dtype=torch.float64, device=dev) if n_rep else None
     rep_counts = torch.empty((n_rep, seg), dtype=torch.int64, device=dev) if n_rep else None
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    nbytes = lib.cdc_eval_rank_ci_workspace_bytes(n, n_domain, n_user, n_k, int(paired), n_rep)
-    if nbytes <= 0:
-        raise RuntimeError(f"cdc_eval_rank_ci_workspace_bytes refused n={n}, n_domain={n_domain}, n_user={n_user}, n_k={n_k}, n_rep={n_rep}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    L.launch("cdc_eval_rank_ci", lib.cdc_eval_rank_ci,
-             (pred.data_ptr(), pred_b.data_ptr() if paired else None, label.data_ptr(), user.data_ptr(), ld_user, n_user,
-              None if domain is None else domain.data_ptr(), ld_domain, n_domain, None if user_weight is None else user_weight.data_ptr(),
-              ks_dev.data_ptr(), n_k, disc.data_ptr(), n, n_rep, seed, out.data_ptr(), reps.data_ptr() if n_rep else None,
-              counts.data_ptr(), rep_counts.data_ptr() if n_rep else None, err.data_ptr(), ws.data_ptr(), nbytes),
-             C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    eval_rank_ci.last_err = err
+    _call(eval_rank_ci, "cdc_eval_rank_ci", (pred.data_ptr(), _ptr(pred_b), label.data_ptr(), user.data_ptr(), ld_user, n_user, domain_p,
+                                             ld_domain, n_domain, weight_p, ks_dev.data_ptr(), n_k, disc.data_ptr(), n, n_rep, seed,
+                                             out.data_ptr(), _ptr(reps), counts.data_ptr(), _ptr(rep_counts)), dev,
+          ("cdc_eval_rank_ci_workspace_bytes", n, n_domain, n_user, n_k, int(paired), n_rep),
+          f"cdc_eval_rank_ci_workspace_bytes refused n={n}, n_domain={n_domain}, n_user={n_user}, n_k={n_k}, n_rep={n_rep}")
     fig = out[0]
     tail = (reps[0] if n_rep else None, reps[1] if n_rep and paired else None, rep_counts)
     if paired:
@@ -851,22 +704,11 @@ def eval_calibration(pred, label, domain=None, n_domain=1, n_bins=10):
     `PlattRecalibration` (Platt, temperature, bias scaling); `eval_calibration_bootstrap` gives pcoc, brier, ece and ece_q their
     bootstrap intervals, `Evaluator(calibration_ci=True)` reports them and the calibration deltas of `Evaluator.compare`.  Not
     offered: selection or early stopping by a calibration figure in `Runner`."""
-    lib = L.load()
     n_domain, n_bins = int(n_domain), int(n_bins)
     if not 1 <= n_bins <= MAX_CALIBRATION_BINS:
         raise ValueError(f"n_bins={n_bins} must lie in [1, {MAX_CALIBRATION_BINS}]")
-    if not pred.is_cuda:
-        raise L.HipExtensionError("eval_calibration needs device tensors; there is no CPU fallback")
-    pred = pred.reshape(-1).to(torch.float32).contiguous()
-    label = label.reshape(-1).to(torch.int16).contiguous()
-    n = pred.numel()
-    if label.numel() != n:
-        raise ValueError(f"{n} predictions but {label.numel()} labels")
-    ld = 0
-    if domain is not None:
-        domain, ld = _id_column(domain, n, "domain")
-    elif n_domain != 1:
-        raise ValueError("n_domain > 1 needs the domain column")
+    pred, label, _, n = _rows("eval_calibration", pred, label)
+    domain, ld, domain_p = _domain_arg(domain, n, n_domain)
     dev = pred.device
     seg = n_domain + 1
     seg_out = torch.empty((8, seg), dtype=torch.float64, device=dev)
@@ -874,16 +716,10 @@ def eval_calibration(pred, label, domain=None, n_domain=1, n_bins=10):
     tab_out = torch.empty((2, 2, seg, n_bins), dtype=torch.float64, device=dev)
     tab_counts = torch.empty((2, 2, seg, n_bins), dtype=torch.int64, device=dev)
     tab_range = torch.empty((2, 2, seg, n_bins), dtype=torch.float32, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    nbytes = lib.cdc_eval_calibration_workspace_bytes(n, n_domain, n_bins)
-    if nbytes <= 0:
-        raise RuntimeError(f"cdc_eval_calibration_workspace_bytes refused n={n}, n_domain={n_domain}, n_bins={n_bins}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    L.launch("cdc_eval_calibration", lib.cdc_eval_calibration,
-             (pred.data_ptr(), label.data_ptr(), None if domain is None else domain.data_ptr(), ld, n, n_domain, n_bins, seg_out.data_ptr(),
-              seg_counts.data_ptr(), tab_out.data_ptr(), tab_counts.data_ptr(), tab_range.data_ptr(), err.data_ptr(), ws.data_ptr(), nbytes),
-             C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    eval_calibration.last_err = err
+    _call(eval_calibration, "cdc_eval_calibration", (pred.data_ptr(), label.data_ptr(), domain_p, ld, n, n_domain, n_bins, seg_out.data_ptr(),
+                                                     seg_counts.data_ptr(), tab_out.data_ptr(), tab_counts.data_ptr(), tab_range.data_ptr()),
+          dev, ("cdc_eval_calibration_workspace_bytes", n, n_domain, n_bins),
+          f"cdc_eval_calibration_workspace_bytes refused n={n}, n_domain={n_domain}, n_bins={n_bins}")
     tables = [CalibrationTable(tab_counts[t, 0], tab_counts[t, 1], tab_out[t, 0], tab_out[t, 1], tab_range[t, 0], tab_range[t, 1]) for t in (0, 1)]
     return Calibration(seg_counts[0], seg_counts[1], *seg_out.unbind(0), tables[0], tables[1])
 
@@ -914,7 +750,6 @@ def eval_calibration_bootstrap(pred, label, cluster=None, n_cluster=None, domain
     ECE is biased upwards on small segments, replicates included: the interval of a delta is more trustworthy than that of a level.
     Not offered: MCE replicates, per-bin reliability bands, BCa or studentised intervals, selection by a calibration figure in
     `Runner`."""
-    lib = L.load()
     n_domain, n_bins, n_rep, seed = int(n_domain), int(n_bins), int(n_rep), int(seed)
     if n_domain <= 0:
         raise ValueError(f"n_domain={n_domain} must be positive")
@@ -935,57 +770,23 @@ def eval_calibration_bootstrap(pred, label, cluster=None, n_cluster=None, domain
             raise ValueError(f"n_cluster={n_cluster} must be positive")
     else:
         n_cluster = 0
-    if not pred.is_cuda:
-        raise L.HipExtensionError("eval_calibration_bootstrap needs device tensors; there is no CPU fallback")
-    pred = pred.reshape(-1).to(torch.float32).contiguous()
-    label = label.reshape(-1).to(torch.int16).contiguous()
-    n = pred.numel()
-    if label.numel() != n:
-        raise ValueError(f"{n} predictions but {label.numel()} labels")
-    if n > BOOT_MAX_ROWS:
-        raise ValueError(f"{n} rows exceed the {BOOT_MAX_ROWS} whose weighted sums fit 64 bits")
-    if pred_b is not None:
-        pred_b = pred_b.reshape(-1).to(device=pred.device, dtype=torch.float32).contiguous()
-        if pred_b.numel() != n:
-            raise ValueError(f"{n} predictions but {pred_b.numel()} in pred_b")
-    ld_cluster = 0
-    if cluster is not None:
-        cluster, ld_cluster = _id_column(cluster, n, "cluster")
-    ld_domain = 0
-    if domain is not None:
-        domain, ld_domain = _id_column(domain, n, "domain")
-    elif n_domain != 1:
-        raise ValueError("n_domain > 1 needs the domain column")
+    pred, label, pred_b, n = _rows("eval_calibration_bootstrap", pred, label, pred_b, (BOOT_MAX_ROWS, "whose weighted sums fit 64 bits"))
+    cluster, ld_cluster, cluster_p = _id_arg(cluster, n, "cluster")
+    domain, ld_domain, domain_p = _domain_arg(domain, n, n_domain)
     dev = pred.device
     seg = n_domain + 1
     paired = pred_b is not None
     out = torch.empty((8 if paired else 4, n_rep, seg), dtype=torch.float64, device=dev)
     counts = torch.empty((2, n_rep, seg), dtype=torch.int64, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    nbytes = lib.cdc_eval_calibration_bootstrap_workspace_bytes(n, n_domain, n_bins, n_rep, int(paired))
-    if nbytes <= 0:
-        raise RuntimeError(f"cdc_eval_calibration_bootstrap_workspace_bytes refused n={n}, n_domain={n_domain}, n_bins={n_bins}, "
-                           f"n_rep={n_rep}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    L.launch("cdc_eval_calibration_bootstrap", lib.cdc_eval_calibration_bootstrap,
-             (pred.data_ptr(), pred_b.data_ptr() if paired else None, label.data_ptr(), None if cluster is None else cluster.data_ptr(),
-              ld_cluster, n_cluster, None if domain is None else domain.data_ptr(), ld_domain, n_domain, n_bins, n, n_rep, seed,
-              out.data_ptr(), counts.data_ptr(), err.data_ptr(), ws.data_ptr(), nbytes),
-             C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    eval_calibration_bootstrap.last_err = err
+    _call(eval_calibration_bootstrap, "cdc_eval_calibration_bootstrap",
+          (pred.data_ptr(), _ptr(pred_b), label.data_ptr(), cluster_p, ld_cluster, n_cluster, domain_p, ld_domain, n_domain, n_bins, n, n_rep,
+           seed, out.data_ptr(), counts.data_ptr()), dev, ("cdc_eval_calibration_bootstrap_workspace_bytes", n, n_domain, n_bins, n_rep, int(paired)),
+          f"cdc_eval_calibration_bootstrap_workspace_bytes refused n={n}, n_domain={n_domain}, n_bins={n_bins}, n_rep={n_rep}")
     second = tuple(out[4:]) if paired else (None,) * 4
     return CalibrationBootstrap(out[0], out[1], out[2], out[3], counts[0], counts[1], *second)
 
 
 IsotonicFit = collections.namedtuple("IsotonicFit", "start x_lo x_hi count positives value rows seg_positives")
-
-
-def _iso_domain(domain, n, n_domain):
-    if domain is not None:
-        return _id_column(domain, n, "domain")
-    if n_domain != 1:
-        raise ValueError("n_domain > 1 needs the domain column")
-    return None, 0
 
 
 def eval_isotonic_fit(pred, label, domain=None, n_domain=1):
@@ -998,34 +799,24 @@ def eval_isotonic_fit(pred, label, domain=None, n_domain=1):
     (integer comparisons until the one division), so the same rows in any order give the same bits.  No host synchronisation; the
     error word (1 + a row with a NaN or infinite score, a label outside {0, 1} or a domain outside range) is kept as
     `eval_isotonic_fit.last_err`."""
-    lib = L.load()
     n_domain = int(n_domain)
-    if not pred.is_cuda:
-        raise L.HipExtensionError("eval_isotonic_fit needs device tensors; there is no CPU fallback")
-    pred = pred.reshape(-1).to(torch.float32).contiguous()
-    label = label.reshape(-1).to(torch.int16).contiguous()
-    n = pred.numel()
-    if label.numel() != n:
-        raise ValueError(f"{n} predictions but {label.numel()} labels")
-    domain, ld = _iso_domain(domain, n, n_domain)
+    pred, label, _, n = _rows("eval_isotonic_fit", pred, label)
+    domain, ld, domain_p = _domain_arg(domain, n, n_domain)
     dev = pred.device
     seg = n_domain + 1
-    cap = lib.cdc_eval_isotonic_max_blocks(n, n_domain)
-    nbytes = lib.cdc_eval_isotonic_fit_workspace_bytes(n, n_domain)
-    if cap <= 0 or nbytes <= 0:
-        raise RuntimeError(f"cdc_eval_isotonic_fit_workspace_bytes refused n={n}, n_domain={n_domain}")
+    refused = f"cdc_eval_isotonic_fit_workspace_bytes refused n={n}, n_domain={n_domain}"
+    cap = L.load().cdc_eval_isotonic_max_blocks(n, n_domain)
+    if cap <= 0:
+        raise RuntimeError(refused)
     start = torch.empty(seg + 1, dtype=torch.int64, device=dev)
     x = torch.empty((2, cap), dtype=torch.float32, device=dev)
     cnt = torch.empty((2, cap), dtype=torch.int64, device=dev)
     value = torch.empty(cap, dtype=torch.float64, device=dev)
     seg_counts = torch.empty((2, seg), dtype=torch.int64, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    L.launch("cdc_eval_isotonic_fit", lib.cdc_eval_isotonic_fit,
-             (pred.data_ptr(), label.data_ptr(), None if domain is None else domain.data_ptr(), ld, n, n_domain, start.data_ptr(),
-              x[0].data_ptr(), x[1].data_ptr(), cnt[0].data_ptr(), cnt[1].data_ptr(), value.data_ptr(), cap, seg_counts[0].data_ptr(),
-              seg_counts[1].data_ptr(), err.data_ptr(), ws.data_ptr(), nbytes), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    eval_isotonic_fit.last_err = err
+    _call(eval_isotonic_fit, "cdc_eval_isotonic_fit", (pred.data_ptr(), label.data_ptr(), domain_p, ld, n, n_domain, start.data_ptr(),
+                                                       x[0].data_ptr(), x[1].data_ptr(), cnt[0].data_ptr(), cnt[1].data_ptr(), value.data_ptr(),
+                                                       cap, seg_counts[0].data_ptr(), seg_counts[1].data_ptr()), dev,
+          ("cdc_eval_isotonic_fit_workspace_bytes", n, n_domain), refused)
     return IsotonicFit(start, x[0], x[1], cnt[0], cnt[1], value, seg_counts[0], seg_counts[1])
 
 
@@ -1037,13 +828,9 @@ def eval_isotonic_apply(pred, fit_or_map, domain=None, n_domain=1, seg_of_domain
     outside range or a segment without blocks gives NaN and sets the error word (1 + the row), kept as
     `eval_isotonic_apply.last_err`.  No host synchronisation.  Not offered: a "step" interpolation (the parametric maps are
     `eval_platt_fit` / `eval_platt_apply`)."""
-    lib = L.load()
     n_domain = int(n_domain)
-    if not pred.is_cuda:
-        raise L.HipExtensionError("eval_isotonic_apply needs device tensors; there is no CPU fallback")
-    pred = pred.reshape(-1).to(torch.float32).contiguous()
-    n = pred.numel()
-    domain, ld = _iso_domain(domain, n, n_domain)
+    pred, _, _, n = _rows("eval_isotonic_apply", pred)
+    domain, ld, domain_p = _domain_arg(domain, n, n_domain)
     dev = pred.device
     m = fit_or_map
     if m.start.numel() != n_domain + 2:
@@ -1058,12 +845,9 @@ def eval_isotonic_apply(pred, fit_or_map, domain=None, n_domain=1, seg_of_domain
     if not 0.0 <= float(eps) <= 0.5:
         raise ValueError(f"eps={eps} must lie in [0, 0.5]")
     out = torch.empty(n, dtype=torch.float32, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    L.launch("cdc_eval_isotonic_apply", lib.cdc_eval_isotonic_apply,
-             (pred.data_ptr(), None if domain is None else domain.data_ptr(), ld, n, n_domain, seg_of_domain.data_ptr(), m.start.data_ptr(),
-              m.x_lo.data_ptr(), m.x_hi.data_ptr(), m.value.data_ptr(), float(eps), out.data_ptr(), err.data_ptr()),
-             C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    eval_isotonic_apply.last_err = err
+    _call(eval_isotonic_apply, "cdc_eval_isotonic_apply", (pred.data_ptr(), domain_p, ld, n, n_domain, seg_of_domain.data_ptr(),
+                                                           m.start.data_ptr(), m.x_lo.data_ptr(), m.x_hi.data_ptr(), m.value.data_ptr(),
+                                                           float(eps), out.data_ptr()), dev)
     return out
 
 
@@ -1160,37 +944,25 @@ def eval_platt_fit(pred, label, domain=None, n_domain=1, method="platt", input="
     order give the same bits.  No host synchronisation; the error word (1 + a row with a NaN score, a probability outside [0, 1], a
     label outside {0, 1} or a domain outside range; such a row counts with z = 0 and label 0) is kept as `eval_platt_fit.last_err`.
     Not offered: beta calibration, vector or matrix scaling."""
-    lib = L.load()
     n_domain, max_iter = int(n_domain), int(max_iter)
-    if not pred.is_cuda:
-        raise L.HipExtensionError("eval_platt_fit needs device tensors; there is no CPU fallback")
+    _need_device("eval_platt_fit", pred)                                   # before the option checks, as ever
     _platt_args(method, input, clip)
     if not float(gtol) > 0.0:
         raise ValueError(f"gtol={gtol} must be positive")
     if not 1 <= max_iter <= 1024:
         raise ValueError(f"max_iter={max_iter} must lie in [1, 1024]")
-    pred = pred.reshape(-1).to(torch.float32).contiguous()
-    label = label.reshape(-1).to(torch.int16).contiguous()
-    n = pred.numel()
-    if label.numel() != n:
-        raise ValueError(f"{n} predictions but {label.numel()} labels")
-    domain, ld = _iso_domain(domain, n, n_domain)
+    pred, label, _, n = _rows("eval_platt_fit", pred, label)
+    domain, ld, domain_p = _domain_arg(domain, n, n_domain)
     dev = pred.device
     seg = n_domain + 1
-    nbytes = lib.cdc_eval_platt_fit_workspace_bytes(n, n_domain)
-    if nbytes <= 0:
-        raise RuntimeError(f"cdc_eval_platt_fit_workspace_bytes refused n={n}, n_domain={n_domain}")
     f64 = torch.empty((5, seg), dtype=torch.float64, device=dev)
     i64 = torch.empty((2, seg), dtype=torch.int64, device=dev)
     i32 = torch.empty((2, seg), dtype=torch.int32, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    L.launch("cdc_eval_platt_fit", lib.cdc_eval_platt_fit,
-             (pred.data_ptr(), label.data_ptr(), None if domain is None else domain.data_ptr(), ld, n, n_domain, PLATT_METHODS[method],
-              PLATT_INPUTS[input], float(clip), float(gtol), max_iter, f64[0].data_ptr(), f64[1].data_ptr(), f64[2].data_ptr(),
-              f64[3].data_ptr(), f64[4].data_ptr(), i64[0].data_ptr(), i64[1].data_ptr(), i32[0].data_ptr(), i32[1].data_ptr(),
-              err.data_ptr(), ws.data_ptr(), nbytes), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    eval_platt_fit.last_err = err
+    _call(eval_platt_fit, "cdc_eval_platt_fit", (pred.data_ptr(), label.data_ptr(), domain_p, ld, n, n_domain, PLATT_METHODS[method],
+                                                 PLATT_INPUTS[input], float(clip), float(gtol), max_iter, f64[0].data_ptr(), f64[1].data_ptr(),
+                                                 f64[2].data_ptr(), f64[3].data_ptr(), f64[4].data_ptr(), i64[0].data_ptr(), i64[1].data_ptr(),
+                                                 i32[0].data_ptr(), i32[1].data_ptr()), dev, ("cdc_eval_platt_fit_workspace_bytes", n, n_domain),
+          f"cdc_eval_platt_fit_workspace_bytes refused n={n}, n_domain={n_domain}")
     return PlattFit(f64[0], f64[1], i64[0], i64[1], f64[2], f64[3], f64[4], i32[0], i32[1])
 
 
@@ -1201,14 +973,11 @@ def eval_platt_apply(pred, fit_or_map, domain=None, n_domain=1, seg_of_domain=No
     float32, clamped to [eps, 1 - eps] when eps > 0.  Returns float32 [n] on the device.  A NaN score, a probability outside [0, 1]
     or a domain outside range gives NaN and sets the error word (1 + the row), kept as `eval_platt_apply.last_err`.  No host
     synchronisation."""
-    lib = L.load()
     n_domain = int(n_domain)
-    if not pred.is_cuda:
-        raise L.HipExtensionError("eval_platt_apply needs device tensors; there is no CPU fallback")
+    _need_device("eval_platt_apply", pred)                                 # before the option checks, as ever
     _platt_args(None, input, clip)
-    pred = pred.reshape(-1).to(torch.float32).contiguous()
-    n = pred.numel()
-    domain, ld = _iso_domain(domain, n, n_domain)
+    pred, _, _, n = _rows("eval_platt_apply", pred)
+    domain, ld, domain_p = _domain_arg(domain, n, n_domain)
     dev = pred.device
     m = fit_or_map
     if m.a.numel() != n_domain + 1:
@@ -1225,12 +994,8 @@ def eval_platt_apply(pred, fit_or_map, domain=None, n_domain=1, seg_of_domain=No
     a = m.a.to(device=dev, dtype=torch.float64).contiguous()
     b = m.b.to(device=dev, dtype=torch.float64).contiguous()
     out = torch.empty(n, dtype=torch.float32, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    L.launch("cdc_eval_platt_apply", lib.cdc_eval_platt_apply,
-             (pred.data_ptr(), None if domain is None else domain.data_ptr(), ld, n, n_domain, seg_of_domain.data_ptr(), a.data_ptr(),
-              b.data_ptr(), PLATT_INPUTS[input], float(clip), float(eps), out.data_ptr(), err.data_ptr()),
-             C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    eval_platt_apply.last_err = err
+    _call(eval_platt_apply, "cdc_eval_platt_apply", (pred.data_ptr(), domain_p, ld, n, n_domain, seg_of_domain.data_ptr(), a.data_ptr(),
+                                                     b.data_ptr(), PLATT_INPUTS[input], float(clip), float(eps), out.data_ptr()), dev)
     return out
 
 

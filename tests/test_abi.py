@@ -243,6 +243,33 @@ def test_entry_points_reject_bad_arguments_without_touching_the_device():
         _lib.check(-1, "probe")
 
 
+def test_eval_metrics_refuses_bad_arguments_without_touching_the_device():
+    """cdc_eval_metrics checks its workspace against plain arithmetic before it asks rocPRIM anything, as the later evaluation
+    calls do: a workspace that is too small is CDC_E_BADARG with both sizes in the message, with or without a device."""
+    from cdcmdr_amd import _lib
+    lib = _lib.load()
+    p = C.c_void_p(4096)                                   # non-null, 256-byte aligned, never dereferenced on the host
+    big = 1 << 40
+
+    def call(pred=p, label=p, domain=p, ld=1, n=10, n_domain=3, out=p, counts=p, ws=p, ws_bytes=big):
+        return lib.cdc_eval_metrics(pred, label, domain, ld, n, n_domain, out, counts, None, ws, ws_bytes, None)
+
+    for kw in ({"pred": None}, {"label": None}, {"out": None}, {"counts": None}, {"ws": None}):
+        assert call(**kw) == -1 and b"eval_metrics: null pointer" in lib.cdc_last_error(), kw
+    for kw in ({"n": 0}, {"n": -5}, {"n": 1 << 31}, {"n_domain": 0}, {"n_domain": -1}, {"n_domain": 1 << 20}, {"domain": None}, {"ld": -1}):
+        assert call(**kw) == -1 and b"eval_metrics: bad sizes" in lib.cdc_last_error(), kw
+    # 2n keys twice, 2n label bytes twice, start and three per-segment sums: 256 + 256 + 256 + 256 + 256 + 3 * 256 bytes at n = 10
+    assert call(ws_bytes=8) == -1 and lib.cdc_last_error() == b"eval_metrics: workspace 8 < 2048 bytes"
+    assert call(ws_bytes=1024, domain=None, n_domain=1) == -1 and b"eval_metrics: workspace 1024 < 2048 bytes" in lib.cdc_last_error()
+    assert call(ws_bytes=8, n=5000) == -1 and b"eval_metrics: workspace 8 < " in lib.cdc_last_error()
+    # this entry looks at the size before the alignment: a workspace that is both too small and misaligned is told its size
+    odd = C.c_void_p(4096 + 64)
+    assert call(ws=odd, ws_bytes=8) == -1 and lib.cdc_last_error() == b"eval_metrics: workspace 8 < 2048 bytes"
+    assert call(ws=odd) == -1 and lib.cdc_last_error() == b"eval_metrics: workspace must be 256-byte aligned"
+    f = lib.cdc_eval_workspace_bytes
+    assert f(0, 3) == 0 and f(10, 0) == 0 and f(-1, 3) == 0
+
+
 def test_fused_tower_launch_refuses_bad_arguments_without_a_launch():
     from cdcmdr_amd import _lib as L
     lib = L.load()
