@@ -473,172 +473,28 @@ extern "C" int cdc_gate_pool_wide_bwd(const cdc_pool_wide_bwd_args* a, void* str
 
 // =================================================================================================
 // BatchNorm1d (+ReLU +dropout)  (model/layer.py:187,199-205 ; model/star.py:117-181)
-// block = 64 columns x 64 rows: lane = column, wave w takes rows w, w+4, ...
+// Four kernels (forward / backward x statistics / apply), one family <V, LS>: a lane owns V neighbouring columns of a row,
+// LPR = 1 << LS lanes make a row of the tile (V * LPR columns), a wave instruction covers 64 / LPR rows and the block one 64-row
+// chunk.  The kernels are bound by the number of memory instructions, not by bytes (dropping a whole 33.5 MB output stream did
+// not move the apply kernel), hence V = 4 — 16-byte lanes, LS = 3..6 by the widest segment — whenever every segment has
+// C % 4 == 0 and 16-byte (bf16: 8-byte) aligned rows; anything else launches <1, 6>, one column per lane.  The partial-sum
+// workspace ([chunk][column] pairs of doubles) does not depend on V or LS.  The rows' loads are issued BEFORE the block sums
+// the chunk partials (which is a chain of L2 reads of its own).  The dropout decisions of V = 4 come from the 32-bit stream of
+// csrc/common.h, those of V = 1 from cdc_uniform on the 64-bit seed: which columns are dropped depends on the launch's V.
+// The kernels take `wave` through readfirstlane when V = 1.  With one column per lane all lanes of a wave are on the same row:
+// saying so keeps the row predicates and offsets of the 16 unrolled rows in SGPRs (without it the <1, 6> apply kernels take 70
+// and 118 VGPRs and lose a wave per SIMD against the loads-last kernels they replace).  <4, 6> has uniform rows too and is left
+// as it was measured.
 // =================================================================================================
 struct BnTile { int seg, c0, row_lo, M, chunk, col_base; };
-// an operand stored as fp32 or (block-uniform choice) as bf16
-__device__ __forceinline__ float bn_ld(const void* p, bool half, int64_t i) {
-    return half ? (float)reinterpret_cast<const __bf16*>(p)[i] : reinterpret_cast<const float*>(p)[i];
-}
-
-template <typename Args>
-__device__ __forceinline__ bool bn_locate(const Args& a, int n_chunks, BnTile& t) {
-    // blockIdx.x -> (segment, 64-column tile, row chunk)
-    int tile = blockIdx.x / n_chunks;
-    t.chunk = blockIdx.x % n_chunks;
-    int64_t col_base = 0;
-    const int s = find_group<true>(a.n_seg, tile, [&](int l) { return (a.s[l].C + 63) / 64; }, [&](int l) { return (int64_t)a.s[l].C; },
-                                   tile, &col_base);
-    if (s < 0) return false;
-    t.seg = s; t.c0 = tile * 64; t.col_base = (int)col_base;
-    t.row_lo = 0; t.M = (int)a.M;
-    if (a.row_offsets) { const int rg = a.s[s].row_group; t.row_lo = a.row_offsets[rg]; t.M = a.row_offsets[rg + 1] - t.row_lo; }
-    return true;
-}
-
-// pass 1: per (row chunk, column) partial sum and sum of squares in double
-__global__ void __launch_bounds__(ROW_THREADS) k_bn_stats(const cdc_bn_fwd_args a, int n_chunks, int total_c) {
-    BnTile t;
-    if (!bn_locate(a, n_chunks, t)) return;
-    const cdc_bn_seg& S = a.s[t.seg];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c = t.c0 + lane;
-    double s1 = 0.0, s2 = 0.0;
-    const int r_begin = t.chunk * CDC_BN_ROWS_PER_BLOCK;
-    const int r_end = min(r_begin + CDC_BN_ROWS_PER_BLOCK, t.M);
-    if (c < S.C) {
-        constexpr int RPW = CDC_BN_ROWS_PER_BLOCK / WAVES_PER_BLOCK;      // a wave's rows of the chunk: all loads issued before the sums
-        const bool xh = S.half & CDC_BN_X_BF16;
-        float xv[RPW];
-#pragma unroll
-        for (int k = 0; k < RPW; ++k) {
-            const int r = r_begin + wave + k * WAVES_PER_BLOCK;
-            xv[k] = r < r_end ? bn_ld(S.x, xh, (int64_t)(t.row_lo + r) * S.ldx + c) : 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k < RPW; ++k) {                                  // rows past r_end contribute exact zeros
-            const double x = (double)xv[k];
-            s1 += x; s2 += x * x;
-        }
-    }
-    __shared__ double sh[2][WAVES_PER_BLOCK][64];
-    sh[0][wave][lane] = s1; sh[1][wave][lane] = s2;
-    __syncthreads();
-    if (wave == 0 && c < S.C) {
-        s1 = sh[0][0][lane] + sh[0][1][lane] + sh[0][2][lane] + sh[0][3][lane];
-        s2 = sh[1][0][lane] + sh[1][1][lane] + sh[1][2][lane] + sh[1][3][lane];
-        double* ws = a.workspace + ((int64_t)t.chunk * total_c + t.col_base + c) * 2;
-        ws[0] = s1; ws[1] = s2;
-    }
-}
-
-// Sum of a column's per-chunk partials (s1, s2): the block's four waves take chunks w, w+4, ... (loads of a wave in flight
-// together) and the four wave sums are added in wave order — every block of a column forms the same bits.  ALL threads of the
-// block must call this (barrier inside); lanes past the segment's columns read column 0 and ignore the result.
-__device__ __forceinline__ void bn_sum_partials(const double* __restrict__ ws, int used, int total_c, int col, double& s1, double& s2) {
-    __shared__ double bn_part[2][WAVES_PER_BLOCK][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double a1 = 0.0, a2 = 0.0;
-#pragma unroll 4
-    for (int k = wave; k < used; k += WAVES_PER_BLOCK) {
-        const double* p = ws + ((int64_t)k * total_c + col) * 2;
-        a1 += p[0]; a2 += p[1];
-    }
-    bn_part[0][wave][lane] = a1; bn_part[1][wave][lane] = a2;
-    __syncthreads();
-    s1 = ((bn_part[0][0][lane] + bn_part[0][1][lane]) + bn_part[0][2][lane]) + bn_part[0][3][lane];
-    s2 = ((bn_part[1][0][lane] + bn_part[1][1][lane]) + bn_part[1][2][lane]) + bn_part[1][3][lane];
-}
-
-// pass 2: finalise stats for the tile's columns (every block redundantly, fixed order), normalise its rows
-__global__ void __launch_bounds__(ROW_THREADS) k_bn_apply(const cdc_bn_fwd_args a, int n_chunks, int total_c) {
-    BnTile t;
-    if (!bn_locate(a, n_chunks, t)) return;
-    const cdc_bn_seg& S = a.s[t.seg];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c = t.c0 + lane;
-    // rows the statistics are over: this launch's rows, or (phase 2, data parallel) the all-reduced global count
-    const bool global_stats = a.training && a.phase == 2 && a.exchange;
-    const int Ms = global_stats ? (int)(a.exchange[2 * (int64_t)total_c + t.seg] + 0.5) : t.M;
-    // the reference skips BN when the (group's) batch has one row (MLP / MDR_BatchNorm) or at most one row (DNN)
-    const bool skip_norm = (Ms == 1) || (a.skip_le1 && Ms <= 1);
-    float mean = 0.f, invstd = 1.f;
-    double p1 = 0.0, p2 = 0.0;
-    if (a.training && !skip_norm && !global_stats)                       // block-uniform
-        bn_sum_partials(a.workspace, (t.M + CDC_BN_ROWS_PER_BLOCK - 1) / CDC_BN_ROWS_PER_BLOCK, total_c, t.col_base + (c < S.C ? c : 0), p1, p2);
-    if (c < S.C && !skip_norm) {
-        if (a.training) {
-            double s1 = p1, s2 = p2;
-            if (global_stats) {
-                s1 = a.exchange[2 * (int64_t)(t.col_base + c)];
-                s2 = a.exchange[2 * (int64_t)(t.col_base + c) + 1];
-            }
-            const double mu = Ms > 0 ? s1 / Ms : 0.0;
-            double var = Ms > 0 ? s2 / Ms - mu * mu : 0.0;
-            if (var < 0.0) var = 0.0;
-            mean = (float)mu;
-            invstd = (float)(1.0 / sqrt(var + (double)a.eps));
-            if (t.chunk == 0 && wave == 0) {
-                if (S.save_mean) S.save_mean[c] = mean;
-                if (S.save_invstd) S.save_invstd[c] = invstd;
-                if (S.running_mean && Ms > 0) {
-                    const double unbiased = Ms > 1 ? var * ((double)Ms / (double)(Ms - 1)) : var;
-                    S.running_mean[c] = (1.f - a.momentum) * S.running_mean[c] + a.momentum * mean;
-                    S.running_var[c] = (1.f - a.momentum) * S.running_var[c] + a.momentum * (float)unbiased;
-                }
-            }
-        } else {
-            mean = S.running_mean[c];
-            invstd = 1.f / sqrtf(S.running_var[c] + a.eps);
-        }
-    }
-    if (a.training && !skip_norm && t.chunk == 0 && t.c0 == 0 && threadIdx.x == 0 && S.num_batches_tracked) *S.num_batches_tracked += 1;
-    if (c >= S.C) return;
-    const float gam = (skip_norm || !S.gamma) ? 1.f : S.gamma[c];
-    const float bet = (skip_norm || !S.beta) ? 0.f : S.beta[c];
-    const float keep_scale = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
-    uint64_t seed = a.seed;
-    if (a.drop_p > 0.f && a.seed_offset_dev) seed += (uint64_t)(uint32_t)(*a.seed_offset_dev) * 0xD1342543DE82EF95ull;
-    const int r_begin = t.chunk * CDC_BN_ROWS_PER_BLOCK;
-    const int r_end = min(r_begin + CDC_BN_ROWS_PER_BLOCK, t.M);
-    constexpr int RPW = CDC_BN_ROWS_PER_BLOCK / WAVES_PER_BLOCK;
-    const bool xh = S.half & CDC_BN_X_BF16;
-    float xv[RPW];
-#pragma unroll
-    for (int k = 0; k < RPW; ++k) {                                      // the wave's 16 loads are in flight together
-        const int r = r_begin + wave + k * WAVES_PER_BLOCK;
-        xv[k] = r < r_end ? bn_ld(S.x, xh, (int64_t)(t.row_lo + r) * S.ldx + c) : 0.f;
-    }
-#pragma unroll
-    for (int k = 0; k < RPW; ++k) {
-        const int r = r_begin + wave + k * WAVES_PER_BLOCK;
-        if (r >= r_end) break;
-        const int64_t gr = t.row_lo + r;
-        float v = xv[k];
-        if (!skip_norm) v = (v - mean) * invstd * gam + bet;
-        if (a.relu) v = fmaxf(v, 0.f);
-        if (a.drop_p > 0.f) {
-            const uint64_t e = ((uint64_t)(t.seg + 64) << 56) ^ ((uint64_t)gr * (uint64_t)S.C + (uint64_t)c);
-            v = cdc_uniform(seed, e) < a.drop_p ? 0.f : v * keep_scale;
-        }
-        if (S.y) S.y[gr * S.ldy + c] = v;
-        if (S.yh) reinterpret_cast<__bf16*>(S.yh)[gr * S.ldyh + c] = (__bf16)v;
-    }
-}
-
-// -------------------------------------------------------------------------------------------------
-// BatchNorm with 16-byte lanes (all four kernels).  The kernels above give a lane ONE column, i.e. a wave instruction moves 256
-// bytes (128 for a bf16 operand): they are bound by the number of memory instructions, not by bytes (dropping a whole 33.5 MB
-// output stream did not move k_bn_apply).  Here a lane owns FOUR neighbouring columns of a row: LPR = 8..64 lanes per row
-// (tile of 4*LPR columns), 64/LPR rows per wave instruction, the block still covers one 64-row chunk, so the partial-sum
-// workspace layout ([chunk][column] pairs of doubles) is the same and the two families mix freely.  The rows' loads are issued
-// BEFORE the block sums the chunk partials (which is a chain of L2 reads of its own), and the dropout decisions come from the
-// 32-bit stream of csrc/common.h.  Requires C % 4 == 0 and 16-byte (bf16: 8-byte) aligned rows; anything else -> kernels above.
-// -------------------------------------------------------------------------------------------------
-struct bn_f4 { float v[4]; };
-__device__ __forceinline__ bn_f4 bn_ld4(const void* p, bool half, int64_t i) {
-    bn_f4 r;
-    if (half) {
+// V neighbouring columns of an operand stored as fp32 or (block-uniform choice) as bf16
+template <int V> struct bn_fv { float v[V]; };
+template <int V>
+__device__ __forceinline__ bn_fv<V> bn_ldv(const void* p, bool half, int64_t i) {
+    bn_fv<V> r;
+    if constexpr (V == 1) {
+        r.v[0] = half ? (float)reinterpret_cast<const __bf16*>(p)[i] : reinterpret_cast<const float*>(p)[i];
+    } else if (half) {
         const uint2 u = *reinterpret_cast<const uint2*>(reinterpret_cast<const __bf16*>(p) + i);
         r.v[0] = __uint_as_float(u.x << 16); r.v[1] = __uint_as_float(u.x & 0xFFFF0000u);
         r.v[2] = __uint_as_float(u.y << 16); r.v[3] = __uint_as_float(u.y & 0xFFFF0000u);
@@ -648,15 +504,29 @@ __device__ __forceinline__ bn_f4 bn_ld4(const void* p, bool half, int64_t i) {
     }
     return r;
 }
-__device__ __forceinline__ void bn_st4h(void* p, int64_t i, const float (&v)[4]) {
-    union { __bf16 h[4]; uint2 u; } o;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) o.h[q] = (__bf16)v[q];
-    *reinterpret_cast<uint2*>(reinterpret_cast<__bf16*>(p) + i) = o.u;
+template <int V>
+__device__ __forceinline__ void bn_stv(float* p, const float (&v)[V]) {
+    if constexpr (V == 1) *p = v[0];
+    else *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
 }
-template <int LS, typename Args>
+template <int V>
+__device__ __forceinline__ void bn_stvh(void* p, int64_t i, const float (&v)[V]) {
+    if constexpr (V == 1) reinterpret_cast<__bf16*>(p)[i] = (__bf16)v[0];
+    else {
+        union { __bf16 h[4]; uint2 u; } o;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) o.h[q] = (__bf16)v[q];
+        *reinterpret_cast<uint2*>(reinterpret_cast<__bf16*>(p) + i) = o.u;
+    }
+}
+// lane geometry of a block (V columns per lane, LS = log2 lanes per row)
+template <int V, int LS> struct BnGeo {
+    static constexpr int LPR = 1 << LS, TW = V * LPR, RW = 64 / LPR, ITER = CDC_BN_ROWS_PER_BLOCK / (WAVES_PER_BLOCK * RW);
+};
+// blockIdx.x -> (segment, tile of TW columns, row chunk)
+template <int V, int LS, typename Args>
 __device__ __forceinline__ bool bn_locate_v(const Args& a, int n_chunks, BnTile& t) {
-    constexpr int TW = 4 << LS;
+    constexpr int TW = BnGeo<V, LS>::TW;
     int tile = blockIdx.x / n_chunks;
     t.chunk = blockIdx.x % n_chunks;
     int64_t col_base = 0;
@@ -668,26 +538,22 @@ __device__ __forceinline__ bool bn_locate_v(const Args& a, int n_chunks, BnTile&
     if (a.row_offsets) { const int rg = a.s[s].row_group; t.row_lo = a.row_offsets[rg]; t.M = a.row_offsets[rg + 1] - t.row_lo; }
     return true;
 }
-// lane geometry of a block (LS = log2 lanes per row)
-template <int LS> struct BnGeo {
-    static constexpr int LPR = 1 << LS, TW = 4 * LPR, RW = 64 / LPR, ITER = CDC_BN_ROWS_PER_BLOCK / (WAVES_PER_BLOCK * RW);
-};
-// per-lane partial sums (4 columns) -> workspace [chunk][column] pairs: lanes of the same columns inside the wave by shuffles,
+// per-lane partial sums (V columns) -> workspace [chunk][column] pairs: lanes of the same columns inside the wave by shuffles,
 // then the four waves through LDS in wave order
-template <int LS>
-__device__ __forceinline__ void bn_store_partials(double (&s1)[4], double (&s2)[4], double* __restrict__ ws_chunk, int col0, int C) {
-    using G = BnGeo<LS>;
+template <int V, int LS>
+__device__ __forceinline__ void bn_store_partials(double (&s1)[V], double (&s2)[V], double* __restrict__ ws_chunk, int col0, int C) {
+    using G = BnGeo<V, LS>;
     __shared__ double sh[2][WAVES_PER_BLOCK][G::TW];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int cg = lane & (G::LPR - 1);
 #pragma unroll
     for (int o = G::LPR; o < 64; o <<= 1) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) { s1[q] += __shfl_xor(s1[q], o, 64); s2[q] += __shfl_xor(s2[q], o, 64); }
+        for (int q = 0; q < V; ++q) { s1[q] += __shfl_xor(s1[q], o, 64); s2[q] += __shfl_xor(s2[q], o, 64); }
     }
     if (lane < G::LPR) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) { sh[0][wave][cg * 4 + q] = s1[q]; sh[1][wave][cg * 4 + q] = s2[q]; }
+        for (int q = 0; q < V; ++q) { sh[0][wave][cg * V + q] = s1[q]; sh[1][wave][cg * V + q] = s2[q]; }
     }
     __syncthreads();
     for (int j = threadIdx.x; j < G::TW; j += ROW_THREADS) {
@@ -698,10 +564,10 @@ __device__ __forceinline__ void bn_store_partials(double (&s1)[4], double (&s2)[
     }
 }
 // the block's TW columns: sums of the per-chunk partials in a fixed order -> LDS (every block of a column forms the same bits)
-template <int LS>
-__device__ __forceinline__ void bn_sum_partials_v(const double* __restrict__ ws, int used, int total_c, int col_base, int c0, int C,
-                                                  double (*out)[BnGeo<LS>::TW]) {
-    using G = BnGeo<LS>;
+template <int V, int LS>
+__device__ __forceinline__ void bn_sum_chunks(const double* __restrict__ ws, int used, int total_c, int col_base, int c0, int C,
+                                                  double (*out)[BnGeo<V, LS>::TW]) {
+    using G = BnGeo<V, LS>;
     constexpr int NP = ROW_THREADS / G::TW > 0 ? ROW_THREADS / G::TW : 1;
     __shared__ double part[2][NP][G::TW];
     {
@@ -726,62 +592,70 @@ __device__ __forceinline__ void bn_sum_partials_v(const double* __restrict__ ws,
     __syncthreads();
 }
 
-template <int LS>
-__global__ void __launch_bounds__(ROW_THREADS) k_bn_stats_v4(const cdc_bn_fwd_args a, int n_chunks, int total_c) {
+// pass 1: per (row chunk, column) partial sum and sum of squares in double
+template <int V, int LS>
+__global__ void __launch_bounds__(ROW_THREADS) k_bn_stats(const cdc_bn_fwd_args a, int n_chunks, int total_c) {
     CDC_PRIO_MAIN();
-    using G = BnGeo<LS>;
+    using G = BnGeo<V, LS>;
     BnTile t;
-    if (!bn_locate_v<LS>(a, n_chunks, t)) return;
+    if (!bn_locate_v<V, LS>(a, n_chunks, t)) return;
     const cdc_bn_seg& S = a.s[t.seg];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = V == 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
     const int cg = lane & (G::LPR - 1), rs = lane >> LS;
-    const int c = t.c0 + cg * 4;
+    const int c = t.c0 + cg * V;
     const int r_begin = t.chunk * CDC_BN_ROWS_PER_BLOCK, r_end = min(r_begin + CDC_BN_ROWS_PER_BLOCK, t.M);
-    double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
+    double s1[V] = {}, s2[V] = {};
     if (c < S.C) {
         const bool xh = S.half & CDC_BN_X_BF16;
-        bn_f4 xv[G::ITER];
+        bn_fv<V> xv[G::ITER];
 #pragma unroll
         for (int k = 0; k < G::ITER; ++k) {
             const int r = r_begin + (k * WAVES_PER_BLOCK + wave) * G::RW + rs;
-            if (r < r_end) xv[k] = bn_ld4(S.x, xh, (int64_t)(t.row_lo + r) * S.ldx + c);
-            else xv[k] = bn_f4{{0.f, 0.f, 0.f, 0.f}};
+            // rows past r_end contribute exact zeros.  V = 1 says so with a select: written as the two assignments below, the
+            // conversion to double moves up beside each load and the wave waits for its 16 loads one after the other (measured:
+            // 15 us against 11 at 32768 x 199).  The select shortens <4, LS> too; those keep the form they were measured in.
+            if constexpr (V == 1) xv[k] = r < r_end ? bn_ldv<V>(S.x, xh, (int64_t)(t.row_lo + r) * S.ldx + c) : bn_fv<V>{};
+            else if (r < r_end) xv[k] = bn_ldv<V>(S.x, xh, (int64_t)(t.row_lo + r) * S.ldx + c);
+            else xv[k] = bn_fv<V>{};
         }
 #pragma unroll
         for (int k = 0; k < G::ITER; ++k)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) { const double x = (double)xv[k].v[q]; s1[q] += x; s2[q] += x * x; }
+            for (int q = 0; q < V; ++q) { const double x = (double)xv[k].v[q]; s1[q] += x; s2[q] += x * x; }
     }
-    bn_store_partials<LS>(s1, s2, a.workspace + ((int64_t)t.chunk * total_c + t.col_base + t.c0) * 2, t.c0, S.C);
+    bn_store_partials<V, LS>(s1, s2, a.workspace + ((int64_t)t.chunk * total_c + t.col_base + t.c0) * 2, t.c0, S.C);
 }
 
-template <int LS>
-__global__ void __launch_bounds__(ROW_THREADS) k_bn_apply_v4(const cdc_bn_fwd_args a, int n_chunks, int total_c) {
+// pass 2: finalise stats for the tile's columns (every block redundantly, fixed order), normalise its rows
+template <int V, int LS>
+__global__ void __launch_bounds__(ROW_THREADS) k_bn_apply(const cdc_bn_fwd_args a, int n_chunks, int total_c) {
     CDC_PRIO_MAIN();
-    using G = BnGeo<LS>;
+    using G = BnGeo<V, LS>;
     BnTile t;
-    if (!bn_locate_v<LS>(a, n_chunks, t)) return;
+    if (!bn_locate_v<V, LS>(a, n_chunks, t)) return;
     const cdc_bn_seg& S = a.s[t.seg];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = V == 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
     const int cg = lane & (G::LPR - 1), rs = lane >> LS;
-    const int c = t.c0 + cg * 4;
+    const int c = t.c0 + cg * V;
     const bool in_c = c < S.C;
     const int r_begin = t.chunk * CDC_BN_ROWS_PER_BLOCK, r_end = min(r_begin + CDC_BN_ROWS_PER_BLOCK, t.M);
     const bool xh = S.half & CDC_BN_X_BF16;
-    bn_f4 xv[G::ITER];
+    bn_fv<V> xv[G::ITER];
 #pragma unroll
     for (int k = 0; k < G::ITER; ++k) {                                  // in flight while the statistics are put together
         const int r = r_begin + (k * WAVES_PER_BLOCK + wave) * G::RW + rs;
-        if (in_c && r < r_end) xv[k] = bn_ld4(S.x, xh, (int64_t)(t.row_lo + r) * S.ldx + c);
-        else xv[k] = bn_f4{{0.f, 0.f, 0.f, 0.f}};
+        if (in_c && r < r_end) xv[k] = bn_ldv<V>(S.x, xh, (int64_t)(t.row_lo + r) * S.ldx + c);
+        else xv[k] = bn_fv<V>{};
     }
+    // rows the statistics are over: this launch's rows, or (phase 2, data parallel) the all-reduced global count
     const bool global_stats = a.training && a.phase == 2 && a.exchange;
     const int Ms = global_stats ? (int)(a.exchange[2 * (int64_t)total_c + t.seg] + 0.5) : t.M;
+    // the reference skips BN when the (group's) batch has one row (MLP / MDR_BatchNorm) or at most one row (DNN)
     const bool skip_norm = (Ms == 1) || (a.skip_le1 && Ms <= 1);
     __shared__ double sums[2][G::TW];
     __shared__ float col_mean[G::TW], col_inv[G::TW];
     if (a.training && !skip_norm && !global_stats)
-        bn_sum_partials_v<LS>(a.workspace, (t.M + CDC_BN_ROWS_PER_BLOCK - 1) / CDC_BN_ROWS_PER_BLOCK, total_c, t.col_base, t.c0, S.C, sums);
+        bn_sum_chunks<V, LS>(a.workspace, (t.M + CDC_BN_ROWS_PER_BLOCK - 1) / CDC_BN_ROWS_PER_BLOCK, total_c, t.col_base, t.c0, S.C, sums);
     for (int j = threadIdx.x; j < G::TW; j += ROW_THREADS) {             // one thread per column of the tile
         const int cj = t.c0 + j;
         float mean = 0.f, invstd = 1.f;
@@ -816,61 +690,70 @@ __global__ void __launch_bounds__(ROW_THREADS) k_bn_apply_v4(const cdc_bn_fwd_ar
     if (a.training && !skip_norm && t.chunk == 0 && t.c0 == 0 && threadIdx.x == 0 && S.num_batches_tracked) *S.num_batches_tracked += 1;
     __syncthreads();
     if (!in_c) return;
-    float mean[4], scale[4], bet[4], gamv[4];                           // (v - mean) * invstd * gamma + beta, in the scalar kernel's order
+    float mean[V], scale[V], bet[V], gamv[V];                           // (v - mean) * invstd * gamma + beta, in this order
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
+    for (int q = 0; q < V; ++q) {
         gamv[q] = (skip_norm || !S.gamma) ? 1.f : S.gamma[c + q];
         bet[q] = (skip_norm || !S.beta) ? 0.f : S.beta[c + q];
-        mean[q] = col_mean[cg * 4 + q];
-        scale[q] = col_inv[cg * 4 + q];
+        mean[q] = col_mean[cg * V + q];
+        scale[q] = col_inv[cg * V + q];
     }
     const float keep_scale = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
+    // the dropout stream goes with V (the one not taken is dead code): 16 bits per column of the 32-bit stream, or cdc_uniform
     const uint32_t thr16 = (uint32_t)(a.drop_p * 65536.f + 0.5f);
-    const uint32_t seed32 = a.drop_p > 0.f ? g2_seed32(a.seed, a.seed_offset_dev, 64 + t.seg) : 0u;
+    const uint32_t seed32 = V == 4 && a.drop_p > 0.f ? g2_seed32(a.seed, a.seed_offset_dev, 64 + t.seg) : 0u;
+    uint64_t seed64 = a.seed;
+    if (V == 1 && a.drop_p > 0.f && a.seed_offset_dev) seed64 += (uint64_t)(uint32_t)(*a.seed_offset_dev) * 0xD1342543DE82EF95ull;
 #pragma unroll
     for (int k = 0; k < G::ITER; ++k) {
         const int r = r_begin + (k * WAVES_PER_BLOCK + wave) * G::RW + rs;
         if (r >= r_end) continue;
         const int64_t gr = t.row_lo + r;
-        float v[4];
+        float v[V];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
+        for (int q = 0; q < V; ++q) {
             float x = xv[k].v[q];
             if (!skip_norm) x = (x - mean[q]) * scale[q] * gamv[q] + bet[q];
             if (a.relu) x = fmaxf(x, 0.f);
             v[q] = x;
         }
         if (a.drop_p > 0.f) {
-            const uint32_t h0 = g2_drop_bits(seed32, (int)gr, c >> 1), h1 = g2_drop_bits(seed32, (int)gr, (c >> 1) + 1);
-            v[0] = (h0 & 0xFFFFu) < thr16 ? 0.f : v[0] * keep_scale;
-            v[1] = (h0 >> 16) < thr16 ? 0.f : v[1] * keep_scale;
-            v[2] = (h1 & 0xFFFFu) < thr16 ? 0.f : v[2] * keep_scale;
-            v[3] = (h1 >> 16) < thr16 ? 0.f : v[3] * keep_scale;
+            if constexpr (V == 1) {
+                const uint64_t e = ((uint64_t)(t.seg + 64) << 56) ^ ((uint64_t)gr * (uint64_t)S.C + (uint64_t)c);
+                v[0] = cdc_uniform(seed64, e) < a.drop_p ? 0.f : v[0] * keep_scale;
+            } else {
+                const uint32_t h0 = g2_drop_bits(seed32, (int)gr, c >> 1), h1 = g2_drop_bits(seed32, (int)gr, (c >> 1) + 1);
+                v[0] = (h0 & 0xFFFFu) < thr16 ? 0.f : v[0] * keep_scale;
+                v[1] = (h0 >> 16) < thr16 ? 0.f : v[1] * keep_scale;
+                v[2] = (h1 & 0xFFFFu) < thr16 ? 0.f : v[2] * keep_scale;
+                v[3] = (h1 >> 16) < thr16 ? 0.f : v[3] * keep_scale;
+            }
         }
-        if (S.y) *reinterpret_cast<float4*>(S.y + gr * S.ldy + c) = make_float4(v[0], v[1], v[2], v[3]);
-        if (S.yh) bn_st4h(S.yh, gr * S.ldyh + c, v);
+        if (S.y) bn_stv<V>(S.y + gr * S.ldy + c, v);
+        if (S.yh) bn_stvh<V>(S.yh, gr * S.ldyh + c, v);
     }
 }
 
-template <int LS>
-__global__ void __launch_bounds__(ROW_THREADS) k_bn_bwd_stats_v4(const cdc_bn_bwd_args a, int n_chunks, int total_c) {
+// backward pass 1: partial sums of dz (-> dbeta) and dz * xhat (-> dgamma), dz = activation-masked dy
+template <int V, int LS>
+__global__ void __launch_bounds__(ROW_THREADS) k_bn_bwd_stats(const cdc_bn_bwd_args a, int n_chunks, int total_c) {
     CDC_PRIO_MAIN();
-    using G = BnGeo<LS>;
+    using G = BnGeo<V, LS>;
     BnTile t;
-    if (!bn_locate_v<LS>(a, n_chunks, t)) return;
+    if (!bn_locate_v<V, LS>(a, n_chunks, t)) return;
     const cdc_bn_bseg& S = a.s[t.seg];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = V == 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
     const int cg = lane & (G::LPR - 1), rs = lane >> LS;
-    const int c = t.c0 + cg * 4;
+    const int c = t.c0 + cg * V;
     const int r_begin = t.chunk * CDC_BN_ROWS_PER_BLOCK, r_end = min(r_begin + CDC_BN_ROWS_PER_BLOCK, t.M);
-    double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
+    double s1[V] = {}, s2[V] = {};
     // a one-row group is skipped (dx = dz, no parameter gradients) — unless this is phase 1: the group may have more rows on
     // other ranks, and then this rank's row belongs in the exchanged sums and in its own dgamma / dbeta (apply ignores the sums
     // when the GLOBAL count is one).  tests/test_gpu_batchnorm.py::test_bn_data_parallel_phases[1+5-*] showed the missing row.
     if (c < S.C && (t.M != 1 || a.phase == 1)) {
         const bool masked = a.relu || a.mask_scale != 1.f;
         const bool xh = S.half & CDC_BN_X_BF16, yh = S.half & CDC_BN_Y_BF16, dyh = S.half & CDC_BN_DY_BF16;
-        bn_f4 dv[G::ITER], yv[G::ITER], xv[G::ITER];
+        bn_fv<V> dv[G::ITER], yv[G::ITER], xv[G::ITER];
 #pragma unroll
         for (int k = 0; k < G::ITER; ++k) {
             const int r = r_begin + (k * WAVES_PER_BLOCK + wave) * G::RW + rs;
@@ -878,39 +761,43 @@ __global__ void __launch_bounds__(ROW_THREADS) k_bn_bwd_stats_v4(const cdc_bn_bw
             // the buffer for the chunks the group does not have — round 2 read them and zeroed the value afterwards)
             const bool ok = r < r_end;
             const int64_t gr = t.row_lo + r;
-            dv[k] = yv[k] = xv[k] = bn_f4{{0.f, 0.f, 0.f, 0.f}};
-            if (ok) {
-                dv[k] = bn_ld4(S.dy, dyh, gr * S.lddy + c);
-                if (masked) yv[k] = bn_ld4(S.y, yh, gr * S.ldy + c);
-                xv[k] = bn_ld4(S.x, xh, gr * S.ldx + c);
+            dv[k] = yv[k] = xv[k] = bn_fv<V>{};                          // dz = 0: exact zeros in both sums
+            if constexpr (V == 1) {                                      // selects, as in k_bn_stats
+                dv[k] = ok ? bn_ldv<V>(S.dy, dyh, gr * S.lddy + c) : bn_fv<V>{};
+                yv[k] = ok && masked ? bn_ldv<V>(S.y, yh, gr * S.ldy + c) : bn_fv<V>{};
+                xv[k] = ok ? bn_ldv<V>(S.x, xh, gr * S.ldx + c) : bn_fv<V>{};
+            } else if (ok) {
+                dv[k] = bn_ldv<V>(S.dy, dyh, gr * S.lddy + c);
+                if (masked) yv[k] = bn_ldv<V>(S.y, yh, gr * S.ldy + c);
+                xv[k] = bn_ldv<V>(S.x, xh, gr * S.ldx + c);
             }
         }
-        float mean[4], invstd[4];
+        float mean[V], invstd[V];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) { mean[q] = S.save_mean[c + q]; invstd[q] = S.save_invstd[c + q]; }
+        for (int q = 0; q < V; ++q) { mean[q] = S.save_mean[c + q]; invstd[q] = S.save_invstd[c + q]; }
 #pragma unroll
         for (int k = 0; k < G::ITER; ++k)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
+            for (int q = 0; q < V; ++q) {
                 float dz = dv[k].v[q];
                 if (masked) dz = yv[k].v[q] > 0.f ? dz * a.mask_scale : 0.f;
                 const float xhat = (xv[k].v[q] - mean[q]) * invstd[q];
                 s1[q] += (double)dz; s2[q] += (double)dz * (double)xhat;
             }
     }
-    bn_store_partials<LS>(s1, s2, a.workspace + ((int64_t)t.chunk * total_c + t.col_base + t.c0) * 2, t.c0, S.C);
+    bn_store_partials<V, LS>(s1, s2, a.workspace + ((int64_t)t.chunk * total_c + t.col_base + t.c0) * 2, t.c0, S.C);
 }
 
-template <int LS>
-__global__ void __launch_bounds__(ROW_THREADS) k_bn_bwd_apply_v4(const cdc_bn_bwd_args a, int n_chunks, int total_c) {
+template <int V, int LS>
+__global__ void __launch_bounds__(ROW_THREADS) k_bn_bwd_apply(const cdc_bn_bwd_args a, int n_chunks, int total_c) {
     CDC_PRIO_MAIN();
-    using G = BnGeo<LS>;
+    using G = BnGeo<V, LS>;
     BnTile t;
-    if (!bn_locate_v<LS>(a, n_chunks, t)) return;
+    if (!bn_locate_v<V, LS>(a, n_chunks, t)) return;
     const cdc_bn_bseg& S = a.s[t.seg];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = V == 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
     const int cg = lane & (G::LPR - 1), rs = lane >> LS;
-    const int c = t.c0 + cg * 4;
+    const int c = t.c0 + cg * V;
     const bool in_c = c < S.C;
     const bool global_stats = a.training && a.phase == 2 && a.exchange;
     const int Ms = global_stats ? (int)(a.exchange[2 * (int64_t)total_c + t.seg] + 0.5) : t.M;
@@ -919,21 +806,21 @@ __global__ void __launch_bounds__(ROW_THREADS) k_bn_bwd_apply_v4(const cdc_bn_bw
     const bool masked = a.relu || a.mask_scale != 1.f;
     const bool need_x = !skip_norm && a.training;
     const bool xh = S.half & CDC_BN_X_BF16, yh = S.half & CDC_BN_Y_BF16, dyh = S.half & CDC_BN_DY_BF16;
-    bn_f4 dv[G::ITER], yv[G::ITER], xv[G::ITER];
+    bn_fv<V> dv[G::ITER], yv[G::ITER], xv[G::ITER];
 #pragma unroll
     for (int k = 0; k < G::ITER; ++k) {                                  // in flight while the column sums are put together
         const int r = r_begin + (k * WAVES_PER_BLOCK + wave) * G::RW + rs;
         const bool ok = in_c && r < r_end;
         const int64_t gr = t.row_lo + r;
         if (ok) {
-            dv[k] = bn_ld4(S.dy, dyh, gr * S.lddy + c);
-            if (masked) yv[k] = bn_ld4(S.y, yh, gr * S.ldy + c);
-            if (need_x) xv[k] = bn_ld4(S.x, xh, gr * S.ldx + c);
+            dv[k] = bn_ldv<V>(S.dy, dyh, gr * S.lddy + c);
+            if (masked) yv[k] = bn_ldv<V>(S.y, yh, gr * S.ldy + c);
+            if (need_x) xv[k] = bn_ldv<V>(S.x, xh, gr * S.ldx + c);
         }
     }
     __shared__ double sums[2][G::TW];
     if (!skip_norm)
-        bn_sum_partials_v<LS>(a.workspace, (t.M + CDC_BN_ROWS_PER_BLOCK - 1) / CDC_BN_ROWS_PER_BLOCK, total_c, t.col_base, t.c0, S.C, sums);
+        bn_sum_chunks<V, LS>(a.workspace, (t.M + CDC_BN_ROWS_PER_BLOCK - 1) / CDC_BN_ROWS_PER_BLOCK, total_c, t.col_base, t.c0, S.C, sums);
     else {
         for (int j = threadIdx.x; j < G::TW; j += ROW_THREADS) { sums[0][j] = 0.0; sums[1][j] = 0.0; }
         __syncthreads();
@@ -947,10 +834,10 @@ __global__ void __launch_bounds__(ROW_THREADS) k_bn_bwd_apply_v4(const cdc_bn_bw
         }
     }
     if (!in_c) return;
-    float gam[4], mean[4], invstd[4], db[4], dg[4];
+    float gam[V], mean[V], invstd[V], db[V], dg[V];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        double s1 = sums[0][cg * 4 + q], s2 = sums[1][cg * 4 + q];
+    for (int q = 0; q < V; ++q) {
+        double s1 = sums[0][cg * V + q], s2 = sums[1][cg * V + q];
         if (global_stats && !skip_norm) {      // the input gradient needs the sums over the GLOBAL batch
             s1 = a.exchange[2 * (int64_t)(t.col_base + c + q)];
             s2 = a.exchange[2 * (int64_t)(t.col_base + c + q) + 1];
@@ -966,9 +853,9 @@ __global__ void __launch_bounds__(ROW_THREADS) k_bn_bwd_apply_v4(const cdc_bn_bw
         const int r = r_begin + (k * WAVES_PER_BLOCK + wave) * G::RW + rs;
         if (r >= r_end) continue;
         const int64_t gr = t.row_lo + r;
-        float dx[4];
+        float dx[V];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
+        for (int q = 0; q < V; ++q) {
             float dz = dv[k].v[q];
             if (masked) dz = yv[k].v[q] > 0.f ? dz * a.mask_scale : 0.f;
             if (skip_norm) dx[q] = dz;
@@ -978,45 +865,49 @@ __global__ void __launch_bounds__(ROW_THREADS) k_bn_bwd_apply_v4(const cdc_bn_bw
             } else dx[q] = gam[q] * invstd[q] * dz;
         }
         if (S.dx) {
-            float4* dst = reinterpret_cast<float4*>(S.dx + gr * S.lddx + c);
-            if (S.accumulate_dx) { const float4 o = *dst; dx[0] = o.x + dx[0]; dx[1] = o.y + dx[1]; dx[2] = o.z + dx[2]; dx[3] = o.w + dx[3]; }
-            *dst = make_float4(dx[0], dx[1], dx[2], dx[3]);
+            if constexpr (V == 1) {
+                float* dst = S.dx + gr * S.lddx + c;
+                if (S.accumulate_dx) dx[0] = *dst + dx[0];
+                *dst = dx[0];
+            } else {
+                float4* dst = reinterpret_cast<float4*>(S.dx + gr * S.lddx + c);
+                if (S.accumulate_dx) { const float4 o = *dst; dx[0] = o.x + dx[0]; dx[1] = o.y + dx[1]; dx[2] = o.z + dx[2]; dx[3] = o.w + dx[3]; }
+                *dst = make_float4(dx[0], dx[1], dx[2], dx[3]);
+            }
         }
-        if (S.dxh) bn_st4h(S.dxh, gr * S.lddxh + c, dx);
+        if (S.dxh) bn_stvh<V>(S.dxh, gr * S.lddxh + c, dx);
     }
 }
 
-// 16-byte lanes usable?  -> log2(lanes per row) for the launch (3..6), or -1
+// A launch's lane geometry and grid (column tiles x row chunks): 16-byte lanes when every segment has C % 4 == 0 and rows that
+// `aligned` accepts, LS = 3..6 by the widest segment; else one column per lane
+struct BnLaunch { int v, ls; int64_t grid; };
 static inline bool bn_al(const void* p, int64_t ld, bool half) {
     return !p || ((((uintptr_t)p) & (half ? 7 : 15)) == 0 && ld % 4 == 0);
 }
-static int bn_fwd_ls(const cdc_bn_fwd_args* a) {
+template <typename Args, typename Aligned>
+static BnLaunch bn_launch_geo(const Args* a, int n_chunks, Aligned&& aligned) {
     int cmax = 0;
+    bool v4 = true;
     for (int s = 0; s < a->n_seg; ++s) {
-        const cdc_bn_seg& S = a->s[s];
-        if (S.C % 4 || !bn_al(S.x, S.ldx, S.half & CDC_BN_X_BF16) || !bn_al(S.y, S.ldy, false) || !bn_al(S.yh, S.ldyh, true)) return -1;
-        cmax = std::max(cmax, (int)S.C);
+        v4 = v4 && a->s[s].C % 4 == 0 && aligned(a->s[s]);
+        cmax = std::max(cmax, (int)a->s[s].C);
     }
-    return cmax >= 256 ? 6 : cmax >= 128 ? 5 : cmax >= 64 ? 4 : 3;
+    BnLaunch g{v4 ? 4 : 1, !v4 || cmax >= 256 ? 6 : cmax >= 128 ? 5 : cmax >= 64 ? 4 : 3, 0};
+    for (int s = 0; s < a->n_seg; ++s) g.grid += (int64_t)cdc_ceil_div(a->s[s].C, g.v << g.ls) * n_chunks;
+    return g;
 }
-static int bn_bwd_ls(const cdc_bn_bwd_args* a) {
-    int cmax = 0;
-    for (int s = 0; s < a->n_seg; ++s) {
-        const cdc_bn_bseg& S = a->s[s];
-        if (S.C % 4 || !bn_al(S.x, S.ldx, S.half & CDC_BN_X_BF16) || !bn_al(S.y, S.ldy, S.half & CDC_BN_Y_BF16) ||
-            !bn_al(S.dy, S.lddy, S.half & CDC_BN_DY_BF16) || !bn_al(S.dx, S.lddx, false) || !bn_al(S.dxh, S.lddxh, true)) return -1;
-        cmax = std::max(cmax, (int)S.C);
-    }
-    return cmax >= 256 ? 6 : cmax >= 128 ? 5 : cmax >= 64 ? 4 : 3;
-}
-#define BN_V4_LAUNCH(KERN, LS, GRID, ...)                                                                                   \
-    do {                                                                                                                    \
-        switch (LS) {                                                                                                       \
-            case 6: hipLaunchKernelGGL((KERN<6>), dim3(GRID), dim3(ROW_THREADS), 0, (hipStream_t)stream, __VA_ARGS__); break; \
-            case 5: hipLaunchKernelGGL((KERN<5>), dim3(GRID), dim3(ROW_THREADS), 0, (hipStream_t)stream, __VA_ARGS__); break; \
-            case 4: hipLaunchKernelGGL((KERN<4>), dim3(GRID), dim3(ROW_THREADS), 0, (hipStream_t)stream, __VA_ARGS__); break; \
-            default: hipLaunchKernelGGL((KERN<3>), dim3(GRID), dim3(ROW_THREADS), 0, (hipStream_t)stream, __VA_ARGS__); break; \
-        }                                                                                                                   \
+#define BN_LAUNCH_ONE(KERN, V, LS, G, ...) \
+    hipLaunchKernelGGL((KERN<V, LS>), dim3((G).grid), dim3(ROW_THREADS), 0, (hipStream_t)stream, __VA_ARGS__)
+#define BN_LAUNCH(KERN, G, ...)                                      \
+    do {                                                             \
+        if ((G).v == 1) BN_LAUNCH_ONE(KERN, 1, 6, G, __VA_ARGS__);   \
+        else switch ((G).ls) {                                       \
+            case 6: BN_LAUNCH_ONE(KERN, 4, 6, G, __VA_ARGS__); break; \
+            case 5: BN_LAUNCH_ONE(KERN, 4, 5, G, __VA_ARGS__); break; \
+            case 4: BN_LAUNCH_ONE(KERN, 4, 4, G, __VA_ARGS__); break; \
+            default: BN_LAUNCH_ONE(KERN, 4, 3, G, __VA_ARGS__); break; \
+        }                                                            \
     } while (0)
 
 // data parallel, between the two phases: per-column sums over the row chunks (fixed order) + the segment's row count go to
@@ -1047,28 +938,24 @@ __global__ void __launch_bounds__(ROW_THREADS) k_bn_collect(const Args a, int n_
 extern "C" int cdc_bn_fwd(const cdc_bn_fwd_args* a, void* stream) {
     CDC_CHECK_ARG(a && a->n_seg > 0 && a->n_seg <= CDC_MAX_BN_SEGS && a->M >= 0, CDC_E_BADARG, "bn_fwd: bad argument");
     CDC_CHECK_ARG(!a->training || a->workspace, CDC_E_BADARG, "bn_fwd: training needs a workspace");
-    int total_c = 0, col_tiles = 0;
+    int total_c = 0;
     for (int s = 0; s < a->n_seg; ++s) {
         const cdc_bn_seg& S = a->s[s];
         CDC_CHECK_ARG(S.x && (S.y || S.yh) && S.C > 0 && S.ldx >= S.C && (!S.y || S.ldy >= S.C) && (!S.yh || S.ldyh >= S.C) &&
                           (S.half & ~CDC_BN_X_BF16) == 0, CDC_E_BADARG, "bn_fwd: segment %d malformed", s);
         CDC_CHECK_ARG(a->training || (S.running_mean && S.running_var), CDC_E_BADARG, "bn_fwd: eval needs running stats");
         total_c += S.C;
-        col_tiles += (S.C + 63) / 64;
     }
     CDC_CHECK_ARG(a->phase >= 0 && a->phase <= 2 && (a->phase == 0 || (a->exchange && a->training)), CDC_E_BADARG,
                   "bn_fwd: phases 1/2 need training mode and an exchange buffer");
     if (a->M == 0) return 0;
     const int n_chunks = (int)cdc_ceil_div(a->M, CDC_BN_ROWS_PER_BLOCK);
-    const int64_t grid = (int64_t)col_tiles * n_chunks;
-    CDC_CHECK_ARG(grid < (1ll << 31), CDC_E_TOOBIG, "bn_fwd: grid too large");
-    const int ls = bn_fwd_ls(a);                                         // 16-byte lanes (k_bn_*_v4) when every segment allows them
-    int64_t grid_v = 0;
-    if (ls >= 0)
-        for (int s = 0; s < a->n_seg; ++s) grid_v += (int64_t)cdc_ceil_div(a->s[s].C, 4 << ls) * n_chunks;
+    const BnLaunch g = bn_launch_geo(a, n_chunks, [](const cdc_bn_seg& S) {
+        return bn_al(S.x, S.ldx, S.half & CDC_BN_X_BF16) && bn_al(S.y, S.ldy, false) && bn_al(S.yh, S.ldyh, true);
+    });
+    CDC_CHECK_ARG(g.grid < (1ll << 31), CDC_E_TOOBIG, "bn_fwd: grid too large");
     if (a->training && a->phase != 2 && !a->stats_ready) {
-        if (ls >= 0) BN_V4_LAUNCH(k_bn_stats_v4, ls, grid_v, *a, n_chunks, total_c);
-        else hipLaunchKernelGGL(k_bn_stats, dim3(grid), dim3(ROW_THREADS), 0, (hipStream_t)stream, *a, n_chunks, total_c);
+        BN_LAUNCH(k_bn_stats, g, *a, n_chunks, total_c);
         CDC_LAUNCH_CHECK("bn_stats");
     }
     if (a->phase == 1) {
@@ -1077,144 +964,31 @@ extern "C" int cdc_bn_fwd(const cdc_bn_fwd_args* a, void* stream) {
         CDC_LAUNCH_CHECK("bn_collect");
         return 0;
     }
-    if (ls >= 0) BN_V4_LAUNCH(k_bn_apply_v4, ls, grid_v, *a, n_chunks, total_c);
-    else hipLaunchKernelGGL(k_bn_apply, dim3(grid), dim3(ROW_THREADS), 0, (hipStream_t)stream, *a, n_chunks, total_c);
+    BN_LAUNCH(k_bn_apply, g, *a, n_chunks, total_c);
     CDC_LAUNCH_CHECK("bn_apply");
     return 0;
 }
 
-// backward pass 1: partial sums of dz (-> dbeta) and dz * xhat (-> dgamma), dz = activation-masked dy
-__global__ void __launch_bounds__(ROW_THREADS) k_bn_bwd_stats(const cdc_bn_bwd_args a, int n_chunks, int total_c) {
-    BnTile t;
-    if (!bn_locate(a, n_chunks, t)) return;
-    const cdc_bn_bseg& S = a.s[t.seg];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c = t.c0 + lane;
-    double s1 = 0.0, s2 = 0.0;
-    const int r_begin = t.chunk * CDC_BN_ROWS_PER_BLOCK;
-    const int r_end = min(r_begin + CDC_BN_ROWS_PER_BLOCK, t.M);
-    if (c < S.C && (t.M != 1 || a.phase == 1)) {                        // (phase 1: see k_bn_bwd_stats_v4)
-        const float mean = S.save_mean[c], invstd = S.save_invstd[c];
-        constexpr int RPW = CDC_BN_ROWS_PER_BLOCK / WAVES_PER_BLOCK;
-        const bool masked = a.relu || a.mask_scale != 1.f;
-        const bool xh = S.half & CDC_BN_X_BF16, yh = S.half & CDC_BN_Y_BF16, dyh = S.half & CDC_BN_DY_BF16;
-        float dv[RPW], yv[RPW], xv[RPW];
-#pragma unroll
-        for (int k = 0; k < RPW; ++k) {                                  // 48 loads in flight per lane instead of 3
-            const int r = r_begin + wave + k * WAVES_PER_BLOCK;
-            const bool ok = r < r_end;
-            const int64_t gr = t.row_lo + r;                             // (only dereferenced for rows of the group: see k_bn_bwd_stats_v4)
-            dv[k] = ok ? bn_ld(S.dy, dyh, gr * S.lddy + c) : 0.f;
-            yv[k] = (ok && masked) ? bn_ld(S.y, yh, gr * S.ldy + c) : 1.f;
-            xv[k] = ok ? bn_ld(S.x, xh, gr * S.ldx + c) : 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k < RPW; ++k) {                                  // rows past r_end carry dz = 0: exact zeros in both sums
-            float dz = dv[k];
-            if (masked) dz = yv[k] > 0.f ? dz * a.mask_scale : 0.f;
-            const float xhat = (xv[k] - mean) * invstd;
-            s1 += (double)dz; s2 += (double)dz * (double)xhat;
-        }
-    }
-    __shared__ double sh[2][WAVES_PER_BLOCK][64];
-    sh[0][wave][lane] = s1; sh[1][wave][lane] = s2;
-    __syncthreads();
-    if (wave == 0 && c < S.C) {
-        s1 = sh[0][0][lane] + sh[0][1][lane] + sh[0][2][lane] + sh[0][3][lane];
-        s2 = sh[1][0][lane] + sh[1][1][lane] + sh[1][2][lane] + sh[1][3][lane];
-        double* ws = a.workspace + ((int64_t)t.chunk * total_c + t.col_base + c) * 2;
-        ws[0] = s1; ws[1] = s2;
-    }
-}
-
-__global__ void __launch_bounds__(ROW_THREADS) k_bn_bwd_apply(const cdc_bn_bwd_args a, int n_chunks, int total_c) {
-    BnTile t;
-    if (!bn_locate(a, n_chunks, t)) return;
-    const cdc_bn_bseg& S = a.s[t.seg];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c = t.c0 + lane;
-    const bool global_stats = a.training && a.phase == 2 && a.exchange;
-    const int Ms = global_stats ? (int)(a.exchange[2 * (int64_t)total_c + t.seg] + 0.5) : t.M;
-    const bool skip_norm = (Ms == 1);
-    double s1 = 0.0, s2 = 0.0;
-    if (!skip_norm)                                                      // block-uniform; every thread takes part (barrier inside)
-        bn_sum_partials(a.workspace, (t.M + CDC_BN_ROWS_PER_BLOCK - 1) / CDC_BN_ROWS_PER_BLOCK, total_c, t.col_base + (c < S.C ? c : 0), s1, s2);
-    if (c >= S.C) return;
-    if (t.chunk == 0 && wave == 0) {
-        // parameter gradients stay LOCAL sums: the data-parallel all-reduce of the gradient arena adds the ranks up
-        if (S.dbeta) S.dbeta[c] = (float)s1;
-        if (S.dgamma) S.dgamma[c] = (float)s2;
-    }
-    if (global_stats && !skip_norm) {          // the input gradient needs the sums over the GLOBAL batch
-        s1 = a.exchange[2 * (int64_t)(t.col_base + c)];
-        s2 = a.exchange[2 * (int64_t)(t.col_base + c) + 1];
-    }
-    const float gam = (skip_norm || !S.gamma) ? 1.f : S.gamma[c];
-    const float mean = skip_norm ? 0.f : S.save_mean[c];
-    const float invstd = skip_norm ? 1.f : S.save_invstd[c];
-    const float invM = Ms > 0 ? 1.f / (float)Ms : 0.f;
-    const float db = (float)s1, dg = (float)s2;
-    const int r_begin = t.chunk * CDC_BN_ROWS_PER_BLOCK;
-    const int r_end = min(r_begin + CDC_BN_ROWS_PER_BLOCK, t.M);
-    constexpr int RPW = CDC_BN_ROWS_PER_BLOCK / WAVES_PER_BLOCK;
-    const bool masked = a.relu || a.mask_scale != 1.f;
-    const bool need_x = !skip_norm && a.training;
-    const bool xh = S.half & CDC_BN_X_BF16, yh = S.half & CDC_BN_Y_BF16, dyh = S.half & CDC_BN_DY_BF16;
-    float dv[RPW], yv[RPW], xv[RPW];
-#pragma unroll
-    for (int k = 0; k < RPW; ++k) {
-        const int r = r_begin + wave + k * WAVES_PER_BLOCK;
-        const bool ok = r < r_end;
-        const int64_t gr = t.row_lo + r;
-        dv[k] = ok ? bn_ld(S.dy, dyh, gr * S.lddy + c) : 0.f;
-        yv[k] = (ok && masked) ? bn_ld(S.y, yh, gr * S.ldy + c) : 1.f;
-        xv[k] = (ok && need_x) ? bn_ld(S.x, xh, gr * S.ldx + c) : 0.f;
-    }
-#pragma unroll
-    for (int k = 0; k < RPW; ++k) {
-        const int r = r_begin + wave + k * WAVES_PER_BLOCK;
-        if (r >= r_end) break;
-        const int64_t gr = t.row_lo + r;
-        float dz = dv[k];
-        if (masked) dz = yv[k] > 0.f ? dz * a.mask_scale : 0.f;
-        float dx;
-        if (skip_norm) dx = dz;
-        else if (a.training) {
-            const float xhat = (xv[k] - mean) * invstd;
-            dx = gam * invstd * (dz - invM * (db + xhat * dg));
-        } else dx = gam * invstd * dz;
-        if (S.dx) {
-            float* dst = S.dx + gr * S.lddx + c;
-            if (S.accumulate_dx) dx = *dst + dx;
-            *dst = dx;
-        }
-        if (S.dxh) reinterpret_cast<__bf16*>(S.dxh)[gr * S.lddxh + c] = (__bf16)dx;
-    }
-}
-
 extern "C" int cdc_bn_bwd(const cdc_bn_bwd_args* a, void* stream) {
     CDC_CHECK_ARG(a && a->n_seg > 0 && a->n_seg <= CDC_MAX_BN_SEGS && a->M >= 0 && a->workspace, CDC_E_BADARG, "bn_bwd: bad argument");
-    int total_c = 0, col_tiles = 0;
+    int total_c = 0;
     for (int s = 0; s < a->n_seg; ++s) {
         const cdc_bn_bseg& S = a->s[s];
         CDC_CHECK_ARG(S.dy && S.y && S.x && (S.dx || (S.dxh && !S.accumulate_dx)) && S.save_mean && S.save_invstd && S.C > 0, CDC_E_BADARG,
                       "bn_bwd: segment %d malformed", s);
         total_c += S.C;
-        col_tiles += (S.C + 63) / 64;
     }
     CDC_CHECK_ARG(a->phase >= 0 && a->phase <= 2 && (a->phase == 0 || (a->exchange && a->training)), CDC_E_BADARG,
                   "bn_bwd: phases 1/2 need training mode and an exchange buffer");
     if (a->M == 0) return 0;
     const int n_chunks = (int)cdc_ceil_div(a->M, CDC_BN_ROWS_PER_BLOCK);
-    const int64_t grid = (int64_t)col_tiles * n_chunks;
-    CDC_CHECK_ARG(grid < (1ll << 31), CDC_E_TOOBIG, "bn_bwd: grid too large");
-    const int ls = bn_bwd_ls(a);
-    int64_t grid_v = 0;
-    if (ls >= 0)
-        for (int s = 0; s < a->n_seg; ++s) grid_v += (int64_t)cdc_ceil_div(a->s[s].C, 4 << ls) * n_chunks;
+    const BnLaunch g = bn_launch_geo(a, n_chunks, [](const cdc_bn_bseg& S) {
+        return bn_al(S.x, S.ldx, S.half & CDC_BN_X_BF16) && bn_al(S.y, S.ldy, S.half & CDC_BN_Y_BF16) &&
+               bn_al(S.dy, S.lddy, S.half & CDC_BN_DY_BF16) && bn_al(S.dx, S.lddx, false) && bn_al(S.dxh, S.lddxh, true);
+    });
+    CDC_CHECK_ARG(g.grid < (1ll << 31), CDC_E_TOOBIG, "bn_bwd: grid too large");
     if (a->phase != 2) {
-        if (ls >= 0) BN_V4_LAUNCH(k_bn_bwd_stats_v4, ls, grid_v, *a, n_chunks, total_c);
-        else hipLaunchKernelGGL(k_bn_bwd_stats, dim3(grid), dim3(ROW_THREADS), 0, (hipStream_t)stream, *a, n_chunks, total_c);
+        BN_LAUNCH(k_bn_bwd_stats, g, *a, n_chunks, total_c);
         CDC_LAUNCH_CHECK("bn_bwd_stats");
     }
     if (a->phase == 1) {
@@ -1223,8 +997,7 @@ extern "C" int cdc_bn_bwd(const cdc_bn_bwd_args* a, void* stream) {
         CDC_LAUNCH_CHECK("bn_bwd_collect");
         return 0;
     }
-    if (ls >= 0) BN_V4_LAUNCH(k_bn_bwd_apply_v4, ls, grid_v, *a, n_chunks, total_c);
-    else hipLaunchKernelGGL(k_bn_bwd_apply, dim3(grid), dim3(ROW_THREADS), 0, (hipStream_t)stream, *a, n_chunks, total_c);
+    BN_LAUNCH(k_bn_bwd_apply, g, *a, n_chunks, total_c);
     CDC_LAUNCH_CHECK("bn_bwd_apply");
     return 0;
 }

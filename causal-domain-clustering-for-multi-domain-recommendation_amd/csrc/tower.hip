@@ -27,12 +27,12 @@
 // VGPRs — they fit beside the background replay slice (2 x 64 VGPRs per SIMD, no LDS); kernels of the other queue that hold a
 // CU finish without depending on this launch.
 //
-// Arithmetic = that of the launches replaced (csrc/gemm2.hip, csrc/rowops.hip k_bn_*_v4, csrc/head.hip): bf16 operands rounded
+// Arithmetic = that of the launches replaced (csrc/gemm2.hip, csrc/rowops.hip k_bn_*<4, LS>, csrc/head.hip): bf16 operands rounded
 // to nearest even from fp32, v_mfma_f32_16x16x32_bf16 over K in ascending 32-wide steps, bias added in fp32 afterwards; BatchNorm
 // statistics as fp64 sums per 64-row chunk (wave q adds rows 16q..16q+15, quarters in order) and chunks added as NP interleaved
 // partial sums in order — the bits of cdc_gemm_bf16_nt's statistics epilogue + cdc_bn_fwd; (x - mean) * invstd * gamma + beta;
 // the 32-bit dropout stream of the BatchNorm launches (stream 64 + tower, one hash per column pair).  The backward's column
-// sums are fp64 sums per row block in a fixed order of their own (not the bits of k_bn_bwd_stats_v4's shuffle tree).
+// sums are fp64 sums per row block in a fixed order of their own (not the bits of k_bn_bwd_stats<4, LS>'s shuffle tree).
 #include "common.h"
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -249,7 +249,7 @@ __device__ __forceinline__ void tw_fwd_chunk_sums(const float* ct, int cs, int r
     if (DRAIN) tw_drain();                                                         // (split form: every wave, also what it stored before this call)
     __syncthreads();                                                               // (`quarter` is free again)
 }
-// Sum over `n_parts` published partial records of the tower's C columns, as cdc_bn_fwd's bn_sum_partials_v does: NP = 256 / C
+// Sum over `n_parts` published partial records of the tower's C columns, as cdc_bn_fwd's bn_sum_chunks does: NP = 256 / C
 // threads per column take records pt, pt + NP, ... and the NP sums are added in order.  out[2][C] doubles in LDS.  All threads call.
 // POLL (hdr != nullptr): the monolithic kernels' exchange — a batch is loaded again while any of its records is still unpublished.
 template <int C>
@@ -315,7 +315,7 @@ __device__ __forceinline__ void tw_finish_stats(const double* sums, int Ms, floa
     if (writer && tid == 0 && nbt) *nbt += 1;
     __syncthreads();
 }
-// normalise + ReLU + dropout of 8 neighbouring columns (k_bn_apply_v4's arithmetic and dropout decisions)
+// normalise + ReLU + dropout of 8 neighbouring columns (k_bn_apply<4, LS>'s arithmetic and dropout decisions)
 __device__ __forceinline__ void tw_bn_apply8(float (&v)[8], const float* col_mean, const float* col_inv, const float* gamma, const float* beta, int c,
                                              bool relu, float drop_p, float keep_scale, uint32_t thr16, uint32_t seed32, int grow) {
 #pragma unroll

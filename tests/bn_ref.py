@@ -8,7 +8,7 @@ exist.  ref_forward / ref_backward return, per segment, name -> (want, bound) wi
 
 The bounds, from the kernels' arithmetic (csrc/rowops.hip; the library is built with -ffp-contract=off):
   * the statistics are double sums of fp32 values: 16 adds per wave, the wave and chunk combination, the stride loop over the
-    chunks — N_DBL = chunks + 24 + ranks roundings of 2^-53 cover either family, the GEMM epilogues' partial sums and the
+    chunks — N_DBL = chunks + 24 + ranks roundings of 2^-53 cover either dispatch, the GEMM epilogues' partial sums and the
     data-parallel exchange;
   * save_mean is mu rounded once;
   * var = s2/M - mu^2 in double cancels: N_DBL 2^-53 (s2/M + mu^2) absolute on var, carried through 1/sqrt(var + eps) (further
@@ -68,7 +68,7 @@ def _u64(v):
 
 
 def keep_mask_uniform(seed, step, seg, rows, C, p):
-    """the one-column family: cdc_uniform(seed + step 0xD1342543DE82EF95, ((seg + 64) << 56) ^ (row C + c)) >= p keeps."""
+    """the one-column dispatch (V = 1): cdc_uniform(seed + step 0xD1342543DE82EF95, ((seg + 64) << 56) ^ (row C + c)) >= p keeps."""
     with np.errstate(over="ignore"):
         sd = _u64(seed)
         if step is not None:
@@ -94,7 +94,7 @@ def _hash32(x):
 
 
 def keep_mask_bits16(seed, step, seg, rows, C, p):
-    """the 16-byte family: g2_seed32(seed, step, 64 + seg), g2_drop_bits(row, c >> 1), 16 bits per column (even: low half);
+    """the 16-byte dispatch (V = 4): g2_seed32(seed, step, 64 + seg), g2_drop_bits(row, c >> 1), 16 bits per column (even: low half);
     keeps iff the bits >= round(p 65536)."""
     s = ((seed & 0xFFFFFFFF) ^ (((seed >> 32) & 0xFFFFFFFF) * 0x9E3779B1)) & 0xFFFFFFFF
     if step is not None:
@@ -127,7 +127,8 @@ def spec(name, C, M, **kw):
 
 
 def family(s):
-    """the kernel family the launch must take: 16-byte lanes iff every segment has C % 4 == 0 and 16-byte aligned rows."""
+    """the dispatch and dropout stream the launch must take (one kernel family, k_bn_*<V, LS>): 16-byte lanes ("v4") iff every
+    segment has C % 4 == 0 and 16-byte aligned rows, else one column per lane ("one")."""
     return "v4" if all(c % 4 == 0 for c in s["C"]) and all(p % 4 == 0 for p in s["pad"]) else "one"
 
 
@@ -511,7 +512,7 @@ def group_specs():
 
 
 def flag_specs():
-    """about a dozen launches that together switch every flag of the two argument blocks, in both families"""
+    """about a dozen launches that together switch every flag of the two argument blocks, in both dispatches"""
     T = [
         dict(C=(6, 70), M=65, pad=3, relu=0),
         dict(C=(8, 68), M=65, pad=4, relu=0, drop_p=0.25, step=None),

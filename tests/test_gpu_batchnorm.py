@@ -272,7 +272,7 @@ def test_bn_launch_shapes(cuda, name):
 @pytest.mark.parametrize("k", range(4))
 def test_bn_row_groups(cuda, k):
     """row_offsets with group sizes {0, 1, 2, 64, 65, 130} in shuffled order, segments mapped to groups non-monotonically, two
-    segments on one group, skip_le1 0 and 1, both families.  Rows of other groups stay untouched (Launch reads every output
+    segments on one group, skip_le1 0 and 1, both dispatches.  Rows of other groups stay untouched (Launch reads every output
     through _group_rows).  The empty group is the reference's absent domain: under MDR_BatchNorm (skip_le1 = 0) the batch is
     counted and the running statistics stay, under the DNN's rule (skip_le1 = 1) nothing changes at all."""
     s = R.group_specs()[k]

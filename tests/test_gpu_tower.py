@@ -6,7 +6,7 @@ cdc_head_fwd and the mirror chain — and against the oracle (model/layer.py:35-
 Forward: the contractions, the statistics sums (per 64-row chunk, chunks in cdc_bn_fwd's order) and the dropout stream are those of
 the unfused chain, so every saved tensor up to the second hidden activation is held to BIT equality; the head's dot product over
 the wide input uses 16-byte lanes (another summation order), so probabilities are held to 2e-6.  Backward: column sums per
-128-row block instead of k_bn_bwd_stats_v4's shuffle tree: the towers' gradients within 2e-4 relative L2 of the unfused chain,
+128-row block instead of k_bn_bwd_stats<4, LS>'s shuffle tree: the towers' gradients within 2e-4 relative L2 of the unfused chain,
 the gradient handed to the level below within 2e-5."""
 import ctypes as C
 
