@@ -277,6 +277,8 @@ class RowdotBwdArgs(C.Structure):
 
 
 HEAD_MAX_TOWERS = 8
+CATALOG_MAX_K = 1024
+CATALOG_MAX_F = 256
 
 
 class HeadTower(C.Structure):
@@ -384,6 +386,9 @@ _SIGNATURES = {
     "cdc_eval_topk_workspace_bytes": (c_i64, [c_i64, c_i32, c_i64, c_i32]),
     "cdc_eval_topk": (c_i32, [c_p, c_p, c_i64, c_i64, c_p, c_i64, c_i32, c_p, c_i64, c_i32, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                               c_i64, c_p]),
+    "cdc_catalog_rows": (c_i32, [c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_p, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_i32, c_i32,
+                                 c_p, c_p, c_p]),
+    "cdc_catalog_topk": (c_i32, [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_i32, c_p, c_p, c_p, c_p, c_p, c_p]),
     "cdc_eval_auc_delong_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
     "cdc_eval_auc_delong": (c_i32, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i32, c_p, c_p, c_p, c_p, c_i64, c_p]),
     "cdc_eval_loss_ci_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),

@@ -58,6 +58,13 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// The evaluation path's score order (metrics.hip's sort keys, catalog.hip's list order): one mapping, so that every call ranks alike.
+__device__ __forceinline__ uint32_t score_key(float p) {        // monotone float -> uint32 (-0.0 folded onto +0.0: a tie)
+    if (p == 0.f) p = 0.f;
+    const uint32_t u = __float_as_uint(p);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
 // Counter-based dropout stream: a 64-bit mix of (seed, element index) -> uniform in [0,1).
 // The backward pass never regenerates it: a dropped or relu-clamped unit has output exactly 0,
 // so d_in = (out > 0) ? d_out * 1/(1-p) : 0 recovers the mask from the saved output.

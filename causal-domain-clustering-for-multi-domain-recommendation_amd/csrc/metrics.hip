@@ -21,11 +21,7 @@
 #define MET_THREADS 256
 #define MET_LOSS_THREADS 1024
 
-__device__ __forceinline__ uint32_t score_key(float p) {        // monotone float -> uint32 (-0.0 folded onto +0.0: a tie)
-    if (p == 0.f) p = 0.f;
-    const uint32_t u = __float_as_uint(p);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+// score_key (monotone float -> uint32): common.h, shared with catalog.hip
 __device__ __forceinline__ float key_score(uint32_t k) {
     const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
     return __uint_as_float(u);

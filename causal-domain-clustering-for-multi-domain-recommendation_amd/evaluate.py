@@ -21,6 +21,11 @@ scan); `Evaluator(rank_at=(1, 10))` reports them and `Runner(select_by="mean_ndc
 twice, under a total order (score, item id, row index) that does not depend on how a sort leaves ties (`cdc_eval_topk`); `TopK`
 holds the lists, `TopK.merge` joins the lists of two passes, and `Evaluator.recommend` returns them for a loader.
 
+`catalog_rows` / `catalog_topk` recommend from an item catalogue: the user x item pool is never held as a whole — a tile of it is
+written (`cdc_catalog_rows`), scored by the eval forward, and folded into every context's running list of k entries
+(`cdc_catalog_topk`: threshold, LDS buffer, sort under the same total order); `CatalogTopK` holds the lists, `catalog_seen` builds
+the seen sets, and `Evaluator.recommend_catalog` drives the tiles.
+
 `eval_auc_ci` adds what an AUC needs to be judged: its DeLong standard error on this evaluation set, and for two prediction
 vectors over the same rows the difference of their AUCs with the standard error of that difference (`cdc_eval_auc_delong`);
 `Evaluator(auc_ci=True)` and `Evaluator.compare` report them.
@@ -448,6 +453,150 @@ def eval_topk(pred, user, n_user, domain=None, n_domain=1, item=None, k=10, sync
     row = row[:E]
     it = None if item is None else item[row.to(torch.int64)]
     return TopK(groups[0, :G], groups[1, :G], start[:G + 1], groups[2, :G], row, score[:E], n_out, k, n, n_user, n_domain, it, None, err)
+
+
+CATALOG_MAX_K = L.CATALOG_MAX_K
+
+
+def _catalog_k(k):
+    if isinstance(k, bool) or int(k) != k or not 1 <= k <= CATALOG_MAX_K:
+        raise ValueError(f"k={k!r} is no integer in [1, {CATALOG_MAX_K}]")
+    return int(k)
+
+
+def _id_matrix(t, what):
+    """int32 [rows, cols] whose columns are contiguous -> (tensor, row stride); a column vector may come as 1-D"""
+    if t.dim() == 1:
+        t = t.reshape(-1, 1)
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f"{what} must be a non-empty 2-D id matrix, not {tuple(t.shape)}")
+    if t.dtype != torch.int32:
+        t = t.to(torch.int32)
+    if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        t = t.contiguous()
+    return t, t.stride(0)
+
+
+class CatalogTopK:
+    """Every context's running list of the k best catalogue items (the definitions are in include/cdcmdr.h, `cdc_catalog_topk`):
+      item, cat  int32 [U, k]: the entries' item ids and catalogue row indices, best first; -1 past the list's end
+      score      f32 [U, k]: their scores, bit-copied; NaN past the end
+      n          int32 [U]: the lists' lengths, min(k, survivors)
+      k          the cut;  err: the device error word of the calls that filled it (1 + the largest context with a NaN score or a
+                 negative item id among its candidates), zeroed by `empty`
+    `catalog_topk` folds a tile of scores into it in place."""
+
+    def __init__(self, item, cat, score, n, k, err=None):
+        self.item, self.cat, self.score, self.n, self.k, self.err = item, cat, score, n, int(k), err
+
+    @classmethod
+    def empty(cls, U, k, device):
+        k, U = _catalog_k(k), int(U)
+        if not 1 <= U < 1 << 31:
+            raise ValueError(f"U={U} contexts lie outside [1, 2^31)")
+        return cls(torch.full((U, k), -1, dtype=torch.int32, device=device), torch.full((U, k), -1, dtype=torch.int32, device=device),
+                   torch.full((U, k), math.nan, dtype=torch.float32, device=device), torch.zeros(U, dtype=torch.int32, device=device), k,
+                   torch.zeros(1, dtype=torch.int32, device=device))
+
+    def lists(self):
+        """-> host dict {u: (items, scores)}, two lists per context, for inspection"""
+        n, item, score = self.n.cpu().tolist(), self.item.cpu().tolist(), self.score.cpu().tolist()
+        return {u: (item[u][:n[u]], score[u][:n[u]]) for u in range(len(n))}
+
+
+def catalog_seen(context_index, item, U):
+    """(context, item) pairs, in any order and with repeats, -> (seen_start int32 [U + 1], seen_item int32 [S]): the CSR form
+    `catalog_topk` takes, every context's slice ascending.  One torch sort; works on host or device tensors and stays on theirs."""
+    U = int(U)
+    ctx = torch.as_tensor(context_index).reshape(-1).to(torch.int64)
+    it = torch.as_tensor(item).reshape(-1).to(device=ctx.device, dtype=torch.int64)
+    if ctx.numel() != it.numel():
+        raise ValueError(f"{ctx.numel()} context indices but {it.numel()} items")
+    if ctx.numel() >= 1 << 31:
+        raise ValueError(f"{ctx.numel()} seen pairs reach 2^31")
+    if ctx.numel() and (int(ctx.min()) < 0 or int(ctx.max()) >= U):
+        raise ValueError(f"a context index lies outside [0, {U})")
+    key = torch.sort((ctx << 32) | (it + (1 << 31)))[0]                     # the item biased into [0, 2^32): ascending like the int32
+    start = torch.zeros(U + 1, dtype=torch.int64, device=ctx.device)
+    start[1:] = torch.cumsum(torch.bincount(ctx, minlength=U), 0)
+    return start.to(torch.int32), ((key & 0xffffffff) - (1 << 31)).to(torch.int32)
+
+
+def catalog_rows(context, catalog, item_cols, u0, ub, i0, ib, group_of_domain=None, domain_col=None, err=None):
+    """The tile [u0, u0 + ub) x [i0, i0 + ib) of the user x item pool (`cdc_catalog_rows`): row (u - u0) * ib + (i - i0) is context u
+    (int32 [U, F], rows may be strided) with X[item_cols[c]] = catalog[i, c] (int32 [I, C]).  -> (X int32 [ub * ib, F], group, domain):
+    domain, with domain_col, is X's domain column as a contiguous int32 vector; group, with group_of_domain (int64 [n_domain]) as well,
+    is int64 [ub * ib] = group_of_domain[domain] — a domain outside the table gives group 0 and sets the error word (1 + the largest
+    such context; `err`, an int32 [1] device tensor to share between calls, or a fresh one; kept as `catalog_rows.last_err`).
+    Nothing is read back."""
+    lib = L.load()
+    _need_device("catalog_rows", context)
+    context, ld_context = _id_matrix(context, "context")
+    catalog, ld_catalog = _id_matrix(catalog, "catalog")
+    (U, F), (I, n_cols) = context.shape, catalog.shape
+    cols = [int(c) for c in item_cols]
+    if len(cols) != n_cols:
+        raise ValueError(f"{len(cols)} item_cols for a catalogue of {n_cols} columns")
+    if len(set(cols)) != n_cols or min(cols) < 0 or max(cols) >= F:
+        raise ValueError(f"item_cols={cols} must be distinct columns in [0, {F})")
+    if group_of_domain is not None and domain_col is None:
+        raise ValueError("the group output needs domain_col, the column that holds a row's domain")
+    dev, rows = context.device, int(ub) * int(ib)
+    if not (0 <= u0 and 1 <= ub and u0 + ub <= U and 0 <= i0 and 1 <= ib and i0 + ib <= I and rows < 1 << 31):
+        raise ValueError(f"tile [{u0}, {u0 + ub}) x [{i0}, {i0 + ib}) lies outside [0, {U}) x [0, {I}) or holds 2^31 rows")
+    X = torch.empty((rows, F), dtype=torch.int32, device=dev)
+    group = domain = None
+    n_domain = 0
+    if group_of_domain is not None:
+        group_of_domain = _flat(torch.as_tensor(group_of_domain), torch.int64, dev)
+        n_domain = group_of_domain.numel()
+        group = torch.empty(rows, dtype=torch.int64, device=dev)
+    if domain_col is not None:
+        domain = torch.empty(rows, dtype=torch.int32, device=dev)
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    L.launch("cdc_catalog_rows", lib.cdc_catalog_rows,
+             (context.data_ptr(), ld_context, U, catalog.data_ptr(), ld_catalog, I, (C.c_int32 * len(cols))(*cols), len(cols), F, int(u0),
+              int(ub), int(i0), int(ib), X.data_ptr(), _ptr(group), _ptr(group_of_domain), n_domain, -1 if domain_col is None else int(domain_col),
+              _ptr(domain), err.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    catalog_rows.last_err = err
+    return X, group, domain
+
+
+def catalog_topk(state, score, catalog, u0, ub, i0, ib, seen=None):
+    """Folds the scores of the tile [u0, u0 + ub) x [i0, i0 + ib) — score f32 [ub * ib], context-major, the model's output for
+    `catalog_rows`' tile — into the running lists `state` (a `CatalogTopK`), in place (`cdc_catalog_topk`): every context of the tile
+    keeps the first k, by descending score (-0.0 ties with +0.0), then item id, then catalogue row, of its list so far and the tile's
+    candidates.  catalog: the int32 [I, C] catalogue (column 0 is the item id) or the id column alone.  seen: None or
+    (seen_start int32 [U + 1], seen_item int32 [S]) as `catalog_seen` returns them: a candidate whose id is in its context's slice is
+    left out silently.  A NaN score or a negative id is left out and sets `state.err` (1 + the largest such context; also kept as
+    `catalog_topk.last_err`).  Folding disjoint item tiles in any order gives the bits of one call over all items.  Nothing is read
+    back; returns `state`."""
+    lib = L.load()
+    _need_device("catalog_topk", score)
+    dev = score.device
+    score = _flat(score, torch.float32, dev)
+    catalog, ld_catalog = _id_matrix(catalog, "catalog")
+    U, I = state.n.numel(), catalog.shape[0]
+    if score.numel() != int(ub) * int(ib):
+        raise ValueError(f"{score.numel()} scores for a tile of {ub} x {ib}")
+    if not (0 <= u0 and 1 <= ub and u0 + ub <= U and 0 <= i0 and 1 <= ib and i0 + ib <= I):
+        raise ValueError(f"tile [{u0}, {u0 + ub}) x [{i0}, {i0 + ib}) lies outside [0, {U}) x [0, {I})")
+    seen_start = seen_item = None
+    n_seen = 0
+    if seen is not None and seen[1].numel():
+        seen_start, seen_item = _flat(seen[0], torch.int32, dev), _flat(seen[1], torch.int32, dev)
+        if seen_start.numel() != U + 1:
+            raise ValueError(f"seen_start holds {seen_start.numel()} entries for {U} contexts")
+        n_seen = seen_item.numel()
+    if state.err is None:
+        state.err = torch.zeros(1, dtype=torch.int32, device=dev)
+    L.launch("cdc_catalog_topk", lib.cdc_catalog_topk,
+             (score.data_ptr(), catalog.data_ptr(), ld_catalog, U, I, int(u0), int(ub), int(i0), int(ib), _ptr(seen_start), _ptr(seen_item),
+              n_seen, state.k, state.item.data_ptr(), state.cat.data_ptr(), state.score.data_ptr(), state.n.data_ptr(), state.err.data_ptr()),
+             C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    catalog_topk.last_err = state.err
+    return state
 
 
 def _segment_ci(owner, name, entry, pred, label, domain, n_domain, pred_b):
@@ -1140,8 +1289,11 @@ class Evaluator:
     recommend(loader, k, item_idx, by): (a method, needs user_idx; no constructor argument, test() and compare() are untouched) the
             per-user top-K lists themselves (`eval_topk`): one scoring pass, recalibrated like predict(), -> a `TopK` with every
             (domain, user) group's — by="user": every user's — k best rows, best first, no item of column item_idx twice, and the
-            entries' labels.  Not offered: candidate generation (user x item pool) or a pool-scoring driver (`TopK.merge` is the hook),
-            graded relevance, diversity or business re-ranking, lists under data parallelism.
+            entries' labels.  Not offered: graded relevance, diversity or business re-ranking, lists under data parallelism.
+    recommend_catalog(context, catalog, item_cols, k, seen, domain2group, tile_rows, item_block): (a method; no constructor argument)
+            every context's k best items out of a catalogue (`catalog_rows`, `catalog_topk`: the user x item pool written, scored
+            and ranked tile by tile) -> a `CatalogTopK`.  Not offered: grouping of contexts by user, graded relevance, diversity
+            re-ranking, data parallelism, a survivor count before the cut.
     calibration: test() adds calibration figures (`eval_calibration`; True: 10 bins, an int: that many): total_pcoc (predicted over
             observed CTR), total_brier, total_ece, total_ece_quantile, and with per-domain evaluation domain_pcoc / domain_brier /
             domain_ece / domain_ece_quantile {d: value} and mean_pcoc / mean_brier / mean_ece / mean_ece_quantile, weighted like
@@ -1254,6 +1406,81 @@ class Evaluator:
                              f"[0, {self.n_domain}) or negative item id")
         top.label = label[top.row.to(torch.int64)]
         return top
+
+    def recommend_catalog(self, context, catalog, item_cols, k=10, seen=None, domain2group=None, tile_rows=32768, item_block=None):
+        """Every context's k best items out of a catalogue: the user x item pool is written, scored and ranked tile by tile and never
+        held as a whole.  context int32 [U, F]: one request per row, the model's full id row with the user side and the domain filled
+        in; catalog int32 [I, C] with distinct, non-negative item ids in column 0 (ValueError otherwise: checked once, up front);
+        item_cols: the C columns of X the catalogue's columns overwrite.  seen: None or `catalog_seen`'s pair — a context's seen items
+        are left out.  Tiles hold Ub = max(1, tile_rows // Ib) contexts x Ib = min(I, item_block or tile_rows) items, so at most four
+        batch sizes reach the model's plan cache; tile_rows = 32768 was the fastest of 4096, 8192, 16384 and 32768 in
+        tools/catalog_bench.py's run (profiles/catalog_bench.txt).  Per tile: `catalog_rows`, the eval-mode forward as `predict()` runs it — mode
+        "multi": model(X).gather(1, group) with group = domain2group[X[:, domain_idx]] (domain2group is required there, and
+        domain_idx); "cdc": model(X, mode='split'), which gathers by the model's own table; "single": model(X) — the evaluator's
+        recalibration with the tile's domain column, `catalog_topk`.  One read at the end, of the error words: a NaN score, a negative
+        id or a domain outside domain2group raises ValueError naming the context.  Returns the `CatalogTopK`; one list per context,
+        contexts are never grouped by user."""
+        k = _catalog_k(k)
+        if self.mode == "multi" and (domain2group is None or self.domain_idx is None):
+            raise ValueError("mode 'multi' needs domain2group, the tower group of every domain, and domain_idx, the column that holds a "
+                             "row's domain: the pool's rows are scored by their domain's tower")
+        if isinstance(tile_rows, bool) or int(tile_rows) != tile_rows or not 1 <= tile_rows < 1 << 31:
+            raise ValueError(f"tile_rows={tile_rows!r} is no integer in [1, 2^31)")
+        if item_block is not None and (int(item_block) != item_block or item_block < 1):
+            raise ValueError(f"item_block={item_block!r} is no positive integer")
+        catalog, _ = _id_matrix(torch.as_tensor(catalog), "catalog")
+        context, _ = _id_matrix(torch.as_tensor(context), "context")
+        ids = catalog[:, 0]
+        if int(ids.min()) < 0:                                              # the up-front reads
+            raise ValueError("the catalogue holds a negative item id (column 0)")
+        if torch.unique(ids).numel() != ids.numel():
+            raise ValueError("the catalogue repeats an item id (column 0): ids must be distinct")
+        _need_device("recommend_catalog", context)
+        dev = context.device
+        catalog = catalog.to(dev)
+        (U, _), I = context.shape, catalog.shape[0]
+        ib = min(I, int(item_block or tile_rows))
+        ub = min(U, max(1, int(tile_rows) // ib))
+        g_of_d = None if self.mode != "multi" else _flat(torch.as_tensor(domain2group), torch.int64, dev)
+        recal = self.recalibration
+        need_domain = g_of_d is not None or (recal is not None and recal.n_domain > 1)
+        state = CatalogTopK.empty(U, k, dev)
+        rows_err = torch.zeros(1, dtype=torch.int32, device=dev)
+        model = self.model
+        was_training = model.training
+        model.eval()
+        was_precision = None
+        if self.precision is not None:
+            was_precision = getattr(model, "base_model_instance", model).precision
+            model.set_precision(self.precision)
+        try:
+            with torch.no_grad():
+                for u0 in range(0, U, ub):
+                    nu = min(ub, U - u0)
+                    for i0 in range(0, I, ib):
+                        ni = min(ib, I - i0)
+                        X, group, domain = catalog_rows(context, catalog, item_cols, u0, nu, i0, ni, g_of_d,
+                                                        self.domain_idx if need_domain else None, err=rows_err)
+                        if self.mode == "cdc":
+                            pred = model(X, mode='split')
+                        elif self.mode == "multi":
+                            pred = model(X).gather(1, group.reshape(-1, 1))
+                        else:
+                            pred = model(X)
+                        pred = pred.reshape(-1).to(torch.float32)
+                        if recal is not None:
+                            pred = recal.apply(pred, domain if recal.n_domain > 1 else None, self.recalibration_eps)
+                        catalog_topk(state, pred, catalog, u0, nu, i0, ni, seen)
+        finally:
+            model.train(was_training)
+            if was_precision is not None and was_precision != self.precision:
+                model.set_precision(was_precision)
+        bad_domain, bad = torch.cat([rows_err, state.err]).cpu().tolist()  # the one read
+        if bad_domain:
+            raise ValueError(f"context {bad_domain - 1}: domain outside domain2group's [0, {g_of_d.numel()})")
+        if bad:
+            raise ValueError(f"context {bad - 1}: NaN prediction or negative item id among its candidates")
+        return state
 
     def _score(self, data_loader, raw=False, with_item=False, item_idx=None):
         """predict() and the user column: -> (pred, label, domain or None, user int32 [n] or None); with a recalibration map (and not

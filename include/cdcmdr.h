@@ -1271,6 +1271,56 @@ int cdc_eval_topk(const float* pred, const int32_t* user, int64_t ld_user, int64
                   int32_t* entry_row, float* entry_score, int32_t* err_flag,
                   void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Recommending from an item CATALOGUE: every context's k best items out of the user x item grid, which is written, scored and
+ * ranked tile by tile and never held as a whole (csrc/catalog.hip; cdc_eval_topk ranks rows that already exist).
+ *   context   one request: row u of `context`, int32 [U, F] with row stride ld_context >= F — the model's full id row with the
+ *             user-side fields and the domain field filled in.
+ *   catalogue `catalog`, int32 [I, C] with row stride ld_catalog >= C.  item_cols (C ints in HOST memory) names the C distinct columns
+ *             of X that the catalogue's columns overwrite.  Catalogue column 0 is the item id: it must be >= 0, and the ids must be
+ *             distinct over the catalogue.
+ *   pool      pool row (u, i) is context u with X[item_cols[c]] = catalog[i, c].  One list is produced per context; contexts are
+ *             never grouped: two contexts of one user are two lists.
+ *   excluded  candidate (u, i) is left out SILENTLY when catalog[i, 0] is in context u's seen set.  The seen set is CSR: seen_start
+ *             int32 [U + 1], seen_item int32 [n_seen], every context's slice ascending; duplicates and ids that are not in the
+ *             catalogue are allowed; both pointers NULL: nothing is seen.  Candidate (u, i) is left out and REPORTED when its score is
+ *             NaN or its item id is negative, whether or not it is seen: err_flag (int32, optional, zeroed by the caller) receives
+ *             1 + the largest such context index.
+ *   order     inside a list: DESCENDING score, -0.0 and +0.0 counting as one score (cdc_eval_topk's mapping, one function); then
+ *             ascending item id; then ascending catalogue row — that last key only matters when the ids are not distinct, and keeps
+ *             the order total, so the output is defined even then.
+ *   result    per context u: n[u] = min(k, survivors); item[u, :], cat[u, :] (the catalogue row index) and score[u, :] (bit-copied),
+ *             each [U, k] row-major, hold the entries best first; the entries past n[u] are written on every call as -1, -1 and the
+ *             NaN 0x7fc00000.  1 <= k <= CDC_CATALOG_MAX_K.
+ *   running   cdc_catalog_topk takes the lists as in/out state (an empty state: n = 0) and replaces context u's list, for every u of
+ *             the tile, by the first k in that order of (old list + this tile's candidates that are not excluded); the lists of the
+ *             other contexts are not touched.  Folding DISJOINT item tiles in any order and with any tile shapes gives the bits of one
+ *             call over all items.  With distinct ids the lists read as (item, score) sequences are those of cdc_eval_topk with an item
+ *             column over the materialised pool, cut at k.
+ * No atomic influences the contents or order of an output (an LDS slot counter decides where a candidate waits for the sort under
+ * the total order, nothing else; the error word is a maximum).
+ *
+ * cdc_catalog_rows writes the tile X[(u - u0) * Ib + (i - i0), :] (int32 [Ub * Ib, F], contiguous), u0 <= u < u0 + Ub, i0 <= i < i0 + Ib.
+ * Optional outputs, both read off column domain_col of X: group int64 [Ub * Ib] = group_of_domain[X[r, domain_col]] (group_of_domain
+ * int64 [n_domain]; a domain outside [0, n_domain) gives group 0 and sets err_flag to 1 + the largest such context index), and
+ * domain_out int32 [Ub * Ib], the column itself, contiguous.
+ * cdc_catalog_topk reads score f32 [Ub * Ib], context-major — the model's output for that tile — and catalog_id, the catalogue's id
+ * column (= catalog, stride ld_catalog), and folds the tile into the running lists.
+ * Both: stream-ordered single launches — no workspace, no allocation, no synchronisation, nothing read back; launch dimensions depend
+ * on (Ub, Ib, F) alone, so a call can be captured in a graph.  Every argument is checked before anything is launched; CDC_E_BADARG
+ * for k outside [1, CDC_CATALOG_MAX_K], U or I outside [1, 2^31), Ub * Ib >= 2^31, a tile outside [0, U) x [0, I), F outside
+ * [1, CDC_CATALOG_MAX_F], C outside [1, F], a NULL input or output, an item_cols entry outside [0, F) or repeated, one seen pointer
+ * without the other.  seen_start is device data: whatever it holds is clamped into [0, n_seen]. */
+#define CDC_CATALOG_MAX_K 1024
+#define CDC_CATALOG_MAX_F 256
+int cdc_catalog_rows(const int32_t* context, int64_t ld_context, int64_t U, const int32_t* catalog, int64_t ld_catalog, int64_t I,
+                     const int32_t* item_cols, int32_t C, int32_t F, int64_t u0, int64_t Ub, int64_t i0, int64_t Ib,
+                     int32_t* X, int64_t* group, const int64_t* group_of_domain, int32_t n_domain, int32_t domain_col,
+                     int32_t* domain_out, int32_t* err_flag, void* stream);
+int cdc_catalog_topk(const float* score, const int32_t* catalog_id, int64_t ld_catalog, int64_t U, int64_t I,
+                     int64_t u0, int64_t Ub, int64_t i0, int64_t Ib,
+                     const int32_t* seen_start, const int32_t* seen_item, int64_t n_seen, int32_t k,
+                     int32_t* item, int32_t* cat, float* out_score, int32_t* n, int32_t* err_flag, void* stream);
+
 /* DeLong standard errors (DeLong, DeLong & Clarke-Pearson 1988) of the AUCs cdc_eval_metrics reports, and the paired comparison of
  * two score vectors on the same rows.  pred_a, label, domain, ld_domain, n_domain as for cdc_eval_metrics; pred_b f32 [n] or NULL
  * (unpaired).  Per segment (domain 0..n_domain-1, then ALL rows) with positives x_1..x_P, negatives y_1..y_N, scores compared in
