@@ -1154,10 +1154,9 @@ extern "C" int cdc_transpose_multi(const cdc_transpose_args* a, void* stream) {
     return 0;
 }
 
-extern "C" int cdc_glinear_bwd_w_pair(const cdc_lin_bwdw_args* wide, const cdc_lin_bwdw_args* narrow, const cdc_lin_bwdw_args* tabs_dev,
-                                      void* stream) {
-    CDC_CHECK_ARG(wide && narrow && tabs_dev, CDC_E_BADARG, "glinear_bwd_w_pair: null argument");
-    int64_t slab[2] = {0, 0};
+// the argument checks of the pair launch (shared with cdc_glinear_bwd_xw); slab[w]: floats of one split-K slab of each class
+static int bwd_w_pair_check(const cdc_lin_bwdw_args* wide, const cdc_lin_bwdw_args* narrow, int64_t slab[2]) {
+    slab[0] = slab[1] = 0;
     for (int w = 0; w < 2; ++w) {
         const cdc_lin_bwdw_args* a = w ? narrow : wide;
         CDC_CHECK_ARG(a->n_groups > 0 && a->n_groups <= CDC_MAX_GROUPS && !a->row_offsets && a->split_k <= 256, CDC_E_BADARG,
@@ -1171,7 +1170,24 @@ extern "C" int cdc_glinear_bwd_w_pair(const cdc_lin_bwdw_args* wide, const cdc_l
             slab[w] += (int64_t)G.N * G.K + G.N;
         }
     }
+    return 0;
+}
+extern "C" int cdc_glinear_bwd_w_pair(const cdc_lin_bwdw_args* wide, const cdc_lin_bwdw_args* narrow, const cdc_lin_bwdw_args* tabs_dev,
+                                      void* stream) {
+    CDC_CHECK_ARG(wide && narrow && tabs_dev, CDC_E_BADARG, "glinear_bwd_w_pair: null argument");
+    int64_t slab[2];
+    const int rc = bwd_w_pair_check(wide, narrow, slab);
+    if (rc) return rc;
     return g2_launch_bwd_w_dual(wide, narrow, tabs_dev, slab[0], slab[1], (hipStream_t)stream);
+}
+// a step's last grad-input launch (cdc_gemm_bf16_nt, mode 1) and the pair launch behind it as ONE launch (csrc/gemm2.hip k_g2_xw)
+extern "C" int cdc_glinear_bwd_xw(const cdc_g2_args* x, const cdc_lin_bwdw_args* wide, const cdc_lin_bwdw_args* narrow, const void* tabs_dev,
+                                  void* stream) {
+    CDC_CHECK_ARG(x && wide && narrow && tabs_dev, CDC_E_BADARG, "glinear_bwd_xw: null argument");
+    int64_t slab[2];
+    const int rc = bwd_w_pair_check(wide, narrow, slab);
+    if (rc) return rc;
+    return g2_launch_bwd_xw(x, wide, narrow, reinterpret_cast<const cdc_lin_bwdw_args*>(tabs_dev), slab[0], slab[1], (hipStream_t)stream);
 }
 // the same, and the slabs of both classes summed into the gradients by ONE more launch (callers that need the reduced gradient right
 // away: data parallelism all-reduces it; autograd hands it on) — two launches where cdc_glinear_bwd_w twice issues four

@@ -61,13 +61,13 @@ struct G2Cfg {
 
 template <int N> __device__ __forceinline__ void g2_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
+// (the body is a device function so that one launch can run it beside the grad-weight bodies: k_g2_xw below; bid / nblk: the
+// workgroup's index among, and the number of, the workgroups that run THIS body)
 template <int BM, int BN, int NSTAGE>
-__global__ void __launch_bounds__(G2_THREADS, (G2Cfg<BM, BN, NSTAGE>::BLOCKS_PER_CU)) k_g2_nt(const cdc_g2_args a) {
-    CDC_PRIO_MAIN();
+__device__ __forceinline__ void g2_nt_body(const cdc_g2_args& a, const int bid, const int nblk, unsigned char* const smem) {
     typedef G2Cfg<BM, BN, NSTAGE> Cfg;
     constexpr int G2_BM = BM;                                        // (the epilogue below predates the BM template parameter)
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    int tile = g2_xcd_remap(blockIdx.x, gridDim.x);
+    int tile = g2_xcd_remap(bid, nblk);
     const int o = find_group<false>(a.n_out, tile, [&](int l) { return ((a.o[l].M + BM - 1) / BM) * ((a.o[l].N + BN - 1) / BN); },
                                     [](int) { return (int64_t)0; }, tile, nullptr);
     if (o < 0) return;
@@ -436,7 +436,21 @@ __global__ void __launch_bounds__(G2_THREADS, (G2Cfg<BM, BN, NSTAGE>::BLOCKS_PER
     }
 }
 
-extern "C" int cdc_gemm_bf16_nt(const cdc_g2_args* a, void* stream) {
+template <int BM, int BN, int NSTAGE>
+__global__ void __launch_bounds__(G2_THREADS, (G2Cfg<BM, BN, NSTAGE>::BLOCKS_PER_CU)) k_g2_nt(const cdc_g2_args a) {
+    CDC_PRIO_MAIN();
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    g2_nt_body<BM, BN, NSTAGE>(a, blockIdx.x, gridDim.x, smem);
+}
+
+static int64_t g2_nt_tiles(const cdc_g2_args* a, int bm, int bn) {
+    int64_t t = 0;
+    for (int o = 0; o < a->n_out; ++o) t += cdc_ceil_div(a->o[o].M, bm) * cdc_ceil_div(a->o[o].N, bn);
+    return t;
+}
+// every check of a cdc_gemm_bf16_nt launch and its tile class (shared with the fused tail launch, g2_launch_bwd_xw); *cfg = 0: no rows,
+// nothing to launch
+static int g2_nt_check(const cdc_g2_args* a, int* cfg_out) {
     CDC_CHECK_ARG(a && a->n_out > 0 && a->n_out <= CDC_G2_MAX_OUT && a->n_seg > 0 && a->n_seg <= CDC_G2_MAX_SEG, CDC_E_BADARG,
                   "gemm_bf16_nt: bad counts");
     CDC_CHECK_ARG(a->mode == 0 || a->mode == 1, CDC_E_BADARG, "gemm_bf16_nt: mode must be 0 (forward) or 1 (grad-input)");
@@ -465,12 +479,9 @@ extern "C" int cdc_gemm_bf16_nt(const cdc_g2_args* a, void* stream) {
         for (int o = 0; o < a->n_out; ++o)
             if (per_out[o] > max_kr) max_kr = (int)std::min<int64_t>(per_out[o], 1 << 30);
     }
+    *cfg_out = 0;
     if (max_m == 0) return 0;
-    auto tiles = [&](int bm, int bn) {
-        int64_t t = 0;
-        for (int o = 0; o < a->n_out; ++o) t += cdc_ceil_div(a->o[o].M, bm) * cdc_ceil_div(a->o[o].N, bn);
-        return t;
-    };
+    auto tiles = [&](int bm, int bn) { return g2_nt_tiles(a, bm, bn); };
     int cfg = a->tile_cfg;
     if (cfg <= 0 || cfg > 10) {
         // tile shape: narrow outputs (towers, gates) take 64-wide column tiles; few tiles -> 64-row tiles so that the chip fills;
@@ -485,6 +496,15 @@ extern "C" int cdc_gemm_bf16_nt(const cdc_g2_args* a, void* stream) {
         else if (short_rows) cfg = max_kr >= 1024 ? 9 : 10;
         else cfg = 1;
     }
+    *cfg_out = cfg;
+    return 0;
+}
+
+extern "C" int cdc_gemm_bf16_nt(const cdc_g2_args* a, void* stream) {
+    int cfg = 0;
+    const int rc = g2_nt_check(a, &cfg);
+    if (rc || cfg == 0) return rc;
+    auto tiles = [&](int bm, int bn) { return g2_nt_tiles(a, bm, bn); };
     hipStream_t st = (hipStream_t)stream;
 #define G2_LAUNCH(BM_, BN_, NS_)                                                                                              \
     do {                                                                                                                      \
@@ -724,6 +744,31 @@ __global__ void __launch_bounds__(G2_THREADS, 2) k_g2_tn_dual(const cdc_lin_bwdw
     if ((int)blockIdx.x < n_wide) g2_tn_body<128, 128, 2>(tabs[0], slab_wide, blockIdx.x, n_wide, smem);
     else g2_tn_body<64, 64, 3>(tabs[1], slab_narrow, (int)blockIdx.x - n_wide, (int)gridDim.x - n_wide, smem);
 }
+// ... and the grad-input launch that precedes them in a step (dX of the embeddings) in the SAME launch: the grad-weight tiles read the dZ and
+// X shadows and write slabs, the grad-input tiles write a dX nobody of them reads, so no workgroup depends on another.  Each body gets its
+// LOCAL block index and count (its XCD remap and its group search are those of its own launch) and runs the code of its own launch on the
+// same operands in the same order: bit-identical results.  Workgroups start in block-index order; G2_XW_ORDER picks which body owns which
+// block range (0: wide grad-weight, grad-input, narrow grad-weight; 1: grad-input, wide, narrow), measured in profiles/round10.
+#ifndef G2_XW_ORDER
+#define G2_XW_ORDER 0
+#endif
+static_assert(sizeof(cdc_g2_args) + 40 <= 4096, "k_g2_xw: the grad-input block travels in the kernel-argument block");
+template <int BM, int BN, int NSTAGE>
+__global__ void __launch_bounds__(G2_THREADS, 2) k_g2_xw(const cdc_g2_args x, const cdc_lin_bwdw_args* __restrict__ tabs, int64_t slab_wide,
+                                                         int64_t slab_narrow, int n_wide, int n_x) {
+    CDC_PRIO_MAIN();
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int b = (int)blockIdx.x, n_narrow = (int)gridDim.x - n_wide - n_x;
+#if G2_XW_ORDER == 0
+    if (b < n_wide) g2_tn_body<128, 128, 2>(tabs[0], slab_wide, b, n_wide, smem);
+    else if (b < n_wide + n_x) g2_nt_body<BM, BN, NSTAGE>(x, b - n_wide, n_x, smem);
+    else g2_tn_body<64, 64, 3>(tabs[1], slab_narrow, b - n_wide - n_x, n_narrow, smem);
+#else
+    if (b < n_x) g2_nt_body<BM, BN, NSTAGE>(x, b, n_x, smem);
+    else if (b < n_x + n_wide) g2_tn_body<128, 128, 2>(tabs[0], slab_wide, b - n_x, n_wide, smem);
+    else g2_tn_body<64, 64, 3>(tabs[1], slab_narrow, b - n_x - n_wide, n_narrow, smem);
+#endif
+}
 
 int g2_launch_bwd_w(const cdc_lin_bwdw_args* a, int64_t slab_stride, hipStream_t st) {
     int max_n = 0, max_k = 0;
@@ -755,8 +800,8 @@ static int64_t g2_tn_tiles(const cdc_lin_bwdw_args* a, int T) {
     for (int g = 0; g < a->n_groups; ++g) t += cdc_ceil_div(a->g[g].N, T) * cdc_ceil_div(a->g[g].K, T);
     return t;
 }
-int g2_launch_bwd_w_dual(const cdc_lin_bwdw_args* wide, const cdc_lin_bwdw_args* narrow, const cdc_lin_bwdw_args* tabs_dev, int64_t slab_wide,
-                         int64_t slab_narrow, hipStream_t st) {
+// the checks and the two workgroup counts of a launch that runs both grad-weight classes (k_g2_tn_dual, k_g2_xw)
+static int g2_dual_check(const cdc_lin_bwdw_args* wide, const cdc_lin_bwdw_args* narrow, int64_t* nw_out, int64_t* nn_out) {
     for (int w = 0; w < 2; ++w) {
         const cdc_lin_bwdw_args* a = w ? narrow : wide;
         for (int g = 0; g < a->n_groups; ++g) {
@@ -769,7 +814,17 @@ int g2_launch_bwd_w_dual(const cdc_lin_bwdw_args* wide, const cdc_lin_bwdw_args*
     const int64_t nw = g2_tn_tiles(wide, 128) * (wide->split_k > 1 ? wide->split_k : 1);
     const int64_t nn = g2_tn_tiles(narrow, 64) * (narrow->split_k > 1 ? narrow->split_k : 1);
     CDC_CHECK_ARG(nw + nn < (1ll << 31) && nw > 0 && nn > 0, CDC_E_TOOBIG, "glinear_bwd_w_pair: grid out of range");
-    constexpr int LDS_W = 2 * (G2Tn<128>::BYTES * 2), LDS_N = 3 * (G2Tn<64>::BYTES * 2);
+    *nw_out = nw;
+    *nn_out = nn;
+    return 0;
+}
+constexpr int G2_LDS_W = 2 * (G2Tn<128>::BYTES * 2), G2_LDS_N = 3 * (G2Tn<64>::BYTES * 2);
+int g2_launch_bwd_w_dual(const cdc_lin_bwdw_args* wide, const cdc_lin_bwdw_args* narrow, const cdc_lin_bwdw_args* tabs_dev, int64_t slab_wide,
+                         int64_t slab_narrow, hipStream_t st) {
+    int64_t nw = 0, nn = 0;
+    const int rc = g2_dual_check(wide, narrow, &nw, &nn);
+    if (rc) return rc;
+    constexpr int LDS_W = G2_LDS_W, LDS_N = G2_LDS_N;
     static bool attr_done = false;
     if (!attr_done) {
         (void)hipFuncSetAttribute((const void*)k_g2_tn_dual, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_W > LDS_N ? LDS_W : LDS_N);
@@ -778,6 +833,89 @@ int g2_launch_bwd_w_dual(const cdc_lin_bwdw_args* wide, const cdc_lin_bwdw_args*
     hipLaunchKernelGGL(k_g2_tn_dual, dim3((unsigned)(nw + nn)), dim3(G2_THREADS), LDS_W > LDS_N ? LDS_W : LDS_N, st, tabs_dev, slab_wide, slab_narrow,
                        (int)nw);
     CDC_LAUNCH_CHECK("glinear_bwd_w_pair");
+    return 0;
+}
+// byte ranges [lo, hi) of a fused launch's operands: the grad-input tiles and the grad-weight tiles run side by side, so what one part
+// writes may not meet what the other reads or writes
+namespace {
+struct G2Ranges {
+    uintptr_t lo[2 * CDC_G2_MAX_OUT + 2 * CDC_G2_MAX_SEG + 6 * CDC_MAX_GROUPS + 4], hi[2 * CDC_G2_MAX_OUT + 2 * CDC_G2_MAX_SEG + 6 * CDC_MAX_GROUPS + 4];
+    int n = 0;
+    void add(const void* p, int64_t rows, int64_t ld, int64_t cols, int elt) {
+        if (!p || rows <= 0 || cols <= 0) return;
+        lo[n] = (uintptr_t)p;
+        hi[n] = (uintptr_t)p + (uintptr_t)(((rows - 1) * ld + cols) * elt);
+        ++n;
+    }
+    bool meets(const G2Ranges& o) const {
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j < o.n; ++j)
+                if (lo[i] < o.hi[j] && o.lo[j] < hi[i]) return true;
+        return false;
+    }
+};
+}
+// cdc_glinear_bwd_xw (gemm.hip): a step's embedding grad-input launch and its two batched grad-weight classes as ONE launch
+int g2_launch_bwd_xw(const cdc_g2_args* x, const cdc_lin_bwdw_args* wide, const cdc_lin_bwdw_args* narrow, const cdc_lin_bwdw_args* tabs_dev,
+                     int64_t slab_wide, int64_t slab_narrow, hipStream_t st) {
+    int cfg = 0;
+    int rc = g2_nt_check(x, &cfg);
+    if (rc) return rc;
+    CDC_CHECK_ARG(x->mode == 1, CDC_E_BADARG, "glinear_bwd_xw: the contraction block must be a grad-input launch (mode 1)");
+    // the grad-input body is instantiated for the classes such a launch takes: 64 x 64 tiles with three stages, 128 x 128 with two
+    CDC_CHECK_ARG(cfg == 0 || cfg == 1 || cfg == 9, CDC_E_BADARG, "glinear_bwd_xw: tile class %d of the grad-input part cannot ride this launch", cfg);
+    int64_t nw = 0, nn = 0;
+    rc = g2_dual_check(wide, narrow, &nw, &nn);
+    if (rc) return rc;
+    {
+        G2Ranges xw, xr, ww, wr;                                         // grad-input writes / reads, grad-weight writes / reads
+        for (int o = 0; o < x->n_out; ++o) {
+            const cdc_g2_out& O = x->o[o];
+            xw.add(O.y, O.M, O.ldy, O.N, 4);
+            xw.add(O.yh, O.M, O.ldyh, O.N, 2);
+            if (O.act_cols > 0) xr.add(O.mask, O.M, O.ldmask, O.act_cols < O.N ? O.act_cols : O.N, O.mask_bf16 ? 2 : 4);
+        }
+        for (int s = 0; s < x->n_seg; ++s) {
+            const cdc_g2_seg& S = x->s[s];
+            xr.add(S.a, x->o[S.out].M, S.lda, S.Kr, 2);
+            xr.add(S.b, x->o[S.out].N, S.ldb, S.Kr, 2);
+        }
+        for (int w = 0; w < 2; ++w) {
+            const cdc_lin_bwdw_args* a = w ? narrow : wide;
+            const int T = w ? 64 : 128;
+            const int S = a->split_k > 1 ? a->split_k : 1;
+            if (S > 1) ww.add(a->workspace, 1, 0, (int64_t)S * (w ? slab_narrow : slab_wide), 4);
+            for (int g = 0; g < a->n_groups; ++g) {
+                const cdc_bwdw_group& G = a->g[g];
+                const int64_t rows = cdc_ceil_div(G.M, 64) * 64;         // whole slabs of 64 rows, whole tiles of T columns are staged
+                wr.add(G.dzh, rows, G.lddzh, cdc_ceil_div(G.N, T) * T, 2);
+                wr.add(G.xh, rows, G.ldxh, cdc_ceil_div(G.K, T) * T, 2);
+                if (S <= 1) {
+                    ww.add(G.dw, G.N, G.lddw, G.K, 4);
+                    ww.add(G.db, 1, 0, G.N, 4);
+                }
+            }
+        }
+        CDC_CHECK_ARG(!xw.meets(wr) && !xw.meets(ww) && !xr.meets(ww), CDC_E_BADARG,
+                      "glinear_bwd_xw: the grad-input part and the grad-weight part run side by side: what one writes may not overlap what the other reads or writes");
+    }
+    const int64_t nx = cfg == 9 ? g2_nt_tiles(x, 64, 64) : (cfg == 1 ? g2_nt_tiles(x, 128, 128) : 0);
+    CDC_CHECK_ARG(nw + nn + nx < (1ll << 31), CDC_E_TOOBIG, "glinear_bwd_xw: grid too large");
+#define G2_XW_LAUNCH(BM_, BN_, NS_)                                                                                            \
+    do {                                                                                                                      \
+        constexpr int LDS_ = std::max(std::max(G2_LDS_W, G2_LDS_N), (int)G2Cfg<BM_, BN_, NS_>::SMEM);                          \
+        static bool attr_done = false;                                                                                       \
+        if (!attr_done) {                                                                                                     \
+            (void)hipFuncSetAttribute((const void*)k_g2_xw<BM_, BN_, NS_>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_);  \
+            attr_done = true;                                                                                                 \
+        }                                                                                                                     \
+        hipLaunchKernelGGL((k_g2_xw<BM_, BN_, NS_>), dim3((unsigned)(nw + nx + nn)), dim3(G2_THREADS), LDS_, st, *x, tabs_dev, slab_wide,  \
+                           slab_narrow, (int)nw, (int)nx);                                                                    \
+    } while (0)
+    if (cfg == 1) G2_XW_LAUNCH(128, 128, 2);
+    else G2_XW_LAUNCH(64, 64, 3);
+#undef G2_XW_LAUNCH
+    CDC_LAUNCH_CHECK("glinear_bwd_xw");
     return 0;
 }
 bool g2_bwd_w_uses_small_tiles(const cdc_lin_bwdw_args* a) {

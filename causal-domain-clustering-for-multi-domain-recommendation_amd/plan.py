@@ -348,6 +348,54 @@ class _DwBatch:
                           plan._dw_pair_dev.data_ptr(), what="cdc_glinear_bwd_w", flops=sum(la.flops for la in self.launches))]
 
 
+def _g2_tile_class(a):
+    """the tile class cdc_gemm_bf16_nt picks for the argument block `a` (csrc/gemm2.hip g2_nt_check; cdc_g2_args.tile_cfg 1..10)"""
+    if 0 < a.tile_cfg <= 10:
+        return a.tile_cfg
+    outs = [a.o[i] for i in range(a.n_out)]
+    per_out = [sum(a.s[i].Kr for i in range(a.n_seg) if a.s[i].out == o) for o in range(a.n_out)]
+    narrow = max(O.N for O in outs) <= 64
+    bn = 64 if narrow else 128
+    short_rows = sum(-(-O.M // 128) * -(-O.N // bn) for O in outs) < 256
+    if narrow:
+        return 9 if short_rows else 7
+    if short_rows:
+        return 9 if max(per_out) >= 1024 else 10
+    return 1
+
+
+def _xw_operands_meet(x, aw, an, slab_w, slab_n):
+    """Does the grad-input block x write what the grad-weight blocks (wide aw, narrow an) read or write, or do they write what it
+    reads?  Byte ranges as cdc_glinear_bwd_xw forms them (it refuses such a launch)."""
+    def rng(p, rows, ld, cols, elt):
+        p = p if isinstance(p, int) else C.cast(p, C.c_void_p).value
+        return [(p, p + ((rows - 1) * ld + cols) * elt)] if (p and rows > 0 and cols > 0) else []
+
+    xw, xr, ww, wr = [], [], [], []
+    for i in range(x.n_out):
+        O = x.o[i]
+        xw += rng(O.y, O.M, O.ldy, O.N, 4) + rng(O.yh, O.M, O.ldyh, O.N, 2)
+        if O.act_cols > 0:
+            xr += rng(O.mask, O.M, O.ldmask, min(O.act_cols, O.N), 2 if O.mask_bf16 else 4)
+    for i in range(x.n_seg):
+        S = x.s[i]
+        xr += rng(S.a, x.o[S.out].M, S.lda, S.Kr, 2) + rng(S.b, x.o[S.out].N, S.ldb, S.Kr, 2)
+    for a, T, slab in ((aw, 128, slab_w), (an, 64, slab_n)):
+        S = max(a.split_k, 1)
+        if S > 1:
+            ww += rng(a.workspace, 1, 0, S * slab, 4)
+        for i in range(a.n_groups):
+            G = a.g[i]
+            rows = -(-G.M // 64) * 64
+            wr += rng(G.dzh, rows, G.lddzh, -(-G.N // T) * T, 2) + rng(G.xh, rows, G.ldxh, -(-G.K // T) * T, 2)
+            if S <= 1:
+                ww += rng(G.dw, G.N, G.lddw, G.K, 4) + rng(G.db, 1, 0, G.N, 4)
+
+    def meet(p, q):
+        return any(a0 < b1 and b0 < a1 for a0, a1 in p for b0, b1 in q)
+    return meet(xw, wr) or meet(xw, ww) or meet(xr, ww)
+
+
 class Plan:
     def __init__(self, device, B, precision="bf16", training=True, dropout=0.0, seed=0, step_dev=None, grad_arena=None, dist=None, g2=True,
                  defer_dw_reduce=False):
@@ -398,6 +446,7 @@ class Plan:
         # the gradient tensors of those parameters are NOT written by backward()
         self.defer_dw_reduce = bool(defer_dw_reduce)
         self.grad_slabs = {}
+        self.bwd_tail = None              # (grad-input step, grad-weight step, the one launch that does both): _fuse_bwd_tail
         self.finalized = False
         self.loss_inputs = None
         # bf16 contraction path with operands that are bf16 in memory (csrc/gemm2.hip): shadows of activations, gradients, weights
@@ -655,7 +704,30 @@ class Plan:
         for a in self._gemm_ws_users:
             a.workspace = self._gemm_ws.data_ptr()
         self.deferred_dw_steps = batch.emit(self._gemm_ws.data_ptr(), shared)
+        self.bwd_tail = self._fuse_bwd_tail(batch)
         self.bwd_steps += self.deferred_dw_steps
+
+    def _fuse_bwd_tail(self, batch):
+        """The last grad-input launch of the backward and the batched grad-weight launch behind it as ONE launch (csrc/gemm2.hip
+        k_g2_xw): neither reads what the other writes, and as two launches the second one's tiles wait for the first one's tail.
+        bwd_steps keeps both launches (each runs alone: plan.backward(), the data-parallel sequences, per-launch timing); a trainer
+        that issues the step itself puts the fused call where the grad-input launch stands and leaves the grad-weight launch out
+        (TrainStep._backward).  Returns (grad-input step, grad-weight step, fused step), or None when the tail is not of that form:
+        the bf16-shadow path, one cdc_glinear_bwd_w_pair call that leaves its slabs to the consumer, right behind a
+        cdc_gemm_bf16_nt grad-input launch of a tile class the fused kernel is instantiated for, disjoint operands."""
+        if not (self.use_g2 and self.defer_dw_reduce and batch.pair and not batch.pair_reduce and len(self.deferred_dw_steps) == 1):
+            return None
+        x_step = self.bwd_steps[-1] if self.bwd_steps else None
+        x = getattr(x_step, "g2_args", None)
+        if x is None or x.mode != 1 or _g2_tile_class(x) not in (1, 9):
+            return None
+        aw, an = batch.launches[0].args, batch.launches[1].args
+        if _xw_operands_meet(x, aw, an, batch.launches[0].slab, batch.launches[1].slab):
+            return None
+        w_step = self.deferred_dw_steps[0]
+        fused = self.call("cdc_glinear_bwd_xw", C.byref(x), C.byref(aw), C.byref(an), self._dw_pair_dev.data_ptr(),
+                          flops=x_step.flops + w_step.flops)
+        return x_step, w_step, fused
 
     def dp_phases(self, steps, launches, exchanges):
         """Data parallel: a computation split into phases around the all-reduces of its global-batch sums is appended to `steps`:
@@ -704,6 +776,7 @@ class Plan:
         def run(stream):
             L.launch(what, fn, args, stream, flops, nbytes)
         run.what = what                   # (the launch's name: tests compare plans by their kernel sequences)
+        run.flops = flops
         return run
 
 
@@ -1071,7 +1144,9 @@ class GLinear(Op):
             a.n_seg = si
             self._keep.append(a)
             fl = _flops(self.M, (allg[gi]["w"] for _, gis in la for gi in gis))
-            plan.bwd_steps.append(plan.call("cdc_gemm_bf16_nt", C.byref(a), what="cdc_glinear_bwd_x", flops=fl))
+            step = plan.call("cdc_gemm_bf16_nt", C.byref(a), what="cdc_glinear_bwd_x", flops=fl)
+            step.g2_args = a                               # (Plan._fuse_bwd_tail: the last one may ride the grad-weight launch)
+            plan.bwd_steps.append(step)
 
 
 class GatePool(Op):

@@ -95,7 +95,7 @@ class TrainStep:
     def __init__(self, model, optimizer: FusedAdam, batch_size, mode="multi", use_graph=False, dist=None, sync_bn=True,
                  table_dist=None, shard_slack=1.5, train_mode=True, overlap=True, overlap_waves=2, sort_ahead=True, fuse_gather=False,
                  defer_dw_reduce=None, global_rows=None, cap_rows=None, tower_one_launch=True, rows_dense_one_launch=True,
-                 loss_weights=None):
+                 loss_weights=None, bwd_tail_one_launch=True):
         """sync_bn (data parallel only): BatchNorm statistics over the GLOBAL batch, as the reference's single process
         computes them — two small all-reduces per BatchNorm launch; False = per-rank statistics.
         table_dist (data parallel only): "sharded" (row r owned by rank r % world; default with the lazy table optimiser)
@@ -109,7 +109,10 @@ class TrainStep:
         batch's row sort on that chain (step(..., next_X=); sort_ahead=False ignores next_X), the catch-up launch that also writes
         the gathered embeddings (slower: profiles/round3/README.md section 3).
         loss_weights: a LossWeights — per-row, per-domain and positive-class weights of the loss, decided here so that a captured
-        graph has fixed pointers; None (or one that weights nothing) is the unweighted step."""
+        graph has fixed pointers; None (or one that weights nothing) is the unweighted step.
+        bwd_tail_one_launch (single GPU): the embeddings' grad-input launch and the batched grad-weight launch that end the backward
+        go out as one launch (cdc_glinear_bwd_xw) where the plan's tail has that form (Plan.bwd_tail; bwd_tail_fused tells);
+        bit-identical results."""
         self.model, self.opt, self.B, self.mode = model, optimizer, int(batch_size), mode
         self.lib = L.load()
         self.dist = dist
@@ -125,6 +128,8 @@ class TrainStep:
         # the two updates that end a single-GPU step with the lazy table (the step's rows; the dense parameters) as one launch
         self._rows_dense_one = bool(rows_dense_one_launch) and not self.dp_on
         self.tower_one_launch = bool(tower_one_launch)        # the fused towers' forward and backward as one launch (cdc_tower_step)
+        self.bwd_tail_one_launch = bool(bwd_tail_one_launch)  # the backward's last grad-input launch rides the grad-weight launch
+        self._per_launch_timing = False                       # profile(overlap=False) is running: every launch of bwd_steps on its own
         # split-K slabs of the batched grad-weight launches summed by the dense Adam launch (single GPU; under data parallelism the
         # reduced gradient is what is all-reduced)
         self._defer_dw = (not self.dp_on) if defer_dw_reduce is None else (bool(defer_dw_reduce) and not self.dp_on)
@@ -303,6 +308,27 @@ class TrainStep:
         if self._tower_both is not None:
             self._tower_both.one_launch = bool(on)
 
+    @property
+    def bwd_tail_fused(self):
+        """Does the single-GPU launch sequence (_launch) end its backward with cdc_glinear_bwd_xw instead of two launches?"""
+        return self.bwd_tail_one_launch and not self.dp_on and self.plan.bwd_tail is not None
+
+    def _backward(self, st):
+        """plan.backward(), with the fused tail where it is in use: bwd_steps up to the last grad-input launch, then one launch for
+        it and the grad-weight launch behind it.  Per-launch timing on one stream (profile(overlap=False)) keeps the two launches:
+        their names and durations are what the per-kernel tables are built from."""
+        plan = self.plan
+        if not (self.bwd_tail_fused and not self._per_launch_timing):
+            for fn in plan.bwd_steps:
+                fn(st)
+            return
+        x_step, w_step, fused = plan.bwd_tail
+        for fn in plan.bwd_steps:
+            if fn is x_step:
+                fused(st)
+            elif fn is not w_step:
+                fn(st)
+
     def _bce(self):
         og = self.out.grad
         head = self._head_lookup()
@@ -375,6 +401,9 @@ class TrainStep:
         into workspace a<1-p>; begin_step's work was done by the staging launch (cdc_stage_batch_next).
             side:  [sort] catch-up * | slice, [sort of the next batch]
             main:  weight shadows    | (wait *) gather, forward, BCE, backward, grad-weight launches, dense Adam | join | row update
+        The backward ends with the embeddings' grad-input launch and the batched grad-weight launch; where the plan's tail has that form
+        (Plan.bwd_tail) and bwd_tail_one_launch is set, the two go out as ONE launch (cdc_glinear_bwd_xw, _backward):
+            ... cgc_mid_bwd, level-1 grad-input, [embedding grad-input + grad-weight tiles] | join | rows + dense Adam
         The side chain is a second stream on its own hardware queue (two branches of the hipGraph when captured) when the slice runs
         in the BACKGROUND (overlap, the default), and the main stream itself otherwise: no fork, no event, no join, and the slice
         goes out with its full grid.  The fork sits at the head of the step: the weight-shadow launch reads nothing of the table and
@@ -398,7 +427,7 @@ class TrainStep:
                 opt.begin_step()
                 plan.forward()
                 self._bce()
-                plan.backward()
+                self._backward(st)
                 opt.table_step(emb.idx, emb.out.grad.root, B, F, D)
                 opt.dense_step(plan.param_grads, plan._param_refs, plan.grad_slabs)
                 self._reg()
@@ -437,7 +466,7 @@ class TrainStep:
                 if not (fused and fn is emb.fwd_step):
                     fn(st)
             self._bce()
-            plan.backward()                   # (ends with the grad-weight launches: plan.deferred_dw_steps)
+            self._backward(st)                # (ends with the grad-weight launches: plan.deferred_dw_steps, or the fused tail)
             if self._rows_dense_one:
                 # the step's rows and the dense parameters in one launch behind the join (optim.rows_and_dense_step)
                 if bg:
@@ -844,6 +873,7 @@ class TrainStep:
         to itself."""
         was_graph, self.use_graph = self.use_graph, False
         was_overlap, self._overlap_ok = self._overlap_ok, bool(self._overlap_ok and overlap)
+        self._per_launch_timing = not overlap
         rec = []
         out = {}
         used = max(n_steps - skip, 1)
@@ -872,6 +902,7 @@ class TrainStep:
             L.PROFILE = None
             self.use_graph = was_graph
             self._overlap_ok = was_overlap
+            self._per_launch_timing = False
         return out
 
     def sibling(self, batch_size, global_rows=None, cap_rows=None):

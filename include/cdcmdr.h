@@ -397,6 +397,14 @@ int cdc_glinear_bwd_w_pair(const cdc_lin_bwdw_args* wide, const cdc_lin_bwdw_arg
  * own reduce launch): for callers that need the reduced gradient at once (data parallelism all-reduces it).  Both classes split. */
 int cdc_glinear_bwd_w_pair_reduce(const cdc_lin_bwdw_args* wide, const cdc_lin_bwdw_args* narrow, const cdc_lin_bwdw_args* tabs_dev,
                                   void* stream);
+/* a grad-input launch (cdc_gemm_bf16_nt, mode 1) and the cdc_glinear_bwd_w_pair launch that follows it as ONE launch: the end of a step's
+ * backward, where the embeddings' dX and the batched grad-weight tiles depend on nothing of each other.  Every workgroup runs the code of the
+ * launch it comes from on the same operands in the same order: the results are bit-identical to the two calls.  Checks and error codes are
+ * those of the two calls; in addition CDC_E_BADARG (nothing launched) when the grad-input part's tile class is not one of 64 x 64 x 3 stages
+ * / 128 x 128 x 2 stages (tile_cfg 9 / 1, or what the library picks), or when a range the grad-input part writes (every o[i].y / o[i].yh)
+ * meets one the grad-weight part reads (dzh, xh) or writes (slab workspace, dw / db), or the grad-weight part writes what the grad-input
+ * part reads.  tabs_dev: as for cdc_glinear_bwd_w_pair. */
+int cdc_glinear_bwd_xw(const cdc_g2_args* x, const cdc_lin_bwdw_args* wide, const cdc_lin_bwdw_args* narrow, const void* tabs_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Gate softmax + expert pooling (reference: model/ple.py:89-94,105-123; model/mmoe.py:37-40,58-60)

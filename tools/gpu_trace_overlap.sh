@@ -37,3 +37,5 @@ if len(st) >= 4:
         f.write(f"# step length by the trace: {(ev[b][0] - t0) / 1e3:.1f} us\n")
     print(open(f"{O}/step_timeline.txt").read())
 PY
+# the backward tail over every replayed step: the grad-input / grad-weight launches (or the fused k_g2_xw) and when each chain reaches the join
+python tools/trace_tail_summary.py $O | tee $O/tail_summary.txt

@@ -51,13 +51,21 @@ order = [n for n, *_ in names]
 plan = ts.plan
 st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 steps = [("fwd", f) for f in plan.fwd_steps] + [("bwd", f) for f in plan.bwd_steps]
+if plan.bwd_tail is not None:
+    # the fused tail beside the two launches it replaces (the last two entries of bwd_steps), and the two issued alternately
+    x_step, w_step, fused = plan.bwd_tail
+
+    def both(s, x_step=x_step, w_step=w_step):
+        x_step(s)
+        w_step(s)
+    steps += [("bwd", fused), ("bwd", both)]
 for kind, fn in steps:
     rec = []
     L.PROFILE = rec
     fn(st)
     torch.cuda.synchronize()
     L.PROFILE = None
-    name = rec[0][0] if rec else "?"
+    name = " + ".join(r[0] for r in rec) if rec else "?"
     if args.filter and args.filter not in name:
         continue
     for _ in range(10):
